@@ -2,6 +2,7 @@
 """Benchmark of the render hot path: ray-samples/sec at 800x800x128 (BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W [--mode render|train] [--precision fp16|bf16|fp32]
+                    [--full] [--dump-outputs DIR]
 
 --mode render (default; BASELINE config 3).  One step = one full 800x800 single-view render with
 128 samples per ray through the C ABI: ONE launch (nerf_amd_render_pixels_forward: sampling +
@@ -19,10 +20,17 @@ Launch: `python bench.py --gpus N` starts its own N rank processes (one per GPU,
 call is made in the parent); under `python -m torch.distributed.run ... bench.py --gpus N` the
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* environment is used as given.
 
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR then also
+writes what the last timed step computed as DIR/<name>.npy (render: rgb, disp of every pixel; train:
+the loss and every parameter after the step).  Everything else the benchmark measures -- cpu_baseline,
+the second entry of by_dtype / by_storage, aux, the live PMC passes and the train-mode roofline --
+runs only with --full (--no-cpu-baseline / --no-aux narrow that down).
+
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline      the dominant kernel against its roofline, duration from HIP events on the launch
-                stream inside the timed steps, HBM traffic from the committed PMC summary of this
-                same command (null when no committed pass holds this kernel instantiation);
+                stream inside the timed steps (train mode, --full: 20 launches of its own after
+                them), HBM traffic from the committed PMC summary of this same command (null when
+                no committed pass holds this kernel instantiation);
   cpu_baseline  the CPU oracle (a PyTorch-CPU port of the reference) timed on this box's host
                 cores on a bounded sample (N=1 only), and the PSNR criterion of BASELINE.json on
                 the weights that were timed;
@@ -76,15 +84,23 @@ def parse():
                     help="MFMA operand type of the render (train mode is bf16)")
     ap.add_argument("--storage", default="bf16", choices=["bf16", "e4m3"],
                     help="train mode: how the saved activations and dY travel through HBM (GraphedTrainStep(storage=...))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary configurations (render mode, N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other operand type / storage form, the other "
+                         "BASELINE configurations, the CPU baseline with the PSNR criterion, live PMC passes and (train mode) "
+                         "the dominant kernel's own launches")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the auxiliary configurations (N=1)")
     ap.add_argument("--cpu-rays", type=int, default=16000,
                     help="rays of the CPU-baseline sample (x128 samples; the reference's test batch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 150 if a.mode == "render" else 6000
     if a.warmup is None:
         a.warmup = 5 if a.mode == "render" else 50
+    if not a.full:                       # a plain run: set up, warm up, time the steps, print the line
+        a.no_cpu_baseline = a.no_aux = True
     return a
 
 
@@ -250,6 +266,15 @@ def emit(res):
     """The one JSON line, on the process's original stdout."""
     out = _JSON_OUT or sys.stdout
     print(json.dumps(res), file=out, flush=True)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy in float32 (the inputs are seeded: two builds compare array for
+    array)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().float().cpu().numpy())
 
 
 def init_rank(args):
@@ -684,6 +709,8 @@ def run_render(args):
             events.append(ev)
 
     elapsed = timed_loop(step, args, dist, dev, world)
+    if args.dump_outputs and rank == 0:          # the last timed step's image: clip(rgb, 0, 1) and disparity per pixel
+        dump_outputs(args.dump_outputs, {"rgb": image[:, :3], "disp": image[:, 3]})
     seen = ranks_seen(dist, dev, world)
     kern_ms = sum(e[0].elapsed_time(e[1]) for e in events) / max(len(events), 1)
     coll_ms = sum(e[1].elapsed_time(e[2]) for e in events) / max(len(events), 1) if multi else 0.0
@@ -834,6 +861,8 @@ def run_train(args):
         it[0] += 1
 
     elapsed = timed_loop(step, args, dist, dev, world)
+    if args.dump_outputs and rank == 0:          # what a caller holds after the last timed step: its loss and the updated weights
+        dump_outputs(args.dump_outputs, {"loss": stepper.loss, **{f"param.{k}": p for k, p in net.named_parameters()}})
     coll = stepper.collective_times() if multi else None      # (span, exposed) ms per timed step
     # the other storage form of the saved tensors, timed alike in the same process (N = 1): a second module from the same
     # initial weights, its own optimizer and graphs, the same table and seeds
@@ -860,36 +889,38 @@ def run_train(args):
     # duration of the dominant kernel (the dW products: nerf_amd_param_gradients_finish*): 20 more launches on the same
     # buffers right after the timed steps, each bracketed by events on the launch stream.  What precedes it in a step -- the
     # zero fill of the gradient vector and the d_raw pack (_begin; the 8-bit form: the conversion of the narrow operands) --
-    # is launched in front of the first event: the products add into the vector with atomics.
-    st = _lib.stream_ptr(dev)
-    image = net.packed_weights(_lib.BF16_BWD)
-    evs = []
-    for _ in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        _lib.check(lib.nerf_amd_param_gradients_begin(_lib.ptr(stepper.d_raw), _lib.ptr(stepper.scratch), _lib.ptr(stepper.grads), P, st),
-                   "nerf_amd_param_gradients_begin")
-        if e4m3:
-            _lib.check(lib.nerf_amd_param_gradients_convert_e4m3(_lib.ptr(stepper.posx), _lib.ptr(stepper.posd), _lib.ptr(stepper.scratch),
-                                                                 _lib.ptr(stepper.scratch8), P, 3, st), "nerf_amd_param_gradients_convert_e4m3")
-            e0.record()
-            _lib.check(lib.nerf_amd_param_gradients_finish_e4m3(_lib.ptr(stepper.acts), _lib.ptr(stepper.dys), _lib.ptr(stepper.scratch8),
-                                                                _lib.ptr(stepper.grads), P, 0, st), "nerf_amd_param_gradients_finish_e4m3")
-        else:
-            e0.record()
-            _lib.check(lib.nerf_amd_param_gradients_finish(_lib.ptr(stepper.acts), _lib.ptr(stepper.dys), _lib.ptr(stepper.posx),
-                                                           _lib.ptr(stepper.posd), _lib.ptr(stepper.scratch), _lib.ptr(stepper.grads), P, st),
-                       "nerf_amd_param_gradients_finish")
-        e1.record()
-        evs.append((e0, e1))
-    torch.cuda.synchronize(dev)
-    dw_ms = sorted(a.elapsed_time(b) for a, b in evs)[len(evs) // 2]
-    dw_ms_ranks = gather_floats(dist, dev, world, dw_ms)
+    # is launched in front of the first event: the products add into the vector with atomics.  Launches of their own: --full.
+    dw_ms, dw_ms_ranks = None, []
+    if args.full:
+        st = _lib.stream_ptr(dev)
+        image = net.packed_weights(_lib.BF16_BWD)
+        evs = []
+        for _ in range(20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            _lib.check(lib.nerf_amd_param_gradients_begin(_lib.ptr(stepper.d_raw), _lib.ptr(stepper.scratch), _lib.ptr(stepper.grads), P, st),
+                       "nerf_amd_param_gradients_begin")
+            if e4m3:
+                _lib.check(lib.nerf_amd_param_gradients_convert_e4m3(_lib.ptr(stepper.posx), _lib.ptr(stepper.posd), _lib.ptr(stepper.scratch),
+                                                                     _lib.ptr(stepper.scratch8), P, 3, st), "nerf_amd_param_gradients_convert_e4m3")
+                e0.record()
+                _lib.check(lib.nerf_amd_param_gradients_finish_e4m3(_lib.ptr(stepper.acts), _lib.ptr(stepper.dys), _lib.ptr(stepper.scratch8),
+                                                                    _lib.ptr(stepper.grads), P, 0, st), "nerf_amd_param_gradients_finish_e4m3")
+            else:
+                e0.record()
+                _lib.check(lib.nerf_amd_param_gradients_finish(_lib.ptr(stepper.acts), _lib.ptr(stepper.dys), _lib.ptr(stepper.posx),
+                                                               _lib.ptr(stepper.posd), _lib.ptr(stepper.scratch), _lib.ptr(stepper.grads), P, st),
+                           "nerf_amd_param_gradients_finish")
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize(dev)
+        dw_ms = sorted(a.elapsed_time(b) for a, b in evs)[len(evs) // 2]
+        dw_ms_ranks = gather_floats(dist, dev, world, dw_ms)
     span_ranks = gather_floats(dist, dev, world, coll[0] if coll else 0.0)
     exposed_ranks = gather_floats(dist, dev, world, coll[1] if coll else 0.0)
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * P * args.steps / elapsed
-        achieved = dw_bytes * P / (dw_ms * 1e-3) / 1e9
+        achieved = dw_bytes * P / (dw_ms * 1e-3) / 1e9 if dw_ms is not None else None
         traffic, traffic_src = pmc_traffic(dw_kernel, "train") if not multi else (None, None)
         traffic_kind = "HBM bytes per launch from the committed rocprofv3 PMC passes of this command; not re-measured in this run"
         if not multi and not args.no_aux and os.environ.get("NERF_BENCH_LIVE_PMC", "1") == "1":
@@ -939,7 +970,7 @@ def run_train(args):
                          "traffic": traffic, "traffic_source": traffic_src, "traffic_kind": traffic_kind, "kernel_ms": dw_ms,
                          "algorithmic_bytes_per_point": dw_bytes,
                          "kernel_ms_note": "median of 20 extra launches on the step's own buffers after the timed region",
-                         "step_mfma_frac": 3 * FLOP_PER_SAMPLE * P / (ms * 1e-3) / PEAK_BF16},
+                         "step_mfma_frac": 3 * FLOP_PER_SAMPLE * P / (ms * 1e-3) / PEAK_BF16} if dw_ms is not None else None,
         }
         emit(res)
     if multi:

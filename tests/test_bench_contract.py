@@ -114,3 +114,21 @@ def test_pmc_lookup_needs_the_exact_instantiation(bench):
     assert tt and tt > 2.5e9
     t8, src8 = bench.pmc_traffic("dw_gemm_e4m3_kernel(", "train")
     assert t8 and 1.3e9 < t8 < 1.7e9 and "e4m3" in src8
+
+
+def test_plain_run_leaves_the_extras_to_full(bench):
+    """A plain run measures only the headline; --full brings back the other legs, and --no-aux / --no-cpu-baseline still
+    narrow a full run.  --steps / --warmup are taken as given."""
+    def parse(*words):
+        argv = sys.argv
+        sys.argv = ["bench.py"] + list(words)
+        try:
+            return bench.parse()
+        finally:
+            sys.argv = argv
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.no_aux and a.no_cpu_baseline and a.dump_outputs is None
+    a = parse("--full")
+    assert a.full and not a.no_aux and not a.no_cpu_baseline and a.steps == 150 and a.warmup == 5
+    a = parse("--full", "--no-aux", "--mode", "train", "--dump-outputs", "out")
+    assert a.full and a.no_aux and not a.no_cpu_baseline and a.steps == 6000 and a.dump_outputs == "out"

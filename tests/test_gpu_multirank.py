@@ -138,8 +138,9 @@ def test_bench_self_launch_two_ranks(mode):
     env = dict(os.environ, NERF_BENCH_BACKEND="gloo", NERF_BENCH_SHARE_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
+    full = ["--full"] if mode == "train" else []          # train mode: kernel_ms_per_rank times the dW launch on its own
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--mode", mode], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--mode", mode] + full, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -163,6 +164,8 @@ def test_bench_rccl_single_rank_rehearsal(mode):
                NERF_BENCH_BUCKETS=("2" if mode.startswith("train2") else "1"))
     extra = ["--storage", "e4m3"] if mode.endswith("_e4m3") else []     # the 8-bit storage form through the bucketed launches
     mode = "train" if mode.startswith("train2") else mode
+    if mode == "train":
+        extra.append("--full")                                          # kernel_ms_per_rank: the dW launch timed on its own
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "NERF_BENCH_BACKEND", "NERF_BENCH_SHARE_GPU"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",

@@ -6,7 +6,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1 || { echo "rocprofv3 failed"; tail -5 $OUT/run.log; exit 1; }
+rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1 || { echo "rocprofv3 failed"; tail -5 $OUT/run.log; exit 1; }
 python3 - <<PY
 import csv,glob
 from collections import defaultdict
