@@ -166,6 +166,23 @@ int nerf_amd_volume_render_mse_backward(const float* raw, const float* ts, const
                                         const float* target, float* rgb, float* d_raw,
                                         int64_t B, int N, void* stream);
 
+/* Coarse head of the hierarchical training step (BASELINE config 4; the NeRF paper's objective
+ * MSE(rgb_c, gt) + MSE(rgb_f, gt)).  ONE launch, one wavefront per ray, doing what
+ *   nerf_amd_volume_render_mse_backward(raw, ts, rays, target, rgb, d_raw)         (train.py:51-54 on the coarse pass)
+ *   + nerf_amd_volume_render_rays(...) for w                                      (utils/rendering.py:69, w = alpha * T)
+ *   + nerf_amd_sample_pdf(ts, w, u, ...) -> ts_out                                 (no reference counterpart)
+ * would, bit for bit: raw[B,Nc,4], ts[B,Nc], rays[B,6], target[B,3] -> rgb[B,3] (may be NULL), d_raw[B,Nc,4] and
+ * ts_out[B,Nc+Nf] (the fine pass's merged, sorted positions).  The weights go from registers to LDS and never reach
+ * HBM; they carry no gradient (the coarse net learns from its own loss only: w.detach()).
+ * Jitter of the Nf new samples: u[B,Nf]; or NERF_AMD_DEVICE_RNG with nerf_amd_sample_pdf's key (seed, ray_id0);
+ * or NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY, `u` then the DEVICE ADDRESS of the 64-bit seed offset (a node
+ * of a replayed graph).  3 <= Nc <= 256, Nc + Nf <= 512, otherwise NERF_AMD_EUNSUP.  Parity unpinned like
+ * nerf_amd_sample_pdf (the reference has no hierarchical path). */
+int nerf_amd_volume_render_mse_backward_pdf(const float* raw, const float* ts, const float* rays,
+                                            const float* target, const float* u, uint32_t flags,
+                                            uint64_t seed, int64_t ray_id0, float* rgb, float* d_raw,
+                                            float* ts_out, int64_t B, int Nc, int Nf, void* stream);
+
 /* ---- the whole path: render_nerf, utils/rendering.py:13-45 ------------------- */
 /* rays[B,6] = [origin, direction] -> (rgb[B,3], disp[B], alpha[B,N], acc[B], w[B,N]).
  *   u        jitter in [0,1) [B,N] exactly as the reference draws it with

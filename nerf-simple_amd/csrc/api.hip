@@ -12,6 +12,9 @@ int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
 int nerf_amd_launch_pack_train(const float*, void*, void*, hipStream_t);
 int nerf_amd_launch_composite_mse_backward(const float*, const float*, const float*, const float*, float*, float*, long long,
                                            int, hipStream_t);
+int nerf_amd_launch_composite_mse_backward_pdf(const float*, const float*, const float*, const float*, float*, float*,
+                                               const float*, float*, long long, int, int, unsigned long long, long long, int,
+                                               int, hipStream_t);
 int nerf_amd_launch_param_gradients_begin(const float*, void*, float*, long long, hipStream_t);
 int nerf_amd_launch_param_gradients_finish(const void*, const void*, const void*, const void*, const void*, float*, long long,
                                            int, hipStream_t);
@@ -277,6 +280,26 @@ int nerf_amd_volume_render_mse_backward(const float* raw, const float* ts, const
     if (N > 512) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
     return nerf_amd_launch_composite_mse_backward(raw, ts, rays, target, rgb, d_raw, B, N, S(stream));
+}
+
+int nerf_amd_volume_render_mse_backward_pdf(const float* raw, const float* ts, const float* rays, const float* target,
+                                            const float* u, uint32_t flags, uint64_t seed, int64_t ray_id0,
+                                            float* rgb, float* d_raw, float* ts_out, int64_t B, int Nc, int Nf,
+                                            void* stream) {
+    if (B < 0 || Nc <= 0 || Nf < 0) return NERF_AMD_EINVAL;
+    if (flags & ~(NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return NERF_AMD_EINVAL;
+    if (flags & NERF_AMD_SEED_IN_MEMORY) {
+        // `u` is the address of the 64-bit seed offset (the graphed step's hyper vector)
+        if (!(flags & NERF_AMD_DEVICE_RNG) || !u || (reinterpret_cast<uintptr_t>(u) & 7)) return NERF_AMD_EINVAL;
+    } else if (!(flags & NERF_AMD_DEVICE_RNG) && !u && Nf > 0) {
+        return NERF_AMD_EINVAL;
+    }
+    if (B == 0) return 0;
+    if (Nc < 3 || Nc > 256 || Nc + Nf > 512) return NERF_AMD_EUNSUP;
+    if (!raw || !ts || !rays || !target || !d_raw || !ts_out) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_composite_mse_backward_pdf(raw, ts, rays, target, rgb, d_raw, u, ts_out, B, Nc, Nf, seed, ray_id0,
+                                                      (flags & NERF_AMD_DEVICE_RNG) ? 1 : 0,
+                                                      (flags & NERF_AMD_SEED_IN_MEMORY) ? 1 : 0, S(stream));
 }
 
 int nerf_amd_mse_loss(const float* pred, const float* target, float* loss, float* g_pred, int64_t n, void* stream) {

@@ -14,6 +14,7 @@
 // Not HBM-bound in practice: the exact-fp32 softplus / exp (ocml expf, log1pf) and the two scans
 // cost ~400 VALU instructions per 64 samples, which is what sets its 3.4 TB/s.
 #include "composite_device.h"
+#include "sample_pdf_device.h"
 
 namespace {
 
@@ -52,6 +53,19 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_kernel(
 // are walked forward once (recomputing alpha, T, w) and backward once.
 constexpr int MAX_CHUNKS = 8;          // N <= 512
 
+// The coarse training head (E > 0): the same kernel also places the fine pass's samples from the weights of its
+// forward sweep (sample_pdf_device.h).  The weights go from registers to the wave's LDS slice with the positions; the
+// sampler reads them there after the backward sweep, so neither ts nor w is read from HBM a second time.
+struct PdfHead {
+    const float* u;                    // u[B,Nf]; with seed_in_mem the DEVICE ADDRESS of the 64-bit seed offset
+    float* ts_out;                     // [B, Nc+Nf]
+    int Nf;
+    int device_rng;
+    int seed_in_mem;
+    unsigned long long seed;
+    long long ray_id0;
+};
+
 __device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& total) {
     // inclusive suffix sum, then shift down by one lane
     float incl = v;
@@ -66,13 +80,20 @@ __device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& tota
     return ex;
 }
 
+// E = 0: the compositor's backward alone (N <= 512).  E > 0: the coarse training head, N = Nc <= 256 (four chunks)
+// and Nf new samples sorted E keys per lane.
+template <int E>
 __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel(
     const float* __restrict__ raw, const float* __restrict__ ts, const float* __restrict__ dirs,
     long long dirs_stride, const float* __restrict__ g_rgb, const float* __restrict__ g_disp,
     const float* __restrict__ g_alpha, const float* __restrict__ g_acc, const float* __restrict__ g_w,
     float* __restrict__ d_raw, long long B, int N, int normalize_dirs,
-    const float* __restrict__ mse_target, float* __restrict__ rgb_out, float mse_scale) {
-    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
+    const float* __restrict__ mse_target, float* __restrict__ rgb_out, float mse_scale, PdfHead pdf) {
+    constexpr int CHUNKS = E > 0 ? nerf_pdf::MAXC / 64 : MAX_CHUNKS;
+    __shared__ nerf_pdf::WaveLds<(E > 0 ? E : 1)> s_pdf[E > 0 ? RAYS_PER_BLOCK : 1];
+    __shared__ float s_pdf_w[E > 0 ? RAYS_PER_BLOCK : 1][nerf_pdf::MAXC];
+    const int wv = threadIdx.x >> 6;
+    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + wv;
     if (ray >= B) return;
     const int lane = threadIdx.x & 63;
     const float* d = dirs + ray * dirs_stride;
@@ -95,12 +116,12 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
     }
 
     // forward sweep: per chunk keep alpha, T, fac, delta*softplus' and the colour
-    float al[MAX_CHUNKS], Tt[MAX_CHUNKS], fc[MAX_CHUNKS], ds[MAX_CHUNKS], tt[MAX_CHUNKS];
-    f32x4 cc[MAX_CHUNKS];
+    float al[CHUNKS], Tt[CHUNKS], fc[CHUNKS], ds[CHUNKS], tt[CHUNKS];
+    f32x4 cc[CHUNKS];
     float carry = 1.0f, depth = 0.f, accw = 0.f;
     float sr = 0.f, sg = 0.f, sb = 0.f;            // training form: the forward's rgb, for the loss gradient
 #pragma unroll
-    for (int ch = 0; ch < MAX_CHUNKS; ++ch) {
+    for (int ch = 0; ch < CHUNKS; ++ch) {
         const int base = ch * 64;
         al[ch] = 0.f; Tt[ch] = 0.f; fc[ch] = 1.f; ds[ch] = 0.f; tt[ch] = 0.f;
         cc[ch] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -131,6 +152,10 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
                 // the same ops as the forward compositor (composite_device.h), so rgb_out equals its rgb
                 const float wt = mul_rn(a, Tt[ch]);
                 sr = __fmaf_rn(wt, cc[ch][0], sr); sg = __fmaf_rn(wt, cc[ch][1], sg); sb = __fmaf_rn(wt, cc[ch][2], sb);
+                if constexpr (E > 0) {      // the sampler's inputs: these positions and the forward compositor's weights
+                    s_pdf[wv].ts[i] = tt[ch];
+                    s_pdf_w[wv][i] = wt;
+                }
             }
         }
     }
@@ -159,7 +184,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
     // backward sweep over chunks, carrying sum_{k in later chunks} G_k w_k
     float later = 0.f;
 #pragma unroll
-    for (int ch = MAX_CHUNKS - 1; ch >= 0; --ch) {
+    for (int ch = CHUNKS - 1; ch >= 0; --ch) {
         const int base = ch * 64;
         if (base < N) {
             const int i = base + lane;
@@ -180,6 +205,18 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
                 rout[i] = o;
             }
         }
+    }
+    if constexpr (E > 0) {
+        // the fine pass's positions from this ray's weights (nerf_amd_sample_pdf's body, same draws)
+        nerf_pdf::wave_lds_fence();
+        unsigned long long seed = pdf.seed;
+        if (pdf.seed_in_mem) {
+            const unsigned long long v = *reinterpret_cast<const unsigned long long*>(pdf.u);
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+            seed += ((unsigned long long)hi << 32) | lo;
+        }
+        nerf_pdf::sample_ray<E>(s_pdf[wv], s_pdf_w[wv], N, pdf.Nf, lane, pdf.u, pdf.device_rng != 0, seed, pdf.ray_id0, ray,
+                                pdf.ts_out + ray * (N + pdf.Nf));
     }
 }
 
@@ -216,9 +253,9 @@ extern "C" int nerf_amd_launch_composite_backward(const float* raw, const float*
     if (B == 0) return 0;
     if (N > 64 * MAX_CHUNKS) return -2;
     const long long blocks = (B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
-    hipLaunchKernelGGL(composite_backward_kernel, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
+    hipLaunchKernelGGL(composite_backward_kernel<0>, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
                        raw, ts, dirs, dirs_stride, g_rgb, g_disp, g_alpha, g_acc, g_w, d_raw, B, N,
-                       normalize_dirs, nullptr, nullptr, 0.f);
+                       normalize_dirs, nullptr, nullptr, 0.f, PdfHead{});
     return (int)hipGetLastError();
 }
 
@@ -230,9 +267,34 @@ extern "C" int nerf_amd_launch_composite_mse_backward(const float* raw, const fl
     if (B == 0) return 0;
     if (N > 64 * MAX_CHUNKS) return -2;
     const long long blocks = (B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
-    hipLaunchKernelGGL(composite_backward_kernel, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
+    hipLaunchKernelGGL(composite_backward_kernel<0>, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
                        raw, ts, rays + 3, 6ll, nullptr, nullptr, nullptr, nullptr, nullptr, d_raw, B, N, 1,
-                       target, rgb, 1.0f / (3.0f * (float)B));
+                       target, rgb, 1.0f / (3.0f * (float)B), PdfHead{});
+    return (int)hipGetLastError();
+}
+
+// the coarse training head: the launch above + the fine pass's sample placement (sample_pdf) in the same waves
+extern "C" int nerf_amd_launch_composite_mse_backward_pdf(const float* raw, const float* ts, const float* rays,
+                                                          const float* target, float* rgb, float* d_raw, const float* u,
+                                                          float* ts_out, long long B, int Nc, int Nf, unsigned long long seed,
+                                                          long long ray_id0, int device_rng, int seed_in_mem,
+                                                          hipStream_t stream) {
+    (void)hipGetLastError();
+    if (B == 0) return 0;
+    if (Nc < 3 || Nc > nerf_pdf::MAXC || Nf < 0 || Nc + Nf > nerf_pdf::MAXM) return -2;
+    const dim3 grid((unsigned)((B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
+    const PdfHead pdf{u, ts_out, Nf, device_rng, seed_in_mem, seed, ray_id0};
+    const float scale = 1.0f / (3.0f * (float)B);
+#define NERF_PDF_HEAD(E_)                                                                                             \
+    hipLaunchKernelGGL(composite_backward_kernel<E_>, grid, block, 0, stream, raw, ts, rays + 3, 6ll, nullptr, nullptr, \
+                       nullptr, nullptr, nullptr, d_raw, B, Nc, 1, target, rgb, scale, pdf)
+    switch (nerf_pdf::keys_per_lane(Nf)) {
+        case 1: NERF_PDF_HEAD(1); break;
+        case 2: NERF_PDF_HEAD(2); break;
+        case 4: NERF_PDF_HEAD(4); break;
+        default: NERF_PDF_HEAD(8); break;
+    }
+#undef NERF_PDF_HEAD
     return (int)hipGetLastError();
 }
 

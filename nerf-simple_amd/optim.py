@@ -11,6 +11,11 @@
   * ``param_groups[0]['lr']`` is honoured every step, so the reference's
     ``for p in optimizer.param_groups: p['lr'] *= decay`` loop (train.py:56-57) works
     unchanged.
+
+``FusedAdam([net_c, net_f])`` (the hierarchical pair, training.train_step_hierarchical): the modules'
+parameters, in the order given and state_dict order within each, share ONE flat vector (2 x 595,844
+elements), so one Adam launch updates both; each module's packed images are then re-derived from its
+own slice.  ``nets`` is that tuple (None for a single module) and ``slices`` their views of ``flat``.
 """
 import torch
 
@@ -18,9 +23,17 @@ from . import _lib
 
 
 class FusedAdam:
+    nets = None
+
     def __init__(self, net, lr=5e-4, betas=(0.9, 0.999), eps=1e-8):
-        self.net = net
-        self.params = [p for _, p in net.named_parameters()]
+        if isinstance(net, (list, tuple)):
+            nets = tuple(net)
+            if not nets or len({id(n) for n in nets}) != len(nets):
+                raise ValueError("FusedAdam([...]) takes distinct modules (the same module twice would be updated twice)")
+            self.nets = nets
+        self.net = net if self.nets is None else self.nets
+        mods = (net,) if self.nets is None else self.nets
+        self.params = [p for m in mods for _, p in m.named_parameters()]
         dev = self.params[0].device
         if dev.type != "cuda":
             raise RuntimeError("FusedAdam needs the module on the GPU")
@@ -31,6 +44,12 @@ class FusedAdam:
                 n = p.numel()
                 p.data = self.flat[off:off + n].view(p.shape)
                 off += n
+        if self.nets is not None:
+            self.slices, off = [], 0
+            for m in mods:
+                k = sum(p.numel() for p in m.parameters())
+                self.slices.append(self.flat[off:off + k])
+                off += k
         self.exp_avg = torch.zeros_like(self.flat)
         self.exp_avg_sq = torch.zeros_like(self.flat)
         self.param_groups = [{"params": self.params, "lr": lr, "betas": betas, "eps": eps}]
@@ -68,4 +87,8 @@ class FusedAdam:
                 float(pg["eps"]), self.step_count, _lib.stream_ptr(dev)), "nerf_amd_adam_step")
         # the kernel wrote through the flat buffer (the parameters' _version did not move):
         # re-derive the packed images now and stamp the cache with the current versions
-        self.net.repack_from_flat(self.flat)
+        if self.nets is None:
+            self.net.repack_from_flat(self.flat)
+        else:
+            for m, sl in zip(self.nets, self.slices):
+                m.repack_from_flat(sl)

@@ -307,6 +307,110 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
 
 
 # --------------------------------------------------------------------------
+# the hierarchical pair (BASELINE config 4): coarse and fine networks trained together
+# --------------------------------------------------------------------------
+def _check_pair(net_c, net_f, Nc, Nf, precision):
+    """The pair's limits, checked before anything is drawn or launched: two distinct modules with one precision, and
+    nerf_amd_sample_pdf's sample counts (3 <= Nc <= 256, 0 <= Nf, Nc + Nf <= 512)."""
+    if net_c is net_f:
+        raise ValueError("the coarse and the fine network must be two distinct modules")
+    if net_c.precision != net_f.precision:
+        raise ValueError(f"the coarse and the fine network differ in precision ({net_c.precision!r} vs {net_f.precision!r})")
+    Nc, Nf = int(Nc), int(Nf)
+    if Nc < 3 or Nc > 256 or Nf < 0 or Nc + Nf > 512:
+        raise ValueError(f"hierarchical sampling needs 3 <= Nc <= 256 and Nc + Nf <= 512 (got Nc={Nc}, Nf={Nf})")
+    return _lib.precision_code(net_c.precision if precision is None else precision)
+
+
+def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0):
+    """render_nerf_autograd that also hands back the sample positions it drew (the coarse pass of the pair)."""
+    from .utils.rendering import _tbins
+    from .utils.xyz import range_check_rays
+    dev, B = rays.device, rays.size(0)
+    tbins = _tbins(tn, tf, N, dev)
+    range_check_rays(rays, jit, tbins, flags, seed, ray_id0, N)
+    if _lib.precision_code(precision) == _lib.F32:
+        from .utils import generic_mlp
+        lib = _lib.lib()
+        q = torch.empty((B * N, 6), dtype=torch.float32, device=dev)
+        ts = torch.empty((B, N), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_query_points(_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0),
+                                                 _lib.ptr(q), _lib.ptr(ts), B, N, _lib.stream_ptr(dev)), "nerf_amd_query_points")
+        raw = generic_mlp.forward(net, q).reshape(B, N, 4).float()
+    else:
+        params = [p for _, p in net.named_parameters()]
+        raw, ts = _FusedDense.apply(net, rays, jit, tbins, flags, seed, ray_id0, N, None, *params)
+    return _VolumeRender.apply(raw, ts, rays, True), ts
+
+
+def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
+                            decay=1.0, group=None, precision=None, device_rng=False, seed=0, ray_id0=0):
+    """One optimisation step of the coarse / fine pair (the NeRF paper's objective; the reference has no hierarchical
+    path, its CoarseNet / FineNet are empty): zero_grad -> coarse render_nerf with gradients (Nc stratified samples) ->
+    sample_pdf on the DETACHED coarse weights (the coarse net learns from its own loss only) -> fine render_nerf of
+    ``net_f`` on the Nc+Nf merged positions with gradients -> MSE(rgb_c, gt) + MSE(rgb_f, gt) -> backward ->
+    [all-reduce of the combined gradient, one bucket] -> optimizer.step -> lr *= decay.
+
+    ``optimizer``: ``optim.FusedAdam([net_c, net_f])`` or any torch optimizer over exactly both modules' parameters.
+    Jitter: ``u_c`` [B,Nc] / ``u_f`` [B,Nf]; default the render_hierarchical draws, torch.rand(B,Nc) then
+    torch.rand(B,Nf) from torch's CPU generator (continued on the device); ``device_rng=True``: the counter RNG keyed by
+    (seed, ray_id0 + ray).  precision 'fp32' trains both exactly, layer by layer (utils/generic_mlp.py).
+    Returns the detached total loss; ``.losses`` on it holds the [coarse, fine] terms, ``.ts_f`` the fine positions."""
+    from . import parallel
+    from .optim import FusedAdam
+    from .utils.host_rng import reference_rand
+    from .utils.rendering import render_nerf, sample_pdf
+    _check_pair(net_c, net_f, Nc, Nf, precision)
+    Nc, Nf = int(Nc), int(Nf)
+    params = list(net_c.parameters()) + list(net_f.parameters())
+    if isinstance(optimizer, FusedAdam):
+        if optimizer.nets is None or len(optimizer.nets) != 2 or optimizer.nets[0] is not net_c or optimizer.nets[1] is not net_f:
+            raise RuntimeError("the optimizer is not FusedAdam([net_c, net_f]) of this pair")
+    else:
+        opt_ids = {id(p) for pg in optimizer.param_groups for p in pg["params"]}
+        if opt_ids != {id(p) for p in params}:
+            raise RuntimeError("the optimizer does not hold exactly the parameters of the coarse and the fine network")
+    _lib.require_cuda_f32(rays, "rays")
+    if rays.dim() != 2 or rays.shape[1] != 6:
+        raise RuntimeError("rays must be [B, 6]")
+    B, dev = rays.size(0), rays.device
+    for name, t_, n in (("u_c", u_c, Nc), ("u_f", u_f, Nf)):
+        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
+            raise RuntimeError(f"{name} must be [B, {n}]")
+    rays = rays.detach().contiguous()
+    flags = 0
+    if device_rng and u_c is None:
+        flags = _lib.FLAG_DEVICE_RNG
+    elif u_c is None:
+        u_c, pend = reference_rand(B, Nc, dev)
+        pend.finish()
+    if u_f is None and not device_rng:
+        u_f, pend = reference_rand(B, Nf, dev)
+        pend.finish()
+    jit_c = None if u_c is None else u_c.contiguous()
+
+    optimizer.zero_grad(set_to_none=True)
+    coarse, ts_c = _render_train_with_ts(rays, net_c, Nc, tn, tf, jit_c, flags,
+                                         net_c.precision if precision is None else precision, seed, ray_id0)
+    # the fine positions carry no gradient: w.detach() -- the coarse net learns from MSE(rgb_c, gt) alone
+    ts_f = sample_pdf(ts_c, coarse[4].detach(), Nf, u=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+    fine = render_nerf(rays, net_f, Nc + Nf, tn, tf, ts=ts_f, precision=precision)
+    loss_c = mse_loss(coarse[0], gt)
+    loss_f = mse_loss(fine[0], gt)
+    loss = loss_c + loss_f
+    loss.backward()
+    parallel.allreduce_gradients(params, group=group)
+    optimizer.step()
+    if decay != 1.0:
+        for pg in optimizer.param_groups:
+            pg["lr"] = pg["lr"] * decay
+    out = loss.detach()
+    out.losses, out.ts_f = [loss_c.detach(), loss_f.detach()], ts_f
+    return out
+
+
+# --------------------------------------------------------------------------
 # the same step as ONE captured hipGraph (launch-bound at 4096-ray batches)
 # --------------------------------------------------------------------------
 class _HyperRing:
@@ -453,13 +557,7 @@ class GraphedTrainStep:
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
                  device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16"):
         from . import parallel
-        from .optim import FusedAdam
-        from .utils.rendering import _tbins
-        if not isinstance(optimizer, FusedAdam):
-            raise RuntimeError("GraphedTrainStep needs optim.FusedAdam (one flat parameter vector)")
-        if optimizer.net is not net:
-            raise RuntimeError("the optimizer belongs to another module")
-        _check_fused_trainable(net.precision)
+        self._check_modules(net, optimizer)
         self.net, self.opt, self.group = net, optimizer, group
         if buckets not in (1, 2):
             raise ValueError("buckets must be 1 (one all-reduce between the two graphs, the default) or 2 (overlapped)")
@@ -491,24 +589,8 @@ class GraphedTrainStep:
         self.rays[:, 5] = -1.0                      # a valid direction: the capture warm-up runs on these buffers
         self.gt = torch.zeros((B, 3), **f32)
         self.u = torch.zeros((B, N_), **f32)
-        self.tbins = _tbins(tn, tf, N_, dev)
-        self.raw = torch.empty((B, N_, 4), **f32)
-        self.ts = torch.empty((B, N_), **f32)
-        if self._e4m3:
-            self.acts = torch.empty(int(lib.nerf_amd_train_activation_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
-            self.dys = torch.empty(int(lib.nerf_amd_train_gradient_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
-            self.scratch8 = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_e4m3_bytes(P)), 16), dtype=torch.uint8, device=dev)
-        else:
-            nb = int(lib.nerf_amd_train_activation_bytes(P))
-            self.acts = torch.empty(nb, dtype=torch.uint8, device=dev)
-            self.dys = torch.empty(nb, dtype=torch.uint8, device=dev)
-        self.posx = torch.empty((P, 64), dtype=torch.bfloat16, device=dev)
-        self.posd = torch.empty((P, 32), dtype=torch.bfloat16, device=dev)
-        self.rgb = torch.empty((B, 3), **f32)
-        self.d_raw = torch.empty((B, N_, 4), **f32)
-        self.grads = torch.zeros(int(lib.nerf_amd_param_count()), **f32)
-        self.scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8,
-                                   device=dev)
+        self._alloc_pass_buffers(tn, tf)
+        self.grads = torch.zeros(optimizer.flat.numel(), **f32)
         self.loss = torch.zeros((), **f32)
         self._ids_next = torch.zeros((B,), dtype=torch.int64, device=dev)      # rays_from: rows of the table (see ray_ids)
         self._ids_cur, self._ids_step, self._primed_for = torch.zeros_like(self._ids_next), -1, -1
@@ -530,6 +612,39 @@ class GraphedTrainStep:
             p.grad = self.grads[off:off + k].view(p.shape)
             off += k
         self._capture()
+
+    def _check_modules(self, net, optimizer):
+        from .optim import FusedAdam
+        if not isinstance(optimizer, FusedAdam):
+            raise RuntimeError("GraphedTrainStep needs optim.FusedAdam (one flat parameter vector)")
+        if optimizer.net is not net:
+            raise RuntimeError("the optimizer belongs to another module")
+        _check_fused_trainable(net.precision)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        """The buffers of the one forward / backward pass: sample bins, raw / ts, saved activations, encoder rows, d_raw."""
+        from .utils.rendering import _tbins
+        lib, dev = _lib.lib(), self.dev
+        B, N_, P = self.B, self.N, self.B * self.N
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.tbins = _tbins(tn, tf, N_, dev)
+        self._first_N, self._first_u = N_, self.u          # the stratified pass: what the range check looks at
+        self.raw = torch.empty((B, N_, 4), **f32)
+        self.ts = torch.empty((B, N_), **f32)
+        if self._e4m3:
+            self.acts = torch.empty(int(lib.nerf_amd_train_activation_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
+            self.dys = torch.empty(int(lib.nerf_amd_train_gradient_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
+            self.scratch8 = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_e4m3_bytes(P)), 16), dtype=torch.uint8, device=dev)
+        else:
+            nb = int(lib.nerf_amd_train_activation_bytes(P))
+            self.acts = torch.empty(nb, dtype=torch.uint8, device=dev)
+            self.dys = torch.empty(nb, dtype=torch.uint8, device=dev)
+        self.posx = torch.empty((P, 64), dtype=torch.bfloat16, device=dev)
+        self.posd = torch.empty((P, 32), dtype=torch.bfloat16, device=dev)
+        self.rgb = torch.empty((B, 3), **f32)
+        self.d_raw = torch.empty((B, N_, 4), **f32)
+        self.scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8,
+                                   device=dev)
 
     # ---- the two launch sequences --------------------------------------------------
     def _forward_backward(self, bucket=0):
@@ -638,7 +753,8 @@ class GraphedTrainStep:
         _lib.check(lib.nerf_amd_adam_step_hyper(_lib.ptr(opt.flat), _lib.ptr(self.grads), _lib.ptr(opt.exp_avg),
                                                 _lib.ptr(opt.exp_avg_sq), opt.flat.numel(), _lib.ptr(self.hyper),
                                                 _lib.stream_ptr(self.dev)), "nerf_amd_adam_step_hyper")
-        self.net.repack_from_flat(opt.flat)
+        for net, flat, _ in self._images:                  # every trained module from its slice of the flat vector
+            net.repack_from_flat(flat)
 
     def _set_hyper(self, step):
         pg = self.opt.param_groups[0]
@@ -650,8 +766,7 @@ class GraphedTrainStep:
         with torch.cuda.device(self.dev):
             # both images must exist (and be cached) before capture: packing allocates.  Their addresses are baked into
             # the graphs, so this object owns them from here on (_own_images): the module's cache must never replace them
-            self._packed_fwd = self.net.packed_weights(_lib.BF16)
-            self._packed_bwd = self.net.packed_weights(_lib.BF16_BWD)
+            self._bind_images()
             self._set_hyper(1)
             params0 = self.opt.flat.clone()
             side = torch.cuda.Stream(self.dev)
@@ -693,24 +808,33 @@ class GraphedTrainStep:
         versions tell), the module's cache would pack NEW buffers on its next query and free these -- while every replay
         still reads and rewrites them.  So: re-pack from the flat vector (the parameters are views of it) into the
         captured buffers, as new weights (status words cleared), and put exactly these buffers back into the cache."""
+        for net, flat, bufs in self._images:
+            self._own_images_of(net, flat, bufs, force)
+
+    def _bind_images(self):
+        """(module, its slice of the optimizer's flat vector, (forward image, backward image)) per trained module."""
+        self._packed_fwd = self.net.packed_weights(_lib.BF16)
+        self._packed_bwd = self.net.packed_weights(_lib.BF16_BWD)
+        self._images = [(self.net, self.opt.flat, (self._packed_fwd, self._packed_bwd))]
+
+    def _own_images_of(self, net, flat, bufs, force):
         from .utils.nets import _Packed
-        net, dev = self.net, self.dev
+        dev = self.dev
         params = net._param_list()
         stamp = tuple((p.data_ptr(), p._version) for p in params)
         ents = [net._packed.get((dev, c)) for c in (_lib.BF16, _lib.BF16_BWD)]
-        bufs = (self._packed_fwd, self._packed_bwd)
         if not force and all(e is not None and e.stamp == stamp and e.buf is b for e, b in zip(ents, bufs)):
             return
         off = 0
         for p in params:                                   # FusedAdam made them views of its flat vector; still true?
-            if p.data_ptr() != self.opt.flat.data_ptr() + 4 * off:
+            if p.data_ptr() != flat.data_ptr() + 4 * off:
                 raise RuntimeError("a parameter no longer lives in the optimizer's flat vector (its .data was replaced): "
-                                   "build a new FusedAdam and GraphedTrainStep")
+                                   f"build a new FusedAdam and {type(self).__name__}")
             off += p.numel()
         lib = _lib.lib()
         with torch.cuda.device(dev):
             for code, buf in zip((_lib.BF16, _lib.BF16_BWD), bufs):
-                _lib.check(lib.nerf_amd_pack_weights(_lib.ptr(self.opt.flat), _lib.ptr(buf), code, _lib.stream_ptr(dev)),
+                _lib.check(lib.nerf_amd_pack_weights(_lib.ptr(flat), _lib.ptr(buf), code, _lib.stream_ptr(dev)),
                            "nerf_amd_pack_weights")
                 net._packed[(dev, code)] = _Packed(stamp, buf)
         net.drop_packed(dev, keep=(_lib.BF16, _lib.BF16_BWD))
@@ -788,16 +912,11 @@ class GraphedTrainStep:
             self._primed_for = self.opt.step_count + 1          # graph A left the next step's batch in the buffers
         if watch:
             # behind the forward, in front of graph B's re-pack (which clears the flag for the next step)
-            self._watch.push(self._packed_fwd, self.opt.step_count)
+            for _, _, bufs in self._images:
+                self._watch.push(bufs[0], self.opt.step_count)
             # the reference's |x| > 1 warning (utils/xyz.py:8-9) on the batch in the buffers (with the selection inside the
             # graph that is already the next step's), verdict raised lazily
-            from .utils.xyz import range_check_rays
-            if self.device_rng:
-                import ctypes
-                range_check_rays(self.rays, ctypes.c_void_p(self.hyper.data_ptr() + 24), self.tbins,
-                                 _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0, self.N)
-            else:
-                range_check_rays(self.rays, self.u, self.tbins, 0, 0, 0, self.N)
+            self._range_check()
         if self.bucketed:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.timing else None
             if ev:
@@ -825,13 +944,24 @@ class GraphedTrainStep:
             self.graph_b.replay()
         # graph B re-packed the two training images; any other image of the module (fp16 / fp32 inference) is now
         # stale -- and the kernels wrote through the flat buffer, so the parameters' versions did not move
-        self.net.drop_packed(self.dev, keep=(_lib.BF16, _lib.BF16_BWD))
+        for net, _, _ in self._images:
+            net.drop_packed(self.dev, keep=(_lib.BF16, _lib.BF16_BWD))
         if decay != 1.0:
             for pg in self.opt.param_groups:
                 pg["lr"] = pg["lr"] * decay
         return self.loss
 
     __call__ = step
+
+    def _range_check(self):
+        """The reference's |x| > 1 warning on the stratified pass's first / last samples (the finer passes lie between)."""
+        from .utils.xyz import range_check_rays
+        if self.device_rng:
+            import ctypes
+            range_check_rays(self.rays, ctypes.c_void_p(self.hyper.data_ptr() + 24), self.tbins,
+                             _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0, self._first_N)
+        else:
+            range_check_rays(self.rays, self._first_u, self.tbins, 0, 0, 0, self._first_N)
 
     def reset_timing(self):
         """Forget the exchange events recorded so far (warm-up steps: the first collective creates the communicator)."""
@@ -848,3 +978,147 @@ class GraphedTrainStep:
         exposed = sum(e[1].elapsed_time(e[2]) for e in self._events) / len(self._events)
         self._events = []
         return span, exposed
+
+
+class GraphedHierarchicalTrainStep(GraphedTrainStep):
+    """``train_step_hierarchical`` for the fused bf16 path as captured hipGraphs, on GraphedTrainStep's machinery (hyper
+    ring, status watch, ``rays_from`` selection in both jitter modes, exchange, capture):
+
+        graph A: hyper fetch -> coarse training forward (Nc stratified samples) -> coarse head (compositor + MSE gradient
+                 + compositor backward + sample_pdf on the coarse weights, ONE kernel:
+                 nerf_amd_volume_render_mse_backward_pdf, writes ts_f) -> fine training forward on ts_f (Nc+Nf samples,
+                 NERF_AMD_TS_GIVEN) -> fine compositor + MSE gradient + backward -> both dX chains -> both sets of dW
+                 products into ONE combined gradient vector (coarse first, the optimizer's order); the encoder rows, the two
+                 loss values, the zero fill and both d_raw packs on the single side branch
+        graph B: one Adam launch over both networks' flat vector -> re-pack of both networks' training images
+
+    ``optimizer`` must be ``optim.FusedAdam([net_c, net_f])``.  Jitter as in GraphedTrainStep: default the reference-style
+    CPU draws torch.rand(B,Nc) then torch.rand(B,Nf) (one draw of B*(Nc+Nf) from the same stream, continued on the
+    device); ``device_rng=True`` keys both draws by seed + step (the eager step's values with ``seed=seed + k`` at step k).
+    ``step(rays=None, gt=None, u_c=None, u_f=None, decay=1.0)`` returns the total loss as a 0-d device tensor (no sync);
+    ``losses`` holds [coarse, fine]; ``net_c`` / ``net_f`` are the two modules, ``net`` = ``nets`` the pair (as
+    ``FusedAdam([net_c, net_f]).net``).  bf16 storage, one exchange bucket."""
+
+    def __init__(self, net_c, net_f, optimizer, n_rays, Nc=64, Nf=128, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train"):
+        _check_pair(net_c, net_f, Nc, Nf, None)
+        self.net_c, self.net_f, self.Nc, self.Nf = net_c, net_f, int(Nc), int(Nf)
+        # ``net`` / ``nets`` are the pair, as FusedAdam([net_c, net_f]).net / .nets hold it
+        self.nets = (net_c, net_f)
+        super().__init__(self.nets, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng,
+                         seed=seed, ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+
+    def _check_modules(self, net, optimizer):
+        from .optim import FusedAdam
+        if not isinstance(optimizer, FusedAdam):
+            raise RuntimeError("GraphedHierarchicalTrainStep needs optim.FusedAdam([net_c, net_f])")
+        if optimizer.nets is None or len(optimizer.nets) != 2 or optimizer.nets[0] is not net[0] or optimizer.nets[1] is not net[1]:
+            raise RuntimeError("the optimizer is not FusedAdam([net_c, net_f]) of this pair")
+        _check_fused_trainable(net[0].precision)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        from .utils.rendering import _tbins
+        lib, dev = _lib.lib(), self.dev
+        B, Nc, M = self.B, self.Nc, self.Nc + self.Nf
+        f32 = dict(dtype=torch.float32, device=dev)
+        # self.u [B, Nc+Nf] is ONE draw of the reference stream: its first B*Nc values are torch.rand(B,Nc), the rest
+        # torch.rand(B,Nf) -- the same numbers as the two draws in a row
+        flat_u = self.u.view(-1)
+        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, self.Nf)
+        self.tbins = _tbins(tn, tf, Nc, dev)
+        self._first_N, self._first_u = Nc, self.u_c
+        self.losses = torch.zeros(2, **f32)
+        self.passes = []
+        for N_ in (Nc, M):
+            P = B * N_
+            nb = int(lib.nerf_amd_train_activation_bytes(P))
+            self.passes.append(dict(
+                N=N_, P=P, raw=torch.empty((B, N_, 4), **f32), ts=torch.empty((B, N_), **f32),
+                acts=torch.empty(nb, dtype=torch.uint8, device=dev), dys=torch.empty(nb, dtype=torch.uint8, device=dev),
+                posx=torch.empty((P, 64), dtype=torch.bfloat16, device=dev), posd=torch.empty((P, 32), dtype=torch.bfloat16, device=dev),
+                rgb=torch.empty((B, 3), **f32), d_raw=torch.empty((B, N_, 4), **f32),
+                scratch=torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8, device=dev)))
+        self.ts_f = torch.empty((B, M), **f32)          # the coarse head's output: the fine pass's positions
+
+    def _bind_images(self):
+        n = self.opt.slices
+        self._images = [(m, sl, (m.packed_weights(_lib.BF16), m.packed_weights(_lib.BF16_BWD)))
+                        for m, sl in zip((self.net_c, self.net_f), n)]
+        self._packed_fwd, self._packed_bwd = self._images[0][2]
+
+    def _forward_backward(self, bucket=0):
+        lib, B, Nc, Nf = _lib.lib(), self.B, self.Nc, self.Nf
+        ck, ptr = _lib.check, _lib.ptr
+        c, f = self.passes
+        (_, _, (fwd_c, bwd_c)), (_, _, (fwd_f, bwd_f)) = self._images
+        main = torch.cuda.current_stream(self.dev)
+        side = self._side
+        st, ss = ctypes_stream(main), ctypes_stream(side)
+        self._ring.fetch(self.hyper, self.dev)
+        if self.device_rng:
+            import ctypes
+            jit_c = jit_f = ctypes.c_void_p(self.hyper.data_ptr() + 24)
+            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
+        else:
+            jit_c, jit_f, flags, seed, rid = ptr(self.u_c), ptr(self.u_f), 0, 0, 0
+        ck(lib.nerf_amd_mlp_forward_train(ptr(self.rays), jit_c, ptr(self.tbins), ptr(fwd_c), flags, seed, rid,
+                                          ptr(c["raw"]), ptr(c["ts"]), ptr(c["acts"]), B, Nc, st), "nerf_amd_mlp_forward_train")
+        self._coarse_head(c, jit_f, flags, seed, rid, st)
+        ck(lib.nerf_amd_mlp_forward_train(ptr(self.rays), ptr(self.ts_f), None, ptr(fwd_f), _lib.FLAG_TS_GIVEN, 0, 0,
+                                          ptr(f["raw"]), ptr(f["ts"]), ptr(f["acts"]), B, Nc + Nf, st), "nerf_amd_mlp_forward_train")
+        ck(lib.nerf_amd_volume_render_mse_backward(ptr(f["raw"]), ptr(f["ts"]), ptr(self.rays), ptr(self.gt), ptr(f["rgb"]),
+                                                   ptr(f["d_raw"]), B, Nc + Nf, st), "nerf_amd_volume_render_mse_backward")
+        fork = torch.cuda.Event()
+        fork.record(main)                           # both heads done: rgb / d_raw of both passes and ts_f are final
+        for p, image in ((c, bwd_c), (f, bwd_f)):
+            ck(lib.nerf_amd_mlp_backward(ptr(p["d_raw"]), ptr(image), ptr(p["acts"]), ptr(p["dys"]), p["P"], st),
+               "nerf_amd_mlp_backward")
+        side.wait_event(fork)
+        n = self.opt.slices[0].numel()
+        grads = (self.grads[:n], self.grads[n:])
+        ck(lib.nerf_amd_sample_encode_bf16(ptr(self.rays), jit_c, ptr(self.tbins), flags, seed, rid,
+                                           ptr(c["posx"]), ptr(c["posd"]), None, B, Nc, ss), "nerf_amd_sample_encode_bf16")
+        ck(lib.nerf_amd_sample_encode_bf16(ptr(self.rays), ptr(self.ts_f), None, _lib.FLAG_TS_GIVEN, 0, 0,
+                                           ptr(f["posx"]), ptr(f["posd"]), None, B, Nc + Nf, ss), "nerf_amd_sample_encode_bf16")
+        for k, (p, g) in enumerate(zip((c, f), grads)):
+            ck(lib.nerf_amd_mse_loss(ptr(p["rgb"]), ptr(self.gt), ptr(self.losses[k]), None, B * 3, ss), "nerf_amd_mse_loss")
+            ck(lib.nerf_amd_param_gradients_begin(ptr(p["d_raw"]), ptr(p["scratch"]), ptr(g), p["P"], ss),
+               "nerf_amd_param_gradients_begin")
+        with torch.cuda.stream(side):
+            torch.add(self.losses[0], self.losses[1], out=self.loss)       # the total, MSE(rgb_c) + MSE(rgb_f)
+        if self.rays_from is not None and self.device_rng:
+            import ctypes        # the next step's batch, beside the dX chains (GraphedTrainStep._forward_backward)
+            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
+                                  self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
+        main.wait_stream(side)
+        for p, g in zip((c, f), grads):
+            ck(lib.nerf_amd_param_gradients_finish_bucket(ptr(p["acts"]), ptr(p["dys"]), ptr(p["posx"]), ptr(p["posd"]),
+                                                          ptr(p["scratch"]), ptr(g), p["P"], 0, st),
+               "nerf_amd_param_gradients_finish_bucket")
+
+    def _coarse_head(self, c, jit_f, flags, seed, rid, st):
+        """rgb_c, d_raw_c and the fine positions ts_f from the coarse weights, which never reach HBM: one launch."""
+        _lib.check(_lib.lib().nerf_amd_volume_render_mse_backward_pdf(
+            _lib.ptr(c["raw"]), _lib.ptr(c["ts"]), _lib.ptr(self.rays), _lib.ptr(self.gt), jit_f, flags, seed, rid,
+            _lib.ptr(c["rgb"]), _lib.ptr(c["d_raw"]), _lib.ptr(self.ts_f), self.B, self.Nc, self.Nf, st),
+            "nerf_amd_volume_render_mse_backward_pdf")
+
+    def _head_gradients(self):
+        pass                                         # one exchange bucket: graph A forms every product
+
+    def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
+        if (u_c is None) != (u_f is None):
+            raise RuntimeError("step(): u_c and u_f come together (or neither)")
+        u = None
+        if u_c is not None:
+            if tuple(u_c.shape) != tuple(self.u_c.shape) or tuple(u_f.shape) != tuple(self.u_f.shape):
+                raise RuntimeError(f"u_c / u_f must be {tuple(self.u_c.shape)} / {tuple(self.u_f.shape)}")
+            if self.device_rng:
+                raise RuntimeError("this GraphedHierarchicalTrainStep draws its jitter on the device (device_rng=True): "
+                                   "u_c / u_f must be None")
+            self.u_c.copy_(u_c, non_blocking=True)
+            self.u_f.copy_(u_f, non_blocking=True)
+            u = self.u
+        return super().step(rays, gt, u=u, decay=decay)
+
+    __call__ = step
