@@ -477,6 +477,30 @@ int nerf_amd_linear_f32(const float* A, int64_t sa_i, int64_t sa_k, const float*
                         const float* B, int64_t sb_k, int64_t sb_j, const float* bias,
                         float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, uint32_t flags, void* stream);
 
+/* ---- gradients with respect to the inputs: query points and rays (pose refinement) ------------------------------ */
+/* The reference's render_nerf (utils/rendering.py:13-45), Nerf.forward (utils/nets.py:34-43) and positional_encoder /
+ * gamma (utils/xyz.py:6-36) are differentiable in their inputs; these entries give the same gradients.
+ *
+ * nerf_amd_input_gradients: after nerf_amd_mlp_backward, its dys (bf16, P points) and the flat fp32 parameters (state_dict
+ * order; the three weight slices that touch the encoder are rounded to bf16 as the packers round them) ->
+ *   points mode (pts [P,6] given, rays == ts == d_rays == NULL): dv [P,6] = d loss / d pts     (utils/nets.py:34-43);
+ *   rays mode   (pts == NULL; rays [B,6], ts [B,N] = the sample positions of the forward, P = B*N):
+ *               dv [P,6] = d loss / d query points (written, also a workspace), d_rays [B,6] = d loss / d rays
+ *               (utils/rendering.py:24-40: x = o + t d, d_hat = d / |d|; t carries no gradient).
+ * bf16 MFMA products into the encoder features, fp32 encoder Jacobian on the point recomputed in fp32, rays reduced in
+ * sample order; no atomics: bit-identical results run to run. */
+int nerf_amd_input_gradients(const void* dys, const float* params, const float* pts, const float* rays, const float* ts,
+                             float* dv, float* d_rays, int64_t P, int N, void* stream);
+/* d_q [B*N,6] (gradient w.r.t. nerf_amd_query_points' output) -> d_rays [B,6] (utils/rendering.py:24-40), with the
+ * ray reduction of nerf_amd_input_gradients.  ts [B,N]: the sample positions the query points were formed with. */
+int nerf_amd_query_points_backward(const float* rays, const float* ts, const float* d_q, float* d_rays, int64_t B, int N,
+                                   void* stream);
+/* backward of nerf_amd_gamma (utils/xyz.py:6-14): d_out [n, 2L] (contiguous) -> d_x [n] */
+int nerf_amd_gamma_backward(const float* x, int64_t x_stride, const float* d_out, float* d_x, int64_t n, int L, void* stream);
+/* backward of nerf_amd_positional_encoder (utils/xyz.py:16-36): d_posx [P,3+6Lp], d_posd [P,3+6Ld] -> d_vec [P,6] */
+int nerf_amd_positional_encoder_backward(const float* vec, const float* d_posx, const float* d_posd, float* d_vec,
+                                         int64_t P, int Lp, int Ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,10 @@ _SIGNATURES = {
                                               _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_mlp_forward_rays": (_i32, [_vp, _vp, _vp, _vp, _i32, _u32, _u64, _i64,
                                          _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_input_gradients": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_query_points_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_gamma_backward": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_positional_encoder_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -58,6 +58,11 @@ int nerf_amd_launch_adam(float*, const float*, float*, float*, long long, float,
 int nerf_amd_launch_sample_encode_bf16(const MlpArgs*, void*, void*, hipStream_t);
 int nerf_amd_launch_param_gradients(const float*, const void*, const void*, const void*, const void*, void*, float*,
                                     long long, hipStream_t);
+int nerf_amd_launch_input_gradients(const void*, const float*, const float*, const float*, const float*, float*, float*,
+                                    long long, int, hipStream_t);
+int nerf_amd_launch_query_points_backward(const float*, const float*, const float*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_gamma_backward(const float*, long long, const float*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_posenc_backward(const float*, const float*, const float*, float*, long long, int, int, hipStream_t);
 }
 
 namespace {
@@ -196,6 +201,40 @@ int nerf_amd_positional_encoder(const float* vec, float* posx, float* posd, int6
     if (P == 0) return 0;
     if (!vec || !posx || !posd) return NERF_AMD_EINVAL;
     return nerf_amd_launch_posenc(vec, posx, posd, P, Lp, Ld, S(stream));
+}
+
+int nerf_amd_gamma_backward(const float* x, int64_t x_stride, const float* d_out, float* d_x, int64_t n, int L, void* stream) {
+    if (n < 0 || L < 0 || x_stride < 0) return NERF_AMD_EINVAL;
+    if (n == 0) return 0;
+    if (!x || !d_out || !d_x) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_gamma_backward(x, x_stride, d_out, d_x, n, L, S(stream));
+}
+
+int nerf_amd_positional_encoder_backward(const float* vec, const float* d_posx, const float* d_posd, float* d_vec,
+                                         int64_t P, int Lp, int Ld, void* stream) {
+    if (P < 0 || Lp < 0 || Ld < 0) return NERF_AMD_EINVAL;
+    if (P == 0) return 0;
+    if (!vec || !d_posx || !d_posd || !d_vec) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_posenc_backward(vec, d_posx, d_posd, d_vec, P, Lp, Ld, S(stream));
+}
+
+int nerf_amd_query_points_backward(const float* rays, const float* ts, const float* d_q, float* d_rays, int64_t B, int N,
+                                   void* stream) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (!rays || !ts || !d_q || !d_rays) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_query_points_backward(rays, ts, d_q, d_rays, B, N, S(stream));
+}
+
+int nerf_amd_input_gradients(const void* dys, const float* params, const float* pts, const float* rays, const float* ts,
+                             float* dv, float* d_rays, int64_t P, int N, void* stream) {
+    if (P < 0) return NERF_AMD_EINVAL;
+    const bool rays_mode = pts == nullptr;
+    if (rays_mode && (N <= 0 || P % N != 0)) return NERF_AMD_EINVAL;
+    if (P == 0) return 0;
+    if (!dys || !params || !dv) return NERF_AMD_EINVAL;
+    if (rays_mode ? (!rays || !ts || !d_rays) : (rays || ts || d_rays)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_input_gradients(dys, params, pts, rays, ts, dv, d_rays, P, rays_mode ? N : 1, S(stream));
 }
 
 int nerf_amd_query_points(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,

@@ -165,7 +165,12 @@ class _FusedDense(torch.autograd.Function):
     """(rays, jitter) -> raw [B,N,4], ts [B,N]  -- or, with ``rays`` None, points v [P,6] -> raw [P,1,4] --
     through nerf_amd_mlp_forward_train[_points]; backward: nerf_amd_mlp_backward for every layer's
     pre-activation gradient, then nerf_amd_param_gradients (split-K GEMMs + column sums) into ONE flat
-    fp32 vector in state_dict order, handed back to autograd as 24 views."""
+    fp32 vector in state_dict order, handed back to autograd as 24 views.
+
+    Gradients to the inputs (``rays`` or ``pts`` requiring grad: pose refinement, iNeRF) come from
+    nerf_amd_input_gradients on the same dY.  Only what autograd asks for is computed: with no parameter
+    needing a gradient the encoder rows and the dW products are skipped, with no input needing one
+    nothing beyond the parameter path is launched."""
 
     @staticmethod
     def forward(ctx, net, rays, jit, tbins, flags, seed, ray_id0, N, pts, *params):
@@ -185,11 +190,14 @@ class _FusedDense(torch.autograd.Function):
             raise FloatingPointError(f"non-finite values inside the network in training forward {bad[0]} ({what}): "
                                      "NaN / inf weights or inputs, the run has diverged")
         packed = net.packed_weights(_lib.BF16)
+        need_w = any(ctx.needs_input_grad[9:])
+        need_in = ctx.needs_input_grad[1] or ctx.needs_input_grad[8]
         raw = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
         ts = torch.empty((B, N), dtype=torch.float32, device=dev)
         acts = torch.empty(int(lib.nerf_amd_train_activation_bytes(P)), dtype=torch.uint8, device=dev)
-        posx = torch.empty((P, 64), dtype=torch.bfloat16, device=dev)
-        posd = torch.empty((P, 32), dtype=torch.bfloat16, device=dev)
+        # the bf16 encoder rows are operands of the dW products only
+        posx = torch.empty((P, 64) if need_w else (0,), dtype=torch.bfloat16, device=dev)
+        posd = torch.empty((P, 32) if need_w else (0,), dtype=torch.bfloat16, device=dev)
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
             if rays is not None:
@@ -198,65 +206,88 @@ class _FusedDense(torch.autograd.Function):
                     _lib.ptr(raw), _lib.ptr(ts), _lib.ptr(acts), B, N, st), "nerf_amd_mlp_forward_train")
                 # encoder outputs in the reference's column order: the inputs of the dW products of
                 # layers_0.0 / skip_conn_layer / color_fc.0 (same sample positions: ts given)
-                _lib.check(lib.nerf_amd_sample_encode_bf16(
-                    _lib.ptr(rays), _lib.ptr(ts), None, _lib.FLAG_TS_GIVEN, 0, 0,
-                    _lib.ptr(posx), _lib.ptr(posd), None, B, N, st), "nerf_amd_sample_encode_bf16")
+                if need_w:
+                    _lib.check(lib.nerf_amd_sample_encode_bf16(
+                        _lib.ptr(rays), _lib.ptr(ts), None, _lib.FLAG_TS_GIVEN, 0, 0,
+                        _lib.ptr(posx), _lib.ptr(posd), None, B, N, st), "nerf_amd_sample_encode_bf16")
             else:
                 _lib.check(lib.nerf_amd_mlp_forward_train_points(
                     _lib.ptr(pts), _lib.ptr(packed), _lib.ptr(raw), _lib.ptr(acts), P, st),
                     "nerf_amd_mlp_forward_train_points")
-                _lib.check(lib.nerf_amd_encode_points_bf16(_lib.ptr(pts), _lib.ptr(posx), _lib.ptr(posd), P, st),
-                           "nerf_amd_encode_points_bf16")
+                if need_w:
+                    _lib.check(lib.nerf_amd_encode_points_bf16(_lib.ptr(pts), _lib.ptr(posx), _lib.ptr(posd), P, st),
+                               "nerf_amd_encode_points_bf16")
         net.__dict__["_watch_calls"] += 1
         watch.push(packed, net.__dict__["_watch_calls"])
-        ctx.net, ctx.P = net, P
+        ctx.net, ctx.P, ctx.N = net, P, N
         ctx.shapes = [tuple(p.shape) for p in params]
-        ctx.save_for_backward(acts, posx, posd)
+        ctx.need_w, ctx.need_in = need_w, need_in
+        # the input gradient reads the forward's weights (fp32, state_dict order) and its inputs: the points, or the
+        # rays and the sample positions the forward drew
+        wflat = torch.cat([p.detach().reshape(-1).float() for p in params]) if need_in else None
+        ctx.save_for_backward(acts, posx, posd, wflat, src if need_in else None, ts if need_in else None)
+        ctx.rays_mode = rays is not None
         ctx.mark_non_differentiable(ts)
         return raw, ts
 
     @staticmethod
     def backward(ctx, g_raw, _g_ts):
         lib = _lib.lib()
-        acts, posx, posd = ctx.saved_tensors
+        acts, posx, posd, wflat, src, ts = ctx.saved_tensors
         net, P = ctx.net, ctx.P
         dev = acts.device
         g = g_raw.reshape(P, 4).contiguous().float()
         image = net.packed_weights(_lib.BF16_BWD)
         dys = torch.empty_like(acts)
-        flat = torch.empty(int(lib.nerf_amd_param_count()), dtype=torch.float32, device=dev)
-        scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8, device=dev)
+        d_in = None
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
             _lib.check(lib.nerf_amd_mlp_backward(_lib.ptr(g), _lib.ptr(image), _lib.ptr(acts), _lib.ptr(dys), P, st),
                        "nerf_amd_mlp_backward")
-            _lib.check(lib.nerf_amd_param_gradients(_lib.ptr(g), _lib.ptr(acts), _lib.ptr(dys), _lib.ptr(posx),
-                                                    _lib.ptr(posd), _lib.ptr(scratch), _lib.ptr(flat), P, st),
-                       "nerf_amd_param_gradients")
+            if ctx.need_in:
+                dv = torch.empty((P, 6), dtype=torch.float32, device=dev)
+                if ctx.rays_mode:
+                    d_in = torch.empty((P // ctx.N, 6), dtype=torch.float32, device=dev)
+                    _lib.check(lib.nerf_amd_input_gradients(_lib.ptr(dys), _lib.ptr(wflat), None, _lib.ptr(src), _lib.ptr(ts),
+                                                            _lib.ptr(dv), _lib.ptr(d_in), P, ctx.N, st),
+                               "nerf_amd_input_gradients")
+                else:
+                    d_in = dv
+                    _lib.check(lib.nerf_amd_input_gradients(_lib.ptr(dys), _lib.ptr(wflat), _lib.ptr(src), None, None,
+                                                            _lib.ptr(dv), None, P, 1, st), "nerf_amd_input_gradients")
+            if ctx.need_w:
+                flat = torch.empty(int(lib.nerf_amd_param_count()), dtype=torch.float32, device=dev)
+                scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8,
+                                      device=dev)
+                _lib.check(lib.nerf_amd_param_gradients(_lib.ptr(g), _lib.ptr(acts), _lib.ptr(dys), _lib.ptr(posx),
+                                                        _lib.ptr(posd), _lib.ptr(scratch), _lib.ptr(flat), P, st),
+                           "nerf_amd_param_gradients")
         grads, off = [], 0
         for shp in ctx.shapes:
             n = 1
             for s_ in shp:
                 n *= s_
-            grads.append(flat[off:off + n].view(shp))
+            grads.append(flat[off:off + n].view(shp) if ctx.need_w else None)
             off += n
-        return (None,) * 9 + tuple(grads)
+        d_rays = d_in if ctx.rays_mode else None
+        d_pts = None if ctx.rays_mode else d_in
+        return (None, d_rays) + (None,) * 6 + (d_pts,) + tuple(grads)
 
 
 def nerf_forward_autograd(net, v, precision):
-    """Nerf.forward (reference utils/nets.py:34-43) with gradients to the parameters: the fused
+    """Nerf.forward (reference utils/nets.py:34-43) with gradients to the parameters and / or to v: the fused
     training forward on points, v [P,6] -> [P,4] (precision 'fp32': the exact layer-by-layer path)."""
     if _lib.precision_code(precision) == _lib.F32:
         from .utils import generic_mlp
         return generic_mlp.forward(net, v)
     params = [p for _, p in net.named_parameters()]
-    raw, _ = _FusedDense.apply(net, None, None, None, 0, 0, 0, 1, v.detach().contiguous(), *params)
+    raw, _ = _FusedDense.apply(net, None, None, None, 0, 0, 0, 1, v.contiguous(), *params)
     return raw.reshape(-1, 4)
 
 
 def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0):
     """render_nerf (reference utils/rendering.py:13-45) with gradients to the
-    parameters of ``net``; returns the same 5-tuple."""
+    parameters of ``net`` and, when ``rays`` requires grad, to the rays; returns the same 5-tuple."""
     from .utils.rendering import _tbins
     if _lib.precision_code(precision) == _lib.F32:
         # exact fp32: the reference's own composition (sampling -> net.forward -> volume_render), each stage a HIP kernel
@@ -272,7 +303,8 @@ def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_
     dev = rays.device
     params = [p for _, p in net.named_parameters()]
     raw, ts = _FusedDense.apply(net, rays, jit, _tbins(tn, tf, N, dev), flags, seed, ray_id0, N, None, *params)
-    return _VolumeRender.apply(raw, ts, rays, True)
+    # the compositor's |d_hat| factor carries no gradient (|d_hat| == 1): the rays enter it detached
+    return _VolumeRender.apply(raw, ts, rays.detach(), True)
 
 
 # --------------------------------------------------------------------------

@@ -12,7 +12,10 @@ unusual shapes, not the fast one.
         rgb = color_fc(cat(f, d))             Linear + ReLU + Linear
         out = cat(rgb, sigma)                 both heads write their columns of out[P, 4]
     backward: autograd of exactly that, hand-written: dX = (dY * relu') W, dW = (dY * relu')^T X, db = (dY * relu')^T 1,
-    the ReLU derivative taken from the saved activation inside the GEMM's operand load.
+    the ReLU derivative taken from the saved activation inside the GEMM's operand load.  With v requiring grad the
+    chain continues into the encoder features (d posx from layers_0.0 and the x part of the skip layer, d posd from
+    the d part of color_fc.0) and through the encoder's Jacobian (nerf_amd_positional_encoder_backward) to d v;
+    what no caller asks for (dW with frozen parameters, d posx / d posd without an input gradient) is not computed.
 """
 import torch
 
@@ -56,7 +59,7 @@ class _GenericMlp(torch.autograd.Function):
         P, H = v.shape[0], w[0].shape[0]
         new = lambda n: torch.empty((P, n), dtype=torch.float32, device=v.device)    # noqa: E731
         posx, posd = positional_encoder(v.detach(), Lp, Ld)
-        keep = any(ctx.needs_input_grad[3:])
+        keep = any(ctx.needs_input_grad[3:]) or ctx.needs_input_grad[0]
         acts = []                                  # post-ReLU outputs of layers 0..7 (what the backward needs)
         h = posx
         for L in range(5):
@@ -88,17 +91,17 @@ class _GenericMlp(torch.autograd.Function):
         _linear(posd, w[10], None, c1, relu=True, w_col0=H, accumulate=True)
         _linear(c1, w[11], b[11], out, relu=False)                                   # rgb -> out[:, 0:3]
         if keep:
-            ctx.save_for_backward(posx, posd, f, c1, *acts, *w)
+            ctx.save_for_backward(posx, posd, f, c1, *acts, *w, v if ctx.needs_input_grad[0] else None)
         ctx.shapes = (P, H)
+        ctx.L = (Lp, Ld)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        if ctx.needs_input_grad[0]:
-            raise RuntimeError("Nerf.forward: gradients with respect to the input points are not provided")
+        need_v, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[3:])
         saved = ctx.saved_tensors
         posx, posd, f, c1 = saved[:4]
-        acts, w = saved[4:12], saved[12:]
+        acts, w, v = saved[4:12], saved[12:24], saved[24]
         P, H = ctx.shapes
         dev = g_out.device
         g = _lib.require_cuda_f32(g_out, "grad").contiguous()
@@ -116,6 +119,8 @@ class _GenericMlp(torch.autograd.Function):
 
         def wgrad(L, dy, ld_dy, n_out, x, *, dy_off=0, mask=None, w_col0=0):
             """gw[L][:, w_col0 : w_col0 + x.shape[1]] += (dy * relu')^T x ;  gb[L] += (dy * relu')^T 1 (once per layer)."""
+            if not need_w:
+                return
             K_in = x.shape[1]
             _gemm(dy, 1, ld_dy, x, K_in, 1, gw[L], gw[L].shape[1], n_out, K_in, P, mask=mask, a_off=dy_off,
                   c_off=w_col0, flags=ACC)
@@ -134,6 +139,10 @@ class _GenericMlp(torch.autograd.Function):
         xgrad(g, 4, 3, w[11], d_c1)
         wgrad(10, d_c1, Hc, Hc, f, mask=c1)
         wgrad(10, d_c1, Hc, Hc, posd, mask=c1, w_col0=H)
+        if need_v:
+            d_posd = torch.empty_like(posd)           # the d part of cat(f, posd): color_fc.0's columns H ..
+            xgrad(d_c1, Hc, Hc, w[10], d_posd, mask=c1, w_col0=H)
+            d_posx = torch.empty_like(posx)
         d_f = new(H)
         xgrad(d_c1, Hc, Hc, w[10], d_f, mask=c1)
         # f = h7 @ W9^T + b9 (no ReLU) ; sigma = h7 @ W8^T + b8
@@ -152,6 +161,8 @@ class _GenericMlp(torch.autograd.Function):
             d_h = d_prev
         wgrad(5, d_h, H, H, acts[4], mask=acts[5])
         wgrad(5, d_h, H, H, posx, mask=acts[5], w_col0=H)
+        if need_v:                                     # the x part of cat(h5, posx): skip_conn_layer's columns H ..
+            xgrad(d_h, H, H, w[5], d_posx, mask=acts[5], w_col0=H)
         d_prev = new(H)
         xgrad(d_h, H, H, w[5], d_prev, mask=acts[5])
         d_h = d_prev
@@ -161,10 +172,19 @@ class _GenericMlp(torch.autograd.Function):
             xgrad(d_h, H, H, w[L], d_prev, mask=acts[L])
             d_h = d_prev
         wgrad(0, d_h, H, H, posx, mask=acts[0])
+        d_v = None
+        if need_v:
+            xgrad(d_h, H, H, w[0], d_posx, mask=acts[0], accumulate=True)                 # layers_0.0
+            d_v = torch.empty((P, 6), dtype=torch.float32, device=dev)
+            Lp, Ld = ctx.L
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().nerf_amd_positional_encoder_backward(
+                    _lib.ptr(v), _lib.ptr(d_posx), _lib.ptr(d_posd), _lib.ptr(d_v), P, Lp, Ld, _lib.stream_ptr(dev)),
+                    "nerf_amd_positional_encoder_backward")
         grads = []
         for L in range(12):
-            grads += [gw[L], gb[L]]
-        return (None, None, None, *grads)
+            grads += [gw[L], gb[L]] if need_w else [None, None]
+        return (d_v, None, None, *grads)
 
 
 INFERENCE_CHUNK = 1 << 20      # points per pass without gradients: bounds the activations in HBM (~ 6 x H x 4 B per point live)
@@ -177,7 +197,7 @@ def forward(net, v):
     for name in LAYER_NAMES:
         m = mods[name]
         params += [m.weight, m.bias]
-    needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    needs_grad = torch.is_grad_enabled() and (v.requires_grad or any(p.requires_grad for p in params))
     if needs_grad or v.shape[0] <= INFERENCE_CHUNK:
         return _GenericMlp.apply(v, net.Lp, net.Ld, *params)
     # inference on many points (an image's worth of samples): chunk by chunk, nothing kept between chunks

@@ -128,6 +128,8 @@ class Nerf(nn.Module):
                superset of the reference signature.  It selects the INFERENCE kernel;
                with gradients enabled 'bf16' and 'fp16' modules both run the bf16
                training kernels (training.py); 'fp32' trains exactly, layer by layer (utils/generic_mlp.py).
+               The same holds for gradients with respect to the INPUTS (v.requires_grad here, rays.requires_grad
+               in render_nerf: pose refinement), which autograd returns whether or not the parameters are frozen.
     """
 
     def __init__(self, Lp=10, Ld=4, H=256, *, precision=None):
@@ -273,7 +275,9 @@ class Nerf(nn.Module):
                 return generic_mlp.forward(self, v)
             with torch.no_grad():
                 return generic_mlp.forward(self, v)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        # autograd when anything asks for a gradient: the parameters, or the points themselves (v.requires_grad, also
+        # with frozen parameters -- the reference's forward is differentiable in v)
+        if torch.is_grad_enabled() and (v.requires_grad or any(p.requires_grad for p in self.parameters())):
             from ..training import nerf_forward_autograd
             return nerf_forward_autograd(self, v, self.precision if precision is None else precision)
         return self.forward_inference(v, precision=precision)

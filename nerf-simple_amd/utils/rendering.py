@@ -13,6 +13,13 @@ does (utils/rendering.py:28), so a seeded run consumes the RNG identically.
 ``u=`` / ``ts=`` inject explicit jitter / sample positions; ``device_rng=True``
 draws jitter from a counter RNG on the GPU instead (no PCIe copy, results
 independent of batching and sharding, not bit-comparable to the reference).
+
+Gradients: ``render_nerf`` is differentiable in its rays, as the reference is: with ``rays.requires_grad`` (and
+grad enabled) ``d loss / d rays`` comes back through autograd for a trainable or a frozen ``Nerf`` and for any
+foreign net whose forward is differentiable in its input (camera-pose refinement, pose estimation against a
+trained NeRF: INTEGRATION.md).  The sample positions carry no gradient (jitter, ``u=`` and ``ts=`` are constants),
+and a direct ``volume_render`` call gives none to ``ts`` / ``dirs``.  Precision under autograd is the training
+path's: 'fp16' / 'bf16' modules run the bf16 training kernels, 'fp32' modules exact fp32.
 """
 import torch
 from tqdm import tqdm
@@ -91,10 +98,13 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
         raise RuntimeError("rays must be [B, 6]")
     B, N = rays.size(0), int(N)
     dev = rays.device
+    # d loss / d rays (utils/rendering.py:31-40 is differentiable in the rays): autograd runs even for a frozen net
+    rays_grad = torch.is_grad_enabled() and rays.requires_grad
+    rays_in = rays.contiguous() if rays_grad else None
     rays = rays.detach().contiguous()
 
     fused = isinstance(net, Nerf) and net._fused_ok()
-    training = fused and torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())
+    training = fused and torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in net.parameters()))
     # everything that can raise cheaply is checked BEFORE the jitter is drawn, so a failed call
     # leaves torch's CPU generator untouched
     for name, t_ in (("ts", ts), ("u", u)):
@@ -128,14 +138,14 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     if training:
         from ..training import render_nerf_autograd
         try:
-            return render_nerf_autograd(rays, net, N, tn, tf, jit, flags,
+            return render_nerf_autograd(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags,
                                         net.precision if precision is None else precision,
                                         seed, ray_id0)
         finally:
             if pending_rng is not None:
                 pending_rng.finish()          # the forward is enqueued behind the generator kernel: only that is awaited
     if not fused:
-        return _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0)
+        return _render_generic(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0)
 
     def launch(code, packed):
         lib = _lib.lib()
@@ -167,15 +177,15 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0):
     """Any other net object: sampling and query-point assembly in one HIP kernel (nerf_amd_query_points =
     utils/rendering.py:24-40; the same jitter sources as the fused path, counter RNG included), the net's own
     forward exactly as the reference calls it (:41), compositing by the HIP kernel with the directions taken
-    from the rays (:37,43).  Gradients flow to whatever ``net.forward`` attaches to its output."""
+    from the rays (:37,43).  Gradients flow to whatever ``net.forward`` attaches to its output, and to the rays
+    when they require grad (nerf_amd_query_points_backward)."""
     B, dev = rays.size(0), rays.device
+    if torch.is_grad_enabled() and rays.requires_grad:
+        q, ts = _QueryPoints.apply(rays, jit, _tbins(tn, tf, N, dev), flags, seed, ray_id0, N)
+        rays = rays.detach()
+    else:
+        q, ts = _query_points(rays, jit, _tbins(tn, tf, N, dev), flags, seed, ray_id0, N)
     lib = _lib.lib()
-    q = torch.empty((B * N, 6), dtype=torch.float32, device=dev)
-    ts = torch.empty((B, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.nerf_amd_query_points(_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)), flags,
-                                             int(seed), int(ray_id0), _lib.ptr(q), _lib.ptr(ts), B, N,
-                                             _lib.stream_ptr(dev)), "nerf_amd_query_points")
     out = net.forward(q).reshape(B, N, 4).float()
     if torch.is_grad_enabled() and out.requires_grad:
         from ..training import _VolumeRender
@@ -191,6 +201,43 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0):
                                                    _lib.ptr(alpha), _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)),
                    "nerf_amd_volume_render_rays")
     return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+
+
+def _query_points(rays, jit, tbins, flags, seed, ray_id0, N):
+    """query points [B*N,6] and sample positions [B,N] of nerf_amd_query_points (utils/rendering.py:24-40)."""
+    B, dev = rays.size(0), rays.device
+    q = torch.empty((B * N, 6), dtype=torch.float32, device=dev)
+    ts = torch.empty((B, N), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nerf_amd_query_points(_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed),
+                                                    int(ray_id0), _lib.ptr(q), _lib.ptr(ts), B, N, _lib.stream_ptr(dev)),
+                   "nerf_amd_query_points")
+    return q, ts
+
+
+class _QueryPoints(torch.autograd.Function):
+    """rays [B,6] -> (query points [B*N,6], ts [B,N]) with the gradient to the rays: d_o = sum_n dx_n,
+    d_d = sum_n t_n dx_n + (g - d_hat (d_hat . g)) / |d| (nerf_amd_query_points_backward)."""
+
+    @staticmethod
+    def forward(ctx, rays, jit, tbins, flags, seed, ray_id0, N):
+        q, ts = _query_points(rays.detach(), jit, tbins, flags, seed, ray_id0, N)
+        ctx.save_for_backward(rays, ts)
+        ctx.N = N
+        ctx.mark_non_differentiable(ts)
+        return q, ts
+
+    @staticmethod
+    def backward(ctx, g_q, _g_ts):
+        rays, ts = ctx.saved_tensors
+        B, dev = rays.size(0), rays.device
+        d_rays = torch.empty((B, 6), dtype=torch.float32, device=dev)
+        g_q = g_q.contiguous().float()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_query_points_backward(_lib.ptr(rays), _lib.ptr(ts), _lib.ptr(g_q),
+                                                                 _lib.ptr(d_rays), B, ctx.N, _lib.stream_ptr(dev)),
+                       "nerf_amd_query_points_backward")
+        return d_rays, None, None, None, None, None, None
 
 
 def _render_batched(rays, net, batch_size, N, tn, tf, u, progress, id_base=0, **kw):

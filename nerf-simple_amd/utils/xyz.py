@@ -1,7 +1,8 @@
 """Drop-in for the reference's utils/xyz.py.
 
 ``gamma`` / ``positional_encoder`` (reference utils/xyz.py:6-36) run as HIP
-kernels on the tensor's device.  The camera helpers (utils/xyz.py:38-91) are
+kernels on the tensor's device, and are differentiable in their input as the
+reference's are (HIP backward kernels, csrc/input_grad.hip).  The camera helpers (utils/xyz.py:38-91) are
 host-side input generators, as in the reference.
 
 Differences from the reference, on purpose:
@@ -97,13 +98,20 @@ def flush_range_warning(device=None):
 
 def gamma(x, L=4):
     """x [P,C] -> [P, 2*L*C]: cat over levels i of [sin(2^i x), cos(2^i x)] along
-    dim 1 (reference utils/xyz.py:6-14; C = 1 at every reference call site)."""
+    dim 1 (reference utils/xyz.py:6-14; C = 1 at every reference call site).
+    Differentiable in x (nerf_amd_gamma_backward) when x requires grad."""
     assert torch.is_tensor(x), "input needs to be a torch tensor"
     _lib.require_cuda_f32(x, "x")
     if x.dim() != 2:
         raise RuntimeError("gamma expects a [P, C] tensor")
-    P, C = x.shape
     range_check_values(x, stacklevel=3)                 # utils/xyz.py:8-9, lazily
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _Gamma.apply(x, L)
+    return _gamma(x.detach(), L)
+
+
+def _gamma(x, L):
+    P, C = x.shape
     lib = _lib.lib()
     cols = []
     with torch.cuda.device(x.device):
@@ -119,15 +127,50 @@ def gamma(x, L=4):
     return torch.stack(cols, dim=2).reshape(P, 2 * L * C)
 
 
+class _Gamma(torch.autograd.Function):
+    """gamma with the HIP backward: d x_c = sum_i 2^i (cos(2^i x_c) g_sin[i,c] - sin(2^i x_c) g_cos[i,c])."""
+
+    @staticmethod
+    def forward(ctx, x, L):
+        ctx.save_for_backward(x)
+        ctx.L = L
+        return _gamma(x, L)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, = ctx.saved_tensors
+        L = ctx.L
+        P, C = x.shape
+        g = g.float().reshape(P, 2 * L, C)            # output column (2i + trig) * C + c
+        lib = _lib.lib()
+        cols = []
+        with torch.cuda.device(x.device):
+            st = _lib.stream_ptr(x.device)
+            for c in range(C):
+                xc, gc = x[:, c], g[:, :, c].contiguous()
+                dx = torch.empty((P,), dtype=torch.float32, device=x.device)
+                _lib.check(lib.nerf_amd_gamma_backward(_lib.ptr(xc), xc.stride(0) if P > 1 else 1, _lib.ptr(gc),
+                                                       _lib.ptr(dx), P, L, st), "nerf_amd_gamma_backward")
+                cols.append(dx)
+        return torch.stack(cols, dim=1), None
+
+
 def positional_encoder(vec, Lp=10, Ld=4):
     """vec [P,6] = x,y,z,d1,d2,d3 -> (posx [P,3+6Lp], posd [P,3+6Ld]), grouped
-    per coordinate (reference utils/xyz.py:16-36)."""
+    per coordinate (reference utils/xyz.py:16-36).  Differentiable in vec
+    (nerf_amd_positional_encoder_backward) when vec requires grad."""
     _lib.require_cuda_f32(vec, "vec")
     if vec.dim() != 2 or vec.shape[1] != 6:
         raise RuntimeError("positional_encoder expects a [P, 6] tensor")
     vec = vec.contiguous()
-    P = vec.shape[0]
     range_check_values(vec, stacklevel=3)               # gamma's check on all six columns (utils/xyz.py:8-9, :26-31), lazily
+    if torch.is_grad_enabled() and vec.requires_grad:
+        return _PositionalEncoder.apply(vec, Lp, Ld)
+    return _positional_encoder(vec.detach(), Lp, Ld)
+
+
+def _positional_encoder(vec, Lp, Ld):
+    P = vec.shape[0]
     posx = torch.empty((P, 3 + 6 * Lp), dtype=torch.float32, device=vec.device)
     posd = torch.empty((P, 3 + 6 * Ld), dtype=torch.float32, device=vec.device)
     with torch.cuda.device(vec.device):
@@ -135,6 +178,30 @@ def positional_encoder(vec, Lp=10, Ld=4):
             _lib.ptr(vec), _lib.ptr(posx), _lib.ptr(posd), P, Lp, Ld,
             _lib.stream_ptr(vec.device)), "nerf_amd_positional_encoder")
     return posx, posd
+
+
+class _PositionalEncoder(torch.autograd.Function):
+    """positional_encoder with the HIP backward (the Jacobian of gamma per coordinate, plus the raw columns)."""
+
+    @staticmethod
+    def forward(ctx, vec, Lp, Ld):
+        ctx.save_for_backward(vec)
+        ctx.L = (Lp, Ld)
+        return _positional_encoder(vec, Lp, Ld)
+
+    @staticmethod
+    def backward(ctx, g_posx, g_posd):
+        vec, = ctx.saved_tensors
+        Lp, Ld = ctx.L
+        P, dev = vec.shape[0], vec.device
+        g_posx = torch.zeros((P, 3 + 6 * Lp), device=dev) if g_posx is None else g_posx.float().contiguous()
+        g_posd = torch.zeros((P, 3 + 6 * Ld), device=dev) if g_posd is None else g_posd.float().contiguous()
+        d_vec = torch.empty((P, 6), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_positional_encoder_backward(
+                _lib.ptr(vec), _lib.ptr(g_posx), _lib.ptr(g_posd), _lib.ptr(d_vec), P, Lp, Ld, _lib.stream_ptr(dev)),
+                "nerf_amd_positional_encoder_backward")
+        return d_vec, None, None
 
 
 # --------------------------------------------------------------------------

@@ -1,0 +1,349 @@
+"""Gradients with respect to the inputs on the GPU: the encoder, Nerf.forward(v), render_nerf's rays and a camera pose
+recovered through them.  Yardsticks and tolerances: tests/input_grad_model.py (float64 oracle autograd; fp32 paths within
+FACTOR_32 of the fp32 oracle's own error, bf16 paths within FACTOR_16 of an emulation of the kernels' numerics)."""
+import pytest
+import torch
+
+import input_grad_model as M
+import nerf_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+
+
+def _sd(kind="structured"):
+    from nerf_simple_amd.utils import synthetic
+    return synthetic.synthetic_state_dict(0, kind)
+
+
+def _net(sd, precision, frozen):
+    from nerf_simple_amd.utils.nets import Nerf
+    net = Nerf(precision=precision).to(DEV)
+    net.load_state_dict(sd)
+    net.requires_grad_(not frozen)
+    return net
+
+
+def _rays(B, seed=0):
+    from nerf_simple_amd.utils import synthetic
+    from nerf_simple_amd.utils.xyz import camera_rays, spherical_to_pose
+    pose = torch.from_numpy(spherical_to_pose(4, -30, 10)).float()
+    rays = camera_rays([pose], [32, 32, synthetic.focal_from_fov(32)])
+    idx = torch.randperm(rays.shape[0], generator=torch.Generator().manual_seed(seed))[:B]
+    return rays[idx].contiguous()
+
+
+# ---- 1. encoder --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("P,C,L", [(1000, 1, 4), (257, 1, 10), (333, 3, 3)])
+def test_gamma_input_gradient(P, C, L):
+    from nerf_simple_amd.utils.xyz import gamma
+    g = torch.Generator().manual_seed(P)
+    x = torch.rand(P, C, generator=g) * 2 - 1
+    G = torch.randn(P, 2 * L * C, generator=g)
+    xg = x.to(DEV).requires_grad_(True)
+    out = gamma(xg, L)
+    assert out.grad_fn is not None
+    (out * G.to(DEV)).sum().backward()
+    want = {}
+    for dt in (torch.float64, torch.float32):
+        xt = x.to(dt).requires_grad_(True)
+        (O.gamma(xt, L) * G.to(dt)).sum().backward()
+        want[dt] = xt.grad
+    err = M.rel_err(xg.grad, want[torch.float64])
+    assert err <= M.bound_fp32(want[torch.float32], want[torch.float64]), err
+
+
+@pytest.mark.parametrize("P,Lp,Ld", [(1000, 10, 4), (77, 6, 2)])
+def test_positional_encoder_input_gradient(P, Lp, Ld):
+    from nerf_simple_amd.utils.xyz import positional_encoder
+    g = torch.Generator().manual_seed(P)
+    v = torch.rand(P, 6, generator=g) * 2 - 1
+    Gx, Gd = torch.randn(P, 3 + 6 * Lp, generator=g), torch.randn(P, 3 + 6 * Ld, generator=g)
+    vg = v.to(DEV).requires_grad_(True)
+    px, pd = positional_encoder(vg, Lp, Ld)
+    ((px * Gx.to(DEV)).sum() + (pd * Gd.to(DEV)).sum()).backward()
+    want = {}
+    for dt in (torch.float64, torch.float32):
+        vt = v.to(dt).requires_grad_(True)
+        a, b = O.positional_encoder(vt, Lp, Ld)
+        ((a * Gx.to(dt)).sum() + (b * Gd.to(dt)).sum()).backward()
+        want[dt] = vt.grad
+    err = M.rel_err(vg.grad, want[torch.float64])
+    assert err <= M.bound_fp32(want[torch.float32], want[torch.float64]), err
+    # only posd used: the posx gradient is zero, not missing
+    vg.grad = None
+    _, pd = positional_encoder(vg, Lp, Ld)
+    pd.sum().backward()
+    assert float(vg.grad[:, :3].abs().max()) == 0.0
+
+
+# ---- 2. Nerf.forward(v) ------------------------------------------------------------------------------------------------
+def _points(P, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    xyz = torch.rand(P, 3, generator=g) * 2 - 1
+    d = torch.randn(P, 3, generator=g)
+    return torch.cat([xyz, d / d.norm(dim=1, keepdim=True)], 1)
+
+
+@pytest.mark.parametrize("frozen", [True, False])
+@pytest.mark.parametrize("precision", ["bf16", "fp16", "fp32"])
+def test_nerf_forward_input_gradient(precision, frozen):
+    sd = _sd()
+    P = 1000
+    v = _points(P)
+    G = torch.randn(P, 4, generator=torch.Generator().manual_seed(5))
+    net = _net(sd, precision, frozen)
+    vg = v.to(DEV).requires_grad_(True)
+    out = net(vg)
+    (out * G.to(DEV)).sum().backward()
+    g64, _ = M.points_grad(M.exact_forward, sd, v, G, torch.float64)
+    g32, _ = M.points_grad(M.exact_forward, sd, v, G, torch.float32)
+    if precision == "fp32":
+        bound = M.bound_fp32(g32, g64)
+    else:                              # fp16 modules train (and differentiate) on the bf16 kernels
+        g16, _ = M.points_grad(M.emulated_forward, sd, v, G, torch.float32)
+        bound = M.bound_bf16(g16, g32, g64)
+    err = M.rel_err(vg.grad, g64)
+    assert err <= bound, (err, bound)
+    assert all((p.grad is None) == frozen for p in net.parameters())
+
+
+@pytest.mark.parametrize("Lp,Ld,H", [(6, 2, 64), (8, 3, 128)])
+def test_generic_size_input_gradient(Lp, Ld, H):
+    from nerf_simple_amd.utils.nets import Nerf
+    torch.manual_seed(3)
+    net = Nerf(Lp, Ld, H).to(DEV)
+    sd = {k: t.detach().cpu() for k, t in net.state_dict().items()}
+    P = 513
+    v = _points(P, 1)
+    G = torch.randn(P, 4, generator=torch.Generator().manual_seed(6))
+    vg = v.to(DEV).requires_grad_(True)
+    (net(vg) * G.to(DEV)).sum().backward()
+    fwd = lambda s, x: O.nerf_forward(s, x, Lp, Ld)                  # noqa: E731
+    g64, _ = M.points_grad(fwd, sd, v, G, torch.float64)
+    g32, _ = M.points_grad(fwd, sd, v, G, torch.float32)
+    err = M.rel_err(vg.grad, g64)
+    assert err <= M.bound_fp32(g32, g64), err
+
+
+# ---- 3. render_nerf -> rays --------------------------------------------------------------------------------------------
+class _Foreign:
+    """A net object that is not a Nerf: the oracle's forward in torch ops on the GPU (differentiable in its input)."""
+
+    def __init__(self, sd):
+        self.sd = {k: t.to(DEV) for k, t in sd.items()}
+
+    def forward(self, q):
+        return O.nerf_forward(self.sd, q)
+
+
+CASES = [  # net, N, B, jitter source, frozen
+    ("bf16", 64, 300, "u", True), ("bf16", 32, 300, "ts", False), ("bf16", 128, 130, "device_rng", True),
+    ("bf16", 64, 130, "reference", False),
+    ("fp32", 64, 300, "u", True), ("fp32", 32, 130, "device_rng", False), ("fp32", 128, 130, "reference", True),
+    ("fp32", 64, 300, "ts", True),
+    ("foreign", 64, 300, "u", True), ("foreign", 32, 130, "reference", True),
+]
+
+
+def _render_with(net, rays, N, src, seed=7):
+    """render_nerf with the given jitter source; returns (outputs, the ts the call used [B,N] on the CPU)."""
+    from nerf_simple_amd import _lib
+    from nerf_simple_amd.utils.rendering import _query_points, _tbins, render_nerf
+    B = rays.shape[0]
+    g = torch.Generator().manual_seed(seed)
+    if src == "u":
+        u = torch.rand(B, N, generator=g)
+        return render_nerf(rays, net, N, u=u.to(DEV)), O.sample_ts(u)
+    if src == "ts":
+        ts = O.sample_ts(torch.rand(B, N, generator=g))
+        return render_nerf(rays, net, N, ts=ts.to(DEV)), ts
+    if src == "device_rng":
+        out = render_nerf(rays, net, N, device_rng=True, seed=seed)
+        _, ts = _query_points(rays.detach(), None, _tbins(2, 6, N, rays.device), _lib.FLAG_DEVICE_RNG, seed, 0, N)
+        return out, ts.cpu()
+    torch.manual_seed(seed)
+    u = torch.rand(B, N)
+    torch.manual_seed(seed)
+    out = render_nerf(rays, net, N)
+    return out, O.sample_ts(u)
+
+
+@pytest.mark.parametrize("kind,N,B,src,frozen", CASES)
+def test_render_nerf_ray_gradient(kind, N, B, src, frozen):
+    sd = _sd()
+    net = _Foreign(sd) if kind == "foreign" else _net(sd, kind, frozen)
+    rays = _rays(B)
+    target = torch.rand(B, 3, generator=torch.Generator().manual_seed(11))
+    rg = rays.to(DEV).requires_grad_(True)
+    out, ts = _render_with(net, rg, N, src)
+    assert out[0].grad_fn is not None
+    M.ray_loss(out, target.to(DEV)).backward()
+    assert rg.grad is not None
+    g64 = M.rays_grad(M.exact_forward, sd, rays, N, target, torch.float64, ts=ts)
+    g32 = M.rays_grad(M.exact_forward, sd, rays, N, target, torch.float32, ts=ts)
+    if kind == "bf16":
+        g16 = M.rays_grad(M.emulated_forward, sd, rays, N, target, torch.float32, ts=ts)
+        bound = M.bound_bf16(g16, g32, g64)
+    else:
+        bound = M.bound_fp32(g32, g64)
+    err = M.rel_err(rg.grad, g64)
+    assert err <= bound, (err, bound)
+    if kind != "foreign":
+        assert all((p.grad is None) == frozen for p in net.parameters())
+
+
+def test_reference_stream_advances_as_without_gradients():
+    from nerf_simple_amd.utils.rendering import render_nerf
+    net = _net(_sd(), "bf16", True)
+    rays = _rays(130).to(DEV)
+    torch.manual_seed(3)
+    with torch.no_grad():
+        render_nerf(rays, net, 64)
+    want = torch.get_rng_state()
+    torch.manual_seed(3)
+    out = render_nerf(rays.clone().requires_grad_(True), net, 64)
+    out[0].sum().backward()
+    assert torch.equal(torch.get_rng_state(), want)
+
+
+# ---- 4..6: nothing else changes, nothing extra runs, same bits twice ----------------------------------------------------
+def _train_call(net, rays, u, target):
+    from nerf_simple_amd.utils.rendering import render_nerf
+    net.zero_grad(set_to_none=True)
+    loss = M.ray_loss(render_nerf(rays, net, u.shape[1], u=u), target)
+    loss.backward()
+    return loss.detach().clone(), {k: p.grad.clone() for k, p in net.named_parameters()}
+
+
+def test_ray_gradients_leave_loss_and_parameter_gradients_unchanged():
+    """rays.requires_grad adds launches after the dX chain and changes nothing before or beside it: the loss is
+    bit-identical, and the 24 parameter gradients agree with the call without ray gradients as closely as two calls
+    without them agree with each other (nerf_amd_param_gradients sums split-K partials with float atomics, so its
+    own repeats match to rounding: tests/test_gpu_training.py::test_training_kernels_are_deterministic)."""
+    net = _net(_sd(), "bf16", False)
+    rays = _rays(300).to(DEV)
+    u = torch.rand(300, 64, generator=torch.Generator().manual_seed(2)).to(DEV)
+    target = torch.rand(300, 3, generator=torch.Generator().manual_seed(4)).to(DEV)
+    l0, g0 = _train_call(net, rays, u, target)
+    rg = rays.clone().requires_grad_(True)
+    l1, g1 = _train_call(net, rg, u, target)
+    assert rg.grad is not None
+    assert torch.equal(l0, l1)
+    assert len(g0) == 24
+    for k in g0:
+        assert float((g1[k] - g0[k]).abs().max()) <= 1e-5 * float(g0[k].abs().max()), k
+
+
+class _Spy:
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("nerf_amd_"):
+            return fn
+
+        def call(*a):
+            self.calls.append(name)
+            return fn(*a)
+        return call
+
+
+NEW_ENTRIES = {"nerf_amd_input_gradients", "nerf_amd_query_points_backward", "nerf_amd_gamma_backward",
+               "nerf_amd_positional_encoder_backward"}
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+def test_frozen_net_skips_parameter_gradients(monkeypatch, precision):
+    from nerf_simple_amd import _lib
+    from nerf_simple_amd.utils.rendering import render_nerf
+    net = _net(_sd(), precision, True)
+    rays = _rays(130).to(DEV).requires_grad_(True)
+    u = torch.rand(130, 64, generator=torch.Generator().manual_seed(2)).to(DEV)
+    spy = _Spy(_lib.lib())
+    monkeypatch.setattr(_lib, "lib", lambda: spy)
+    render_nerf(rays, net, 64, u=u)[0].sum().backward()
+    assert rays.grad is not None
+    assert all(p.grad is None for p in net.parameters())
+    assert not any(c.startswith("nerf_amd_param_gradients") for c in spy.calls), spy.calls
+    assert NEW_ENTRIES & set(spy.calls)
+
+
+def test_trainable_net_without_ray_gradients_launches_nothing_new(monkeypatch):
+    from nerf_simple_amd import _lib
+    from nerf_simple_amd.utils.rendering import render_nerf
+    net = _net(_sd(), "bf16", False)
+    rays = _rays(130).to(DEV)
+    u = torch.rand(130, 64, generator=torch.Generator().manual_seed(2)).to(DEV)
+    spy = _Spy(_lib.lib())
+    monkeypatch.setattr(_lib, "lib", lambda: spy)
+    render_nerf(rays, net, 64, u=u)[0].sum().backward()
+    assert "nerf_amd_param_gradients" in spy.calls
+    assert not NEW_ENTRIES & set(spy.calls), spy.calls
+
+
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+def test_ray_gradients_are_deterministic(precision):
+    from nerf_simple_amd.utils.rendering import render_nerf
+    net = _net(_sd(), precision, True)
+    rays = _rays(300).to(DEV)
+    u = torch.rand(300, 64, generator=torch.Generator().manual_seed(2)).to(DEV)
+    grads = []
+    for _ in range(2):
+        rg = rays.clone().requires_grad_(True)
+        render_nerf(rg, net, 64, u=u)[0].square().sum().backward()
+        grads.append(rg.grad)
+    assert torch.equal(grads[0], grads[1])
+
+
+# ---- 7. pose recovery ------------------------------------------------------------------------------------------------
+POSE_HW, POSE_N, POSE_LR, POSE_STEPS, POSE_FACTOR, POSE_LEVELS = 24, 32, 2e-3, 30, 3.0, 3
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_pose_recovery(precision):
+    """Camera-pose estimation against a frozen network (iNeRF): the structured synthetic weights with position-encoder
+    levels >= 3 cut (input_grad_model.smooth_state_dict: at full bandwidth a random network's image is noise on the scale
+    of a degree and the CPU oracle's loop does not descend), a 24x24 image with N = 32 samples per ray at spherical pose
+    (4, -30 deg, 0), fixed jitter; the start pose is off by 1 degree about an oblique axis and 0.03 in translation
+    (input_grad_model.start_perturbation).  Adam (lr 2e-3) on the 6-vector must cut the pose error (rotation angle +
+    translation distance) by POSE_FACTOR = 3 within 30 steps.  Settings chosen beforehand with the same loop on the fp32
+    CPU oracle, which cuts the error 5.4x in 30 steps (7.7x in 40).  The first step's pose gradient of the fp32 net is
+    held to the fp32 rule against float64 oracle autograd."""
+    from nerf_simple_amd.utils import synthetic
+    from nerf_simple_amd.utils.rendering import render_nerf
+    from nerf_simple_amd.utils.xyz import rays_single_cam, spherical_to_pose
+    sd = M.smooth_state_dict(_sd(), POSE_LEVELS)
+    net = _net(sd, precision, True)
+    pose0 = torch.from_numpy(spherical_to_pose(4, -30, 0)).float()
+    dirs = rays_single_cam([POSE_HW, POSE_HW, synthetic.focal_from_fov(POSE_HW)])
+    u = torch.rand(POSE_HW * POSE_HW, POSE_N, generator=torch.Generator().manual_seed(0))
+    ud = u.to(DEV)
+    with torch.no_grad():
+        target = render_nerf(M.pose_rays(torch.zeros(6), pose0, dirs).to(DEV), net, POSE_N, u=ud)[0]
+    xi0 = M.start_perturbation()
+    if precision == "fp32":
+        # oracle agreement of the first pose gradient (float64 truth, fp32 rule)
+        tgt = target.cpu()
+        want = {}
+        for dt in (torch.float64, torch.float32):
+            xi = xi0.detach().to(dt).clone().requires_grad_(True)
+            rays = M.pose_rays(xi, pose0.to(dt), dirs.to(dt))
+            M.ray_loss(M.render(M.exact_forward, M.cast_sd(sd, dt), rays, POSE_N, u=u), tgt).backward()
+            want[dt] = xi.grad
+        xi = xi0.detach().clone().to(DEV).requires_grad_(True)
+        M.ray_loss(render_nerf(M.pose_rays(xi, pose0.to(DEV), dirs.to(DEV)), net, POSE_N, u=ud), target).backward()
+        err = M.rel_err(xi.grad, want[torch.float64])
+        assert err <= M.bound_fp32(want[torch.float32], want[torch.float64]), err
+    xi = xi0.detach().clone().to(DEV).requires_grad_(True)
+    opt = torch.optim.Adam([xi], lr=POSE_LR)
+    p0, dd = pose0.to(DEV), dirs.to(DEV)
+    e0 = M.pose_error(xi0, torch.zeros(6))
+    for _ in range(POSE_STEPS):
+        opt.zero_grad()
+        M.ray_loss(render_nerf(M.pose_rays(xi, p0, dd), net, POSE_N, u=ud), target).backward()
+        opt.step()
+    e1 = M.pose_error(xi.detach().cpu(), torch.zeros(6))
+    assert e1 * POSE_FACTOR <= e0, (e0, e1)
