@@ -501,6 +501,62 @@ int nerf_amd_gamma_backward(const float* x, int64_t x_stride, const float* d_out
 int nerf_amd_positional_encoder_backward(const float* vec, const float* d_posx, const float* d_posd, float* d_vec,
                                          int64_t P, int Lp, int Ld, void* stream);
 
+/* ---- density grid and surface extraction (not in the reference) ------------------------------------------------------
+ * The reference can only evaluate sigma through the whole Nerf.forward (utils/nets.py:34-43) and has no mesh export.
+ *
+ * nerf_amd_density_forward: sigma[P] = raw sigma (pre-softplus, column 3 of nerf_amd_mlp_forward's output) of the points
+ * pts[P, stride >= 3] (their first three columns).  Not in the reference.  sigma does not depend on the view direction
+ * (sigma_fc reads h8 before the direction concat, utils/nets.py:36-40): the kernel runs layers 0..7 and the sigma row of
+ * layers_2 only (82.6 % of the MFMAs) with the arithmetic of nerf_amd_mlp_forward, and equals its column 3 bit for bit.
+ * precision: NERF_AMD_BF16 or NERF_AMD_FP16 on the image of nerf_amd_pack_weights (NERF_AMD_F32: NERF_AMD_EUNSUP -- run
+ * nerf_amd_grid_points + nerf_amd_mlp_forward instead).  The range guard of the 16-bit kernels applies: status word 0 is
+ * set on a non-finite accumulator in layers 1..7 or a non-finite sigma (nerf_amd_packed_status_offset).
+ *
+ * nerf_amd_density_grid: the same on the grid points of an [nx, ny, nz] volume, formed in the kernel (no input buffer):
+ * sigma[(i ny + j) nz + k] (C order, z fastest) at (x(i), y(j), z(k)), x_a(i) = fl(lo_a + fl(i step_a)) with two separately
+ * rounded float32 operations -- torch's float32 `lo + i * step` is the same number.  h_lo[3], h_step[3]: HOST floats
+ * (the conventional step is fl32((hi - lo) / (n - 1))).  Each extent in [2, 2^24], at most 2^40 points (64-bit indices).
+ *
+ * nerf_amd_grid_points: pts6[count, 6] = (x(i), y(j), z(k), 0, 0, 1) of grid points first .. first + count - 1, the same
+ * coordinates: the input of the fp32 forward (or of another network size) on a chunk of the grid.  Not in the reference. */
+int nerf_amd_density_forward(const float* pts, int64_t stride, void* packed, int precision, float* sigma, int64_t P,
+                             void* stream);
+int nerf_amd_density_grid(const float* h_lo, const float* h_step, int64_t nx, int64_t ny, int64_t nz, void* packed,
+                          int precision, float* sigma, void* stream);
+int nerf_amd_grid_points(const float* h_lo, const float* h_step, int64_t nx, int64_t ny, int64_t nz, int64_t first,
+                         int64_t count, float* pts6, void* stream);
+
+/* Marching cubes on an fp32 volume sigma[nx, ny, nz] (C order, z fastest; any device volume, e.g. nerf_amd_density_grid's).
+ * Not in the reference.  Semantics (tests/mesh_model.py restates them in numpy, bit for bit):
+ *   - a corner is inside iff sigma > level (a tie is outside); an edge crosses iff exactly one endpoint is inside and both
+ *     are finite; a cell with a non-finite corner emits no face;
+ *   - one vertex per crossing edge.  On edge a -> b (a = the endpoint with the lower linear index):
+ *     t = fl(fl(level - sa) / fl(sb - sa)); on the edge's axis x = fl(xa + fl(t fl(xb - xa))), the other two coordinates
+ *     are exact grid coordinates x_a(i) = fl(lo_a + fl(i step_a));
+ *   - normal: -grad sigma by central differences on the grid (one-sided on the grid's faces: (s[hi] - s[lo]) /
+ *     (x(hi) - x(lo))), interpolated with t between the endpoints and normalised: it points outward, towards lower sigma;
+ *     a zero or non-finite one is (0, 0, 0);
+ *   - vertices are numbered by (linear index of the lower endpoint, axis x < y < z), faces by (linear cell index, table
+ *     order); faces are int32 vertex triples, oriented outward;
+ *   - the case tables are generated by rule (tools/make_mc_tables.py): on each cube face the crossing edges are joined by
+ *     a rule that depends on that face's four corners only (an ambiguous face separates its inside corners), the segments
+ *     chain into loops and each loop is fanned.  A surface that stays inside the grid gives a closed, consistently
+ *     oriented mesh: every edge belongs to two faces, once in each direction.
+ * Deterministic: fixed partitions and hand-written scans, no atomics -- every run writes the same bytes.
+ *
+ * nerf_amd_marching_cubes_workspace_bytes: bytes of the workspace both passes share (about 5 per grid point).
+ * nerf_amd_marching_cubes_count: counts[2] (DEVICE int64) = (vertices, faces).  Also fills the workspace for _emit.
+ * nerf_amd_marching_cubes_emit: after _count on the same sigma, extents, level and workspace: verts[V,3], normals[V,3]
+ *   (may be NULL), faces[F,3].  Writes vertex v only if v < max_verts and face f only if f < max_faces -- never past the
+ *   capacities; the mesh is complete when max_verts >= counts[0] and max_faces >= counts[1].  max_verts < 2^31 (vertex
+ *   numbers are int32: a vertex count of 2^31 or more cannot be emitted). */
+int64_t nerf_amd_marching_cubes_workspace_bytes(int64_t nx, int64_t ny, int64_t nz);
+int nerf_amd_marching_cubes_count(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
+                                  int64_t* counts, void* stream);
+int nerf_amd_marching_cubes_emit(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, const float* h_lo,
+                                 const float* h_step, void* workspace, float* verts, float* normals, int32_t* faces,
+                                 int64_t max_verts, int64_t max_faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

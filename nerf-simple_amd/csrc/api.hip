@@ -63,6 +63,13 @@ int nerf_amd_launch_input_gradients(const void*, const float*, const float*, con
 int nerf_amd_launch_query_points_backward(const float*, const float*, const float*, float*, long long, int, hipStream_t);
 int nerf_amd_launch_gamma_backward(const float*, long long, const float*, float*, long long, int, hipStream_t);
 int nerf_amd_launch_posenc_backward(const float*, const float*, const float*, float*, long long, int, int, hipStream_t);
+int nerf_amd_launch_density_bf16(const DensityArgs*, hipStream_t);
+int nerf_amd_launch_density_f16(const DensityArgs*, hipStream_t);
+int nerf_amd_launch_grid_points(const DensityArgs*, long long, long long, float*, hipStream_t);
+long long nerf_amd_mc_workspace_bytes(long long);
+int nerf_amd_launch_mc_count(const float*, long long, long long, long long, float, void*, long long*, hipStream_t);
+int nerf_amd_launch_mc_emit(const float*, long long, long long, long long, float, const float*, const float*, void*, float*, float*,
+                            int*, long long, long long, hipStream_t);
 }
 
 namespace {
@@ -90,6 +97,22 @@ int launch_mlp(const MlpArgs& a, int rays_mode, int precision, hipStream_t s) {
     if (precision == NERF_AMD_F32) return nerf_amd_launch_mlp_f32(&a, rays_mode, s);
     if (precision == NERF_AMD_FP16) return nerf_amd_launch_mlp_f16_16(&a, rays_mode, s);
     return nerf_amd_launch_mlp_bf16_16(&a, rays_mode, s);
+}
+// a density / marching-cubes grid: every extent in [2, 2^24], at most 2^40 points
+constexpr int64_t GRID_MAX_EXTENT = 1ll << 24, GRID_MAX_POINTS = 1ll << 40;
+inline bool bad_grid(int64_t nx, int64_t ny, int64_t nz) {
+    for (int64_t r : {nx, ny, nz})
+        if (r < 2 || r > GRID_MAX_EXTENT) return true;
+    return nx * ny > GRID_MAX_POINTS / nz;
+}
+inline DensityArgs grid_args(const float* h_lo, const float* h_step, int64_t nx, int64_t ny, int64_t nz) {
+    DensityArgs a{};
+    a.P = nx * ny * nz; a.ny = ny; a.nz = nz;
+    for (int i = 0; i < 3; ++i) { a.lo[i] = h_lo[i]; a.step[i] = h_step[i]; }
+    return a;
+}
+int launch_density(const DensityArgs& a, int precision, hipStream_t s) {
+    return precision == NERF_AMD_FP16 ? nerf_amd_launch_density_f16(&a, s) : nerf_amd_launch_density_bf16(&a, s);
 }
 }  // namespace
 
@@ -738,6 +761,59 @@ int nerf_amd_adam_step_hyper(float* params, const float* grads, float* exp_avg, 
     if (n == 0) return 0;
     if (!params || !grads || !exp_avg || !exp_avg_sq || !hyper) return NERF_AMD_EINVAL;
     return nerf_amd_launch_adam_hyper(params, grads, exp_avg, exp_avg_sq, n, hyper, S(stream));
+}
+
+// ---- density grid and marching cubes (not in the reference) ----------------------------------------------------------
+int nerf_amd_density_forward(const float* pts, int64_t stride, void* packed, int precision, float* sigma, int64_t P,
+                             void* stream) {
+    if (P < 0 || stride < 3 || bad_precision(precision)) return NERF_AMD_EINVAL;
+    if (precision == NERF_AMD_F32) return NERF_AMD_EUNSUP;
+    if (P == 0) return 0;
+    if (!pts || !packed || !sigma) return NERF_AMD_EINVAL;
+    DensityArgs a{};
+    a.pts = pts; a.stride = stride; a.packed = packed; a.sigma = sigma; a.P = P;
+    return launch_density(a, precision, S(stream));
+}
+
+int nerf_amd_density_grid(const float* h_lo, const float* h_step, int64_t nx, int64_t ny, int64_t nz, void* packed, int precision,
+                          float* sigma, void* stream) {
+    if (bad_grid(nx, ny, nz) || bad_precision(precision) || !h_lo || !h_step) return NERF_AMD_EINVAL;
+    if (precision == NERF_AMD_F32) return NERF_AMD_EUNSUP;
+    if (!packed || !sigma) return NERF_AMD_EINVAL;
+    DensityArgs a = grid_args(h_lo, h_step, nx, ny, nz);
+    a.packed = packed; a.sigma = sigma;
+    return launch_density(a, precision, S(stream));
+}
+
+int nerf_amd_grid_points(const float* h_lo, const float* h_step, int64_t nx, int64_t ny, int64_t nz, int64_t first, int64_t count,
+                         float* pts6, void* stream) {
+    if (bad_grid(nx, ny, nz) || !h_lo || !h_step || first < 0 || count < 0 || first > nx * ny * nz - count) return NERF_AMD_EINVAL;
+    if (count == 0) return 0;
+    if (!pts6) return NERF_AMD_EINVAL;
+    const DensityArgs a = grid_args(h_lo, h_step, nx, ny, nz);
+    return nerf_amd_launch_grid_points(&a, first, count, pts6, S(stream));
+}
+
+int64_t nerf_amd_marching_cubes_workspace_bytes(int64_t nx, int64_t ny, int64_t nz) {
+    if (bad_grid(nx, ny, nz)) return NERF_AMD_EINVAL;
+    return nerf_amd_mc_workspace_bytes(nx * ny * nz);
+}
+
+int nerf_amd_marching_cubes_count(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
+                                  int64_t* counts, void* stream) {
+    if (bad_grid(nx, ny, nz) || !sigma || !workspace || !counts) return NERF_AMD_EINVAL;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)counts & 7)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_mc_count(sigma, nx, ny, nz, level, workspace, reinterpret_cast<long long*>(counts), S(stream));
+}
+
+int nerf_amd_marching_cubes_emit(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, const float* h_lo,
+                                 const float* h_step, void* workspace, float* verts, float* normals, int32_t* faces,
+                                 int64_t max_verts, int64_t max_faces, void* stream) {
+    if (bad_grid(nx, ny, nz) || !sigma || !workspace || !h_lo || !h_step) return NERF_AMD_EINVAL;
+    if (max_verts < 0 || max_faces < 0 || max_verts > INT32_MAX) return NERF_AMD_EINVAL;      // vertex numbers are int32
+    if ((max_verts > 0 && !verts) || (max_faces > 0 && !faces) || ((uintptr_t)workspace & 15)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_mc_emit(sigma, nx, ny, nz, level, h_lo, h_step, workspace, verts, normals, faces, max_verts, max_faces,
+                                   S(stream));
 }
 
 }  // extern "C"

@@ -492,13 +492,6 @@ __device__ __forceinline__ void run_layer(const Ctx& c, State& st, ex8 (&in)[NCB
     run_layer_seq<L, SAVE>(c, st, in, out, std::make_integer_sequence<int, layer_chunks(L)>{});
 }
 
-// sin(2 pi (2^level q + trig/4)) with a per-lane level / trig
-__device__ __forceinline__ float enc_lane(TwoF q, int idx) {
-    const float sc = __builtin_amdgcn_ldexpf(1.0f, idx >> 1);
-    const float fr = __builtin_amdgcn_fractf(q.hi * sc) + q.lo * sc + ((idx & 1) ? 0.25f : 0.f);
-    return __builtin_amdgcn_sinf(fr);
-}
-
 // SAVE (the training forward, launched in rays mode) also serves Nerf.forward(v) with gradients:
 // a.pts != NULL switches the point fetch at run time, so training needs no third instantiation.
 template <bool RAYS, int SAVE, bool COMP>

@@ -46,6 +46,17 @@ struct MlpArgs {
     float* pixels;        // [B,4] = [clip(rgb,0,1), disparity]
 };
 
+// Arguments of the sigma-only kernels (density.hip).
+struct DensityArgs {
+    const float* pts;     // points mode: [P, stride]; grid mode: NULL
+    long long stride;
+    const void* packed;   // packed 16-bit image (nerf_amd_pack_weights)
+    float* sigma;         // out [P]
+    long long P;
+    long long ny, nz;     // grid mode: extents of the two fastest axes (C order, z fastest)
+    float lo[3], step[3]; // grid mode: x_a(i) = fl(lo_a + fl(i step_a))
+};
+
 // ---- host: per-device launch facts, looked up once ----------------------------------
 // Every launcher used to call hipGetDevice + hipDeviceGetAttribute + hipFuncSetAttribute per launch: a few
 // microseconds each on the eager small-batch path.  Both answers are constants of (device) and (kernel, device).
@@ -392,6 +403,13 @@ __device__ __forceinline__ TwoF to_revolutions(float x) {
     const float err = __fmaf_rn(x, C_HI, -q.hi);
     q.lo = __fmaf_rn(x, C_LO, err);
     return q;
+}
+// sin(2 pi (2^level q + trig/4)) with a per-lane level / trig: the posx / posd features of the 16-bit kernels
+// (mlp_bf16_16.hip, density.hip), which must form them identically
+__device__ __forceinline__ float enc_lane(TwoF q, int idx) {
+    const float sc = __builtin_amdgcn_ldexpf(1.0f, idx >> 1);
+    const float fr = __builtin_amdgcn_fractf(q.hi * sc) + q.lo * sc + ((idx & 1) ? 0.25f : 0.f);
+    return __builtin_amdgcn_sinf(fr);
 }
 // sin / cos of (2 pi * 2^k * q) via the hardware v_sin/v_cos (argument in
 // revolutions).  Accuracy ~1e-6 abs: used by the bf16 path only.

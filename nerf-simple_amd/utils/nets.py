@@ -300,6 +300,37 @@ class Nerf(nn.Module):
 
         return guarded_launch([self], code, launch)
 
+    def density(self, x, *, precision=None):
+        """Raw sigma [P] (pre-softplus, column 3 of forward) of the points x [P,3], or of the first three columns of a
+        [P,6].  Not in the reference.  sigma does not depend on the view direction (reference utils/nets.py:36-40): with
+        the default shape and no gradient requested this runs the sigma-only kernel (csrc/density.hip: 82.6 % of the
+        network's MFMAs, bit for bit forward's column 3, under the same range guard); otherwise it is
+        ``self.forward(...)[:, 3]``, so autograd is unchanged (utils/mesh.py builds grids and meshes on it)."""
+        _lib.require_cuda_f32(x, "x")
+        if x.dim() != 2 or x.shape[1] not in (3, 6):
+            raise RuntimeError("Nerf.density expects a [P, 3] or [P, 6] tensor")
+        wants_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        code = _lib.precision_code(self.precision if precision is None else precision)
+        if not self._fused_ok() or wants_grad or code == _lib.F32:
+            v = x if x.shape[1] == 6 else torch.cat([x, torch.zeros_like(x[:, :2]), torch.ones_like(x[:, :1])], 1)
+            return self.forward(v, precision=precision)[:, 3]
+        from .xyz import range_check_values
+        range_check_values(x)                        # what forward checks on these columns (utils/xyz.py:8-9), lazily
+        x = x.detach().contiguous()
+        P = x.shape[0]
+
+        def launch(code, packed):
+            if code == _lib.F32:                     # demoted by the range guard: the fp32 forward
+                v = x if x.shape[1] == 6 else torch.cat([x, torch.zeros_like(x[:, :2]), torch.ones_like(x[:, :1])], 1)
+                return self.forward_inference(v, precision="fp32")[:, 3]
+            sigma = torch.empty(P, dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.lib().nerf_amd_density_forward(_lib.ptr(x), x.shape[1], _lib.ptr(packed[0]), code,
+                                                               _lib.ptr(sigma), P, _lib.stream_ptr(x.device)),
+                           "nerf_amd_density_forward")
+            return sigma
+
+        return guarded_launch([self], code, launch)
 
     def fp16_headroom(self, v):
         """Largest hidden activation of the network on the query points v [P,6], as a fraction of the fp16
