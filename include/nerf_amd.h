@@ -41,6 +41,14 @@ extern "C" {
 #define NERF_AMD_BF16  1   /* bf16 operands on v_mfma_f32_16x16x32_bf16, fp32 accumulate (the flagship) */
 #define NERF_AMD_BF16_BWD 3 /* nerf_amd_pack_weights / nerf_amd_packed_bytes only: the transposed image of nerf_amd_mlp_backward */
 #define NERF_AMD_FP16  2   /* fp16 operands on v_mfma_f32_16x16x32_f16: same rate, 11-bit mantissa; range 65504 */
+/* The NERF_AMD_FP16 image is FOLDED: layers_2 (a linear layer with no activation behind it, feeding color_fc.0 alone) is
+ * multiplied into the colour layer by the packer.  Same byte size and the same offsets of every layer, of the bias table
+ * and of the status block as the NERF_AMD_BF16 image; the colour layer's first 256 k positions hold
+ * Wc[:, :256] W2 (fp32 fma chain, ascending k, then rounded to fp16) in the k order they held Wc[:, :256] in, its bias rows
+ * hold bc + Wc[:, :256] b2, and the 16 layers_2 tiles (128 KiB) stay filled with layers_2 but are read by no fp16 kernel:
+ * the fp16 inference kernels run 65,536 of the 600,064 padded multiply-accumulates per point less than the bf16 ones.
+ * A folded element that does not fit fp16 sets NERF_AMD_STATUS_WORD_WEIGHT_RANGE like any weight that does not.  An fp16
+ * image must therefore come from nerf_amd_pack_weights(..., NERF_AMD_FP16), never from converting a bf16 one. */
 
 /* flags of nerf_amd_render_forward / nerf_amd_mlp_forward_rays */
 #define NERF_AMD_TS_GIVEN   1u  /* `u` holds sample positions ts[B,N], not jitter */
@@ -507,7 +515,7 @@ int nerf_amd_positional_encoder_backward(const float* vec, const float* d_posx, 
  * nerf_amd_density_forward: sigma[P] = raw sigma (pre-softplus, column 3 of nerf_amd_mlp_forward's output) of the points
  * pts[P, stride >= 3] (their first three columns).  Not in the reference.  sigma does not depend on the view direction
  * (sigma_fc reads h8 before the direction concat, utils/nets.py:36-40): the kernel runs layers 0..7 and the sigma row of
- * layers_2 only (82.6 % of the MFMAs) with the arithmetic of nerf_amd_mlp_forward, and equals its column 3 bit for bit.
+ * layers_2 only (82.6 % of the MFMAs of the bf16 forward, 92.7 % of the folded fp16 one's) with the arithmetic of nerf_amd_mlp_forward, and equals its column 3 bit for bit.
  * precision: NERF_AMD_BF16 or NERF_AMD_FP16 on the image of nerf_amd_pack_weights (NERF_AMD_F32: NERF_AMD_EUNSUP -- run
  * nerf_amd_grid_points + nerf_amd_mlp_forward instead).  The range guard of the 16-bit kernels applies: status word 0 is
  * set on a non-finite accumulator in layers 1..7 or a non-finite sigma (nerf_amd_packed_status_offset).

@@ -8,12 +8,13 @@
 //     pairwise, ARE the B fragment of the next layer's k-step q (32 features): activations never
 //     leave the registers;
 //   * weights stream L2 -> LDS by LDS-DMA in chunks of four 16-row tiles (eight for the K = 64 first
-//     layer; 38 chunks per tile), double buffered, one barrier per chunk; one weight fragment read
+//     layer; 38 chunks per tile, 34 in fp16), double buffered, one barrier per chunk; one weight fragment read
 //     from LDS (16 rows x 32 k, 1 KiB) feeds two MFMAs (the two column blocks);
 //   * the chunk barrier sits three fragments before the END of a chunk and the next chunk's first
 //     fragments are requested right behind it, so no chunk starts with an LDS round trip; the next
 //     chunk's DMA pieces go out one per four MFMAs (chunk_step);
-//   * the sigma head rides as row 256 of the layers_2 product, the rgb head is one 16-row tile;
+//   * the sigma head rides as row 256 of the layers_2 product, the rgb head is one 16-row tile; the fp16 build
+//     has no layers_2 product (folded into the colour layer by the packer) and keeps that row's tile as layer 8;
 //   * a workgroup = 8 waves = a 256-point tile, persistent over tiles;
 //   * COMP (the render path): compositing (utils/rendering.py:47-85) runs in the same launch.  A
 //     workgroup owns a contiguous range of RAYS; each tile drops its 256 x (rgb, sigma, t) into an
@@ -55,13 +56,27 @@ constexpr int TILE_PTS = WAVES * 16 * NCB;
 // double buffer's parity is cyclic over tiles.
 __host__ __device__ constexpr int tpc(int L) { return L == 0 ? 8 : 4; }
 
-__host__ __device__ constexpr int layer_chunks(int L) { return (b16_mt(L) + tpc(L) - 1) / tpc(L); }
+// The fp16 build runs the folded view of the layer table (nerf_layout.h): layer 8 is its sigma tile alone (one 8 KiB
+// chunk, 16 MFMAs) and the colour layer takes h8 through the pre-multiplied Wc[:, :256] W2 -- layers_2's 256 MFMAs and
+// four of its five chunk barriers are gone, 2088 MFMAs and 34 chunks per tile.  The bf16 build, whose image and
+// instantiations are shared with training (h9 is saved for dW), runs the table as it stands.
+#ifdef NERF_HALF
+constexpr bool FOLD = true;
+#else
+constexpr bool FOLD = false;
+#endif
+// the 16-row tiles of layer L this build streams, where they start in the image and in the bias table
+__host__ __device__ constexpr int k_mt(int L) { return FOLD ? fold_mt(L) : b16_mt(L); }
+__host__ __device__ constexpr int k_layer_off_kib(int L) { return FOLD ? fold_layer_off_kib(L) : b16_layer_off_kib(L); }
+__host__ __device__ constexpr int k_bias_off(int L) { return FOLD ? fold_bias_off(L) : b16_bias_off(L); }
+
+__host__ __device__ constexpr int layer_chunks(int L) { return (k_mt(L) + tpc(L) - 1) / tpc(L); }
 __host__ __device__ constexpr int chunk_first(int L) {
     int c = 0;
     for (int i = 0; i < L; ++i) c += layer_chunks(i);
     return c;
 }
-constexpr int NUM_CHUNKS = chunk_first(NUM_LAYERS);           // 38
+constexpr int NUM_CHUNKS = chunk_first(NUM_LAYERS);           // 38 (fp16: 34)
 __host__ __device__ constexpr int chunk_layer(int cc) {
     int L = 0;
     while (cc >= layer_chunks(L)) { cc -= layer_chunks(L); ++L; }
@@ -69,13 +84,13 @@ __host__ __device__ constexpr int chunk_layer(int cc) {
 }
 __host__ __device__ constexpr int chunk_tiles(int cc) {
     const int L = chunk_layer(cc), C = cc - chunk_first(L);
-    const int left = b16_mt(L) - C * tpc(L);
+    const int left = k_mt(L) - C * tpc(L);
     return left < tpc(L) ? left : tpc(L);
 }
 __host__ __device__ constexpr int chunk_kib(int cc) { return chunk_tiles(cc) * b16_ks(chunk_layer(cc)); }
 __host__ __device__ constexpr int chunk_off_kib(int cc) {
     const int L = chunk_layer(cc), C = cc - chunk_first(L);
-    return b16_layer_off_kib(L) + C * tpc(L) * b16_ks(L);
+    return k_layer_off_kib(L) + C * tpc(L) * b16_ks(L);
 }
 
 constexpr int LDS_WBUF = 40 * 1024;
@@ -93,6 +108,7 @@ constexpr int COMP_MAX_N = RING_PTS - TILE_PTS;      // an unfinished ray plus o
 static_assert(COMP_MAX_N == FUSED_RENDER_MAX_N, "api.hip routes by this limit");
 static_assert(B16_BIAS_FLOATS * 4 <= LDS_W0, "bias table");
 static_assert(LDS_TOTAL_COMP <= 160 * 1024 && NUM_CHUNKS % 2 == 0, "LDS budget / parity");
+static_assert(NUM_CHUNKS == (FOLD ? 34 : 38), "chunks per tile");
 static_assert((RING_PTS & (RING_PTS - 1)) == 0 && RING_PTS % TILE_PTS == 0, "ring indexing");
 
 static_assert(ACT_TILE_PTS == TILE_PTS && MASK_TILE_PTS == TILE_PTS, "activation blocks and mask tiles are the kernel's tiles");
@@ -191,6 +207,8 @@ __device__ __forceinline__ void epilogue_piece(int i, const f32x4 (&acc)[NCB][2]
         // rows sums w * inf: +-inf, or NaN with two of them -- so one accumulator element per point tells.  (The
         // outputs alone do not: the integer ReLU below turns a NaN with the sign bit set into 0, and a layer whose
         // rows are all NaN comes out as all zeros, finite from there on.)  One compare per column block and layer.
+        // (Folded build: layer 8 is the sigma tile alone and has no pair 0; an inf in h8 shows in the colour layer,
+        // which reads h8 itself, and in sigma, which the tile's finite4 check sees.)
         if (j2 == 0) st.bad |= __builtin_amdgcn_classf(acc[cb][0][0], 0x207);      // sNaN | qNaN | -inf | +inf
     }
     if constexpr (L == 10) {
@@ -332,7 +350,7 @@ __device__ __forceinline__ void chunk_step(const Ctx& c, State& st, ex8 (&in)[NC
     constexpr int RT0 = C * tpc(L);
     constexpr int F = NT * KS;                      // weight fragments (each feeds 2 MFMAs)
     constexpr int AHEAD = 4;                         // weight fragments in flight ahead of their MFMAs (2..8 measure alike)
-    constexpr int BIAS_OFF = LDS_BIAS + (b16_bias_off(L) + 16 * RT0) * 4;
+    constexpr int BIAS_OFF = LDS_BIAS + (k_bias_off(L) + 16 * RT0) * 4;
     constexpr int XBLK = D.extra_kind == 1 ? 2048 : 1024;
     // chunk-linear MFMA index m = (t*KS + ks)*2 + cb
     constexpr int MT = NCB * KS;                      // MFMAs per row tile
@@ -353,7 +371,7 @@ __device__ __forceinline__ void chunk_step(const Ctx& c, State& st, ex8 (&in)[NC
     constexpr int NCC = (CC + 1) % NUM_CHUNKS;
     constexpr int NL = chunk_layer(NCC);
     constexpr int NF = chunk_tiles(NCC) * (layer_desc(NL).chain_k / 32 + layer_desc(NL).extra_slots / 32);
-    constexpr int NBIAS_OFF = LDS_BIAS + (b16_bias_off(NL) + 16 * (NCC - chunk_first(NL)) * tpc(NL)) * 4;
+    constexpr int NBIAS_OFF = LDS_BIAS + (k_bias_off(NL) + 16 * (NCC - chunk_first(NL)) * tpc(NL)) * 4;
     const unsigned nwb = c.b_wread[NCC & 1];
     // Where the chunk's barrier sits, as a fragment index: TAIL fragments before the end of the chunk.
     constexpr int TAIL = 3;
@@ -479,7 +497,7 @@ __host__ __device__ constexpr int prev_layer(int L, int C) { return C > 0 ? L : 
 __host__ __device__ constexpr int prev_pair(int L, int C) {
     // pending pair when chunk (L, C) starts: same layer -> the last pair of chunk C-1; else the previous
     // layer's last pair (L8 ends with its lone sigma tile, marked as pair 8)
-    return C > 0 ? C * tpc(L) / 2 - 1 : (L > 0 ? (L - 1 == 8 ? 8 : b16_mt(L - 1) / 2 - 1) : 0);
+    return C > 0 ? C * tpc(L) / 2 - 1 : (L > 0 ? (L - 1 == 8 ? 8 : k_mt(L - 1) / 2 - 1) : 0);
 }
 
 template <int L, int SAVE, int... Cs>
@@ -628,9 +646,12 @@ __device__ __forceinline__ void run_tile(const Ctx& c, const MlpArgs& a, long lo
     run_layer<5, SAVE>(c, st, st.X, st.Y);
     run_layer<6, SAVE>(c, st, st.Y, st.X);
     run_layer<7, SAVE>(c, st, st.X, st.Y);
+    // folded (fp16): layer 8 is the sigma tile alone and writes no fragment, the colour layer reads h8 where layer 7 left it
+    ex8 (&c_in)[NCB][8] = FOLD ? st.Y : st.X;
+    ex8 (&c_out)[NCB][8] = FOLD ? st.X : st.Y;
     run_layer<8, SAVE>(c, st, st.Y, st.X);
-    run_layer<9, SAVE>(c, st, st.X, st.Y);
-    run_layer<10, SAVE>(c, st, st.Y, st.X);
+    run_layer<9, SAVE>(c, st, c_in, c_out);
+    run_layer<10, SAVE>(c, st, c_out, c_in);
     epilogue_piece<10, 0>(0, st.pend, st.X, st);     // the rgb tile is still pending
     for (int cb_ = 1; cb_ < NCB; ++cb_) epilogue_piece<10, 0>(4 * cb_, st.pend, st.X, st);
 }
@@ -691,7 +712,7 @@ __device__ __forceinline__ void kernel_body(const MlpArgs& a, long long ntiles) 
         constexpr int F0 = chunk_tiles(0) * (layer_desc(0).chain_k / 32 + layer_desc(0).extra_slots / 32);
 #pragma unroll
         for (int f = 0; f < 4 && f < F0; ++f) wf.a[f] = lds_load<ex8>(c.b_wread[0], f * 1024);
-        wf.bias0 = lds_load<f32x4>(c.b_bias, LDS_BIAS + b16_bias_off(0) * 4);
+        wf.bias0 = lds_load<f32x4>(c.b_bias, LDS_BIAS + k_bias_off(0) * 4);
     }
 
     if constexpr (!COMP) {
@@ -725,7 +746,7 @@ __device__ __forceinline__ void kernel_body(const MlpArgs& a, long long ntiles) 
         const long long B = a.P / a.N;
         const long long r_lo = (long long)blockIdx.x * B / gridDim.x, r_hi = ((long long)blockIdx.x + 1) * B / gridDim.x;
         const long long range_base = r_lo * a.N;
-        const int n_pts = (int)((r_hi - r_lo) * a.N);                 // < 2^31: the launcher splits larger calls
+        const int n_pts = (int)((r_hi - r_lo) * a.N);                 // < 2^31: the launcher returns -2 otherwise
         const nerf_composite::RayOut out{a.rgb, a.disp, a.alpha, a.acc, a.w, a.pixels};
         int next_ray = 0, n_complete = 0;                             // rays composited / completely in the ring (uniform)
         for (int q_tile = 0; q_tile < n_pts; q_tile += TILE_PTS) {

@@ -15,6 +15,17 @@
 //   L8      256 (h8)                      -> 288  none   rows 0..255 layers_2, row 256 sigma_fc, rest 0
 //   L9      256 (h9) + posd 32 slots      -> 128  relu   color_fc.0        [h ; d]
 //   L10     128                           -> 32   none   rows 0..2 color_fc.2, rest 0
+//
+// The fp16 inference kernels run a FOLDED view of the same table ("folded view" below): layers_2 has no
+// activation behind it and h9 feeds color_fc.0 alone, so Wc[:, :256] (W2 h8 + b2) = (Wc[:, :256] W2) h8 +
+// Wc[:, :256] b2 and the 256x256 product per point is done once per weight update, by the packer:
+//
+//   L0..L7  as above
+//   L8      256 (h8)                      -> 16   none   row tile 16 of L8 alone: row 256 sigma_fc, rest 0
+//   L9      256 (h8) + posd 32 slots      -> 128  relu   [Wc[:, :256] W2 | Wc[:, 256:]], bias bc + Wc[:, :256] b2
+//   L10     as above
+//
+// bf16, fp32, training and the sigma-only kernel (density.hip) use the unfolded table.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -174,6 +185,39 @@ constexpr int B16_STATUS_BYTES = 256;
 constexpr int NERF_STATUS_WORD_NONFINITE = 0, NERF_STATUS_WORD_WEIGHT_RANGE = 1;
 constexpr long long B16_IMAGE_BYTES = B16_STATUS_OFF + B16_STATUS_BYTES;
 static_assert(B16_STATUS_OFF % 16 == 0, "aligned status block");
+
+// ---- folded view of the packed fp16 image (fp16 inference kernels, mlp_bf16_16.hip built with -DNERF_HALF) ----------
+// Same bytes, same offsets of every layer, of the bias table and of the status block as above; what differs is what the
+// fp16 packer (pack.hip, NERF_AMD_FP16) puts into the colour layer and which tiles the kernels stream:
+//   * L9's chain fragments (k-steps 0..7) hold Wf = Wc[:, :256] W2 instead of Wc[:, :256] -- the k order is the same,
+//     h8's accumulators sit where h9's did (chain_feat_b16) -- and its bias rows hold bc + Wc[:, :256] b2;
+//   * of L8 the kernels stream row tile 16 (sigma_fc) only.  Its 16 layers_2 tiles (128 KiB) stay FILLED with
+//     layers_2 as in the bf16 image; no fp16 kernel reads them.
+constexpr int FOLD_SIGMA_TILE = 16;                                  // L8's 16-row tile that holds row 256 (sigma_fc)
+NL_HD constexpr int fold_rt0(int L) { return L == 8 ? FOLD_SIGMA_TILE : 0; }     // first 16-row tile streamed
+NL_HD constexpr int fold_mt(int L) { return L == 8 ? 1 : b16_mt(L); }            // 16-row tiles streamed
+NL_HD constexpr int fold_layer_off_kib(int L) { return b16_layer_off_kib(L) + fold_rt0(L) * b16_ks(L); }
+NL_HD constexpr int fold_bias_off(int L) { return b16_bias_off(L) + fold_rt0(L) * 16; }
+// padded multiply-accumulates per point: 600,064 unfolded, 65,536 (layers_2) fewer folded
+NL_HD constexpr int b16_padded_macs(bool fold) {
+    int m = 0;
+    for (int L = 0; L < NUM_LAYERS; ++L) m += (fold ? fold_mt(L) : b16_mt(L)) * 16 * layer_k(L);
+    return m;
+}
+static_assert(b16_padded_macs(false) == 600064 && b16_padded_macs(true) == 600064 - 65536, "padded MACs per point");
+// Wf[row][col] and the folded bias, fp32, a fixed ascending-k fma chain: two packs of the same weights are bit-equal
+template <class T>
+NL_HD inline float fold_weight_at(const T* params, int row, int col) {
+    float s = 0.f;
+    for (int k = 0; k < 256; ++k) s = __builtin_fmaf(params[OFF_C0_W + row * 283 + k], params[OFF_L2_W + k * 256 + col], s);
+    return s;
+}
+template <class T>
+NL_HD inline float fold_bias_at(const T* params, int row) {
+    float s = 0.f;
+    for (int k = 0; k < 256; ++k) s = __builtin_fmaf(params[OFF_C0_W + row * 283 + k], params[OFF_L2_B + k], s);
+    return params[OFF_C0_B + row] + s;
+}
 
 // ---- backward (dX chain) image, bf16, 16-row tiles -------------------------------
 // Training backward of the dense layers: dX = W^T dY.  The same on-chip chaining

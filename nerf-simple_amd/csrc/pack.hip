@@ -8,7 +8,7 @@ using namespace nerf_layout;
 namespace {
 
 // 16-bit image (bf16 or fp16), 16-row tiles: [tile (layer, rt)][k-step][lane][8 elements]
-template <class T>
+template <class T, bool FOLD>
 __global__ void pack_b16_kernel(const float* __restrict__ params, T* __restrict__ out, unsigned* __restrict__ status) {
     const long long total = (long long)B16_WEIGHT_KIB * 512;
     for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
@@ -20,11 +20,15 @@ __global__ void pack_b16_kernel(const float* __restrict__ params, T* __restrict_
         const int rt = rel / b16_ks(L), s = rel % b16_ks(L);
         const int lane = (int)(e >> 3) & 63, j = (int)e & 7;
         const int row = 16 * rt + (lane & 15), g = lane >> 4;
-        const float wv = weight_at(params, L, row, src_col_b16(L, s, g, j));
+        const int col = src_col_b16(L, s, g, j);
+        // fp16 image: the colour layer's chain part is folded with layers_2 (nerf_layout.h, folded view); every thread
+        // forms its own 256-term dot product, 8.4 M fused multiply-adds per pack
+        const float wv = (FOLD && L == 9 && s < layer_desc(9).chain_k / 32) ? fold_weight_at(params, row, col)
+                                                                            : weight_at(params, L, row, col);
         const T cv = (T)wv;
         out[e] = cv;
-        // a weight that is not finite in the operand type -- beyond its range (fp16: |w| > 65504), or NaN / inf to
-        // begin with (a diverged run): sticky flag (the status block was zeroed by pack_bias_kernel, launched in front
+        // a weight that is not finite in the operand type -- beyond its range (fp16: |w| > 65504; a folded element
+        // likewise, whatever its factors are), or NaN / inf to begin with (a diverged run): sticky flag (the status block was zeroed by pack_bias_kernel, launched in front
         // of this kernel)
         if (!(__builtin_fabsf((float)cv) < __builtin_inff())) status[NERF_STATUS_WORD_WEIGHT_RANGE] = 1u;
     }
@@ -71,13 +75,15 @@ __global__ void pack_f32_kernel(const float* __restrict__ params, float* __restr
 
 // bias table: natural row order, 16 rows per tile (the 16-bit and the f32 kernels share it)
 // status != NULL (16-bit images): also zero the status block behind the bias table
-__global__ void pack_bias_kernel(const float* __restrict__ params, float* __restrict__ out, unsigned* __restrict__ status) {
+// fold (fp16 image): the colour layer's rows hold bc + Wc[:, :256] b2 (nerf_layout.h, folded view)
+__global__ void pack_bias_kernel(const float* __restrict__ params, float* __restrict__ out, unsigned* __restrict__ status, int fold) {
     static_assert(B16_BIAS_FLOATS == F32_BIAS_FLOATS, "one bias table layout");
     if (status && blockIdx.x == 0 && threadIdx.x < B16_STATUS_BYTES / 4) status[threadIdx.x] = 0u;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < F32_BIAS_FLOATS; e += gridDim.x * blockDim.x) {
         int L = 0;
         while (L + 1 < NUM_LAYERS && e >= f32_bias_off(L + 1)) ++L;
-        out[e] = bias_at(params, L, e - f32_bias_off(L));
+        const int row = e - f32_bias_off(L);
+        out[e] = (fold && L == 9 && row < layer_desc(9).rows) ? fold_bias_at(params, row) : bias_at(params, L, row);
     }
 }
 
@@ -162,12 +168,12 @@ extern "C" int nerf_amd_launch_pack(const float* params, void* packed, int preci
     if (precision == 1 || precision == 2) {
         unsigned* status = reinterpret_cast<unsigned*>(img + B16_STATUS_OFF);
         hipLaunchKernelGGL(pack_bias_kernel, dim3(10), dim3(256), 0, stream, params,
-                           reinterpret_cast<float*>(img + (long long)B16_WEIGHT_KIB * 1024), status);
+                           reinterpret_cast<float*>(img + (long long)B16_WEIGHT_KIB * 1024), status, precision == 2 ? 1 : 0);
         if (precision == 1)
-            hipLaunchKernelGGL(pack_b16_kernel<__bf16>, dim3(1024), dim3(256), 0, stream, params,
+            hipLaunchKernelGGL((pack_b16_kernel<__bf16, false>), dim3(1024), dim3(256), 0, stream, params,
                                reinterpret_cast<__bf16*>(img), status);
         else
-            hipLaunchKernelGGL(pack_b16_kernel<_Float16>, dim3(1024), dim3(256), 0, stream, params,
+            hipLaunchKernelGGL((pack_b16_kernel<_Float16, true>), dim3(1024), dim3(256), 0, stream, params,
                                reinterpret_cast<_Float16*>(img), status);
     } else if (precision == 3) {
         // training backward image (bf16)
@@ -177,7 +183,7 @@ extern "C" int nerf_amd_launch_pack(const float* params, void* packed, int preci
         hipLaunchKernelGGL(pack_f32_kernel, dim3(1024), dim3(256), 0, stream, params,
                            reinterpret_cast<float*>(img));
         hipLaunchKernelGGL(pack_bias_kernel, dim3(10), dim3(256), 0, stream, params,
-                           reinterpret_cast<float*>(img + (long long)F32_WEIGHT_KIB * 1024), static_cast<unsigned*>(nullptr));
+                           reinterpret_cast<float*>(img + (long long)F32_WEIGHT_KIB * 1024), static_cast<unsigned*>(nullptr), 0);
     }
     return (int)hipGetLastError();
 }

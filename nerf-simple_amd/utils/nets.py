@@ -123,8 +123,11 @@ class Nerf(nn.Module):
     weight images and the fused training kernels concerns the default shape.
 
     precision: 'fp16' (fp16 MFMA operands, fp32 accumulate; default: 11-bit mantissa,
-               hidden activations must stay below 65504), 'bf16' (bf16 operands: same
-               cycles, 5 % faster clock, 8-bit mantissa) or 'fp32' (exact-f32 MFMA).  Keyword-only
+               hidden activations must stay below 65504; layers_2, which has no activation behind
+               it, is folded into color_fc.0 when the weights are packed -- Wc[:, :256] W2 in fp32, then
+               rounded to fp16, flagged like a weight beyond 65504 if it does not fit -- so these kernels
+               run one 256x256 layer less than the others), 'bf16' (bf16 operands, unfolded: 12 % more
+               MFMAs than fp16 at a clock about 5 % higher, 8-bit mantissa) or 'fp32' (exact-f32 MFMA).  Keyword-only
                superset of the reference signature.  It selects the INFERENCE kernel;
                with gradients enabled 'bf16' and 'fp16' modules both run the bf16
                training kernels (training.py); 'fp32' trains exactly, layer by layer (utils/generic_mlp.py).

@@ -5,7 +5,8 @@
     python tools/stamp_tiles.py --run          # on the MI355X: 40 launches of 800x800x128 fp16, print the table
 
 The shipped kernels carry no stamp.  --build copies nerf-simple_amd/csrc to .scratch/stamp/csrc, inserts
-`s_memtime` reads at the tile's phase boundaries (prologue, each of the 11 layers, ring barrier, compositing
+`s_memtime` reads at the tile's phase boundaries (prologue, each of the 11 layers -- in the fp16 build that is
+run, layer 8 is the one-tile sigma layer and layer 9 the folded colour layer --, ring barrier, compositing
 block and inside it) and a debug symbol the values are copied out of, and builds a second libnerf_amd.so there;
 every insertion point is matched literally and must occur exactly once, so the tool fails loudly when the kernel
 source has moved on.  Stamps are kept in scalar registers and written out after the tile (waves 0 and 5 of every
@@ -138,7 +139,10 @@ def run():
     buf = np.zeros(256 * 2 * ST_TILES * ST_N, dtype=np.uint64)
     _lib.check(h.nerf_amd_debug_read_stamps(buf.ctypes.data_as(vp)), "stamps")
     s = buf.reshape(256, 2, ST_TILES, ST_N).astype(np.int64)
-    names = ["prologue"] + [f"layer {L}" for L in range(11)] + ["outputs to ring + barrier", "compositing block"]
+    # the stamped launch is the fp16 kernel, which runs the folded layer table (csrc/nerf_layout.h): layer 8 is the
+    # sigma tile alone, layer 9 the colour layer fed by h8 through Wc[:, :256] W2
+    names = (["prologue"] + [f"layer {L}" for L in range(8)] + ["layer 8 (sigma tile)", "layer 9 (colour, folded)", "layer 10"]
+             + ["outputs to ring + barrier", "compositing block"])
     for w, wn in ((0, "wave 0"), (1, "wave 5")):
         d = np.diff(s[:, w, :, :15], axis=-1)
         period = s[:, w, 1:, 0] - s[:, w, :-1, 0]
