@@ -47,11 +47,19 @@ def _round_dy(y):
     return y
 
 
-def emulated_forward(sd, v, Lp=10, Ld=4):
-    """Nerf.forward with the bf16 training kernels' numerics (forward and backward), fp32: [P,6] -> [P,4]."""
+def emulated_forward(sd, v, Lp=10, Ld=4, train_heads=False):
+    """Nerf.forward with the bf16 training kernels' numerics (forward and backward), fp32: [P,6] -> [P,4].
+
+    ``train_heads`` adds the two roundings that only the PARAMETER gradients see (tests/train_chain_model.py): d_raw is
+    rounded to bf16 where it enters the dX chain (csrc/mlp_bwd_16.hip bx_rgb / bx_sig) and in the two head products
+    (csrc/dw_gemm.hip pack_draw_kernel: sigma_fc.0.weight, color_fc.2.weight); the head biases sum the fp32 d_raw.  The
+    input-gradient tests were written against the emulation without it."""
     r = _RoundBf16.apply
 
     def lin(h, name, dy=True):
+        if train_heads and not dy:
+            y = _round_dy(F.linear(r(h), r(sd[name + ".weight"])))      # weight and input see bf16(d_raw) ...
+            return y + sd[name + ".bias"]                               # ... the bias the fp32 one
         y = F.linear(r(h), r(sd[name + ".weight"]), sd[name + ".bias"])
         return _round_dy(y) if dy else y
 

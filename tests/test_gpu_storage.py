@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 import torch
 
+from train_chain_model import bf16_to_f32, decode_bf16_layers     # the bf16 form's layout lives with its model
+
 pytestmark = pytest.mark.gpu
 
 
@@ -36,20 +38,6 @@ def dev():
 E4M3 = np.array([np.nan if (v & 0x7f) == 0x7f else
                  (-1.0 if v & 0x80 else 1.0) * ((v & 7) / 8.0 * 2.0 ** -6 if (v >> 3) & 15 == 0 else (1 + (v & 7) / 8.0) * 2.0 ** (((v >> 3) & 15) - 7))
                  for v in range(256)])
-
-
-def bf16_to_f32(u16):
-    return (u16.astype(np.uint32) << 16).view(np.float32)
-
-
-def decode_bf16_layers(host, P):
-    """[10][P, 256] float32 from the point-blocked bf16 buffer (nerf_layout.h act_elem_offset)."""
-    nt = (P + 255) // 256
-    out = []
-    for L in range(10):
-        blk = host[L * nt * 131072:(L + 1) * nt * 131072].view(np.uint16).reshape(nt, 32, 256, 8)
-        out.append(bf16_to_f32(blk.transpose(0, 2, 1, 3).reshape(nt * 256, 256)[:P]))
-    return out
 
 
 def decode_e4m3_layers(host, P):
@@ -70,15 +58,17 @@ def decode_e4m3_layers(host, P):
     return vals, raws, exps
 
 
-def run_chain(dev, synthetic, B, N, e4m3, kind="default", seed=4, buckets=False):
+def run_chain(dev, synthetic, B, N, e4m3, kind="default", seed=4, buckets=False, sd=None, d_raw_in=None):
     """Forward (saving), compositor backward, dX chain, dW through the C ABI in either storage form; returns the host
-    copies of everything."""
+    copies of everything.  ``sd``: a state dict to run instead of the synthetic one of ``kind``; ``d_raw_in`` [P, 4]: an
+    upstream gradient that replaces the compositor's behind its launch (at N = 1 the reference composites an empty sample
+    axis, so the compositor's own d_raw is identically zero there)."""
     from nerf_simple_amd import _lib
     from nerf_simple_amd.utils.nets import Nerf
     from nerf_simple_amd.utils.xyz import camera_rays, spherical_to_pose
     lib = _lib.lib()
     net = Nerf().to(dev)
-    net.load_state_dict({k: torch.as_tensor(v) for k, v in synthetic.synthetic_state_dict(5, kind).items()})
+    net.load_state_dict({k: torch.as_tensor(v) for k, v in (sd or synthetic.synthetic_state_dict(5, kind)).items()})
     side = int(np.ceil(np.sqrt(B)))
     pose = torch.from_numpy(spherical_to_pose(4, -30, 0)).float()
     rays = camera_rays([pose], [side, side, synthetic.focal_from_fov(side)]).float().contiguous()[:B].contiguous().to(dev)
@@ -106,6 +96,8 @@ def run_chain(dev, synthetic, B, N, e4m3, kind="default", seed=4, buckets=False)
     ck(lib.nerf_amd_mlp_forward_train(ptr(rays), ptr(u), ptr(tbins), ptr(packed), _lib.FLAG_STORE_E4M3 if e4m3 else 0, 0, 0,
                                       ptr(raw), ptr(ts), ptr(acts), B, N, st), "forward")
     ck(lib.nerf_amd_volume_render_mse_backward(ptr(raw), ptr(ts), ptr(rays), ptr(gt), ptr(rgb), ptr(d_raw), B, N, st), "composite")
+    if d_raw_in is not None:
+        d_raw.copy_(d_raw_in.to(dev).reshape(B, N, 4))
     ck(lib.nerf_amd_param_gradients_begin(ptr(d_raw), ptr(scratch), ptr(grads), P, st), "begin")
     if e4m3:
         ck(lib.nerf_amd_mlp_backward_e4m3(ptr(d_raw), ptr(image), ptr(acts), ptr(dys), P, st), "backward")
