@@ -565,6 +565,58 @@ int nerf_amd_marching_cubes_emit(const float* sigma, int64_t nx, int64_t ny, int
                                  const float* h_step, void* workspace, float* verts, float* normals, int32_t* faces,
                                  int64_t max_verts, int64_t max_faces, void* stream);
 
+/* ---- occupancy grid and the masked render: skip the samples that lie in empty space (inference; not in the reference) ---
+ * Grid: [nx, ny, nz] grid points (the axes of nerf_amd_density_grid: x_a(i) = fl(lo_a + fl(i step_a))) make
+ * C = (nx - 1, ny - 1, nz - 1) cells; cell (i, j, k) spans points i .. i + 1, j .. j + 1, k .. k + 1.  Semantics
+ * (tests/occupancy_model.py restates them in numpy, bit for bit):
+ *   - packing: one bit per cell, z fastest, 32 cells per uint32: cell (i, j, k) is bit (k & 31) of word
+ *     (i Cy + j) Wz + (k >> 5), Wz = ceil(Cz / 32); every z row is padded to a whole word and the padding bits are zero.
+ *     nerf_amd_occupancy_grid_words = Cx Cy Wz.  A set bit means live.
+ *   - from a sigma volume: a cell is DEAD iff every corner of every cell within `dilate` cells of it (Chebyshev distance,
+ *     clipped at the grid's edge) has sigma <= level; a NaN corner therefore makes it live.  0 <= dilate <= 15.
+ *   - cell of a point, per axis, in float32 with separately rounded operations: c = floor(fl(fl(x - lo) * inv_step)), where
+ *     h_inv_step is fl32(1 / step) formed on the host.  c < 0, c >= C or a NaN coordinate on any axis: the point is
+ *     OUTSIDE, and is live unless NERF_AMD_OUTSIDE_EMPTY is given.  Otherwise it is live iff its cell's bit is set.
+ *   - the sample positions ts[B,N] and points o + d t of a ray are exactly those of nerf_amd_query_points /
+ *     nerf_amd_render_forward for the same (u, tbins, flags, seed, ray_id0); no stage reads or writes them in memory.
+ *   - mask[B, ceil(N / 64)] uint64: bit (i & 63) of word i >> 6 of a ray is set iff sample i is live (bits >= N are zero).
+ *     offsets[B + 1] int64: exclusive scan of the rays' live counts; offsets[B] = the live count P'.
+ *   - the masked render is volume_render over all N samples with the network's output replaced by (0, 0, 0, -inf) at a dead
+ *     sample: alpha = w = 0 exactly there, the delta of a live sample is still the distance to the NEXT SAMPLE, dead or not.
+ *     It equals nerf_amd_query_points -> nerf_amd_mlp_forward on all B N points -> dead rows overwritten ->
+ *     nerf_amd_volume_render_rays (_pixels) bit for bit.  A ray with no live sample: rgb = acc = 0, disparity NaN.
+ * N <= 768 and B <= 2^32 (NERF_AMD_EUNSUP beyond).  No atomics: fixed partitions, hand-written scans, same bytes every run.
+ *
+ * nerf_amd_occupancy_from_density: bits <- sigma[nx, ny, nz] (fp32, C order), level, dilate.
+ * nerf_amd_occupancy_from_mask:    bits <- cells[Cx, Cy, Cz], one byte per cell (non-zero = live).
+ * nerf_amd_occupancy_mark: stages mark + scan.  flags: the jitter flags, plus NERF_AMD_OUTSIDE_EMPTY.  h_lo[3], h_inv_step[3]:
+ *   HOST floats.  Writes mask, offsets[B + 1] and, if not NULL, *live = P' (DEVICE int64: the host reads it to size the next
+ *   two buffers -- the one synchronisation of a masked render).  workspace: nerf_amd_occupancy_workspace_bytes(B), 16-aligned.
+ * nerf_amd_occupancy_points: pts[P', 6] = the rows of nerf_amd_query_points of the live samples, ray-major, sample order
+ *   inside a ray: the input of nerf_amd_mlp_forward.  Writes row r only if r < max_points.
+ * nerf_amd_volume_render_masked(_pixels): raw_live[P', 4] = the network's output on those points (NULL allowed when P' = 0);
+ *   outputs as nerf_amd_volume_render_rays (alpha / w [B, N] or NULL) / nerf_amd_volume_render_pixels. */
+#define NERF_AMD_OUTSIDE_EMPTY 16u /* nerf_amd_occupancy_mark only: a sample outside the grid is dead (default: live) */
+int64_t nerf_amd_occupancy_grid_words(int64_t nx, int64_t ny, int64_t nz);
+int nerf_amd_occupancy_from_density(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, int dilate,
+                                    uint32_t* bits, void* stream);
+int nerf_amd_occupancy_from_mask(const uint8_t* cells, int64_t nx, int64_t ny, int64_t nz, uint32_t* bits, void* stream);
+int64_t nerf_amd_occupancy_mask_words(int64_t B, int N);
+int64_t nerf_amd_occupancy_workspace_bytes(int64_t B);
+int nerf_amd_occupancy_mark(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
+                            int64_t ray_id0, const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, const float* h_lo,
+                            const float* h_inv_step, uint64_t* mask, int64_t* offsets, int64_t* live, void* workspace,
+                            int64_t B, int N, void* stream);
+int nerf_amd_occupancy_points(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
+                              int64_t ray_id0, const uint64_t* mask, const int64_t* offsets, float* pts, int64_t max_points,
+                              int64_t B, int N, void* stream);
+int nerf_amd_volume_render_masked(const float* raw_live, const float* rays, const float* u, const float* tbins, uint32_t flags,
+                                  uint64_t seed, int64_t ray_id0, const uint64_t* mask, const int64_t* offsets, float* rgb,
+                                  float* disp, float* alpha, float* acc, float* w, int64_t B, int N, void* stream);
+int nerf_amd_volume_render_masked_pixels(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                         uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                         const int64_t* offsets, float* pixels, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

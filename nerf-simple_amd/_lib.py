@@ -21,6 +21,7 @@ LIB_PATH = os.path.join(_HERE, "libnerf_amd.so")
 F32, BF16, FP16, BF16_BWD = 0, 1, 2, 3
 FLAG_TS_GIVEN, FLAG_DEVICE_RNG, FLAG_SEED_IN_MEMORY = 1, 2, 4
 FLAG_STORE_E4M3 = 8          # nerf_amd_mlp_forward_train: the 8-bit storage form of the saved activations
+FLAG_OUTSIDE_EMPTY = 16      # nerf_amd_occupancy_mark: a sample outside the occupancy grid is dead
 STATUS_NONFINITE, STATUS_WEIGHT_RANGE = 1, 2
 _PRECISIONS = {"fp32": F32, "f32": F32, "float32": F32, F32: F32,
                "bf16": BF16, "bfloat16": BF16, BF16: BF16,
@@ -116,6 +117,17 @@ _SIGNATURES = {
     "nerf_amd_marching_cubes_count": (_i32, [_vp, _i64, _i64, _i64, ctypes.c_float, _vp, _vp, _vp]),
     "nerf_amd_marching_cubes_emit": (_i32, [_vp, _i64, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _i64, _i64, _vp]),
+    "nerf_amd_occupancy_grid_words": (_i64, [_i64, _i64, _i64]),
+    "nerf_amd_occupancy_from_density": (_i32, [_vp, _i64, _i64, _i64, ctypes.c_float, _i32, _vp, _vp]),
+    "nerf_amd_occupancy_from_mask": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "nerf_amd_occupancy_mask_words": (_i64, [_i64, _i32]),
+    "nerf_amd_occupancy_workspace_bytes": (_i64, [_i64]),
+    "nerf_amd_occupancy_mark": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _i64, _i32, _vp]),
+    "nerf_amd_occupancy_points": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "nerf_amd_volume_render_masked": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                             _i32, _vp]),
+    "nerf_amd_volume_render_masked_pixels": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

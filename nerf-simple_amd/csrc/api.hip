@@ -70,6 +70,15 @@ long long nerf_amd_mc_workspace_bytes(long long);
 int nerf_amd_launch_mc_count(const float*, long long, long long, long long, float, void*, long long*, hipStream_t);
 int nerf_amd_launch_mc_emit(const float*, long long, long long, long long, float, const float*, const float*, void*, float*, float*,
                             int*, long long, long long, hipStream_t);
+int nerf_amd_occ_max_n(void);
+int nerf_amd_occ_max_dilate(void);
+long long nerf_amd_occ_workspace_bytes(long long);
+int nerf_amd_launch_occ_bits(const float*, long long, long long, long long, float, int, unsigned*, hipStream_t);
+int nerf_amd_launch_occ_pack(const unsigned char*, long long, long long, long long, unsigned*, hipStream_t);
+int nerf_amd_launch_occ_mark(const MlpArgs*, const unsigned*, long long, long long, long long, const float*, const float*, int,
+                             unsigned long long*, long long*, long long*, void*, long long, hipStream_t);
+int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const long long*, float*, long long, long long, hipStream_t);
+int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
 }
 
 namespace {
@@ -113,6 +122,23 @@ inline DensityArgs grid_args(const float* h_lo, const float* h_step, int64_t nx,
 }
 int launch_density(const DensityArgs& a, int precision, hipStream_t s) {
     return precision == NERF_AMD_FP16 ? nerf_amd_launch_density_f16(&a, s) : nerf_amd_launch_density_bf16(&a, s);
+}
+// the rays, jitter and sizes every stage of the masked render takes (the mark / emit / composite kernels form the sample
+// positions themselves): 0 = go on, otherwise the code to return
+constexpr int64_t OCC_MAX_RAYS = 1ll << 32;
+int occ_rays(const float* rays, const float* u, const float* tbins, uint32_t flags, int64_t B, int N) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
+    if (N > nerf_amd_occ_max_n() || B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (B > 0 && !rays) return NERF_AMD_EINVAL;
+    return 0;
+}
+MlpArgs occ_args(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0, int64_t B,
+                 int N) {
+    MlpArgs a{};
+    a.rays = rays; a.u = u; a.tbins = tbins;
+    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    return a;
 }
 }  // namespace
 
@@ -814,6 +840,92 @@ int nerf_amd_marching_cubes_emit(const float* sigma, int64_t nx, int64_t ny, int
     if ((max_verts > 0 && !verts) || (max_faces > 0 && !faces) || ((uintptr_t)workspace & 15)) return NERF_AMD_EINVAL;
     return nerf_amd_launch_mc_emit(sigma, nx, ny, nz, level, h_lo, h_step, workspace, verts, normals, faces, max_verts, max_faces,
                                    S(stream));
+}
+
+// ---- occupancy grid and the masked render (not in the reference) -------------------------------------------------------
+int64_t nerf_amd_occupancy_grid_words(int64_t nx, int64_t ny, int64_t nz) {
+    if (bad_grid(nx, ny, nz)) return NERF_AMD_EINVAL;
+    return (nx - 1) * (ny - 1) * ((nz - 1 + 31) / 32);
+}
+
+int nerf_amd_occupancy_from_density(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, int dilate,
+                                    uint32_t* bits, void* stream) {
+    if (bad_grid(nx, ny, nz) || dilate < 0 || !sigma || !bits) return NERF_AMD_EINVAL;
+    if (dilate > nerf_amd_occ_max_dilate()) return NERF_AMD_EUNSUP;
+    return nerf_amd_launch_occ_bits(sigma, nx, ny, nz, level, dilate, bits, S(stream));
+}
+
+int nerf_amd_occupancy_from_mask(const uint8_t* cells, int64_t nx, int64_t ny, int64_t nz, uint32_t* bits, void* stream) {
+    if (bad_grid(nx, ny, nz) || !cells || !bits) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_occ_pack(cells, nx - 1, ny - 1, nz - 1, bits, S(stream));
+}
+
+int64_t nerf_amd_occupancy_mask_words(int64_t B, int N) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (N > nerf_amd_occ_max_n() || B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
+    return B * (((int64_t)N + 63) / 64);
+}
+
+int64_t nerf_amd_occupancy_workspace_bytes(int64_t B) {
+    if (B < 0) return NERF_AMD_EINVAL;
+    if (B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
+    return nerf_amd_occ_workspace_bytes(B);
+}
+
+int nerf_amd_occupancy_mark(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0,
+                            const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, const float* h_lo, const float* h_inv_step,
+                            uint64_t* mask, int64_t* offsets, int64_t* live, void* workspace, int64_t B, int N, void* stream) {
+    const int rc = occ_rays(rays, u, tbins, flags & ~NERF_AMD_OUTSIDE_EMPTY, B, N);
+    if (rc) return rc;
+    if (bad_grid(nx, ny, nz) || !bits || !h_lo || !h_inv_step || !offsets || !workspace) return NERF_AMD_EINVAL;
+    if (B > 0 && !mask) return NERF_AMD_EINVAL;
+    if (((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)live & 7) || ((uintptr_t)workspace & 15)) return NERF_AMD_EINVAL;
+    const MlpArgs a = occ_args(rays, u, tbins, flags & ~NERF_AMD_OUTSIDE_EMPTY, seed, ray_id0, B, N);
+    return nerf_amd_launch_occ_mark(&a, bits, nx, ny, nz, h_lo, h_inv_step, (flags & NERF_AMD_OUTSIDE_EMPTY) ? 0 : 1,
+                                    reinterpret_cast<unsigned long long*>(mask), reinterpret_cast<long long*>(offsets),
+                                    reinterpret_cast<long long*>(live), workspace, B, S(stream));
+}
+
+int nerf_amd_occupancy_points(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0,
+                              const uint64_t* mask, const int64_t* offsets, float* pts, int64_t max_points, int64_t B, int N,
+                              void* stream) {
+    const int rc = occ_rays(rays, u, tbins, flags, B, N);
+    if (rc) return rc;
+    if (max_points < 0) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (!mask || !offsets || (max_points > 0 && !pts) || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7)) return NERF_AMD_EINVAL;
+    const MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    return nerf_amd_launch_occ_emit(&a, reinterpret_cast<const unsigned long long*>(mask), reinterpret_cast<const long long*>(offsets),
+                                    pts, max_points, B, S(stream));
+}
+
+int nerf_amd_volume_render_masked(const float* raw_live, const float* rays, const float* u, const float* tbins, uint32_t flags,
+                                  uint64_t seed, int64_t ray_id0, const uint64_t* mask, const int64_t* offsets, float* rgb,
+                                  float* disp, float* alpha, float* acc, float* w, int64_t B, int N, void* stream) {
+    const int rc = occ_rays(rays, u, tbins, flags, B, N);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    if (!mask || !offsets || !rgb || !disp || !acc || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)raw_live & 15))
+        return NERF_AMD_EINVAL;
+    MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.rgb = rgb; a.disp = disp; a.alpha = alpha; a.acc = acc; a.w = w;
+    return nerf_amd_launch_occ_composite(&a, reinterpret_cast<const unsigned long long*>(mask),
+                                         reinterpret_cast<const long long*>(offsets), raw_live, B, S(stream));
+}
+
+int nerf_amd_volume_render_masked_pixels(const float* raw_live, const float* rays, const float* u, const float* tbins, uint32_t flags,
+                                         uint64_t seed, int64_t ray_id0, const uint64_t* mask, const int64_t* offsets, float* pixels,
+                                         int64_t B, int N, void* stream) {
+    const int rc = occ_rays(rays, u, tbins, flags, B, N);
+    if (rc) return rc;
+    if (B == 0) return 0;
+    if (!mask || !offsets || !pixels || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)raw_live & 15) ||
+        ((uintptr_t)pixels & 15))
+        return NERF_AMD_EINVAL;
+    MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.pixels = pixels;
+    return nerf_amd_launch_occ_composite(&a, reinterpret_cast<const unsigned long long*>(mask),
+                                         reinterpret_cast<const long long*>(offsets), raw_live, B, S(stream));
 }
 
 }  // extern "C"

@@ -1,0 +1,259 @@
+"""Empty-space skipping for the inference render: an occupancy grid and the masked render path.  Not in the reference.
+
+    net = Nerf().cuda(); load_checkpoint(net, "model.pth")
+    occ = occupancy_grid(net, 128, level=10.0, outside="empty")          # once per checkpoint
+    pixels = render_view(net, pose, cam_params, device_rng=True, occupancy=occ)
+    rgb, disp, alpha, acc, w = render_nerf(rays, net, 128, occupancy=occ)   # under torch.no_grad()
+
+An ``OccupancyGrid`` is one bit per cell of a regular grid over ``bounds`` (R grid points per axis, the axes of
+``mesh.grid_axes``, make R - 1 cells).  A sample of a ray is *live* iff the bit of the cell it falls in is set; a sample
+outside the grid follows the grid's ``outside`` policy ('live': the grid does not speak for what it does not cover;
+'empty': a bounded scene).  The masked render is the reference's ``volume_render`` over all N samples with the network's
+output replaced by (0, 0, 0, -inf) at every dead sample -- which contributes exactly nothing -- and the network is only
+evaluated at the live ones.  The semantics (packing, dilation rule, cell formula) are stated in include/nerf_amd.h and
+restated in numpy by tests/occupancy_model.py.
+
+Stages (csrc/occupancy.hip): mark (per-ray live masks) -> scan (offsets, live count) -> ONE host read of the live count
+-> emit (compacted query points) -> the existing points-mode forward under the fp16 range guard -> masked composite.
+Inference only, default network shape only, fp16 / bf16 / fp32.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .mesh import DEFAULT_BOUNDS, _host_f32x3, _resolution, density_grid, grid_axes
+
+_POLICIES = ("live", "empty")
+MAX_N = 768                             # samples per ray the mask layout and the masked compositor serve
+
+
+class MarkResult:
+    """What ``OccupancyGrid.mark`` found: ``mask`` [B, ceil(N/64)] int64 (bit i & 63 of word i >> 6: sample i is live),
+    ``offsets`` [B + 1] int64 (exclusive scan of the rays' live counts), ``live`` = offsets[B], a host int, and -- when
+    asked for -- ``points`` [live, 6], the compacted query points the network is evaluated at."""
+
+    def __init__(self, mask, offsets, live, B, N):
+        self.mask, self.offsets, self.live, self.B, self.N = mask, offsets, live, B, N
+        self.points = None
+
+    @property
+    def fraction(self):
+        return self.live / max(1, self.B * self.N)
+
+
+class OccupancyGrid:
+    """Packed occupancy bits on the device.  Fields: ``words`` (int32 tensor, layout of include/nerf_amd.h),
+    ``resolution`` (grid points per axis), ``bounds``, ``outside`` and ``cell_fraction`` (share of live cells).
+    Build one with ``occupancy_grid`` (from a network), ``from_density`` (from a sigma volume) or ``from_mask``."""
+
+    def __init__(self, words, resolution, bounds, outside):
+        if outside not in _POLICIES:
+            raise ValueError(f"outside must be 'live' or 'empty', got {outside!r}")
+        self.words = words
+        self.resolution = _resolution(resolution)
+        self.bounds = (tuple(float(x) for x in bounds[0]), tuple(float(x) for x in bounds[1]))
+        self.outside = outside
+        self.lo, self.step = grid_axes(self.resolution, self.bounds)
+        self.inv_step = (np.float32(1) / self.step).astype(np.float32)
+        self.cell_fraction = self._count() / float(np.prod([r - 1 for r in self.resolution]))
+        self.last_stats = None          # of the latest masked render through this grid
+
+    # ---- construction -------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_mask(cls, mask, bounds=DEFAULT_BOUNDS, *, outside="live"):
+        """mask: bool (or any integer) device tensor [Cx, Cy, Cz], one entry per CELL (non-zero = live)."""
+        if not torch.is_tensor(mask):
+            raise AssertionError("mask needs to be a torch tensor")
+        if not mask.is_cuda:
+            raise RuntimeError(f"mask must live on the GPU (got a {mask.device} tensor); this package has no CPU path")
+        if mask.dim() != 3:
+            raise RuntimeError("from_mask expects a 3-D cell mask [Cx, Cy, Cz]")
+        R = _resolution(tuple(int(c) + 1 for c in mask.shape))
+        cells = (mask != 0).to(torch.uint8).contiguous()
+        lib = _lib.lib()
+        words = torch.empty(_grid_words(lib, R), dtype=torch.int32, device=mask.device)
+        with torch.cuda.device(mask.device):
+            _lib.check(lib.nerf_amd_occupancy_from_mask(_lib.ptr(cells), *R, _lib.ptr(words), _lib.stream_ptr(mask.device)),
+                       "nerf_amd_occupancy_from_mask")
+        return cls(words, R, bounds, outside)
+
+    @classmethod
+    def from_density(cls, sigma, level, bounds=DEFAULT_BOUNDS, dilate=1, outside="live"):
+        """sigma: float32 device volume [Rx, Ry, Rz] of raw sigma on the grid POINTS (``mesh.density_grid``).  A cell is
+        dead iff every corner of every cell within ``dilate`` cells of it has sigma <= level (NaN makes it live)."""
+        _lib.require_cuda_f32(sigma, "sigma")
+        if sigma.dim() != 3:
+            raise RuntimeError("from_density expects a 3-D volume [Rx, Ry, Rz]")
+        if int(dilate) != dilate or dilate < 0:
+            raise ValueError(f"dilate must be a non-negative integer, got {dilate!r}")
+        R = _resolution(tuple(sigma.shape))
+        sigma = sigma.detach().contiguous()
+        lib = _lib.lib()
+        words = torch.empty(_grid_words(lib, R), dtype=torch.int32, device=sigma.device)
+        with torch.cuda.device(sigma.device):
+            _lib.check(lib.nerf_amd_occupancy_from_density(_lib.ptr(sigma), *R, ctypes.c_float(float(level)), int(dilate),
+                                                           _lib.ptr(words), _lib.stream_ptr(sigma.device)),
+                       "nerf_amd_occupancy_from_density")
+        return cls(words, R, bounds, outside)
+
+    # ---- inspection ---------------------------------------------------------------------------------------------------
+    def cells(self):
+        """The bits unpacked: a bool device tensor [Cx, Cy, Cz]."""
+        C = [r - 1 for r in self.resolution]
+        wz = (C[2] + 31) // 32
+        shifts = torch.arange(32, dtype=torch.int32, device=self.words.device)
+        b = (self.words.view(C[0], C[1], wz, 1) >> shifts) & 1
+        return b.view(C[0], C[1], wz * 32)[:, :, :C[2]].bool()
+
+    def _count(self):
+        shifts = torch.arange(32, dtype=torch.int32, device=self.words.device)
+        return int(((self.words.view(-1, 1) >> shifts) & 1).sum())          # padding bits are zero; one host read
+
+    def mark(self, rays, N, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0, points=False):
+        """Which samples a render of ``rays`` with these arguments evaluates: a ``MarkResult`` (with ``points=True``
+        also the compacted query points).  Jitter sources as ``render_nerf`` (u / ts explicit, the counter RNG, default
+        one reference ``torch.rand(B, N)``).  One host synchronisation."""
+        _lib.require_cuda_f32(rays, "rays")
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise RuntimeError("rays must be [B, 6]")
+        B, N = rays.size(0), int(N)
+        jit, flags, pending = _jitter(B, N, rays.device, u, ts, device_rng)
+        try:
+            rays, tbins = rays.detach().contiguous(), _tb(tn, tf, N, rays.device, flags)
+            m = _mark(self, rays, jit, tbins, flags, seed, ray_id0, N)
+            if points:
+                m.points = _points(m, rays, jit, tbins, flags, seed, ray_id0)
+            return m
+        finally:
+            if pending is not None:
+                pending.finish()
+
+
+def _jitter(B, N, dev, u, ts, device_rng):
+    """(jitter tensor or None, flags, pending generator session or None) of the render entry points' jitter arguments."""
+    from .host_rng import reference_rand
+    for name, t_ in (("ts", ts), ("u", u)):
+        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, N):
+            raise RuntimeError("u / ts must be [B, N]")
+    if ts is not None:
+        return ts.contiguous(), _lib.FLAG_TS_GIVEN, None
+    if u is not None:
+        return u.contiguous(), 0, None
+    if device_rng:
+        return None, _lib.FLAG_DEVICE_RNG, None
+    jit, pending = reference_rand(B, N, dev)
+    return jit, 0, pending
+
+
+def _grid_words(lib, R):
+    n = int(lib.nerf_amd_occupancy_grid_words(*R))
+    if n < 0:
+        raise RuntimeError(f"occupancy grid: unsupported resolution {R}")
+    return n
+
+
+def _tb(tn, tf, N, dev, flags):
+    from .rendering import _tbins
+    return None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, N, dev)
+
+
+def occupancy_grid(net, resolution=128, level=None, bounds=DEFAULT_BOUNDS, *, dilate=1, outside="live", precision=None):
+    """``OccupancyGrid.from_density(density_grid(net, resolution, bounds), level, bounds, dilate, outside)``.
+
+    level is in raw-sigma units, like ``extract_mesh``'s, and has NO default: what a level costs in image quality depends
+    on the trained scene, so the caller states it.  Corner sampling cannot see what the network
+    does inside a cell, which is why ``dilate`` defaults to 1."""
+    if level is None:
+        raise TypeError("occupancy_grid() needs a level (raw-sigma units): there is no default, see DESIGN.md section 12")
+    sigma = density_grid(net, resolution, bounds, precision=precision)
+    return OccupancyGrid.from_density(sigma, level, bounds, dilate, outside)
+
+
+def check_renderable(occupancy, net, rays_require_grad):
+    """The masked render's preconditions; raises before any jitter is drawn."""
+    from .nets import Nerf
+    if not isinstance(occupancy, OccupancyGrid):
+        raise TypeError("occupancy must be an OccupancyGrid (utils/occupancy.py)")
+    if not (isinstance(net, Nerf) and net._fused_ok()):
+        raise RuntimeError("the masked render (occupancy=) serves the default Nerf(10, 4, 256) only: other network sizes "
+                           "and foreign nets are not supported; render without occupancy")
+    if torch.is_grad_enabled() and (rays_require_grad or any(p.requires_grad for p in net.parameters())):
+        raise RuntimeError("the masked render (occupancy=) is inference only: call it under torch.no_grad()")
+
+
+def _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N):
+    B, dev = rays.size(0), rays.device
+    if occ.words.device != dev:
+        raise RuntimeError(f"the occupancy grid lives on {occ.words.device}, the rays on {dev}")
+    lib = _lib.lib()
+    nwords = int(lib.nerf_amd_occupancy_mask_words(B, N))
+    if nwords < 0:
+        raise RuntimeError(f"the masked render serves 1 <= N <= {MAX_N} samples per ray, got N = {N}")
+    mask = torch.empty((B, (N + 63) // 64), dtype=torch.int64, device=dev)
+    offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+    mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.nerf_amd_occupancy_mark(
+            _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), mflags, int(seed), int(ray_id0), _lib.ptr(occ.words),
+            *occ.resolution, _host_f32x3(occ.lo), _host_f32x3(occ.inv_step), _lib.ptr(mask), _lib.ptr(offsets), None,
+            _lib.ptr(ws), B, N, _lib.stream_ptr(dev)), "nerf_amd_occupancy_mark")
+        live = int(offsets[B])          # the one host synchronisation of a masked render
+    return MarkResult(mask, offsets, live, B, N)
+
+
+def _points(m, rays, jit, tbins, flags, seed, ray_id0):
+    """The compacted query points [P', 6] of a MarkResult."""
+    dev = rays.device
+    pts = torch.empty((m.live, 6), dtype=torch.float32, device=dev)
+    if m.live:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_occupancy_points(
+                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0), _lib.ptr(m.mask),
+                _lib.ptr(m.offsets), _lib.ptr(pts), m.live, m.B, m.N, _lib.stream_ptr(dev)), "nerf_amd_occupancy_points")
+    return pts
+
+
+def render_masked(occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, outputs, pixels=False):
+    """The body of ``render_nerf(..., occupancy=occ)`` / ``render_view(..., occupancy=occ)`` once rays, jitter and
+    precision are settled.  Returns the 5-tuple, or pixels [B, 4] with ``pixels=True``."""
+    from .nets import guarded_launch
+    from .rendering import _per_sample
+    B, dev = rays.size(0), rays.device
+    lib = _lib.lib()
+    m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N)
+    pts = _points(m, rays, jit, tbins, flags, seed, ray_id0)
+    stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
+    occ.last_stats = stats
+
+    def launch(code, packed):
+        raw = None
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            if m.live:
+                raw = torch.empty((m.live, 4), dtype=torch.float32, device=dev)
+                _lib.check(lib.nerf_amd_mlp_forward(_lib.ptr(pts), _lib.ptr(packed[0]), _lib.ptr(raw), m.live, code, st),
+                           "nerf_amd_mlp_forward")
+                stats["network_launches"] += 1
+            head = (_lib.ptr(raw), _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0),
+                    _lib.ptr(m.mask), _lib.ptr(m.offsets))
+            if pixels:
+                px = torch.empty((B, 4), dtype=torch.float32, device=dev)
+                _lib.check(lib.nerf_amd_volume_render_masked_pixels(*head, _lib.ptr(px), B, N, st),
+                           "nerf_amd_volume_render_masked_pixels")
+                return px
+            rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
+            disp = torch.empty((B,), dtype=torch.float32, device=dev)
+            acc = torch.empty((B,), dtype=torch.float32, device=dev)
+            alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
+            w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+            _lib.check(lib.nerf_amd_volume_render_masked(*head, _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha), _lib.ptr(acc),
+                                                         _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
+        return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+
+    if B == 0 or m.live == 0:
+        # nothing to evaluate: no network launch, hence nothing for the range guard to look at
+        return launch(code, [None])
+    return guarded_launch([net], code, launch)
