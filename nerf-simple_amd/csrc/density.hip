@@ -4,19 +4,18 @@
 //
 // sigma does not depend on the view direction: sigma_fc reads h8 before the direction concat (reference utils/nets.py:36-40).
 // The sigma network is therefore internal layers L0..L7 and the one 16-row tile of L8 that holds row 256 (nerf_layout.h):
-// 1936 of the 2344 MFMAs of a wave-tile (82.6 %), no direction features, no colour layers.  It runs on the packed 16-bit
-// image of nerf_amd_pack_weights with the arithmetic of mlp_bf16_16.hip: the same fragment order, bias-initialised
-// accumulators, k-step order, ReLU / pack conversion and in-kernel encoder (to_revolutions, enc_lane) -- so sigma equals
-// column 3 of nerf_amd_mlp_forward's output on the same points bit for bit.
+// 1936 of the 2344 MFMAs of a wave-tile (82.6 %), no direction features, no colour layers.
 //
-// The schedule is mlp_bf16_16.hip's inference schedule on a shorter chunk sequence: 30 chunks per 256-point tile
-//   L0 (16 tiles, K = 64: one chunk) | L1..L7 (4 chunks of four 16-row tiles each) | the sigma tile of L8 (one chunk);
-// weights stream L2 -> LDS by LDS-DMA, double buffered (an even chunk count keeps the buffer parity cyclic over tiles),
-// one barrier per chunk three fragments before its end; a workgroup = 8 waves = 256 points, persistent over tiles.
+// The kernel is an instantiation of the chain of mlp16_chain.h -- the code mlp_bf16_16.hip runs, not a copy of it -- on a
+// shorter plan over the same packed 16-bit image of nerf_amd_pack_weights: 30 chunks per 256-point tile
+//   L0 (16 tiles, K = 64: one chunk) | L1..L7 (4 chunks of four 16-row tiles each) | the sigma tile of L8 (one chunk).
+// Fragment order, bias-initialised accumulators, k-step order, ReLU / pack conversion, the in-kernel encoder and the
+// range guard are therefore the forward's, and sigma equals column 3 of nerf_amd_mlp_forward's output on the same
+// points bit for bit.  What is this file's own: the plan, the input fetch and the one-float output (and, kept equal to
+// mlp_bf16_16.hip's by hand, the kernel prologue and the posx encoder block: mlp16_chain.h says why).
 // Inputs: explicit points (any row stride >= 3) or grid point p of an [Rx, Ry, Rz] grid (C order, z fastest) with
 // coordinates x_a(i) = fl(lo_a + fl(i s_a)), formed here -- no input buffer.
 #include "nerf_device.h"
-#include <utility>
 
 using namespace nerf_layout;
 
@@ -31,297 +30,37 @@ typedef __bf16 elem_t;
 #define DENSITY_KERNEL nerf_density_bf16_kernel
 #define DENSITY_LAUNCH nerf_amd_launch_density_bf16
 #endif
-typedef elem_t ex8 __attribute__((ext_vector_type(8)));
-typedef elem_t ex2 __attribute__((ext_vector_type(2)));
+#include "mlp16_chain.h"
 
 namespace {
 
-constexpr int NCB = 2;
-constexpr int WAVES = 16 / NCB;
-constexpr int TILE_PTS = WAVES * 16 * NCB;
 constexpr int SIGMA_LAYER = 8;
-constexpr int SIGMA_TILE = 16;                    // L8's 16-row tile that holds row 256 (sigma_fc)
 
-// chunk sequence: L0 in one chunk, L1..L7 in four, the sigma tile of L8 in one
-__host__ __device__ constexpr int tpc(int L) { return L == 0 ? 16 : 4; }
-__host__ __device__ constexpr int layer_chunks(int L) { return L == SIGMA_LAYER ? 1 : (b16_mt(L) + tpc(L) - 1) / tpc(L); }
-__host__ __device__ constexpr int chunk_first(int L) {
-    int c = 0;
-    for (int i = 0; i < L; ++i) c += layer_chunks(i);
-    return c;
-}
-constexpr int NUM_CHUNKS = chunk_first(SIGMA_LAYER + 1);      // 30
-__host__ __device__ constexpr int chunk_layer(int cc) {
-    int L = 0;
-    while (cc >= layer_chunks(L)) { cc -= layer_chunks(L); ++L; }
-    return L;
-}
-// first 16-row tile of chunk C of layer L
-__host__ __device__ constexpr int chunk_rt0(int L, int C) { return L == SIGMA_LAYER ? SIGMA_TILE : C * tpc(L); }
-__host__ __device__ constexpr int chunk_tiles(int cc) {
-    const int L = chunk_layer(cc), C = cc - chunk_first(L);
-    if (L == SIGMA_LAYER) return 1;
-    const int left = b16_mt(L) - C * tpc(L);
-    return left < tpc(L) ? left : tpc(L);
-}
-__host__ __device__ constexpr int chunk_kib(int cc) { return chunk_tiles(cc) * b16_ks(chunk_layer(cc)); }
-__host__ __device__ constexpr int chunk_off_kib(int cc) {
-    const int L = chunk_layer(cc), C = cc - chunk_first(L);
-    return b16_layer_off_kib(L) + chunk_rt0(L, C) * b16_ks(L);
-}
-__host__ __device__ constexpr int sigma_mfmas_per_wave_tile() {
-    int m = 0;
-    for (int cc = 0; cc < NUM_CHUNKS; ++cc) m += chunk_tiles(cc) * b16_ks(chunk_layer(cc)) * NCB;
-    return m;
-}
-static_assert(NUM_CHUNKS == 30 && NUM_CHUNKS % 2 == 0, "the double buffer's parity is cyclic over tiles");
-static_assert(sigma_mfmas_per_wave_tile() == 1936, "L0..L7 + the sigma tile of L8");
+// chunk sequence: L0 in one chunk, L1..L7 in four, then of L8 the sigma tile alone -- the folded view of the layer table
+// (nerf_layout.h: row tile 16 of L8, its weights and its bias row), which coincides with the plain one below L8
+struct SigmaPlan {
+    static constexpr int LAYERS = SIGMA_LAYER + 1;   // the sigma tile ends the sequence
+    static constexpr bool SAVE = false;
+    static constexpr int tpc(int L) { return L == 0 ? 16 : 4; }
+    static constexpr int mt(int L) { return fold_mt(L); }
+    static constexpr int layer_off_kib(int L) { return fold_layer_off_kib(L); }
+    static constexpr int bias_off(int L) { return fold_bias_off(L); }
+};
+static_assert(NUM_CHUNKS<SigmaPlan> == 30 && plan_fits<SigmaPlan>(), "chunks per tile / weight buffer, parity");
+static_assert(tile_mfmas<SigmaPlan>() == 1936, "L0..L7 + the sigma tile of L8");
 
-constexpr int LDS_WBUF = 40 * 1024;
-constexpr int LDS_BIAS = 0;
-constexpr int LDS_W0 = 10 * 1024;
-constexpr int LDS_POSX = LDS_W0 + 2 * LDS_WBUF;
+constexpr int LDS_POSX = LDS_CHAIN_END;
 constexpr int LDS_TOTAL = LDS_POSX + WAVES * NCB * 2048;
-static_assert(B16_BIAS_FLOATS * 4 <= LDS_W0, "bias table");
 static_assert(LDS_TOTAL <= 160 * 1024, "LDS budget");
-__host__ __device__ constexpr bool chunks_fit() {
-    for (int cc = 0; cc < NUM_CHUNKS; ++cc)
-        if (chunk_kib(cc) * 1024 > LDS_WBUF) return false;
-    return true;
-}
-static_assert(chunks_fit(), "a chunk fits its weight buffer");
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lds_void;
-template <class T>
-__device__ __forceinline__ T lds_load(unsigned base, int imm) {
-    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(reinterpret_cast<lds_char*>(0) + base + imm);
-}
-template <class T>
-__device__ __forceinline__ void lds_store(unsigned base, int imm, const T& v) {
-    *reinterpret_cast<__attribute__((address_space(3))) T*>(reinterpret_cast<lds_char*>(0) + base + imm) = v;
-}
-
-struct Ctx {
-    __amdgpu_buffer_rsrc_t wrsrc;
-    unsigned wave_goff, lane16;
-    unsigned b_wread[2];            // weight buffer p + lane*16
-    unsigned s_wdst[2];             // this wave's DMA piece in weight buffer p (wave-uniform)
-    unsigned b_bias;                // (lane>>4)*16
-    unsigned b_posx;
-    int wave, lane;
-};
-
-struct WFrag {
-    ex8 a[4];
-    f32x4 bias0;
-};
 
 struct State {
+    using Plan = SigmaPlan;          // the chain instantiated for this state (mlp16_chain.h)
     ex8 X[NCB][8], Y[NCB][8];        // [column block][k-step of 32]
     f32x4 pend[NCB][2];               // [column block][tile of the pending pair]
     float sigma[NCB];
     bool bad;                         // range guard: a non-finite accumulator was seen
     WFrag* wf;                        // the coming chunk's first weight fragments (outlive a tile)
 };
-
-template <bool RELU>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f32x2 v = {a, b};
-    const ex2 r = __builtin_convertvector(v, ex2);
-    if constexpr (RELU) {
-        const s16x2 z = {0, 0};
-        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, r), z));
-    } else {
-        return __builtin_bit_cast(unsigned, r);
-    }
-}
-
-template <int CC>
-struct Stage {
-    static constexpr int NEXT = (CC + 1) % NUM_CHUNKS;
-    static constexpr int PIECES = (chunk_kib(NEXT) + WAVES - 1) / WAVES;
-    static constexpr int SRC_OFF = chunk_off_kib(NEXT) * 1024;
-    static __device__ __forceinline__ void issue_piece(const Ctx& c, int p) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            c.wrsrc, reinterpret_cast<lds_void*>(reinterpret_cast<lds_char*>(0) + c.s_wdst[NEXT & 1] + p * (WAVES * 1024)), 16,
-            c.lane16, c.wave_goff + (SRC_OFF + p * WAVES * 1024), 0, 0);
-    }
-    static __device__ __forceinline__ void issue(const Ctx& c) {
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p) issue_piece(c, p);
-    }
-};
-
-// One of the 8 pieces of the epilogue of row-tile pair Q of layer L (mlp_bf16_16.hip epilogue_piece without the
-// training-forward stores): piece i -> column block i>>2, word i&3 of the next layer's fragment Q.  (L8, Q = 8) is the
-// lone sigma tile.
-template <int L, int Q>
-__device__ __forceinline__ void epilogue_piece(int i, const f32x4 (&acc)[NCB][2], ex8 (&dst)[NCB][8], State& st) {
-    constexpr LayerDesc D = layer_desc(L);
-    const int cb = i >> 2, j2 = i & 3;
-    if constexpr (Q == 0 && L >= 1 && L <= 7) {
-        // range guard, as in mlp_bf16_16.hip: an inf input feature makes every row of the layer non-finite
-        if (j2 == 0) st.bad |= __builtin_amdgcn_classf(acc[cb][0][0], 0x207);      // sNaN | qNaN | -inf | +inf
-    }
-    if constexpr (L == SIGMA_LAYER) {
-        static_assert(Q == SIGMA_TILE / 2, "only the sigma tile of L8 runs here");
-        if (j2 == 0) st.sigma[cb] = acc[cb][0][0];
-    } else {
-        u32x4 w = __builtin_bit_cast(u32x4, dst[cb][Q]);
-        w[j2] = pack2<D.relu != 0>(acc[cb][j2 >> 1][2 * (j2 & 1)], acc[cb][j2 >> 1][2 * (j2 & 1) + 1]);
-        dst[cb][Q] = __builtin_bit_cast(ex8, w);
-    }
-}
-
-template <int L, int P0, int N, int J = 0>
-__device__ __forceinline__ void in_chunk_epilogue(int j, int i, const f32x4 (&acc)[NCB][2], ex8 (&dst)[NCB][8], State& st) {
-    if constexpr (J < N) {
-        if (j == J) epilogue_piece<L, P0 + J>(i, acc, dst, st);
-        else in_chunk_epilogue<L, P0, N, J + 1>(j, i, acc, dst, st);
-    }
-}
-
-// ---- one chunk: NT 16-row tiles of layer L starting at tile chunk_rt0(L, C) (mlp_bf16_16.hip chunk_step, inference form)
-// PL/PQ: layer / pair of the pending accumulators handed over by the previous chunk.
-template <int L, int C, int PL, int PQ>
-__device__ __forceinline__ void chunk_step(const Ctx& c, State& st, ex8 (&in)[NCB][8], ex8 (&out)[NCB][8]) {
-    constexpr LayerDesc D = layer_desc(L);
-    constexpr int KS_CHAIN = D.chain_k / 32;
-    constexpr int KS_EXTRA = D.extra_slots / 32;
-    constexpr int KS = KS_CHAIN + KS_EXTRA;
-    constexpr int CC = chunk_first(L) + C;
-    constexpr int NT = chunk_tiles(CC);
-    constexpr int RT0 = chunk_rt0(L, C);
-    constexpr int F = NT * KS;
-    constexpr int AHEAD = 4;
-    constexpr int BIAS_OFF = LDS_BIAS + (b16_bias_off(L) + 16 * RT0) * 4;
-    constexpr int MT = NCB * KS;
-    constexpr int PEND_M0 = NT * MT >= 4 * NCB + 4 ? 2 : 0;
-    constexpr int PAIR0 = RT0 / 2;
-    constexpr int NPAIR_IN = NT >= 4 ? NT / 2 - 1 : 0;
-    constexpr int PAIR_M0 = 2 * MT + (MT >= 4 * NCB + 2 ? 2 : 0);
-    static_assert(NT < 4 || NT % 2 == 0, "whole pairs per chunk");
-    static_assert(D.extra_kind != 2, "no direction features in the sigma network");
-    static_assert(PL < 0 || PL == L || NCB * PQ >= PEND_M0 + 4 * NCB, "pending pair finished too late");
-    const unsigned wb = c.b_wread[CC & 1];
-    const unsigned xb = c.b_posx;
-    constexpr int NCC = (CC + 1) % NUM_CHUNKS;
-    constexpr int NL = chunk_layer(NCC);
-    constexpr int NF = chunk_tiles(NCC) * (layer_desc(NL).chain_k / 32 + layer_desc(NL).extra_slots / 32);
-    constexpr int NBIAS_OFF = LDS_BIAS + (b16_bias_off(NL) + 16 * chunk_rt0(NL, NCC - chunk_first(NL))) * 4;
-    const unsigned nwb = c.b_wread[NCC & 1];
-    constexpr int TAIL = 3;
-    constexpr int FB = F <= TAIL ? F : F - TAIL;
-    WFrag& wf = *st.wf;
-    auto barrier_and_prefetch = [&]() {
-        // every fragment read of this chunk was issued two fragment slots ago: lgkmcnt(0) is free; vmcnt(0): this wave's
-        // DMA pieces of the next chunk have landed (the only vector-memory instructions in flight are those pieces and,
-        // in the first chunk of a tile, the previous tile's sigma stores and this tile's point loads)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        chunk_barrier<0>();
-#pragma unroll
-        for (int f = 0; f < AHEAD && f < NF; ++f) wf.a[f] = lds_load<ex8>(nwb, f * 1024);
-        wf.bias0 = lds_load<f32x4>(c.b_bias, NBIAS_OFF);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    // the next chunk's DMA pieces go out one per SPREAD MFMAs, the last one well before the barrier
-    constexpr int SPREAD = 4;
-    constexpr bool DMA_SPREAD = 1 + SPREAD * (Stage<CC>::PIECES - 1) + 8 <= FB * NCB;
-    if constexpr (!DMA_SPREAD) Stage<CC>::issue(c);
-    __builtin_amdgcn_sched_barrier(0);
-
-    ex8 a[AHEAD];
-#pragma unroll
-    for (int f = 0; f < AHEAD && f < F; ++f) a[f] = wf.a[f];
-    ex8 bx[NCB][KS_EXTRA > 0 ? KS_EXTRA : 1];
-    if constexpr (KS_EXTRA > 0) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int e = 0; e < KS_EXTRA; ++e) bx[cb][e] = lds_load<ex8>(xb, cb * 2048 + e * 1024);
-    }
-    f32x4 acc[NCB][NT];
-    acc[0][0] = wf.bias0;
-    for (int cb = 1; cb < NCB; ++cb) acc[cb][0] = acc[0][0];
-    __builtin_amdgcn_sched_barrier(0);
-
-    // register lifetimes against the MFMA write-after-read hazards: see mlp_bf16_16.hip chunk_step
-    ex8 as_prev = a[0];
-    f32x4 c_prev = acc[0][0];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int f = t * KS + ks;
-            if (f == FB) barrier_and_prefetch();
-            const ex8 as = a[f % AHEAD];
-            if (f + AHEAD < F) a[f % AHEAD] = lds_load<ex8>(wb, (f + AHEAD) * 1024);
-            if (t + 1 < NT && ks == KS / 2) {
-                acc[0][t + 1 < NT ? t + 1 : 0] = lds_load<f32x4>(c.b_bias, BIAS_OFF + 64 * (t + 1));
-                for (int cb = 1; cb < NCB; ++cb) acc[cb][t + 1 < NT ? t + 1 : 0] = acc[0][t + 1 < NT ? t + 1 : 0];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                const int m = f * NCB + cb;
-                ex8 bs;
-                if (ks < KS_CHAIN) bs = in[cb][ks < KS_CHAIN ? ks : 0];
-                else bs = bx[cb][KS_EXTRA > 0 ? (ks - KS_CHAIN < KS_EXTRA ? ks - KS_CHAIN : 0) : 0];
-                const f32x4 c_old = acc[cb][t];
-                acc[cb][t] = NERF_MFMA(as, bs, c_old, 0, 0, 0);
-                asm volatile("" ::"v"(c_prev));
-                c_prev = c_old;
-                if constexpr (DMA_SPREAD) {
-                    if (m % SPREAD == 1 && m / SPREAD < Stage<CC>::PIECES) Stage<CC>::issue_piece(c, m / SPREAD);
-                }
-                if constexpr (PL >= 0) {
-                    if (m >= PEND_M0 && m < PEND_M0 + 4 * NCB) {
-                        if constexpr (PL == L) epilogue_piece<PL, PQ>(m - PEND_M0, st.pend, out, st);
-                        else epilogue_piece<PL, PQ>(m - PEND_M0, st.pend, in, st);
-                    }
-                }
-                if constexpr (NPAIR_IN > 0) {
-                    const int j = (m - PAIR_M0) / (2 * MT), pm = (m - PAIR_M0) - j * (2 * MT);
-                    if (m >= PAIR_M0 && j < NPAIR_IN && pm < 4 * NCB) {
-                        f32x4 pr[NCB][2];
-                        for (int q_ = 0; q_ < NCB; ++q_) { pr[q_][0] = acc[q_][2 * j]; pr[q_][1] = acc[q_][2 * j + 1]; }
-                        in_chunk_epilogue<L, PAIR0, NPAIR_IN>(j, pm, pr, out, st);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            asm volatile("" ::"v"(as_prev));
-            as_prev = as;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    asm volatile("" ::"v"(as_prev));
-    asm volatile("" ::"v"(c_prev));
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-        st.pend[cb][0] = acc[cb][NT >= 2 ? NT - 2 : 0];
-        st.pend[cb][1] = acc[cb][NT - 1];
-    }
-    if constexpr (FB == F) barrier_and_prefetch();
-}
-
-__host__ __device__ constexpr int prev_layer(int L, int C) { return C > 0 ? L : L - 1; }
-__host__ __device__ constexpr int prev_pair(int L, int C) {
-    // pending pair when chunk (L, C) starts: the last pair of the previous chunk (L0 of a tile starts with none)
-    return C > 0 ? (chunk_rt0(L, C) / 2 - 1) : (L > 0 ? b16_mt(L - 1) / 2 - 1 : 0);
-}
-
-template <int L, int... Cs>
-__device__ __forceinline__ void run_layer_seq(const Ctx& c, State& st, ex8 (&in)[NCB][8], ex8 (&out)[NCB][8],
-                                              std::integer_sequence<int, Cs...>) {
-    (chunk_step<L, Cs, prev_layer(L, Cs), prev_pair(L, Cs)>(c, st, in, out), ...);
-}
-template <int L>
-__device__ __forceinline__ void run_layer(const Ctx& c, State& st, ex8 (&in)[NCB][8], ex8 (&out)[NCB][8]) {
-    run_layer_seq<L>(c, st, in, out, std::make_integer_sequence<int, layer_chunks(L)>{});
-}
 
 // posx of this lane's two points (nerf_layout::posx_col_f32), exactly as mlp_bf16_16.hip stage_inputs forms them
 template <bool GRID>
@@ -372,15 +111,16 @@ __device__ __forceinline__ void run_tile(const Ctx& c, const DensityArgs& a, lon
     run_layer<6>(c, st, st.Y, st.X);
     run_layer<7>(c, st, st.X, st.Y);
     run_layer<8>(c, st, st.Y, st.X);
-    epilogue_piece<SIGMA_LAYER, SIGMA_TILE / 2>(0, st.pend, st.X, st);     // the sigma tile is still pending
-    for (int cb_ = 1; cb_ < NCB; ++cb_) epilogue_piece<SIGMA_LAYER, SIGMA_TILE / 2>(4 * cb_, st.pend, st.X, st);
+    epilogue_piece<SIGMA_LAYER, 8>(0, st.pend, st.X, st);     // the sigma tile (pair 8) is still pending
+    for (int cb_ = 1; cb_ < NCB; ++cb_) epilogue_piece<SIGMA_LAYER, 8>(4 * cb_, st.pend, st.X, st);
 }
 
 template <bool GRID>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void DENSITY_KERNEL(DensityArgs a, long long ntiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     (void)smem;
-    Ctx c;
+    using P = SigmaPlan;
+    Ctx c;                                              // as mlp_bf16_16.hip kernel_body, without posd
     c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     c.lane = threadIdx.x & 63;
     const char* img = reinterpret_cast<const char*>(a.packed);
@@ -397,16 +137,16 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void DENSITY_KERNEL(DensityA
     {
         const float* bsrc = reinterpret_cast<const float*>(img + (long long)B16_WEIGHT_KIB * 1024);
         for (int i = threadIdx.x; i < B16_BIAS_FLOATS; i += WAVES * 64) lds_store<float>(i * 4, LDS_BIAS, bsrc[i]);
-        Stage<NUM_CHUNKS - 1>::issue(c);         // chunk 0
+        Stage<P, NUM_CHUNKS<P> - 1>::issue(c);         // chunk 0
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     WFrag wf;
     {
-        constexpr int F0 = chunk_tiles(0) * (layer_desc(0).chain_k / 32 + layer_desc(0).extra_slots / 32);
+        constexpr int F0 = chunk_tiles<P>(0) * (layer_desc(0).chain_k / 32 + layer_desc(0).extra_slots / 32);
 #pragma unroll
         for (int f = 0; f < 4 && f < F0; ++f) wf.a[f] = lds_load<ex8>(c.b_wread[0], f * 1024);
-        wf.bias0 = lds_load<f32x4>(c.b_bias, LDS_BIAS + b16_bias_off(0) * 4);
+        wf.bias0 = lds_load<f32x4>(c.b_bias, LDS_BIAS + P::bias_off(0) * 4);
     }
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long tile_base = tile * TILE_PTS;
@@ -426,8 +166,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void DENSITY_KERNEL(DensityA
                 }
             }
         }
-        // sticky range flag (nerf_layout.h B16_STATUS_OFF), the plain vector buffer store of mlp_bf16_16.hip flag_nonfinite
-        if (bad) __builtin_amdgcn_raw_buffer_store_b32(1u, c.wrsrc, (int)(B16_STATUS_OFF + 4 * NERF_STATUS_WORD_NONFINITE), 0, 0);
+        flag_nonfinite(c, bad);
     }
 }
 

@@ -61,9 +61,6 @@ constexpr int RING = 4;                        // slabs resident in LDS: one com
 constexpr int LDS_BYTES = RING * SLOTB;        // 128 KiB
 constexpr int DMA_PER_SLAB = 2 * SLAB / 2 / 8; // 1 KiB wave-instructions per wave per slab (8 waves) = 4
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lds_void;
-
 // LDS image of one operand slab (32 points x 32 chunks of 16 B = 16 KiB), two forms, both filled
 // by lane-linear LDS-DMA with the swizzle applied to each lane's SOURCE granule and again to the
 // read address (cdna_hip_programming.md section 5.4 rule 21), both conflict-free for

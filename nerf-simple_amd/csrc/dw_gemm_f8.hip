@@ -58,8 +58,6 @@ constexpr int LDS_BYTES = RING * SLOTB;         // 144 KiB
 constexpr int DMA_PER_SLAB = 4;                 // wave w issues pieces 4w .. 4w+3 (0..15: A's chunks, 16..31: B's)
 static_assert(ACT_TILE_PTS % SLAB == 0, "a slab never straddles tiles");
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(4))) const u32x4 const_u32x4;
 
 struct Frag { i32x2 q[4]; };                    // the lane's 32 bytes: q[0..1] = K block 0, q[2..3] = block 1

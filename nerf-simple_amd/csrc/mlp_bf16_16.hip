@@ -3,19 +3,15 @@
 // Replaces reference utils/rendering.py:24-40 + utils/xyz.py:6-36 + utils/nets.py:34-43.
 //
 // H^T = W . X^T: output features on MFMA rows, points on MFMA columns / lanes (nerf_layout.h).
-//   * a wave owns 32 points = two 16-point column blocks; 64 lanes = 16 points x 4 lane groups;
-//   * two stacked 16-row accumulator tiles (2q, 2q+1), bias-initialised, ReLU'd and converted
-//     pairwise, ARE the B fragment of the next layer's k-step q (32 features): activations never
-//     leave the registers;
-//   * weights stream L2 -> LDS by LDS-DMA in chunks of four 16-row tiles (eight for the K = 64 first
-//     layer; 38 chunks per tile, 34 in fp16), double buffered, one barrier per chunk; one weight fragment read
-//     from LDS (16 rows x 32 k, 1 KiB) feeds two MFMAs (the two column blocks);
-//   * the chunk barrier sits three fragments before the END of a chunk and the next chunk's first
-//     fragments are requested right behind it, so no chunk starts with an LDS round trip; the next
-//     chunk's DMA pieces go out one per four MFMAs (chunk_step);
+// The MFMA chain itself -- the chunk sequence, chunk_step and its schedule, the epilogues, the range flag -- is
+// mlp16_chain.h, shared with density.hip; its header describes it.  This file is the chain's full instantiation:
+//   * the plan: all 11 layers, weight chunks of four 16-row tiles (eight for the K = 64 first layer): 38 chunks per
+//     tile, 34 in fp16;
 //   * the sigma head rides as row 256 of the layers_2 product, the rgb head is one 16-row tile; the fp16 build
 //     has no layers_2 product (folded into the colour layer by the packer) and keeps that row's tile as layer 8;
 //   * a workgroup = 8 waves = a 256-point tile, persistent over tiles;
+//   * the inputs of a tile (stage_inputs): sampling along the rays or explicit points, jitter, posx and the direction
+//     features; SAVE: the training forward, which also stores every layer's activations and ReLU masks;
 //   * COMP (the render path): compositing (utils/rendering.py:47-85) runs in the same launch.  A
 //     workgroup owns a contiguous range of RAYS; each tile drops its 256 x (rgb, sigma, t) into an
 //     LDS ring of 1024 samples, and whenever 8 rays are complete (or the ring is full) every wave
@@ -24,7 +20,6 @@
 // The chip is power/DVFS-limited on this kernel and holds a higher clock on the 16x16x32 shape
 // than on 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md, DVFS give-back item 7).
 #include "composite_device.h"
-#include <utility>
 
 using namespace nerf_layout;
 
@@ -41,20 +36,9 @@ typedef __bf16 elem_t;
 #define NERF_KERNEL nerf_mlp_bf16_16_kernel
 #define NERF_LAUNCH nerf_amd_launch_mlp_bf16_16
 #endif
-typedef elem_t ex8 __attribute__((ext_vector_type(8)));
-typedef elem_t ex2 __attribute__((ext_vector_type(2)));
+#include "mlp16_chain.h"
 
 namespace {
-
-// NCB 16-point column blocks per wave: 8 waves (2 per SIMD) x 2 blocks.  (4 waves x 4 blocks with
-// the accumulators in AGPRs halves the LDS weight reads but measured 4.5 % slower: DESIGN.md section 5.)
-constexpr int NCB = 2;
-constexpr int WAVES = 16 / NCB;
-constexpr int TILE_PTS = WAVES * 16 * NCB;
-// 16-row output tiles per weight chunk: 4 (64 rows, 8..40 KiB), and 8 for the K = 64 first layer, whose
-// tiles are two fragments each (one barrier per 16 MFMAs otherwise).  The chunk count stays even: the
-// double buffer's parity is cyclic over tiles.
-__host__ __device__ constexpr int tpc(int L) { return L == 0 ? 8 : 4; }
 
 // The fp16 build runs the folded view of the layer table (nerf_layout.h): layer 8 is its sigma tile alone (one 8 KiB
 // chunk, 16 MFMAs) and the colour layer takes h8 through the pre-multiplied Wc[:, :256] W2 -- layers_2's 256 MFMAs and
@@ -65,38 +49,20 @@ constexpr bool FOLD = true;
 #else
 constexpr bool FOLD = false;
 #endif
-// the 16-row tiles of layer L this build streams, where they start in the image and in the bias table
-__host__ __device__ constexpr int k_mt(int L) { return FOLD ? fold_mt(L) : b16_mt(L); }
-__host__ __device__ constexpr int k_layer_off_kib(int L) { return FOLD ? fold_layer_off_kib(L) : b16_layer_off_kib(L); }
-__host__ __device__ constexpr int k_bias_off(int L) { return FOLD ? fold_bias_off(L) : b16_bias_off(L); }
+struct MlpPlan {
+    static constexpr int LAYERS = NUM_LAYERS;
+    static constexpr bool SAVE = !FOLD;              // the training forward exists in bf16 only
+    // 16-row output tiles per weight chunk: 4 (64 rows, 8..40 KiB), and 8 for the K = 64 first layer, whose
+    // tiles are two fragments each (one barrier per 16 MFMAs otherwise).  The chunk count stays even.
+    static constexpr int tpc(int L) { return L == 0 ? 8 : 4; }
+    // the 16-row tiles of layer L this build streams, where they start in the image and in the bias table
+    static constexpr int mt(int L) { return FOLD ? fold_mt(L) : b16_mt(L); }
+    static constexpr int layer_off_kib(int L) { return FOLD ? fold_layer_off_kib(L) : b16_layer_off_kib(L); }
+    static constexpr int bias_off(int L) { return FOLD ? fold_bias_off(L) : b16_bias_off(L); }
+};
+static_assert(NUM_CHUNKS<MlpPlan> == (FOLD ? 34 : 38) && plan_fits<MlpPlan>(), "chunks per tile / weight buffer, parity");
 
-__host__ __device__ constexpr int layer_chunks(int L) { return (k_mt(L) + tpc(L) - 1) / tpc(L); }
-__host__ __device__ constexpr int chunk_first(int L) {
-    int c = 0;
-    for (int i = 0; i < L; ++i) c += layer_chunks(i);
-    return c;
-}
-constexpr int NUM_CHUNKS = chunk_first(NUM_LAYERS);           // 38 (fp16: 34)
-__host__ __device__ constexpr int chunk_layer(int cc) {
-    int L = 0;
-    while (cc >= layer_chunks(L)) { cc -= layer_chunks(L); ++L; }
-    return L;
-}
-__host__ __device__ constexpr int chunk_tiles(int cc) {
-    const int L = chunk_layer(cc), C = cc - chunk_first(L);
-    const int left = k_mt(L) - C * tpc(L);
-    return left < tpc(L) ? left : tpc(L);
-}
-__host__ __device__ constexpr int chunk_kib(int cc) { return chunk_tiles(cc) * b16_ks(chunk_layer(cc)); }
-__host__ __device__ constexpr int chunk_off_kib(int cc) {
-    const int L = chunk_layer(cc), C = cc - chunk_first(L);
-    return k_layer_off_kib(L) + C * tpc(L) * b16_ks(L);
-}
-
-constexpr int LDS_WBUF = 40 * 1024;
-constexpr int LDS_BIAS = 0;
-constexpr int LDS_W0 = 10 * 1024;
-constexpr int LDS_POSD = LDS_W0 + 2 * LDS_WBUF;
+constexpr int LDS_POSD = LDS_CHAIN_END;
 constexpr int LDS_POSX = LDS_POSD + WAVES * NCB * 1024;
 constexpr int LDS_TOTAL = LDS_POSX + WAVES * NCB * 2048;
 // COMP only: the sample ring behind everything else (16 B + 4 B per sample)
@@ -106,37 +72,13 @@ constexpr int LDS_RING_T = LDS_RING_RAW + RING_PTS * 16;
 constexpr int LDS_TOTAL_COMP = LDS_RING_T + RING_PTS * 4;
 constexpr int COMP_MAX_N = RING_PTS - TILE_PTS;      // an unfinished ray plus one more tile must fit
 static_assert(COMP_MAX_N == FUSED_RENDER_MAX_N, "api.hip routes by this limit");
-static_assert(B16_BIAS_FLOATS * 4 <= LDS_W0, "bias table");
-static_assert(LDS_TOTAL_COMP <= 160 * 1024 && NUM_CHUNKS % 2 == 0, "LDS budget / parity");
-static_assert(NUM_CHUNKS == (FOLD ? 34 : 38), "chunks per tile");
+static_assert(LDS_TOTAL_COMP <= 160 * 1024, "LDS budget");
 static_assert((RING_PTS & (RING_PTS - 1)) == 0 && RING_PTS % TILE_PTS == 0, "ring indexing");
 
 static_assert(ACT_TILE_PTS == TILE_PTS && MASK_TILE_PTS == TILE_PTS, "activation blocks and mask tiles are the kernel's tiles");
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lds_void;
-template <class T>
-__device__ __forceinline__ T lds_load(unsigned base, int imm) {
-    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(
-        reinterpret_cast<lds_char*>(0) + base + imm);
-}
-template <class T>
-__device__ __forceinline__ void lds_store(unsigned base, int imm, const T& v) {
-    *reinterpret_cast<__attribute__((address_space(3))) T*>(
-        reinterpret_cast<lds_char*>(0) + base + imm) = v;
-}
-
-struct Ctx {
-    __amdgpu_buffer_rsrc_t wrsrc;
-    unsigned wave_goff, lane16;
-    unsigned b_wread[2];            // weight buffer p + lane*16
-    unsigned s_wdst[2];             // this wave's DMA piece in weight buffer p (wave-uniform)
-    unsigned b_bias;                // (lane>>4)*16
-    unsigned b_posx, b_posd;
-    int wave, lane;
-};
-
 struct State {
+    using Plan = MlpPlan;            // the chain instantiated for this state (mlp16_chain.h)
     ex8 X[NCB][8], Y[NCB][8];        // [column block][k-step of 32]
     f32x4 pend[NCB][2];               // [column block][tile of the pending pair]
     float sigma[NCB], rgb[NCB][3];
@@ -154,361 +96,8 @@ struct State {
     // fused render only (COMP)
     long long p_end;                  // one past this workgroup's last point (uniform)
     unsigned ring_q0;                 // ring slot of the tile's point 0 (uniform)
-    struct WFrag* wf;                 // the coming chunk's first weight fragments (outlive a tile)
+    WFrag* wf;                        // the coming chunk's first weight fragments (outlive a tile)
 };
-// The first AHEAD weight fragments and the first bias vector of the chunk that runs next, requested
-// right behind the barrier that publishes its buffer -- which the inference kernels place three
-// fragments BEFORE the end of the previous chunk, so the LDS round trip of these reads is covered by
-// that chunk's last six MFMAs instead of idling the matrix pipe at every chunk start.
-struct WFrag {
-    ex8 a[4];
-    f32x4 bias0;
-};
-
-template <bool RELU>
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f32x2 v = {a, b};
-    const ex2 r = __builtin_convertvector(v, ex2);
-    if constexpr (RELU) {
-        const s16x2 z = {0, 0};
-        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, r), z));
-    } else {
-        return __builtin_bit_cast(unsigned, r);
-    }
-}
-
-template <int CC>
-struct Stage {
-    static constexpr int NEXT = (CC + 1) % NUM_CHUNKS;
-    static constexpr int PIECES = (chunk_kib(NEXT) + WAVES - 1) / WAVES;
-    static constexpr int SRC_OFF = chunk_off_kib(NEXT) * 1024;
-    static __device__ __forceinline__ void issue_piece(const Ctx& c, int p) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            c.wrsrc,
-            reinterpret_cast<lds_void*>(reinterpret_cast<lds_char*>(0) + c.s_wdst[NEXT & 1] + p * (WAVES * 1024)),
-            16, c.lane16, c.wave_goff + (SRC_OFF + p * WAVES * 1024), 0, 0);
-    }
-    static __device__ __forceinline__ void issue(const Ctx& c) {
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p) issue_piece(c, p);
-    }
-};
-
-// One of the 8 pieces of the epilogue of row-tile pair Q of layer L (tiles
-// 2Q, 2Q+1; both column blocks): piece i -> column block i>>2, word i&3 of the
-// next layer's fragment Q.  Heads: (L8, Q=8) is the lone sigma tile, L10 the
-// rgb tile.
-template <int L, int Q, int SAVE = 0>
-__device__ __forceinline__ void epilogue_piece(int i, const f32x4 (&acc)[NCB][2], ex8 (&dst)[NCB][8], State& st) {
-    constexpr LayerDesc D = layer_desc(L);
-    const int cb = i >> 2, j2 = i & 3;   // i in [0, 4*NCB)
-    if constexpr (Q == 0 && L >= 1 && L <= 9) {
-        // Range guard.  If ANY input feature of this layer is inf (an fp16 activation beyond 65504) every one of its
-        // rows sums w * inf: +-inf, or NaN with two of them -- so one accumulator element per point tells.  (The
-        // outputs alone do not: the integer ReLU below turns a NaN with the sign bit set into 0, and a layer whose
-        // rows are all NaN comes out as all zeros, finite from there on.)  One compare per column block and layer.
-        // (Folded build: layer 8 is the sigma tile alone and has no pair 0; an inf in h8 shows in the colour layer,
-        // which reads h8 itself, and in sigma, which the tile's finite4 check sees.)
-        if (j2 == 0) st.bad |= __builtin_amdgcn_classf(acc[cb][0][0], 0x207);      // sNaN | qNaN | -inf | +inf
-    }
-    if constexpr (L == 10) {
-        if (j2 == 0) { st.rgb[cb][0] = acc[cb][0][0]; st.rgb[cb][1] = acc[cb][0][1]; st.rgb[cb][2] = acc[cb][0][2]; }
-    } else if constexpr (L == 8 && Q == 8) {
-        if (j2 == 0) st.sigma[cb] = acc[cb][0][0];
-    } else {
-        u32x4 w = __builtin_bit_cast(u32x4, dst[cb][Q]);
-        w[j2] = pack2<D.relu != 0>(acc[cb][j2 >> 1][2 * (j2 & 1)], acc[cb][j2 >> 1][2 * (j2 & 1) + 1]);
-        dst[cb][Q] = __builtin_bit_cast(ex8, w);
-        if constexpr (SAVE == 2) {
-            // 8-bit storage form: magnitudes are collected word by word over a group of four fragments (128 features); when
-            // the group's last fragment is complete in both column blocks the wave converts and writes all four under one
-            // exponent (nerf_device.h store_group_f8).  The accumulator is picked by (layer, group) parity: the pending pair
-            // of the previous layer and this layer's first pair can be in flight together.
-            constexpr int GS = (L & 1) * 2 + ((Q >> 2) & 1);
-            st.amax[GS] = f8_absmax<D.relu == 0>(((Q & 3) == 0 && i == 0) ? 0.f : st.amax[GS], acc[cb][j2 >> 1][2 * (j2 & 1)],
-                                                 acc[cb][j2 >> 1][2 * (j2 & 1) + 1]);
-            if constexpr ((Q & 3) == 3) {
-                if (i == 4 * NCB - 1) {
-                    static_assert(NCB == 2, "store_group_f8 takes the two column blocks of a wave");
-                    constexpr int Q0 = Q - 3;
-                    char* tb = st.acts + (f8_offset_bytes(L, st.P) + st.tile * F8_BLOCK_BYTES);
-                    char* sp = st.acts + (f8_scale_offset_bytes(L, st.P) + st.tile * 64);
-                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(tb, 0, (int)F8_BLOCK_BYTES, 0x00020000);
-                    const __amdgpu_buffer_rsrc_t rss = __builtin_amdgcn_make_buffer_rsrc(sp, 0, 64, 0x00020000);
-                    const u32x4 g0[4] = {__builtin_bit_cast(u32x4, dst[0][Q0]), __builtin_bit_cast(u32x4, dst[0][Q0 + 1]),
-                                         __builtin_bit_cast(u32x4, dst[0][Q0 + 2]), __builtin_bit_cast(u32x4, dst[0][Q0 + 3])};
-                    const u32x4 g1[4] = {__builtin_bit_cast(u32x4, dst[1][Q0]), __builtin_bit_cast(u32x4, dst[1][Q0 + 1]),
-                                         __builtin_bit_cast(u32x4, dst[1][Q0 + 2]), w};
-                    store_group_f8<2>(rs, st.loff[0], Q0 * 8192, rss, (int)(threadIdx.x & 63), (int)(threadIdx.x >> 6) * 8 + Q0,
-                                      g0, g1, st.amax[GS]);
-                }
-            }
-        }
-        if constexpr (SAVE) {
-            // the fragment is complete: write this lane's 2 x 4 features of layer L's output
-            // (features 32Q+4g.. and 32Q+16+4g.. of its point) for the backward pass
-            if (SAVE == 1 && j2 == 3) {
-                // Buffer stores into this (layer, tile)'s point-blocked block (nerf_layout.h),
-                // unconditional so the vector-memory instruction count per chunk is a constant
-                // (chunk_barrier); lanes past the last point carry an offset outside num_records.
-                // The lane holds two 8-byte pieces (features 32Q+4g.. and 32Q+16+4g..):
-                // v_permlane16_swap trades one with the neighbouring 16-lane row (g ^ 1) -- even g
-                // ends up with [its first piece | g+1's first piece], odd g with [g-1's second piece |
-                // its second piece], i.e. one whole 16-byte granule (chunk 4Q + swapped_chunk(g)).
-                // The 16 lanes of a quarter-wave then write 256 contiguous bytes.
-                char* tb = st.acts + (act_offset_bytes(L, st.P) + st.tile * ACT_BLOCK_BYTES);
-                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(tb, 0, (int)ACT_BLOCK_BYTES, 0x00020000);
-                store_granule<2>(rs, st.loff[cb], Q * 16384, w);
-            }
-            if constexpr (D.relu != 0) {
-                // ReLU mask for the backward pass: one bit per feature (post-ReLU bf16 != 0), collected
-                // per group of 4 pairs and written as one coalesced dword per thread
-                static_assert(NCB == 2, "mask layout: two column blocks per wave");
-                // t = {low != 0, high != 0} as 0/1 halves: one packed unsigned min with {1, 1} (hipcc
-                // lowers the generic form to two compares, two selects and a permute)
-                const unsigned wj = w[j2];
-                unsigned t;
-                asm("v_pk_min_u16 %0, %1, %2" : "=v"(t) : "v"(wj), "s"(0x00010001u));
-                const int pos = (Q & 3) * 4 + j2;
-                st.mb[cb][Q >> 2] = pos == 0 ? t : ((t << pos) | st.mb[cb][Q >> 2]);
-                if (pos == 15) {
-                    // wave-uniform 64-bit base + this thread's 32-bit offset (scalar base, one offset VGPR)
-                    char* mp = st.acts + (st.mask_tile + ((long long)L * mask_tiles(st.P) * 4 + (cb * 2 + (Q >> 2))) * 2048);
-                    *reinterpret_cast<unsigned*>(mp + (unsigned)(threadIdx.x * 4)) = st.mb[cb][Q >> 2];
-                }
-            }
-        }
-    }
-}
-
-// vector-memory instructions epilogue_piece<L, Q, SAVE> issues over its 4*NCB pieces
-template <int SAVE>
-__host__ __device__ constexpr int pair_vmem_ops(int L, int Q) {
-    if (!SAVE || L < 0 || L == 10 || (L == 8 && Q == 8)) return 0;
-    const int masks = (layer_desc(L).relu != 0 && (Q & 3) == 3) ? NCB : 0;  // a mask dword per block behind every fourth pair
-    // bf16 form: one activation store per block; 8-bit form: a group of four fragments at once (4 stores + 1 exponent dword)
-    return (SAVE == 2 ? ((Q & 3) == 3 ? F8_GROUP + 1 : 0) : NCB) + masks;
-}
-template <int SAVE>
-__host__ __device__ constexpr int pair_mask_ops(int L, int Q) {
-    if (!SAVE || L < 0 || L == 10 || (L == 8 && Q == 8)) return 0;
-    return (layer_desc(L).relu != 0 && (Q & 3) == 3) ? NCB : 0;
-}
-
-// the same summed over the pairs a chunk finishes itself (pairs P0 .. P0 + N - 1 of layer L)
-template <int SAVE>
-__host__ __device__ constexpr int chunk_pair_vmem_ops(int L, int P0, int N) {
-    int n = 0;
-    for (int j = 0; j < N; ++j) n += pair_vmem_ops<SAVE>(L, P0 + j);
-    return n;
-}
-template <int SAVE>
-__host__ __device__ constexpr int vmem_before_barrier(int L, int PL, int PQ, int pair0, int npair_in, int pend_m0, int pend_per,
-                                                      int pair_m0, int mt, int m_limit) {
-    int n = 0;
-    // Column block cb's last piece (4 cb + 3) carries its mask dword and, in the bf16 form, its activation store; in the
-    // 8-bit form the wave's column blocks are converted and written together -- a whole group of four fragments -- by
-    // the last piece of the group's last pair.
-    const int last = 4 * NCB - 1;
-    if (PL >= 0) {
-        const int masks = pair_mask_ops<SAVE>(PL, PQ), data = pair_vmem_ops<SAVE>(PL, PQ) - masks;
-        for (int cb = 0; cb < NCB; ++cb) {
-            const int own = 4 * cb + 3;
-            if (pend_m0 + own / pend_per < m_limit) n += masks / NCB + (SAVE == 2 ? 0 : data / NCB);
-        }
-        if (SAVE == 2 && pend_m0 + last / pend_per < m_limit) n += data;
-    }
-    for (int j = 0; j < npair_in; ++j) {
-        const int masks = pair_mask_ops<SAVE>(L, pair0 + j), data = pair_vmem_ops<SAVE>(L, pair0 + j) - masks;
-        for (int cb = 0; cb < NCB; ++cb) {
-            const int own = 4 * cb + 3;
-            if (pair_m0 + j * 2 * mt + own < m_limit) n += masks / NCB + (SAVE == 2 ? 0 : data / NCB);
-        }
-        if (SAVE == 2 && pair_m0 + j * 2 * mt + last < m_limit) n += data;
-    }
-    return n;
-}
-// epilogue piece `i` of in-chunk pair j (a compile-time pair index is needed: dispatch over the few values)
-template <int L, int P0, int N, int SAVE, int J = 0>
-__device__ __forceinline__ void in_chunk_epilogue(int j, int i, const f32x4 (&acc)[NCB][2], ex8 (&dst)[NCB][8], State& st) {
-    if constexpr (J < N) {
-        if (j == J) epilogue_piece<L, P0 + J, SAVE>(i, acc, dst, st);
-        else in_chunk_epilogue<L, P0, N, SAVE, J + 1>(j, i, acc, dst, st);
-    }
-}
-
-// ---- one chunk: NT 16-row tiles of layer L starting at tile C * tpc(L) -------------------
-// PL/PQ: layer / pair of the pending accumulators handed over by the previous chunk.
-template <int L, int C, int PL, int PQ, int SAVE>
-__device__ __forceinline__ void chunk_step(const Ctx& c, State& st, ex8 (&in)[NCB][8], ex8 (&out)[NCB][8]) {
-    constexpr LayerDesc D = layer_desc(L);
-    constexpr int KS_CHAIN = D.chain_k / 32;
-    constexpr int KS_EXTRA = D.extra_slots / 32;
-    constexpr int KS = KS_CHAIN + KS_EXTRA;
-    constexpr int CC = chunk_first(L) + C;
-    constexpr int NT = chunk_tiles(CC);
-    constexpr int RT0 = C * tpc(L);
-    constexpr int F = NT * KS;                      // weight fragments (each feeds 2 MFMAs)
-    constexpr int AHEAD = 4;                         // weight fragments in flight ahead of their MFMAs (2..8 measure alike)
-    constexpr int BIAS_OFF = LDS_BIAS + (k_bias_off(L) + 16 * RT0) * 4;
-    constexpr int XBLK = D.extra_kind == 1 ? 2048 : 1024;
-    // chunk-linear MFMA index m = (t*KS + ks)*2 + cb
-    constexpr int MT = NCB * KS;                      // MFMAs per row tile
-    constexpr int PEND_M0 = (L == 10) ? 0 : (NT * MT >= 4 * NCB + 4 ? 2 : 0);
-    constexpr int PEND_PER = (L == 10) ? 2 : 1;     // pieces per MFMA for the pending pair
-    // Row-tile pairs of this chunk: pair j (tiles 2j, 2j+1; layer pair PAIR0 + j) gets its epilogue in the shadow
-    // of the MFMAs of pair j + 1, starting at MFMA PAIR_M0 + j * 2 MT; the last pair is handed to the next chunk
-    constexpr int PAIR0 = RT0 / 2;
-    constexpr int NPAIR_IN = NT >= 4 ? NT / 2 - 1 : 0;
-    constexpr int PAIR_M0 = 2 * MT + (MT >= 4 * NCB + 2 ? 2 : 0);
-    static_assert(NT < 4 || NT % 2 == 0, "whole pairs per chunk");
-    // a pending pair of the PREVIOUS layer is this layer's k-step PQ, first read by MFMA 2*PQ
-    static_assert(PL < 0 || PL == L || (PL == 8 && PQ == 8) || NCB * PQ >= PEND_M0 + 4 * NCB / PEND_PER,
-                  "pending pair finished too late");
-    const unsigned wb = c.b_wread[CC & 1];
-    const unsigned xb = c.b_posx;
-    // the chunk that runs next (cyclic: the last chunk of a tile prefetches the first one of the next tile)
-    constexpr int NCC = (CC + 1) % NUM_CHUNKS;
-    constexpr int NL = chunk_layer(NCC);
-    constexpr int NF = chunk_tiles(NCC) * (layer_desc(NL).chain_k / 32 + layer_desc(NL).extra_slots / 32);
-    constexpr int NBIAS_OFF = LDS_BIAS + (k_bias_off(NL) + 16 * (NCC - chunk_first(NL)) * tpc(NL)) * 4;
-    const unsigned nwb = c.b_wread[NCC & 1];
-    // Where the chunk's barrier sits, as a fragment index: TAIL fragments before the end of the chunk.
-    constexpr int TAIL = 3;
-    constexpr int FB = F <= TAIL ? F : F - TAIL;
-    // The training forward's counted wait: vector-memory instructions this wave issues between its DMA pieces
-    // (first in the chunk) and the barrier, i.e. the activation / mask stores of the epilogue pieces that sit in
-    // front of MFMA FB * NCB (piece 4 cb + 3 of a pair carries column block cb's stores); the ones behind the
-    // barrier are older than the next chunk's DMA and need no count.
-    constexpr int VMEM_N = vmem_before_barrier<SAVE>(L, PL, PQ, PAIR0, NPAIR_IN, PEND_M0, PEND_PER, PAIR_M0, MT, FB * NCB);
-    WFrag& wf = *st.wf;
-    auto barrier_and_prefetch = [&]() {
-        // Every fragment read of this chunk has been issued at least two fragment slots ago (AHEAD = 4,
-        // TAIL = 3): lgkmcnt(0) is free, and it makes the buffer reusable -- no wave reads it after its
-        // barrier.  vmcnt: this wave's LDS-DMA pieces of the next chunk (issued first in this chunk) have
-        // landed; the training forward's stores behind them may fly on.
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        chunk_barrier<VMEM_N>();
-#pragma unroll
-        for (int f = 0; f < AHEAD && f < NF; ++f) wf.a[f] = lds_load<ex8>(nwb, f * 1024);
-        wf.bias0 = lds_load<f32x4>(c.b_bias, NBIAS_OFF);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    // DMA of the next chunk: the training forward issues all pieces first (its counted vmcnt assumes every
-    // store of the chunk behind them); the inference kernels, whose first fragments are already in
-    // registers, start their MFMAs at once and issue one piece every SPREAD MFMAs -- provided the last
-    // piece still goes out well before the MFMA in front of which the barrier publishes that buffer
-    // (a piece issued behind the barrier would be read by the prefetch before it has landed)
-    constexpr int SPREAD = 4;
-    constexpr bool DMA_SPREAD = !SAVE && 1 + SPREAD * (Stage<CC>::PIECES - 1) + 8 <= FB * NCB;
-    if constexpr (!DMA_SPREAD) Stage<CC>::issue(c);
-    __builtin_amdgcn_sched_barrier(0);   // every other vector-memory instruction of the chunk stays behind the DMA
-
-    ex8 a[AHEAD];
-#pragma unroll
-    for (int f = 0; f < AHEAD && f < F; ++f) a[f] = wf.a[f];       // requested behind the previous barrier
-    ex8 bx[NCB][KS_EXTRA > 0 ? KS_EXTRA : 1];
-    if constexpr (KS_EXTRA > 0) {
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int e = 0; e < KS_EXTRA; ++e)
-                bx[cb][e] = D.extra_kind == 1 ? lds_load<ex8>(xb, cb * XBLK + e * 1024) : lds_load<ex8>(st.posd_off[cb], e * 1024);
-    }
-    f32x4 acc[NCB][NT];
-    // register i of lane group g is row 16*rt + 4g + i: one 16-B bias read per tile
-    acc[0][0] = wf.bias0;
-    for (int cb = 1; cb < NCB; ++cb) acc[cb][0] = acc[0][0];
-    __builtin_amdgcn_sched_barrier(0);
-
-    // Register lifetimes against the MFMA write-after-read hazards.  The allocator hands the registers an
-    // MFMA has just read for the last time (its weight fragment, and the old accumulator: D != C in the
-    // VGPR form) to the very next definition -- the following ds_read or cvt_pk -- and the hazard
-    // recognizer then puts 2-4 wait states between the two: 617 s_nop per tile, ~1700 cycles per wave,
-    // in a stream whose issue time is what bounds the kernel.  Empty asm uses keep a fragment alive for one
-    // more fragment slot and an accumulator for one more MFMA, so the registers that come free were last
-    // read two instructions ago: 8 more live VGPRs, 190 s_nop per tile, -1.7 ... 2.1 % time.
-    ex8 as_prev = a[0];
-    f32x4 c_prev = acc[0][0];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int f = t * KS + ks;
-            if (f == FB) barrier_and_prefetch();
-            const ex8 as = a[f % AHEAD];
-            if (f + AHEAD < F) a[f % AHEAD] = lds_load<ex8>(wb, (f + AHEAD) * 1024);
-            if (t + 1 < NT && ks == KS / 2) {
-                acc[0][t + 1 < NT ? t + 1 : 0] = lds_load<f32x4>(c.b_bias, BIAS_OFF + 64 * (t + 1));
-                for (int cb = 1; cb < NCB; ++cb) acc[cb][t + 1 < NT ? t + 1 : 0] = acc[0][t + 1 < NT ? t + 1 : 0];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) {
-                const int m = f * NCB + cb;
-                ex8 bs;
-                if (ks < KS_CHAIN) bs = in[cb][ks < KS_CHAIN ? ks : 0];
-                else bs = bx[cb][KS_EXTRA > 0 ? (ks - KS_CHAIN < KS_EXTRA ? ks - KS_CHAIN : 0) : 0];
-                const f32x4 c_old = acc[cb][t];
-                acc[cb][t] = NERF_MFMA(as, bs, c_old, 0, 0, 0);
-                asm volatile("" :: "v"(c_prev));
-                c_prev = c_old;
-                if constexpr (DMA_SPREAD) {
-                    if (m % SPREAD == 1 && m / SPREAD < Stage<CC>::PIECES) Stage<CC>::issue_piece(c, m / SPREAD);
-                }
-                // ---- epilogue pieces in this MFMA's shadow
-                if constexpr (PL >= 0) {
-                    if (m >= PEND_M0 && m < PEND_M0 + 4 * NCB / PEND_PER) {
-#pragma unroll
-                        for (int k = 0; k < PEND_PER; ++k) {
-                            const int i = (m - PEND_M0) * PEND_PER + k;
-                            if constexpr (PL == L) epilogue_piece<PL, PQ, SAVE>(i, st.pend, out, st);
-                            else epilogue_piece<PL, PQ, SAVE>(i, st.pend, in, st);
-                        }
-                    }
-                }
-                if constexpr (NPAIR_IN > 0) {
-                    const int j = (m - PAIR_M0) / (2 * MT), pm = (m - PAIR_M0) - j * (2 * MT);
-                    if (m >= PAIR_M0 && j < NPAIR_IN && pm < 4 * NCB) {
-                        f32x4 pr[NCB][2];
-                        for (int q_ = 0; q_ < NCB; ++q_) { pr[q_][0] = acc[q_][2 * j]; pr[q_][1] = acc[q_][2 * j + 1]; }
-                        in_chunk_epilogue<L, PAIR0, NPAIR_IN, SAVE>(j, pm, pr, out, st);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            asm volatile("" :: "v"(as_prev));
-            as_prev = as;
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    asm volatile("" :: "v"(as_prev));
-    asm volatile("" :: "v"(c_prev));
-#pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) {
-        st.pend[cb][0] = acc[cb][NT >= 2 ? NT - 2 : 0];
-        st.pend[cb][1] = acc[cb][NT - 1];
-    }
-    if constexpr (FB == F) barrier_and_prefetch();
-}
-
-__host__ __device__ constexpr int prev_layer(int L, int C) { return C > 0 ? L : L - 1; }
-__host__ __device__ constexpr int prev_pair(int L, int C) {
-    // pending pair when chunk (L, C) starts: same layer -> the last pair of chunk C-1; else the previous
-    // layer's last pair (L8 ends with its lone sigma tile, marked as pair 8)
-    return C > 0 ? C * tpc(L) / 2 - 1 : (L > 0 ? (L - 1 == 8 ? 8 : k_mt(L - 1) / 2 - 1) : 0);
-}
-
-template <int L, int SAVE, int... Cs>
-__device__ __forceinline__ void run_layer_seq(const Ctx& c, State& st, ex8 (&in)[NCB][8], ex8 (&out)[NCB][8],
-                                              std::integer_sequence<int, Cs...>) {
-    (chunk_step<L, Cs, prev_layer(L, Cs), prev_pair(L, Cs), SAVE>(c, st, in, out), ...);
-}
-template <int L, int SAVE>
-__device__ __forceinline__ void run_layer(const Ctx& c, State& st, ex8 (&in)[NCB][8], ex8 (&out)[NCB][8]) {
-    run_layer_seq<L, SAVE>(c, st, in, out, std::make_integer_sequence<int, layer_chunks(L)>{});
-}
 
 // SAVE (the training forward, launched in rays mode) also serves Nerf.forward(v) with gradients:
 // a.pts != NULL switches the point fetch at run time, so training needs no third instantiation.
@@ -656,14 +245,6 @@ __device__ __forceinline__ void run_tile(const Ctx& c, const MlpArgs& a, long lo
     for (int cb_ = 1; cb_ < NCB; ++cb_) epilogue_piece<10, 0>(4 * cb_, st.pend, st.X, st);
 }
 
-// Sticky range flag (nerf_layout.h B16_STATUS_OFF): a point with a non-finite accumulator in layers 1..9 (epilogue_piece)
-// or a non-finite (rgb, sigma) sets status word 0 behind the packed image.  The host wrapper reads it
-// (utils/nets.py): the reference is fp32 and has no range limit (utils/nets.py:16-32), so an overflowing fp16 render
-// must not pass silently.  A plain store of the constant 1 through the weight image's own buffer descriptor (every
-// writer writes the same value: no atomic, no extra pointer kept live across the tile loop).
-__device__ __forceinline__ void flag_nonfinite(const Ctx& c, bool bad) {
-    if (bad) __builtin_amdgcn_raw_buffer_store_b32(1u, c.wrsrc, (int)(B16_STATUS_OFF + 4 * NERF_STATUS_WORD_NONFINITE), 0, 0);
-}
 __device__ __forceinline__ bool finite4(float x, float y, float z, float w) {
     // |v| < inf is false for inf and NaN; the sum is non-finite iff any term is (no finite sum of four floats overflows
     // unless a term is already beyond half of FLT_MAX -- which fp16 / bf16 MLP outputs of a usable network never are)
@@ -683,6 +264,7 @@ struct RingSamples {                         // a ray's samples in the workgroup
 template <bool RAYS, int SAVE, bool COMP>
 __device__ __forceinline__ void kernel_body(const MlpArgs& a, long long ntiles) {
     static_assert(!COMP || (RAYS && !SAVE), "the fused render is the rays-mode inference kernel");
+    using P = MlpPlan;
     Ctx c;
     c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     c.lane = threadIdx.x & 63;
@@ -703,16 +285,16 @@ __device__ __forceinline__ void kernel_body(const MlpArgs& a, long long ntiles) 
         const float* bsrc = reinterpret_cast<const float*>(img + (long long)B16_WEIGHT_KIB * 1024);
         for (int i = threadIdx.x; i < B16_BIAS_FLOATS; i += WAVES * 64)
             lds_store<float>(i * 4, LDS_BIAS, bsrc[i]);
-        Stage<NUM_CHUNKS - 1>::issue(c);
+        Stage<P, NUM_CHUNKS<P> - 1>::issue(c);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA pieces have landed
     __syncthreads();
     WFrag wf;                                           // chunk 0's first fragments (chunk_step hands them on)
     {
-        constexpr int F0 = chunk_tiles(0) * (layer_desc(0).chain_k / 32 + layer_desc(0).extra_slots / 32);
+        constexpr int F0 = chunk_tiles<P>(0) * (layer_desc(0).chain_k / 32 + layer_desc(0).extra_slots / 32);
 #pragma unroll
         for (int f = 0; f < 4 && f < F0; ++f) wf.a[f] = lds_load<ex8>(c.b_wread[0], f * 1024);
-        wf.bias0 = lds_load<f32x4>(c.b_bias, LDS_BIAS + k_bias_off(0) * 4);
+        wf.bias0 = lds_load<f32x4>(c.b_bias, LDS_BIAS + P::bias_off(0) * 4);
     }
 
     if constexpr (!COMP) {

@@ -66,14 +66,6 @@ static_assert(NUM_CHUNKS % 2 == 0, "buffer parity must repeat per tile");
 
 static_assert(ACT_TILE_PTS == TILE_PTS && MASK_TILE_PTS == TILE_PTS, "activation blocks and mask tiles are the kernel's tiles");
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lds_void;
-template <class T>
-__device__ __forceinline__ T lds_load(unsigned base, int imm) {
-    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(
-        reinterpret_cast<lds_char*>(0) + base + imm);
-}
-
 struct Ctx {
     __amdgpu_buffer_rsrc_t wrsrc;
     unsigned wave_goff, lane16;
@@ -99,20 +91,9 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, ex2));
 }
 
+// LDS-DMA of the chunk behind chunk CC (cyclic over tiles)
 template <int CC>
-struct Stage {
-    static constexpr int NEXT = (CC + 1) % NUM_CHUNKS;
-    static constexpr int PIECES = (chunk_kib(NEXT) + WAVES - 1) / WAVES;
-    static constexpr int SRC_OFF = chunk_off_kib(NEXT) * 1024;
-    static __device__ __forceinline__ void issue(const Ctx& c) {
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                c.wrsrc,
-                reinterpret_cast<lds_void*>(reinterpret_cast<lds_char*>(0) + c.s_wdst[NEXT & 1] + p * (WAVES * 1024)),
-                16, c.lane16, c.wave_goff + (SRC_OFF + p * WAVES * 1024), 0, 0);
-    }
-};
+using Stage = ChunkDma<Ctx, (CC + 1) % NUM_CHUNKS, chunk_kib((CC + 1) % NUM_CHUNKS), chunk_off_kib((CC + 1) % NUM_CHUNKS), WAVES>;
 
 // the four mask dwords of forward activation A for this thread's 2 x 256 (point, feature) cells
 template <int A>

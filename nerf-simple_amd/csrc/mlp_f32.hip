@@ -39,18 +39,6 @@ static_assert(LDS_TOTAL_COMP <= 160 * 1024 && RING_PTS - TILE_PTS >= FUSED_RENDE
 static_assert(F32_BIAS_FLOATS * 4 <= LDS_W0, "bias table");
 static_assert(F32_NUM_CHUNKS % 2 == 0, "buffer parity must repeat per tile");
 
-typedef __attribute__((address_space(3))) char lds_char;
-template <class T>
-__device__ __forceinline__ T lds_load(unsigned base, int imm) {
-    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(
-        reinterpret_cast<lds_char*>(0) + base + imm);
-}
-template <class T>
-__device__ __forceinline__ void lds_store(unsigned base, int imm, const T& v) {
-    *reinterpret_cast<__attribute__((address_space(3))) T*>(
-        reinterpret_cast<lds_char*>(0) + base + imm) = v;
-}
-
 __host__ __device__ constexpr int chunk_layer(int cc) {
     int L = 0;
     while (cc >= f32_mt(L)) { cc -= f32_mt(L); ++L; }

@@ -1,6 +1,6 @@
 // nerf_device.h -- device helpers shared by the gfx950 kernels:
-// vector typedefs, the counter RNG, and per-point input assembly
-// (reference utils/rendering.py:24-40).
+// vector typedefs, LDS access by address and the LDS-DMA chunk issue, the
+// counter RNG, and per-point input assembly (reference utils/rendering.py:24-40).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -244,6 +244,38 @@ __device__ __forceinline__ void chunk_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");            // nothing below is hoisted above the barrier
 }
+
+// ---- LDS by byte address --------------------------------------------------------------
+// The kernels lay their dynamic LDS out by hand (LDS_* constants): base = a register, imm = a constant that lands in the
+// instruction's offset field.
+typedef __attribute__((address_space(3))) char lds_char;
+typedef __attribute__((address_space(3))) void lds_void;
+template <class T>
+__device__ __forceinline__ T lds_load(unsigned base, int imm) {
+    return *reinterpret_cast<const __attribute__((address_space(3))) T*>(reinterpret_cast<lds_char*>(0) + base + imm);
+}
+template <class T>
+__device__ __forceinline__ void lds_store(unsigned base, int imm, const T& v) {
+    *reinterpret_cast<__attribute__((address_space(3))) T*>(reinterpret_cast<lds_char*>(0) + base + imm) = v;
+}
+
+// The LDS-DMA issue of a streamed weight chunk: chunk NEXT (KIB KiB at OFF_KIB KiB of the image behind c.wrsrc) goes
+// into weight buffer NEXT & 1 in pieces of WAVES KiB, every wave 1 KiB of a piece (16 B per lane).  C is the kernel's
+// context: wrsrc, lane16 = lane * 16, wave_goff = wave * 1024, s_wdst[p] = this wave's KiB of weight buffer p.
+template <class C, int NEXT, int KIB, int OFF_KIB, int WAVES>
+struct ChunkDma {
+    static constexpr int PIECES = (KIB + WAVES - 1) / WAVES;
+    static constexpr int SRC_OFF = OFF_KIB * 1024;
+    static __device__ __forceinline__ void issue_piece(const C& c, int p) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(
+            c.wrsrc, reinterpret_cast<lds_void*>(reinterpret_cast<lds_char*>(0) + c.s_wdst[NEXT & 1] + p * (WAVES * 1024)), 16,
+            c.lane16, c.wave_goff + (SRC_OFF + p * WAVES * 1024), 0, 0);
+    }
+    static __device__ __forceinline__ void issue(const C& c) {
+#pragma unroll
+        for (int p = 0; p < PIECES; ++p) issue_piece(c, p);
+    }
+};
 
 // ---- counter RNG: Philox-4x32-10 (Salmon et al. 2011), keyed by seed,
 // counter = global sample id.  One 32-bit word -> u in [0,1) with 24 bits, the

@@ -357,6 +357,21 @@ def test_counted_vmcnt_waits():
         assert sum(n for n, _ in stores.values()) >= (76 if src == "mlp_bf16_16.hip" else 152), (src, stores)
         for name, (n, offenders) in stores.items():
             assert not offenders, (src, name, offenders[:3])
+    # The sigma-only kernels (density.hip) run the same chain (csrc/mlp16_chain.h) on a plan of 30 chunks: 30 chunk
+    # barriers plus the launch's own wait, each vmcnt(0) with nothing issued behind the DMA, in both builds.
+    for flags, op in (((), "bf16"), (("-DNERF_HALF",), "f16")):
+        asm = check_vmcnt.assemble(os.path.join(root, "nerf-simple_amd", "csrc", "density.hip"), flags)
+        res = check_vmcnt.kernels_of(asm)
+        # points mode, grid mode and, built once with the bf16 kernels, nerf_grid_points_kernel
+        assert len(res) == (2 if flags else 3), (flags, list(res))
+        density = {k: v for k, v in res.items() if "nerf_density_" in k}
+        assert len(density) == 2, list(res)
+        for name, lines in density.items():
+            mfma = [ln.split()[0] for ln in lines if ln.lstrip().startswith("v_mfma")]
+            assert len(mfma) == 1936 and set(mfma) == {"v_mfma_f32_16x16x32_" + op}, (name, len(mfma), set(mfma))
+            checked, bad = check_vmcnt.check_kernel(lines)
+            assert checked == 31, (name, checked)
+            assert not bad, (name, bad[:5])
 
 
 def test_inference_kernels_have_few_hazard_nops():
@@ -387,6 +402,20 @@ def test_inference_kernels_have_few_hazard_nops():
         assert len(nops) <= 150, (name, len(nops))
         seen += 1
     assert seen == 3
+    # density.hip instantiates the same chunk_step (csrc/mlp16_chain.h): 59 s_nop between the first and the last of its
+    # 1936 MFMAs in either mode and either build, as measured on the commit before the chain was shared
+    for flags in ((), ("-DNERF_HALF",)):
+        asm = check_vmcnt.assemble(os.path.join(root, "nerf-simple_amd", "csrc", "density.hip"), flags)
+        seen = 0
+        for name, lines in check_vmcnt.kernels_of(asm).items():
+            if "nerf_density_" not in name:
+                continue
+            mfma = [i for i, ln in enumerate(lines) if re.match(r"\s+v_mfma", ln)]
+            assert len(mfma) == 1936, (name, len(mfma))
+            nops = [ln for ln in lines[mfma[0]:mfma[-1] + 1] if re.match(r"\s+s_nop", ln)]
+            assert len(nops) <= 59, (name, len(nops))
+            seen += 1
+        assert seen == 2
 
 
 def test_stamp_tool_insertion_points():
