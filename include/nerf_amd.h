@@ -617,6 +617,33 @@ int nerf_amd_volume_render_masked_pixels(const float* raw_live, const float* ray
                                          uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
                                          const int64_t* offsets, float* pixels, int64_t B, int N, void* stream);
 
+/* ---- training with the occupancy grid: the masked compositor's backward and the running density volume ------------------
+ * Not in the reference.  tests/occupancy_train_model.py restates both in torch / numpy.
+ *
+ * nerf_amd_volume_render_masked_backward: d loss / d raw_live[P', 4] of nerf_amd_volume_render_masked, for the same
+ *   (raw_live, rays, u, tbins, flags, seed, ray_id0, mask, offsets), given the upstream gradients of its five outputs:
+ *   g_rgb[B,3], g_disp[B], g_alpha[B,N], g_acc[B], g_w[B,N] (dense [B,N], whatever the mask; any of them NULL = zero).
+ *   Semantics: d_raw_live is the rows at the live samples of nerf_amd_volume_render_rays_backward run on the dense
+ *   raw[B,N,4] whose dead rows hold (0, 0, 0, -inf), with the sample positions of nerf_amd_query_points.  A dead sample has
+ *   softplus' = 0, alpha = 0 and w = 0 in that kernel: it receives nothing and contributes exact zeros to the suffix sums.
+ *   One wavefront per ray, no atomics: row offsets[ray] + rank is written by exactly one lane, nothing outside [0, P') is
+ *   written, and every run writes the same bytes.  A ray with no live sample writes nothing.  At N = 1 (the reference's
+ *   empty sample axis) every live row gets zeros.  N <= 512 like the dense backward (NERF_AMD_EUNSUP beyond; N <= 0 is
+ *   NERF_AMD_EINVAL).  With P' = 0 raw_live and d_raw_live may both be NULL; otherwise both are given, 16-byte aligned.
+ *   Arguments are checked on the host before any launch.
+ *
+ * nerf_amd_occupancy_decay_max: state[i] = max(fl(state[i] * decay), softplus(sigma_now[i])), i < n, in place.
+ *   sigma_now: raw sigma on the grid points (nerf_amd_density_grid); softplus is the compositor's (beta = 1, identity
+ *   above 20), so state is a density, >= 0, fp32.  A NaN on either side gives NaN, which
+ *   nerf_amd_occupancy_from_density treats as live.  The bits of a training grid are
+ *   nerf_amd_occupancy_from_density(state, softplus(level), dilate).  0 <= decay <= 1 (NERF_AMD_EINVAL otherwise). */
+int nerf_amd_volume_render_masked_backward(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                           uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                           const int64_t* offsets, const float* g_rgb, const float* g_disp,
+                                           const float* g_alpha, const float* g_acc, const float* g_w, float* d_raw_live,
+                                           int64_t B, int N, void* stream);
+int nerf_amd_occupancy_decay_max(float* state, const float* sigma_now, float decay, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

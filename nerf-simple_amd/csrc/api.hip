@@ -79,6 +79,10 @@ int nerf_amd_launch_occ_mark(const MlpArgs*, const unsigned*, long long, long lo
                              unsigned long long*, long long*, long long*, void*, long long, hipStream_t);
 int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const long long*, float*, long long, long long, hipStream_t);
 int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
+int nerf_amd_occ_train_max_n(void);
+int nerf_amd_launch_occ_composite_backward(const MlpArgs*, const unsigned long long*, const long long*, const float*, const float*,
+                                           const float*, const float*, const float*, const float*, float*, long long, hipStream_t);
+int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
 }
 
 namespace {
@@ -926,6 +930,31 @@ int nerf_amd_volume_render_masked_pixels(const float* raw_live, const float* ray
     a.pixels = pixels;
     return nerf_amd_launch_occ_composite(&a, reinterpret_cast<const unsigned long long*>(mask),
                                          reinterpret_cast<const long long*>(offsets), raw_live, B, S(stream));
+}
+
+// ---- training with the occupancy grid (csrc/occupancy_train.hip; not in the reference) ---------------------------------
+int nerf_amd_volume_render_masked_backward(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                           uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                           const int64_t* offsets, const float* g_rgb, const float* g_disp, const float* g_alpha,
+                                           const float* g_acc, const float* g_w, float* d_raw_live, int64_t B, int N, void* stream) {
+    const int rc = occ_rays(rays, u, tbins, flags, B, N);
+    if (rc) return rc;
+    if (N > nerf_amd_occ_train_max_n()) return NERF_AMD_EUNSUP;
+    if (B == 0) return 0;
+    if (!mask || !offsets || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)raw_live & 15) ||
+        ((uintptr_t)d_raw_live & 15) || (!raw_live != !d_raw_live))
+        return NERF_AMD_EINVAL;
+    const MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    return nerf_amd_launch_occ_composite_backward(&a, reinterpret_cast<const unsigned long long*>(mask),
+                                                  reinterpret_cast<const long long*>(offsets), raw_live, g_rgb, g_disp, g_alpha,
+                                                  g_acc, g_w, d_raw_live, B, S(stream));
+}
+
+int nerf_amd_occupancy_decay_max(float* state, const float* sigma_now, float decay, int64_t n, void* stream) {
+    if (n < 0 || !(decay >= 0.f && decay <= 1.f)) return NERF_AMD_EINVAL;
+    if (n == 0) return 0;
+    if (!state || !sigma_now) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_occ_decay_max(state, sigma_now, decay, n, S(stream));
 }
 
 }  // extern "C"

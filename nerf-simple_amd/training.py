@@ -308,6 +308,114 @@ def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_
 
 
 # --------------------------------------------------------------------------
+# training with empty-space skipping: the masked render with gradients
+# --------------------------------------------------------------------------
+class _MaskedVolumeRender(torch.autograd.Function):
+    """raw_live [P',4] -> the 5-tuple of nerf_amd_volume_render_masked (alpha / w dense [B,N], zero at dead samples), with
+    nerf_amd_volume_render_masked_backward.  ``head`` = (rays, jitter, tbins, flags, seed, ray_id0, mask, offsets)."""
+
+    @staticmethod
+    def forward(ctx, raw_live, head, B, N):
+        rays, jit, tbins, flags, seed, ray_id0, mask, offsets = head
+        dev = rays.device
+        raw_live = raw_live.contiguous()
+        rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        disp = torch.empty((B,), dtype=torch.float32, device=dev)
+        acc = torch.empty((B,), dtype=torch.float32, device=dev)
+        alpha = torch.empty((B, N), dtype=torch.float32, device=dev)
+        w = torch.empty((B, N), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_volume_render_masked(
+                _lib.ptr(raw_live) if raw_live.numel() else None, _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags,
+                int(seed), int(ray_id0), _lib.ptr(mask), _lib.ptr(offsets), _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha),
+                _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)), "nerf_amd_volume_render_masked")
+        ctx.save_for_backward(raw_live, rays, jit, tbins, mask, offsets)
+        ctx.args = (flags, int(seed), int(ray_id0), B, N)
+        if N == 1:        # the reference's empty sample axis (utils/rendering.py:60-61; csrc/composite_device.h)
+            alpha, w = alpha[:, :0], w[:, :0]
+        return rgb, disp, alpha, acc, w
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_disp, g_alpha, g_acc, g_w):
+        raw_live, rays, jit, tbins, mask, offsets = ctx.saved_tensors
+        flags, seed, ray_id0, B, N = ctx.args
+        dev = rays.device
+        d_raw = torch.empty_like(raw_live)
+
+        def c(g):
+            return None if (g is None or g.numel() == 0) else g.contiguous().float()
+        g_rgb, g_disp, g_alpha, g_acc, g_w = map(c, (g_rgb, g_disp, g_alpha, g_acc, g_w))
+        live = raw_live.numel() > 0
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_volume_render_masked_backward(
+                _lib.ptr(raw_live) if live else None, _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, seed, ray_id0,
+                _lib.ptr(mask), _lib.ptr(offsets), _lib.ptr(g_rgb), _lib.ptr(g_disp), _lib.ptr(g_alpha), _lib.ptr(g_acc),
+                _lib.ptr(g_w), _lib.ptr(d_raw) if live else None, B, N, _lib.stream_ptr(dev)),
+                "nerf_amd_volume_render_masked_backward")
+        return d_raw, None, None, None
+
+
+class _ZeroParamGrads(torch.autograd.Function):
+    """An empty raw_live [0,4] that still hangs on the parameters: a batch with no live sample launches no network kernel
+    and its backward hands every parameter a zero tensor, not None."""
+
+    @staticmethod
+    def forward(ctx, *params):
+        ctx.like = params
+        return torch.empty((0, 4), dtype=torch.float32, device=params[0].device)
+
+    @staticmethod
+    def backward(ctx, _g):
+        return tuple(torch.zeros_like(p) for p in ctx.like)
+
+
+def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0):
+    """``render_nerf`` through an occupancy grid WITH gradients to the parameters of ``net``: the network is evaluated
+    (fused bf16 training kernels, points mode) at the live samples only, a dead sample is (0, 0, 0, -inf) -- it contributes
+    exactly nothing and receives no gradient.  Returns the same 5-tuple; alpha / w are dense [B,N], zero at dead samples.
+
+    Stages: mark + scan -> ONE host read of the live count P' -> emit pts[P',6] -> training forward on the points ->
+    masked compositor; backward: masked compositor backward -> dX chain -> dW products.  With P' = 0 no network kernel is
+    launched and every parameter gradient is a zero tensor.  Sets ``occupancy.last_stats``.  Raises, before any jitter is
+    drawn, for rays that require grad, precision='fp32' modules, other network sizes, foreign nets and N > 512."""
+    from .utils import occupancy as occ_mod
+    from .utils.rendering import _tbins
+    _lib.require_cuda_f32(rays, "rays")
+    if rays.dim() != 2 or rays.shape[1] != 6:
+        raise RuntimeError("rays must be [B, 6]")
+    B, N = rays.size(0), int(N)
+    dev = rays.device
+    occ_mod.check_trainable(occupancy, net, rays, N)
+    if N < 1:
+        raise RuntimeError(f"masked training serves 1 <= N <= {occ_mod.MAX_N_TRAIN} samples per ray, got N = {N}")
+    if occupancy.words.device != dev:
+        raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {dev}")
+    net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
+    jit, flags, pending = occ_mod._jitter(B, N, dev, u, ts, device_rng)
+    try:
+        rays = rays.detach().contiguous()
+        tbins = None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, N, dev)
+        m = occ_mod._mark(occupancy, rays, jit, tbins, flags, seed, ray_id0, N)
+        pts = occ_mod._points(m, rays, jit, tbins, flags, seed, ray_id0)
+        stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
+        occupancy.last_stats = stats
+        params = [p for _, p in net.named_parameters()]
+        if m.live:
+            # the reference's |x| > 1 warning, on the points the network is asked about (lazily, as Nerf.forward does)
+            from .utils.xyz import range_check_values
+            range_check_values(pts)
+            raw_live, _ = _FusedDense.apply(net, None, None, None, 0, 0, 0, 1, pts, *params)
+            raw_live = raw_live.reshape(-1, 4)
+            stats["network_launches"] = 1
+        else:
+            raw_live = _ZeroParamGrads.apply(*params)
+        return _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+    finally:
+        if pending is not None:
+            pending.finish()
+
+
+# --------------------------------------------------------------------------
 # one optimisation step (reference train.py:47-57)
 # --------------------------------------------------------------------------
 def lr_decay_factor(lr_init, lr_final, num_iters):
@@ -317,17 +425,26 @@ def lr_decay_factor(lr_init, lr_final, num_iters):
 
 
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
-               precision=None, device_rng=False, seed=0, ray_id0=0):
+               precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
     """zero_grad -> render_nerf -> MSELoss(rgb, gt) -> backward -> [grad all-reduce]
     -> optimizer.step -> lr *= decay.  Returns the (detached) loss.
     Only ``rgb`` feeds the loss, as in the reference (train.py:52).
     The dense layers train in bf16 whatever the module's inference precision ('bf16' or 'fp16');
-    precision 'fp32' trains exactly, layer by layer in fp32 (utils/generic_mlp.py): slow, and the reference's numbers."""
+    precision 'fp32' trains exactly, layer by layer in fp32 (utils/generic_mlp.py): slow, and the reference's numbers.
+    occupancy: an ``OccupancyGrid`` -- the render is ``render_nerf_masked`` (the network sees the live samples only; one
+    host synchronisation per step); everything else is the same step."""
     from . import parallel
     from .utils.rendering import render_nerf
+    if occupancy is not None:
+        from .utils.occupancy import check_trainable
+        check_trainable(occupancy, net, rays, N, precision)      # before zero_grad: a refused call changes nothing
     optimizer.zero_grad(set_to_none=True)
-    rgb, _, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
-                                  device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+    if occupancy is not None:
+        rgb, _, _, _, _ = render_nerf_masked(rays, net, N, occupancy, tn, tf, u=u, device_rng=device_rng, seed=seed,
+                                             ray_id0=ray_id0)
+    else:
+        rgb, _, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
+                                      device_rng=device_rng, seed=seed, ray_id0=ray_id0)
     loss = mse_loss(rgb, gt)
     loss.backward()
     parallel.allreduce_gradients(net.parameters(), group=group)

@@ -16,6 +16,15 @@ restated in numpy by tests/occupancy_model.py.
 Stages (csrc/occupancy.hip): mark (per-ray live masks) -> scan (offsets, live count) -> ONE host read of the live count
 -> emit (compacted query points) -> the existing points-mode forward under the fp16 range guard -> masked composite.
 Inference only, default network shape only, fp16 / bf16 / fp32.
+
+Training with a grid: ``TrainingOccupancyGrid`` (a grid that is refreshed from the network while it trains) and
+``training.render_nerf_masked`` / ``training.train_step(..., occupancy=)`` -- DESIGN.md section 13.
+
+    occ = TrainingOccupancyGrid(128, outside="empty", device="cuda")
+    for step in range(steps):
+        if step >= warmup and step % 16 == 0:
+            occ.update(net, level=-1.75)
+        train_step(net, opt, rays, gt, 64, device_rng=True, seed=step, occupancy=occ)
 """
 import ctypes
 
@@ -27,6 +36,7 @@ from .mesh import DEFAULT_BOUNDS, _host_f32x3, _resolution, density_grid, grid_a
 
 _POLICIES = ("live", "empty")
 MAX_N = 768                             # samples per ray the mask layout and the masked compositor serve
+MAX_N_TRAIN = 512                       # ... and the masked compositor's backward (the dense backward's own limit)
 
 
 class MarkResult:
@@ -129,6 +139,75 @@ class OccupancyGrid:
         finally:
             if pending is not None:
                 pending.finish()
+
+
+def softplus_level(level):
+    """softplus(level) as a float32 (beta = 1, identity above 20, numpy's float32 exp / log1p): the threshold a
+    ``TrainingOccupancyGrid`` compares its density-unit state volume with, for a ``level`` given in raw-sigma units."""
+    x = np.float32(level)
+    with np.errstate(over="ignore"):
+        return x if x > np.float32(20) else np.log1p(np.exp(x, dtype=np.float32), dtype=np.float32)
+
+
+class TrainingOccupancyGrid(OccupancyGrid):
+    """An occupancy grid that follows a network while it trains.  It starts with every cell live and
+    keeps ``state``, a float32 volume [Rx, Ry, Rz] on the grid points: a decayed running maximum of the density
+    softplus(sigma) seen at each point, zero at first.  ``update`` refreshes the bits in place, so the grid object handed
+    to ``training.train_step(..., occupancy=)`` / ``training.render_nerf_masked`` stays the same; being an
+    ``OccupancyGrid`` it also serves the inference renders."""
+
+    def __init__(self, resolution, bounds=DEFAULT_BOUNDS, *, outside="empty", device):
+        R = _resolution(resolution)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"the occupancy grid must live on the GPU (got {device}); this package has no CPU path")
+        cells = torch.ones(tuple(r - 1 for r in R), dtype=torch.bool, device=device)
+        words = OccupancyGrid.from_mask(cells, bounds, outside=outside).words
+        super().__init__(words, R, bounds, outside)
+        self.state = torch.zeros(R, dtype=torch.float32, device=device)
+        self.updates = 0
+
+    def update(self, net, level, *, decay=0.95, dilate=1, precision=None):
+        """state <- max(state * decay, softplus(sigma of ``net`` on the grid)); bits <- state against softplus(level) with
+        the corner / dilation rule of ``from_density``, written into the same ``words`` tensor; ``cell_fraction``
+        refreshed (one host read).  level: raw-sigma units, no default.  Runs under ``torch.no_grad()``."""
+        if int(dilate) != dilate or dilate < 0:
+            raise ValueError(f"dilate must be a non-negative integer, got {dilate!r}")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"decay must lie in [0, 1], got {decay!r}")
+        with torch.no_grad():
+            sigma = density_grid(net, self.resolution, self.bounds, precision=precision)
+        if sigma.device != self.state.device:
+            raise RuntimeError(f"the occupancy grid lives on {self.state.device}, the network on {sigma.device}")
+        lib, dev = _lib.lib(), self.state.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            _lib.check(lib.nerf_amd_occupancy_decay_max(_lib.ptr(self.state), _lib.ptr(sigma), ctypes.c_float(float(decay)),
+                                                        self.state.numel(), st), "nerf_amd_occupancy_decay_max")
+            _lib.check(lib.nerf_amd_occupancy_from_density(_lib.ptr(self.state), *self.resolution,
+                                                           ctypes.c_float(float(softplus_level(level))), int(dilate),
+                                                           _lib.ptr(self.words), st), "nerf_amd_occupancy_from_density")
+        self.cell_fraction = self._count() / float(np.prod([r - 1 for r in self.resolution]))
+        self.updates += 1
+        return self
+
+
+def check_trainable(occupancy, net, rays, N, precision=None):
+    """The preconditions of ``training.render_nerf_masked``; raises before any jitter is drawn."""
+    from .nets import Nerf
+    if not isinstance(occupancy, OccupancyGrid):
+        raise TypeError("occupancy must be an OccupancyGrid (utils/occupancy.py)")
+    if not (isinstance(net, Nerf) and net._fused_ok()):
+        raise RuntimeError("masked training (occupancy=) serves the default Nerf(10, 4, 256) only: other network sizes and "
+                           "foreign nets are not supported; train without occupancy")
+    if _lib.precision_code(net.precision if precision is None else precision) == _lib.F32:
+        raise RuntimeError("masked training (occupancy=) runs the fused bf16 training kernels: precision='fp32' modules are "
+                           "not supported; build the module with precision='bf16' or 'fp16', or train without occupancy")
+    if rays.requires_grad:
+        raise RuntimeError("masked training (occupancy=) gives no gradients to the rays; detach them, or render without "
+                           "occupancy")
+    if int(N) > MAX_N_TRAIN:
+        raise RuntimeError(f"masked training serves 1 <= N <= {MAX_N_TRAIN} samples per ray, got N = {N}")
 
 
 def _jitter(B, N, dev, u, ts, device_rng):
