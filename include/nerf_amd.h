@@ -148,7 +148,17 @@ int nerf_amd_volume_render_pixels(const float* raw, const float* ts, const float
 /* Backward of the above: d loss / d raw [B,N,4] from the upstream gradients of
  * the five outputs (any of g_* may be NULL = zero).  Autograd through
  * volume_render in the training step, reference train.py:51-54.  ts and dirs
- * get no gradient (they carry none in the reference either).  N <= 512. */
+ * get no gradient (they carry none in the reference either).  N <= 512.
+ * Per element (tests/test_gpu_ray_routines.py): d alpha / d sigma is e delta softplus'(sigma) with e = exp(-softplus(sigma)
+ * delta) itself and softplus' = exp(sigma) / (1 + exp(sigma)) as autograd forms them, so a nearly opaque sample (e -> 0)
+ * and a hugely negative sigma keep their relative precision.
+ * Where the disparity has no slope: on its clamp branch (depth / acc <= 1e-10) g_disp contributes zero, as in autograd; on an
+ * EMPTY ray (acc == 0: disparity = 1 / max(1e-10, 0/0) = NaN) g_disp contributes ZERO as well, where autograd writes NaN
+ * into the whole sigma column (NaN x softplus', even where softplus' is 0) -- the forward's NaN disparity already reports
+ * the empty ray, and a NaN here would reach every weight.
+ * Non-finite raw values: d_raw has NaN exactly where the reference's fp32 autograd has it (g_rgb upstream: the whole sigma
+ * column of a ray that holds a NaN sigma, the colours from that sample on, 0 x inf products), and every other ray is
+ * bit for bit what it is when run alone. */
 int nerf_amd_volume_render_backward(const float* raw, const float* ts,
                                     const float* dirs, int64_t dirs_stride,
                                     const float* g_rgb, const float* g_disp, const float* g_alpha,
@@ -248,7 +258,12 @@ int nerf_amd_render_image_forward(const float* h_pose, int H, int W, float f,
  * NeRF paper's sample_pdf over interior bins), merged and sorted with the Nc
  * coarse positions: ts[B,Nc], w[B,Nc], u[B,Nf] in [0,1) (or NERF_AMD_DEVICE_RNG)
  * -> ts_out[B,Nc+Nf] ascending.  Feed ts_out to nerf_amd_render_forward with
- * NERF_AMD_TS_GIVEN for the fine pass.  3 <= Nc <= 256, Nc+Nf <= 512. */
+ * NERF_AMD_TS_GIVEN for the fine pass.  3 <= Nc <= 256, Nc+Nf <= 512.
+ * Per ray (tests/test_gpu_ray_routines.py): ts_out is ascending and holds the Nc coarse positions bit for bit.  A new
+ * position is z = b0 + (u - c0) / denom (b1 - b0) between the mids b0, b1 of its bin, accurate to a few
+ * 2^-24 [(b1 - b0) (1 + (c1 + u) / denom) + |z|]: the cdf's rounding divided by the bin's mass.  denom = c1 - c0 is replaced
+ * by 1 below 1e-5 (the paper's guard), so a bin whose mass is within fp32 rounding of 1e-5 -- every empty bin (weight 0
+ * + the 1e-5 floor) of an opaque ray, whose weights sum to 1 -- may place its sample at either end of the bin. */
 int nerf_amd_sample_pdf(const float* ts, const float* w, const float* u,
                         uint32_t flags, uint64_t seed, int64_t ray_id0,
                         float* ts_out, int64_t B, int Nc, int Nf, void* stream);

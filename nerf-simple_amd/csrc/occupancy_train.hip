@@ -97,11 +97,16 @@ __global__ __launch_bounds__(64 * OCCT_RAYS_PER_BLOCK) void occ_composite_backwa
                 float delta = (i == N - 1) ? 1e10f : sub_rn(rts[i + 1], t);
                 delta = mul_rn(delta, dnorm);
                 const float sigma = c[3];
-                const float sp = sigma > 20.f ? sigma : log1pf(expf(sigma));
-                const float spd = sigma > 20.f ? 1.0f : 1.0f / (1.0f + expf(-sigma));
-                a_ = sub_rn(1.0f, expf(mul_rn(-sp, delta)));
+                const float z = expf(sigma);
+                const float sp = sigma > 20.f ? sigma : log1pf(z);
+                // softplus' as torch's backward forms it: z / (z + 1) keeps exp(sigma) down to the subnormals, where
+                // 1 / (1 + exp(-sigma)) is 0 from sigma = -88.7 on (a last sample's delta = 1e10 brings that back up)
+                const float spd = sigma > 20.f ? 1.0f : z / (z + 1.0f);
+                const float e = expf(mul_rn(-sp, delta));
+                a_ = sub_rn(1.0f, e);
                 fac = add_rn(sub_rn(1.0f, a_), 1e-10f);
-                ds[ch] = (1.0f - a_) * delta * spd;      // d alpha / d sigma
+                // e itself, not 1 - alpha: that recovers e to an absolute 2^-24, a relative 2^-24 / e on a nearly opaque sample
+                ds[ch] = e * delta * spd;      // d alpha / d sigma
                 tt[ch] = t; cc[ch] = c;
             }
             before += __popcll(mw);
