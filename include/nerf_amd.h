@@ -659,6 +659,46 @@ int nerf_amd_volume_render_masked_backward(const float* raw_live, const float* r
                                            int64_t B, int N, void* stream);
 int nerf_amd_occupancy_decay_max(float* state, const float* sigma_now, float decay, int64_t n, void* stream);
 
+/* ---- graphed masked training step: device-side live count, fixed capacity (csrc/occupancy_graph.hip) -------------------
+ * Not in the reference.  tests/occupancy_graphed_model.py restates the semantics in numpy.
+ *
+ * A masked step captured into a graph has no host in it, so the live count P' = offsets[B] of a batch can size nothing.
+ * Such a step is captured for a fixed point CAPACITY C, 1 <= C <= B N: every network kernel (nerf_amd_mlp_forward_train_points,
+ * nerf_amd_encode_points_bf16, nerf_amd_mlp_backward, nerf_amd_param_gradients_begin, nerf_amd_param_gradients_finish_bucket)
+ * runs with P = C on every replay, P' comes from nerf_amd_occupancy_mark and stays on the device, and the two entry points
+ * below make the rows that no live sample owns inert:
+ *   - kept samples: sample i of ray b is KEPT iff its mask bit is set and its global rank
+ *     r = offsets[b] + (set bits of the ray below i) is < C.  mask_C is the mask with every other bit cleared,
+ *     offsets_C = min(offsets, C) its scan.  The step IS the masked step above with mask_C / offsets_C in place of
+ *     mask / offsets.  With P' <= C nothing changes; with P' > C (an OVERFLOW) the tail of the live samples in ray-major
+ *     order is dead -- (0, 0, 0, -inf), contributing exactly nothing and receiving no gradient: a well-defined,
+ *     deterministic step under a stricter mask, never an out-of-bounds access.  It is reported through `counts`.
+ *   - surplus rows r in [min(P', C), C): pts[r] = NERF_AMD_OCCUPANCY_PAD_POINT (inside the network's input range),
+ *     d_raw_live[r] = 0, so the dX chain and the dW / db products add exact zeros for them.  Every byte of pts[C, 6] and
+ *     d_raw_live[C, 4] is written on every launch: nothing of an earlier replay survives.
+ *   - counts: DEVICE int64[2] = {P', min(P', C)}, written on every launch.
+ * Both: one wavefront per ray for the kept rows, a grid-stride tail for the surplus rows, no atomics (the two row ranges
+ * are disjoint; every run writes the same bytes).  Jitter flags as the other masked stages, NERF_AMD_DEVICE_RNG |
+ * NERF_AMD_SEED_IN_MEMORY included (a node of a replayed graph).  Arguments are checked on the host before any launch:
+ * NULL or misaligned buffers (mask, offsets, counts 8 bytes; raw_live, d_raw_live 16), B < 0, N <= 0, capacity < 1 or
+ * > B N (so B = 0 as well), unknown flags: NERF_AMD_EINVAL; N > 512 (the masked backward's limit) or B > 2^32:
+ * NERF_AMD_EUNSUP.
+ *
+ * nerf_amd_occupancy_points_capped: pts[C, 6]; rows r < min(P', C) bit for bit the rows of nerf_amd_occupancy_points.
+ * nerf_amd_volume_render_masked_mse_backward: the training head of the masked step in one launch, nerf_amd_volume_render_masked
+ *   (rgb only) -> g_rgb = 2 (rgb - gt) / (3 B), formed in the kernel as nerf_amd_volume_render_mse_backward forms it ->
+ *   nerf_amd_volume_render_masked_backward, all under mask_C / offsets_C.  raw_live[C, 4]: the network's output on pts
+ *   (rows >= min(P', C) are never read).  Writes rgb[B, 3] (bit for bit the masked compositor's; 0 for a ray with nothing
+ *   kept) and all of d_raw_live[C, 4].  At N = 1 (the reference's empty sample axis) every row gets zeros. */
+#define NERF_AMD_OCCUPANCY_PAD_POINT {0.f, 0.f, 0.f, 0.f, 0.f, -1.f}   /* (x, y, z, d1, d2, d3): the origin, looking down -z */
+int nerf_amd_occupancy_points_capped(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
+                                     int64_t ray_id0, const uint64_t* mask, const int64_t* offsets, float* pts,
+                                     int64_t* counts, int64_t capacity, int64_t B, int N, void* stream);
+int nerf_amd_volume_render_masked_mse_backward(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                               uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                               const int64_t* offsets, const float* gt, float* rgb, float* d_raw_live,
+                                               int64_t capacity, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

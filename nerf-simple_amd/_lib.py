@@ -131,6 +131,9 @@ _SIGNATURES = {
     "nerf_amd_volume_render_masked_backward": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                       _vp, _i64, _i32, _vp]),
     "nerf_amd_occupancy_decay_max": (_i32, [_vp, _vp, ctypes.c_float, _i64, _vp]),
+    "nerf_amd_occupancy_points_capped": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "nerf_amd_volume_render_masked_mse_backward": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                          _i64, _i32, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

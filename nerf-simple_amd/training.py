@@ -1129,6 +1129,207 @@ class GraphedTrainStep:
         return span, exposed
 
 
+class _CountsWatch:
+    """Asynchronous read-back of the graphed masked step's ``counts`` (int64[2] = {live, kept}), after _StatusWatch: ``push``
+    enqueues a 16-byte copy into pinned memory behind graph A, ``poll`` hands back the copies that have completed, oldest
+    first, as (step, live, kept) -- no host wait."""
+
+    def __init__(self, slots=4):
+        self.bufs = [torch.zeros(2, dtype=torch.int64).pin_memory() for _ in range(slots)]
+        self.pending = []                       # (event, slot, step)
+        self.k = 0
+
+    def push(self, counts, step):
+        if len(self.pending) >= len(self.bufs):
+            return                              # every slot still in flight: skip this sample
+        slot = self.k % len(self.bufs)
+        self.k += 1
+        self.bufs[slot].copy_(counts, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(counts.device))
+        self.pending.append((ev, slot, step))
+
+    def poll(self, wait=False):
+        done = []
+        while self.pending and (wait or self.pending[0][0].query()):
+            ev, slot, step = self.pending.pop(0)
+            if wait:
+                ev.synchronize()
+            done.append((step, int(self.bufs[slot][0]), int(self.bufs[slot][1])))
+        return done
+
+
+class GraphedMaskedTrainStep(GraphedTrainStep):
+    """``train_step(..., occupancy=)`` as captured hipGraphs, on GraphedTrainStep's machinery (hyper
+    ring, status watch, ``rays_from`` selection, exchange, capture) -- DESIGN.md section 14.  The live count P' of a batch
+    never reaches the host on the step's path: the graph is captured for a fixed point ``capacity`` C (an int number of
+    points, or a float fraction of n_rays * N; NO default -- what is safe depends on the scene and the grid), every network
+    kernel runs on exactly C points, and the rows no live sample owns are inert (include/nerf_amd.h: pad points in,
+    zero d_raw out, so they add exact zeros to every gradient).
+
+        graph A: hyper fetch -> mark + scan (nerf_amd_occupancy_mark) -> capped emit (nerf_amd_occupancy_points_capped:
+                 pts[C, 6], counts) -> training forward on the C points -> masked head (compositor + MSE gradient +
+                 compositor backward, ONE kernel: nerf_amd_volume_render_masked_mse_backward) -> dX chain -> dW products;
+                 the encoder rows, the loss value, the zero fill / d_raw pack and (``rays_from`` with ``device_rng``) the
+                 next batch's selection on the one side branch beside the dX chain
+        graph B and the all-reduce seam: GraphedTrainStep's, unchanged (one exchange bucket).
+
+    With P' <= C the step is the eager masked step.  With P' > C (an overflow) the live samples of global rank >= C -- the
+    tail in ray-major order -- are treated as dead: a well-defined step under a stricter mask, reported, never silent:
+    every ``check_every`` steps ``counts`` is copied back without waiting; ``last_stats`` = {'step', 'samples', 'live',
+    'kept', 'capacity'} of the latest completed copy, an observed overflow raises a RuntimeWarning (``overflow_steps``
+    counts them), ``counts()`` reads the latest step's now (one sync).  To change the capacity build a new stepper on the
+    same optimizer (it holds the state).
+
+    ``occupancy``: an ``OccupancyGrid`` / ``TrainingOccupancyGrid`` on the module's device.  The address of its ``words``
+    is baked into the graph (``step`` raises if the tensor was replaced); ``TrainingOccupancyGrid.update`` writes the bits
+    in place, so an update between two replays simply takes effect.  Jitter and ``step`` as GraphedTrainStep.  bf16 storage,
+    N <= 512, the default network."""
+
+    def __init__(self, net, optimizer, n_rays, N, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+        from .utils import occupancy as occ_mod
+        if storage != "bf16":
+            raise ValueError(f"GraphedMaskedTrainStep keeps its operands in bf16: storage={storage!r} is not supported")
+        if buckets != 1:
+            raise ValueError("GraphedMaskedTrainStep exchanges its gradients in one bucket: buckets must be 1")
+        B, N_ = int(n_rays), int(N)
+        if B < 1 or N_ < 1:
+            raise ValueError(f"GraphedMaskedTrainStep needs n_rays >= 1 and N >= 1 (got {n_rays}, {N})")
+        occ_mod.check_trainable(occupancy, net, torch.empty(0), N_)
+        self._check_modules(net, optimizer)
+        import math
+        import numbers
+        if isinstance(capacity, bool) or not isinstance(capacity, numbers.Real):
+            raise TypeError("capacity must be an int (points) or a float (fraction of n_rays * N)")
+        if isinstance(capacity, numbers.Integral):
+            C = int(capacity)
+        else:
+            if not 0.0 < capacity <= 1.0:
+                raise ValueError(f"a fractional capacity must lie in (0, 1], got {capacity!r}")
+            C = max(1, math.ceil(float(capacity) * B * N_))
+        if not 1 <= C <= B * N_:
+            raise ValueError(f"capacity must lie in [1, n_rays * N = {B * N_}] points, got {C}")
+        if occupancy.words.device != optimizer.flat.device:
+            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the module on {optimizer.flat.device}")
+        self.occupancy, self.capacity = occupancy, int(C)
+        self._words_ptr = occupancy.words.data_ptr()
+        self._counts_watch = _CountsWatch()
+        self.last_stats, self.overflow_steps = None, 0
+        super().__init__(net, optimizer, B, N_, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed, ray_id0=ray_id0,
+                         check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        from .utils.mesh import _host_f32x3
+        from .utils.rendering import _tbins
+        lib, dev, occ = _lib.lib(), self.dev, self.occupancy
+        B, N_, C = self.B, self.N, self.capacity
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.tbins = _tbins(tn, tf, N_, dev)
+        self.mask = torch.zeros((B, (N_ + 63) // 64), dtype=torch.int64, device=dev)
+        self.offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        self._mark_ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+        self._counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        # the grid as the graph sees it: the words' address, the axes as HOST floats, the outside policy
+        self._grid = (tuple(occ.resolution), _host_f32x3(occ.lo), _host_f32x3(occ.inv_step),
+                      _lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
+        self.pts = torch.empty((C, 6), **f32)
+        self.raw = torch.empty((C, 4), **f32)
+        nb = int(lib.nerf_amd_train_activation_bytes(C))
+        self.acts = torch.empty(nb, dtype=torch.uint8, device=dev)
+        self.dys = torch.empty(nb, dtype=torch.uint8, device=dev)
+        self.posx = torch.empty((C, 64), dtype=torch.bfloat16, device=dev)
+        self.posd = torch.empty((C, 32), dtype=torch.bfloat16, device=dev)
+        self.rgb = torch.empty((B, 3), **f32)
+        self.d_raw = torch.empty((C, 4), **f32)
+        self.scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(C)), 16), dtype=torch.uint8, device=dev)
+
+    def _forward_backward(self, bucket=0):
+        import ctypes
+        lib, B, N_, C = _lib.lib(), self.B, self.N, self.capacity
+        packed = self.net.packed_weights(_lib.BF16)
+        image = self.net.packed_weights(_lib.BF16_BWD)
+        ck, ptr = _lib.check, _lib.ptr
+        main = torch.cuda.current_stream(self.dev)
+        side = self._side
+        st, ss = ctypes_stream(main), ctypes_stream(side)
+        self._ring.fetch(self.hyper, self.dev)
+        if self.device_rng:
+            jit = ctypes.c_void_p(self.hyper.data_ptr() + 24)
+            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
+        else:
+            jit, flags, seed, rid = ptr(self.u), 0, 0, 0
+        R, lo, inv, outside = self._grid
+        head = (ptr(self.rays), jit, ptr(self.tbins))
+        ck(lib.nerf_amd_occupancy_mark(*head, flags | outside, seed, rid, ctypes.c_void_p(self._words_ptr), *R, lo, inv,
+                                       ptr(self.mask), ptr(self.offsets), None, ptr(self._mark_ws), B, N_, st),
+           "nerf_amd_occupancy_mark")
+        ck(lib.nerf_amd_occupancy_points_capped(*head, flags, seed, rid, ptr(self.mask), ptr(self.offsets), ptr(self.pts),
+                                                ptr(self._counts), C, B, N_, st), "nerf_amd_occupancy_points_capped")
+        ck(lib.nerf_amd_mlp_forward_train_points(ptr(self.pts), ptr(packed), ptr(self.raw), ptr(self.acts), C, st),
+           "nerf_amd_mlp_forward_train_points")
+        ck(lib.nerf_amd_volume_render_masked_mse_backward(ptr(self.raw), *head, flags, seed, rid, ptr(self.mask), ptr(self.offsets),
+                                                          ptr(self.gt), ptr(self.rgb), ptr(self.d_raw), C, B, N_, st),
+           "nerf_amd_volume_render_masked_mse_backward")
+        fork = torch.cuda.Event()
+        fork.record(main)                           # behind the head: rgb, d_raw (and pts) are final
+        ck(lib.nerf_amd_mlp_backward(ptr(self.d_raw), ptr(image), ptr(self.acts), ptr(self.dys), C, st), "nerf_amd_mlp_backward")
+        side.wait_event(fork)
+        # the side branch as GraphedTrainStep's: what the dW products need besides dY, then the next batch (rays and gt
+        # have been read for the last time: mark, emit, head on the main branch in front of the fork, the loss here)
+        ck(lib.nerf_amd_encode_points_bf16(ptr(self.pts), ptr(self.posx), ptr(self.posd), C, ss), "nerf_amd_encode_points_bf16")
+        ck(lib.nerf_amd_mse_loss(ptr(self.rgb), ptr(self.gt), ptr(self.loss), None, B * 3, ss), "nerf_amd_mse_loss")
+        ck(lib.nerf_amd_param_gradients_begin(ptr(self.d_raw), ptr(self.scratch), ptr(self.grads), C, ss),
+           "nerf_amd_param_gradients_begin")
+        if self.rays_from is not None and self.device_rng:
+            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
+                                  self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
+        main.wait_stream(side)
+        self._finish(bucket, st)
+
+    def _finish(self, bucket, st):
+        lib, ptr, C = _lib.lib(), _lib.ptr, self.capacity
+        _lib.check(lib.nerf_amd_param_gradients_finish_bucket(ptr(self.acts), ptr(self.dys), ptr(self.posx), ptr(self.posd),
+                                                              ptr(self.scratch), ptr(self.grads), C, bucket, st),
+                   "nerf_amd_param_gradients_finish_bucket")
+
+    def _head_gradients(self):
+        pass                                         # one exchange bucket: graph A forms every product
+
+    def _range_check(self):
+        """Runs behind graph A on every ``check_every``-th step: the reference's |x| > 1 warning on the points the network
+        was asked about (the pad point is in range), and the copy of ``counts`` the overflow report reads."""
+        from .utils.xyz import range_check_values
+        range_check_values(self.pts)
+        self._counts_watch.push(self._counts, self.opt.step_count)
+
+    def _note(self, done):
+        import warnings
+        for step, live, kept in done:
+            self.last_stats = {"step": step, "samples": self.B * self.N, "live": live, "kept": kept, "capacity": self.capacity}
+            if live > self.capacity:
+                self.overflow_steps += 1
+                warnings.warn(f"GraphedMaskedTrainStep: step {step} had {live} live samples for a capacity of {self.capacity} "
+                              f"points; the last {live - kept} (ray-major order) were treated as dead.  Build a stepper with "
+                              "a larger capacity.", RuntimeWarning, stacklevel=3)
+
+    def counts(self):
+        """{'step', 'samples', 'live', 'kept', 'capacity'} of the latest step, read now (synchronises); pending reports
+        are delivered first."""
+        self._note(self._counts_watch.poll(wait=True))
+        live, kept = (int(v) for v in self._counts.cpu())
+        return {"step": self.opt.step_count, "samples": self.B * self.N, "live": live, "kept": kept, "capacity": self.capacity}
+
+    def step(self, rays=None, gt=None, u=None, decay=1.0):
+        if self.occupancy.words.data_ptr() != self._words_ptr:
+            raise RuntimeError("the occupancy grid's words tensor was replaced: its address is baked into the captured graph "
+                               "(TrainingOccupancyGrid.update writes in place); build a new GraphedMaskedTrainStep")
+        self._note(self._counts_watch.poll())
+        return super().step(rays, gt, u=u, decay=decay)
+
+    __call__ = step
+
+
 class GraphedHierarchicalTrainStep(GraphedTrainStep):
     """``train_step_hierarchical`` for the fused bf16 path as captured hipGraphs, on GraphedTrainStep's machinery (hyper
     ring, status watch, ``rays_from`` selection in both jitter modes, exchange, capture):
