@@ -699,6 +699,40 @@ int nerf_amd_volume_render_masked_mse_backward(const float* raw_live, const floa
                                                const int64_t* offsets, const float* gt, float* rgb, float* d_raw_live,
                                                int64_t capacity, int64_t B, int N, void* stream);
 
+/* ---- masked hierarchical pair: one occupancy grid for the coarse and the fine pass (csrc/occupancy_hier.hip) -----------
+ * Not in the reference.  tests/occupancy_hierarchical_model.py restates the semantics in numpy; DESIGN.md section 15.
+ *
+ * ONE grid masks both passes (while training it follows the FINE network).  The masked hierarchical render is BY DEFINITION
+ * this composition of existing entry points:
+ *   1. coarse pass: the masked render above on the Nc stratified samples (mark -> emit -> network on the live points ->
+ *      masked compositor): rgb_c and w_c[B, Nc], w_c = 0 exactly at a dead sample; the coarse positions ts_c are those of
+ *      nerf_amd_query_points for the same jitter.
+ *   2. sampler: ts_f = nerf_amd_sample_pdf(ts_c, w_c (detached), Nf, u_f | counter RNG); the coarse samples are kept and
+ *      merged, as in the dense pair.  A ray with no live coarse sample has w_c == 0 and the sampler's 1e-5 floor makes its
+ *      fine samples uniform: the defined result, not an error.
+ *   3. fine pass: the masked render with NERF_AMD_TS_GIVEN on ts_f[B, Nc + Nf] through the SAME grid, by the fine network.
+ *   Training loss: MSE(rgb_c, gt) + MSE(rgb_f, gt); the coarse network learns from its own term only.
+ * Limits (the intersection of the parts'): the default network, bf16 training kernels, 3 <= Nc <= 256, Nc + Nf <= 512, no
+ * gradients to the rays.
+ *
+ * nerf_amd_volume_render_masked_mse_backward_pdf: the masked COARSE head of a captured pair step, one launch, one wavefront per
+ *   ray: nerf_amd_volume_render_masked (rgb and w) -> g_rgb = 2 (rgb - gt) / (3 B) -> nerf_amd_volume_render_masked_backward ->
+ *   nerf_amd_sample_pdf(ts_c, w, ...), every stage under mask_C / offsets_C of the graphed masked step above.  rgb[B, 3] and
+ *   ts_out[B, Nc + Nf] are bit for bit that composition's; d_raw_live[C, 4] is the fused masked head's (kept rows from the
+ *   sweep, rows behind min(P', C) exact zeros, every byte written on every launch).  w never reaches HBM.
+ *   u / tbins / flags / seed / ray_id0: the COARSE jitter, as the other masked stages (NERF_AMD_TS_GIVEN: u = ts_c[B, Nc]).
+ *   The Nf new samples: u_f[B, Nf], or with NERF_AMD_DEVICE_RNG the counter RNG under nerf_amd_sample_pdf's key (seed,
+ *   ray_id0) -- with NERF_AMD_SEED_IN_MEMORY the same 64-bit offset at `u` is added to the seed of both draws, exactly as
+ *   nerf_amd_volume_render_mse_backward_pdf honours it (a node of a replayed graph).
+ *   Checked on the host before any launch: the rules of the two entry points above (NULL or misaligned buffers, B < 0,
+ *   Nc <= 0, Nf < 0, capacity < 1 or > B Nc, unknown flags, NERF_AMD_TS_GIVEN without u, no u_f without the counter RNG when
+ *   Nf > 0: NERF_AMD_EINVAL) and the sampler's limits (Nc < 3, Nc > 256, Nc + Nf > 512, B > 2^32: NERF_AMD_EUNSUP). */
+int nerf_amd_volume_render_masked_mse_backward_pdf(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                                   uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                                   const int64_t* offsets, const float* gt, const float* u_f, float* rgb,
+                                                   float* d_raw_live, float* ts_out, int64_t capacity, int64_t B, int Nc,
+                                                   int Nf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,8 @@ _SIGNATURES = {
     "nerf_amd_occupancy_points_capped": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "nerf_amd_volume_render_masked_mse_backward": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                                                           _i64, _i32, _vp]),
+    "nerf_amd_volume_render_masked_mse_backward_pdf": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                              _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -369,7 +369,8 @@ class _ZeroParamGrads(torch.autograd.Function):
         return tuple(torch.zeros_like(p) for p in ctx.like)
 
 
-def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0):
+def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0,
+                       return_ts=False):
     """``render_nerf`` through an occupancy grid WITH gradients to the parameters of ``net``: the network is evaluated
     (fused bf16 training kernels, points mode) at the live samples only, a dead sample is (0, 0, 0, -inf) -- it contributes
     exactly nothing and receives no gradient.  Returns the same 5-tuple; alpha / w are dense [B,N], zero at dead samples.
@@ -377,7 +378,9 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     Stages: mark + scan -> ONE host read of the live count P' -> emit pts[P',6] -> training forward on the points ->
     masked compositor; backward: masked compositor backward -> dX chain -> dW products.  With P' = 0 no network kernel is
     launched and every parameter gradient is a zero tensor.  Sets ``occupancy.last_stats``.  Raises, before any jitter is
-    drawn, for rays that require grad, precision='fp32' modules, other network sizes, foreign nets and N > 512."""
+    drawn, for rays that require grad, precision='fp32' modules, other network sizes, foreign nets and N > 512.
+    ``return_ts=True``: returns (5-tuple, ts [B,N]) -- the sample positions of this jitter as nerf_amd_query_points forms
+    them (the coarse pass of the masked pair hands them to the sampler)."""
     from .utils import occupancy as occ_mod
     from .utils.rendering import _tbins
     _lib.require_cuda_f32(rays, "rays")
@@ -409,7 +412,10 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
             stats["network_launches"] = 1
         else:
             raw_live = _ZeroParamGrads.apply(*params)
-        return _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+        out = _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+        if return_ts:
+            return out, occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
+        return out
     finally:
         if pending is not None:
             pending.finish()
@@ -471,6 +477,13 @@ def _check_pair(net_c, net_f, Nc, Nf, precision):
     return _lib.precision_code(net_c.precision if precision is None else precision)
 
 
+def _pair_stats(coarse, fine):
+    """``occupancy.last_stats`` of a masked pair render: the sums, and each pass's own report."""
+    out = {k: coarse[k] + fine[k] for k in ("samples", "live", "network_launches")}
+    out.update(rays=coarse["rays"], coarse=coarse, fine=fine)
+    return out
+
+
 def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0):
     """render_nerf_autograd that also hands back the sample positions it drew (the coarse pass of the pair)."""
     from .utils.rendering import _tbins
@@ -494,7 +507,7 @@ def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray
 
 
 def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
-                            decay=1.0, group=None, precision=None, device_rng=False, seed=0, ray_id0=0):
+                            decay=1.0, group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
     """One optimisation step of the coarse / fine pair (the NeRF paper's objective; the reference has no hierarchical
     path, its CoarseNet / FineNet are empty): zero_grad -> coarse render_nerf with gradients (Nc stratified samples) ->
     sample_pdf on the DETACHED coarse weights (the coarse net learns from its own loss only) -> fine render_nerf of
@@ -505,7 +518,14 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     Jitter: ``u_c`` [B,Nc] / ``u_f`` [B,Nf]; default the render_hierarchical draws, torch.rand(B,Nc) then
     torch.rand(B,Nf) from torch's CPU generator (continued on the device); ``device_rng=True``: the counter RNG keyed by
     (seed, ray_id0 + ray).  precision 'fp32' trains both exactly, layer by layer (utils/generic_mlp.py).
-    Returns the detached total loss; ``.losses`` on it holds the [coarse, fine] terms, ``.ts_f`` the fine positions."""
+    Returns the detached total loss; ``.losses`` on it holds the [coarse, fine] terms, ``.ts_f`` the fine positions.
+
+    occupancy: ONE ``OccupancyGrid`` masks both passes: the coarse pass is ``render_nerf_masked``
+    on the Nc stratified samples, the sampler sees its weights (exactly 0 at a dead sample; a ray with no live coarse
+    sample gets uniform fine samples), the fine pass is ``render_nerf_masked(ts=ts_f)`` through the same grid.  Two host
+    synchronisations per step (one live count per pass); ``occupancy.last_stats`` holds the sums and the two passes'
+    own reports under 'coarse' / 'fine'.  The default network and the bf16 training kernels only, rays without
+    requires_grad; refused before any jitter is drawn."""
     from . import parallel
     from .optim import FusedAdam
     from .utils.host_rng import reference_rand
@@ -527,6 +547,12 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     for name, t_, n in (("u_c", u_c, Nc), ("u_f", u_f, Nf)):
         if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
             raise RuntimeError(f"{name} must be [B, {n}]")
+    if occupancy is not None:
+        from .utils.occupancy import check_trainable
+        check_trainable(occupancy, net_c, rays, Nc, precision)       # before any draw: a refused call changes nothing
+        check_trainable(occupancy, net_f, rays, Nc + Nf, precision)
+        if occupancy.words.device != dev:
+            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {dev}")
     rays = rays.detach().contiguous()
     flags = 0
     if device_rng and u_c is None:
@@ -540,11 +566,20 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     jit_c = None if u_c is None else u_c.contiguous()
 
     optimizer.zero_grad(set_to_none=True)
-    coarse, ts_c = _render_train_with_ts(rays, net_c, Nc, tn, tf, jit_c, flags,
-                                         net_c.precision if precision is None else precision, seed, ray_id0)
+    if occupancy is not None:
+        coarse, ts_c = render_nerf_masked(rays, net_c, Nc, occupancy, tn, tf, u=jit_c, device_rng=jit_c is None, seed=seed,
+                                          ray_id0=ray_id0, return_ts=True)
+        stats_c = occupancy.last_stats
+    else:
+        coarse, ts_c = _render_train_with_ts(rays, net_c, Nc, tn, tf, jit_c, flags,
+                                             net_c.precision if precision is None else precision, seed, ray_id0)
     # the fine positions carry no gradient: w.detach() -- the coarse net learns from MSE(rgb_c, gt) alone
     ts_f = sample_pdf(ts_c, coarse[4].detach(), Nf, u=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
-    fine = render_nerf(rays, net_f, Nc + Nf, tn, tf, ts=ts_f, precision=precision)
+    if occupancy is not None:
+        fine = render_nerf_masked(rays, net_f, Nc + Nf, occupancy, tn, tf, ts=ts_f)
+        occupancy.last_stats = _pair_stats(stats_c, occupancy.last_stats)
+    else:
+        fine = render_nerf(rays, net_f, Nc + Nf, tn, tf, ts=ts_f, precision=precision)
     loss_c = mse_loss(coarse[0], gt)
     loss_f = mse_loss(fine[0], gt)
     loss = loss_c + loss_f
@@ -1134,8 +1169,8 @@ class _CountsWatch:
     enqueues a 16-byte copy into pinned memory behind graph A, ``poll`` hands back the copies that have completed, oldest
     first, as (step, live, kept) -- no host wait."""
 
-    def __init__(self, slots=4):
-        self.bufs = [torch.zeros(2, dtype=torch.int64).pin_memory() for _ in range(slots)]
+    def __init__(self, slots=4, width=2):
+        self.bufs = [torch.zeros(width, dtype=torch.int64).pin_memory() for _ in range(slots)]
         self.pending = []                       # (event, slot, step)
         self.k = 0
 
@@ -1155,7 +1190,7 @@ class _CountsWatch:
             ev, slot, step = self.pending.pop(0)
             if wait:
                 ev.synchronize()
-            done.append((step, int(self.bufs[slot][0]), int(self.bufs[slot][1])))
+            done.append((step, *(int(v) for v in self.bufs[slot])))
         return done
 
 
@@ -1470,5 +1505,211 @@ class GraphedHierarchicalTrainStep(GraphedTrainStep):
             self.u_f.copy_(u_f, non_blocking=True)
             u = self.u
         return super().step(rays, gt, u=u, decay=decay)
+
+    __call__ = step
+
+
+def _capacity_points(capacity, total, what):
+    """A capacity argument as points: an int is a number of points, a float a fraction of ``total`` (GraphedMaskedTrainStep's
+    rule).  ``what`` names the argument in the messages."""
+    import math
+    import numbers
+    if isinstance(capacity, bool) or not isinstance(capacity, numbers.Real):
+        raise TypeError(f"{what} must be an int (points) or a float (fraction of the pass's samples)")
+    if isinstance(capacity, numbers.Integral):
+        C = int(capacity)
+    else:
+        if not 0.0 < capacity <= 1.0:
+            raise ValueError(f"a fractional {what} must lie in (0, 1], got {capacity!r}")
+        C = max(1, math.ceil(float(capacity) * total))
+    if not 1 <= C <= total:
+        raise ValueError(f"{what} must lie in [1, {total}] points, got {C}")
+    return C
+
+
+class GraphedMaskedHierarchicalTrainStep(GraphedHierarchicalTrainStep):
+    """``train_step_hierarchical(..., occupancy=)`` as captured hipGraphs: GraphedHierarchicalTrainStep's
+    pair (one FusedAdam([net_c, net_f]), one combined gradient vector, the ``u_c`` / ``u_f`` jitter) with each pass run as
+    GraphedMaskedTrainStep runs its one -- on a fixed point capacity, the live counts never reaching the host.
+
+        graph A: hyper fetch -> mark + scan (coarse jitter) -> capped emit (C_c points) -> coarse training forward on them
+                 -> masked coarse head (masked compositor + MSE gradient + backward + sample_pdf on its weights, ONE kernel:
+                 nerf_amd_volume_render_masked_mse_backward_pdf, writes ts_f) -> mark + scan with NERF_AMD_TS_GIVEN on ts_f
+                 -> capped emit (C_f points) -> fine training forward -> fused masked head (NERF_AMD_TS_GIVEN) -> both dX
+                 chains -> both sets of dW products into the combined gradient vector, coarse first; both encoder-row
+                 launches, the two loss values and their sum, both zero fills / d_raw packs and (``rays_from`` with
+                 ``device_rng``) the next batch's selection on the one side branch beside the dX chains
+        graph B and the all-reduce seam: inherited (one exchange bucket; ``group`` is handed through unchanged).
+
+    ``capacity`` = (C_c, C_f): each an int (points) or a float (fraction of n_rays * Nc, of n_rays * (Nc + Nf)); NO default.
+    The fine samples gather where the coarse weights are, so the fine pass's live fraction is not the coarse pass's.
+    An overflow of either pass treats that pass's tail of live samples (ray-major) as dead, exactly as GraphedMaskedTrainStep:
+    with C_c short the sampler sees weights under the stricter mask.  Device ``counts``: int64[4] = {P'_c, kept_c, P'_f,
+    kept_f}; every ``check_every`` steps they are copied back without waiting: ``last_stats`` = {'step', 'coarse': {...},
+    'fine': {...}} (each {'samples', 'live', 'kept', 'capacity'}), an observed overflow raises a RuntimeWarning naming the
+    pass (``overflow_steps`` counts steps), ``counts()`` reads the latest step's now (one sync).
+
+    ``occupancy``: ONE grid for both passes; its ``words`` address is baked into the graph (``step`` raises if the tensor was
+    replaced; an in-place ``TrainingOccupancyGrid.update(net_f, ...)`` takes effect on the next replay).  ``losses`` holds
+    [coarse, fine].  bf16 storage, the default network, 3 <= Nc <= 256, Nc + Nf <= 512."""
+
+    def __init__(self, net_c, net_f, optimizer, n_rays, Nc, Nf, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
+                 seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+        from .utils import occupancy as occ_mod
+        name = type(self).__name__
+        if storage != "bf16":
+            raise ValueError(f"{name} keeps its operands in bf16: storage={storage!r} is not supported")
+        if buckets != 1:
+            raise ValueError(f"{name} exchanges its gradients in one bucket: buckets must be 1")
+        _check_pair(net_c, net_f, Nc, Nf, None)
+        B, Nc_, Nf_ = int(n_rays), int(Nc), int(Nf)
+        if B < 1:
+            raise ValueError(f"{name} needs n_rays >= 1 (got {n_rays})")
+        occ_mod.check_trainable(occupancy, net_c, torch.empty(0), Nc_)
+        occ_mod.check_trainable(occupancy, net_f, torch.empty(0), Nc_ + Nf_)
+        self._check_modules((net_c, net_f), optimizer)
+        if isinstance(capacity, (str, bytes)) or not hasattr(capacity, "__len__") or len(capacity) != 2:
+            raise TypeError("capacity must be a pair (C_c, C_f), each an int (points) or a float (fraction of the pass's samples)")
+        self.capacity = (_capacity_points(capacity[0], B * Nc_, "the coarse capacity"),
+                         _capacity_points(capacity[1], B * (Nc_ + Nf_), "the fine capacity"))
+        if occupancy.words.device != optimizer.flat.device:
+            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the module on {optimizer.flat.device}")
+        self.occupancy = occupancy
+        self._words_ptr = occupancy.words.data_ptr()
+        self._counts_watch = _CountsWatch(width=4)
+        self.last_stats, self.overflow_steps = None, 0
+        super().__init__(net_c, net_f, optimizer, B, Nc_, Nf_, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        from .utils.mesh import _host_f32x3
+        from .utils.rendering import _tbins
+        lib, dev, occ = _lib.lib(), self.dev, self.occupancy
+        B, Nc, M = self.B, self.Nc, self.Nc + self.Nf
+        f32 = dict(dtype=torch.float32, device=dev)
+        flat_u = self.u.view(-1)                         # ONE draw [B, Nc+Nf]: rand(B,Nc) then rand(B,Nf), as the dense pair
+        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, self.Nf)
+        self.tbins = _tbins(tn, tf, Nc, dev)
+        self._first_N, self._first_u = Nc, self.u_c
+        self.losses = torch.zeros(2, **f32)
+        self._mark_ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+        self._counts = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._grid = (tuple(occ.resolution), _host_f32x3(occ.lo), _host_f32x3(occ.inv_step),
+                      _lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
+        self.passes = []
+        for k, (N_, C) in enumerate(zip((Nc, M), self.capacity)):
+            nb = int(lib.nerf_amd_train_activation_bytes(C))
+            self.passes.append(dict(
+                N=N_, C=C, mask=torch.zeros((B, (N_ + 63) // 64), dtype=torch.int64, device=dev),
+                offsets=torch.zeros(B + 1, dtype=torch.int64, device=dev), counts=self._counts[2 * k:2 * k + 2],
+                pts=torch.empty((C, 6), **f32), raw=torch.empty((C, 4), **f32),
+                acts=torch.empty(nb, dtype=torch.uint8, device=dev), dys=torch.empty(nb, dtype=torch.uint8, device=dev),
+                posx=torch.empty((C, 64), dtype=torch.bfloat16, device=dev), posd=torch.empty((C, 32), dtype=torch.bfloat16, device=dev),
+                rgb=torch.empty((B, 3), **f32), d_raw=torch.empty((C, 4), **f32),
+                scratch=torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(C)), 16), dtype=torch.uint8, device=dev)))
+        self.ts_f = torch.empty((B, M), **f32)          # the masked coarse head's output: the fine pass's positions
+
+    def _forward_backward(self, bucket=0):
+        import ctypes
+        lib, B, Nc, Nf = _lib.lib(), self.B, self.Nc, self.Nf
+        ck, ptr = _lib.check, _lib.ptr
+        c, f = self.passes
+        (_, _, (fwd_c, bwd_c)), (_, _, (fwd_f, bwd_f)) = self._images
+        main = torch.cuda.current_stream(self.dev)
+        side = self._side
+        st, ss = ctypes_stream(main), ctypes_stream(side)
+        self._ring.fetch(self.hyper, self.dev)
+        if self.device_rng:
+            jit_c, jit_f = ctypes.c_void_p(self.hyper.data_ptr() + 24), None
+            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
+        else:
+            jit_c, jit_f, flags, seed, rid = ptr(self.u_c), ptr(self.u_f), 0, 0, 0
+        R, lo, inv, outside = self._grid
+        words = ctypes.c_void_p(self._words_ptr)
+        # (rays, jitter, tbins, flags, seed, ray_id0) of each pass: the coarse jitter; the fine positions as given
+        heads = (((ptr(self.rays), jit_c, ptr(self.tbins)), (flags, seed, rid)),
+                 ((ptr(self.rays), ptr(self.ts_f), None), (_lib.FLAG_TS_GIVEN, 0, 0)))
+        for p, image, (head, (fl, sd, ri)) in zip((c, f), (fwd_c, fwd_f), heads):
+            ck(lib.nerf_amd_occupancy_mark(*head, fl | outside, sd, ri, words, *R, lo, inv, ptr(p["mask"]), ptr(p["offsets"]), None,
+                                           ptr(self._mark_ws), B, p["N"], st), "nerf_amd_occupancy_mark")
+            ck(lib.nerf_amd_occupancy_points_capped(*head, fl, sd, ri, ptr(p["mask"]), ptr(p["offsets"]), ptr(p["pts"]),
+                                                    ptr(p["counts"]), p["C"], B, p["N"], st), "nerf_amd_occupancy_points_capped")
+            ck(lib.nerf_amd_mlp_forward_train_points(ptr(p["pts"]), ptr(image), ptr(p["raw"]), ptr(p["acts"]), p["C"], st),
+               "nerf_amd_mlp_forward_train_points")
+            if p is c:        # rgb_c, d_raw_c and ts_f: the fine pass's mark depends on it, so it is produced inside the graph
+                ck(lib.nerf_amd_volume_render_masked_mse_backward_pdf(
+                    ptr(p["raw"]), *head, fl, sd, ri, ptr(p["mask"]), ptr(p["offsets"]), ptr(self.gt), jit_f, ptr(p["rgb"]),
+                    ptr(p["d_raw"]), ptr(self.ts_f), p["C"], B, Nc, Nf, st), "nerf_amd_volume_render_masked_mse_backward_pdf")
+            else:
+                ck(lib.nerf_amd_volume_render_masked_mse_backward(
+                    ptr(p["raw"]), *head, fl, sd, ri, ptr(p["mask"]), ptr(p["offsets"]), ptr(self.gt), ptr(p["rgb"]),
+                    ptr(p["d_raw"]), p["C"], B, p["N"], st), "nerf_amd_volume_render_masked_mse_backward")
+        fork = torch.cuda.Event()
+        fork.record(main)                           # both heads done: rgb / d_raw / pts of both passes are final
+        for p, image in ((c, bwd_c), (f, bwd_f)):
+            ck(lib.nerf_amd_mlp_backward(ptr(p["d_raw"]), ptr(image), ptr(p["acts"]), ptr(p["dys"]), p["C"], st),
+               "nerf_amd_mlp_backward")
+        side.wait_event(fork)
+        n = self.opt.slices[0].numel()
+        grads = (self.grads[:n], self.grads[n:])
+        for p in (c, f):
+            ck(lib.nerf_amd_encode_points_bf16(ptr(p["pts"]), ptr(p["posx"]), ptr(p["posd"]), p["C"], ss),
+               "nerf_amd_encode_points_bf16")
+        for k, (p, g) in enumerate(zip((c, f), grads)):
+            ck(lib.nerf_amd_mse_loss(ptr(p["rgb"]), ptr(self.gt), ptr(self.losses[k]), None, B * 3, ss), "nerf_amd_mse_loss")
+            ck(lib.nerf_amd_param_gradients_begin(ptr(p["d_raw"]), ptr(p["scratch"]), ptr(g), p["C"], ss),
+               "nerf_amd_param_gradients_begin")
+        with torch.cuda.stream(side):
+            torch.add(self.losses[0], self.losses[1], out=self.loss)       # the total, MSE(rgb_c) + MSE(rgb_f)
+        if self.rays_from is not None and self.device_rng:
+            # the next step's batch, beside the dX chains: rays and gt have been read for the last time (marks, emits and
+            # heads on the main branch in front of the fork, the losses here)
+            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
+                                  self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
+        main.wait_stream(side)
+        for p, g in zip((c, f), grads):
+            ck(lib.nerf_amd_param_gradients_finish_bucket(ptr(p["acts"]), ptr(p["dys"]), ptr(p["posx"]), ptr(p["posd"]),
+                                                          ptr(p["scratch"]), ptr(g), p["C"], 0, st),
+               "nerf_amd_param_gradients_finish_bucket")
+
+    def _range_check(self):
+        """Behind graph A on every ``check_every``-th step: the reference's |x| > 1 warning on the points both networks were
+        asked about (the pad point is in range), and the copy of ``counts`` the overflow report reads."""
+        from .utils.xyz import range_check_values
+        for p in self.passes:
+            range_check_values(p["pts"])
+        self._counts_watch.push(self._counts, self.opt.step_count)
+
+    def _stats(self, step, values):
+        out = {"step": step}
+        for k, name in enumerate(("coarse", "fine")):
+            out[name] = {"samples": self.B * self.passes[k]["N"], "live": values[2 * k], "kept": values[2 * k + 1],
+                         "capacity": self.capacity[k]}
+        return out
+
+    def _note(self, done):
+        import warnings
+        for step, *values in done:
+            self.last_stats = self._stats(step, values)
+            over = [(name, s) for name, s in list(self.last_stats.items())[1:] if s["live"] > s["capacity"]]
+            if over:
+                self.overflow_steps += 1
+                what = "; ".join(f"the {name} pass had {s['live']} live samples for a capacity of {s['capacity']} points, the last "
+                                 f"{s['live'] - s['kept']} (ray-major order) were treated as dead" for name, s in over)
+                warnings.warn(f"{type(self).__name__}: step {step}: {what}.  Build a stepper with a larger capacity.",
+                              RuntimeWarning, stacklevel=3)
+
+    def counts(self):
+        """{'step', 'coarse': {'samples', 'live', 'kept', 'capacity'}, 'fine': {...}} of the latest step, read now
+        (synchronises); pending reports are delivered first."""
+        self._note(self._counts_watch.poll(wait=True))
+        return self._stats(self.opt.step_count, [int(v) for v in self._counts.cpu()])
+
+    def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
+        if self.occupancy.words.data_ptr() != self._words_ptr:
+            raise RuntimeError("the occupancy grid's words tensor was replaced: its address is baked into the captured graph "
+                               f"(TrainingOccupancyGrid.update writes in place); build a new {type(self).__name__}")
+        self._note(self._counts_watch.poll())
+        return super().step(rays, gt, u_c=u_c, u_f=u_f, decay=decay)
 
     __call__ = step

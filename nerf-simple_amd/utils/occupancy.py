@@ -25,6 +25,10 @@ Training with a grid: ``TrainingOccupancyGrid`` (a grid that is refreshed from t
         if step >= warmup and step % 16 == 0:
             occ.update(net, level=-1.75)
         train_step(net, opt, rays, gt, 64, device_rng=True, seed=step, occupancy=occ)
+
+The coarse + fine pair through ONE grid (``render_masked_pair`` below: ``render_hierarchical[_view](..., occupancy=)``;
+``training.train_step_hierarchical(..., occupancy=)`` / ``training.GraphedMaskedHierarchicalTrainStep``) -- DESIGN.md
+section 15.
 """
 import ctypes
 
@@ -295,25 +299,31 @@ def _points(m, rays, jit, tbins, flags, seed, ray_id0):
     return pts
 
 
-def render_masked(occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, outputs, pixels=False):
-    """The body of ``render_nerf(..., occupancy=occ)`` / ``render_view(..., occupancy=occ)`` once rays, jitter and
-    precision are settled.  Returns the 5-tuple, or pixels [B, 4] with ``pixels=True``."""
-    from .nets import guarded_launch
+def sample_positions(rays, jit, tbins, flags, seed, ray_id0, N):
+    """ts [B, N] of these jitter arguments, as nerf_amd_query_points forms them (given positions come back as they are)."""
+    if flags & _lib.FLAG_TS_GIVEN:
+        return jit
+    from .rendering import _query_points
+    return _query_points(rays, jit, tbins, flags, seed, ray_id0, N)[1]
+
+
+def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels):
+    """mark + emit of one masked pass, now (one host read) -> (MarkResult, stats, launch); ``launch(code, image)`` enqueues
+    the network on the live points and the masked compositor and returns the 5-tuple, or pixels [B, 4]."""
     from .rendering import _per_sample
     B, dev = rays.size(0), rays.device
     lib = _lib.lib()
     m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N)
     pts = _points(m, rays, jit, tbins, flags, seed, ray_id0)
     stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
-    occ.last_stats = stats
 
-    def launch(code, packed):
+    def launch(code, image):
         raw = None
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
             if m.live:
                 raw = torch.empty((m.live, 4), dtype=torch.float32, device=dev)
-                _lib.check(lib.nerf_amd_mlp_forward(_lib.ptr(pts), _lib.ptr(packed[0]), _lib.ptr(raw), m.live, code, st),
+                _lib.check(lib.nerf_amd_mlp_forward(_lib.ptr(pts), _lib.ptr(image), _lib.ptr(raw), m.live, code, st),
                            "nerf_amd_mlp_forward")
                 stats["network_launches"] += 1
             head = (_lib.ptr(raw), _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0),
@@ -332,7 +342,40 @@ def render_masked(occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, out
                                                          _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
         return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
 
-    if B == 0 or m.live == 0:
+    return m, stats, launch
+
+
+def render_masked(occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, outputs, pixels=False):
+    """The body of ``render_nerf(..., occupancy=occ)`` / ``render_view(..., occupancy=occ)`` once rays, jitter and
+    precision are settled.  Returns the 5-tuple, or pixels [B, 4] with ``pixels=True``."""
+    from .nets import guarded_launch
+    m, stats, launch = _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels)
+    occ.last_stats = stats
+    if rays.size(0) == 0 or m.live == 0:
         # nothing to evaluate: no network launch, hence nothing for the range guard to look at
-        return launch(code, [None])
-    return guarded_launch([net], code, launch)
+        return launch(code, None)
+    return guarded_launch([net], code, lambda code, packed: launch(code, packed[0]))
+
+
+def render_masked_pair(occ, rays, net_c, net_f, Nc, Nf, tbins, jit_c, flags, u_f, device_rng, seed, ray_id0, code, pixels=False):
+    """The body of ``render_hierarchical(..., occupancy=occ)`` / ``render_hierarchical_view(..., occupancy=occ)``: the
+    masked coarse pass -> ``sample_pdf`` on its weights (0 at a dead sample) -> the masked pass of ``net_f`` on the merged
+    positions through the same grid, both passes at ONE precision under one range guard.  Two host reads (one live count
+    per pass).  Returns (fine 5-tuple or pixels [B, 4], coarse 5-tuple, ts_f); ``occ.last_stats`` reports both passes."""
+    from .nets import guarded_launch
+    from .rendering import ALL_OUTPUTS, sample_pdf
+    ts_c = sample_positions(rays, jit_c, tbins, flags, seed, ray_id0, Nc)
+    _, stats_c, launch_c = _masked_pass(occ, rays, Nc, tbins, jit_c, flags, seed, ray_id0, ALL_OUTPUTS, False)
+
+    def launch(code, packed):
+        coarse = launch_c(code, packed[0])
+        ts_f = sample_pdf(ts_c, coarse[4], Nf, u=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+        _, stats_f, launch_f = _masked_pass(occ, rays, Nc + Nf, None, ts_f, _lib.FLAG_TS_GIVEN, 0, 0, ALL_OUTPUTS, pixels)
+        fine = launch_f(code, packed[-1])
+        stats = {k: stats_c[k] + stats_f[k] for k in ("samples", "live", "network_launches")}
+        stats.update(rays=stats_c["rays"], coarse=stats_c, fine=stats_f)
+        occ.last_stats = stats
+        return fine, coarse, ts_f
+
+    # one precision for both passes: if either network left the fp16 range, both render with bf16 operands
+    return guarded_launch([net_c] if net_f is net_c else [net_c, net_f], code, launch)

@@ -483,8 +483,37 @@ def sample_pdf(ts, w, Nf, *, u=None, device_rng=False, seed=0, ray_id0=0):
     return out
 
 
+def _masked_pair_args(occupancy, net_coarse, net_fine, B, Nc, Nf, u_c, u_f, precision, device_rng, dev):
+    """What ``render_hierarchical[_view](..., occupancy=)`` settles before anything is launched or drawn: the grid's and
+    the sampler's preconditions, then the jitter (u_c, then u_f, from torch's CPU generator unless given / device_rng).
+    -> (precision code, coarse jitter or None, coarse flags, u_f or None)"""
+    from .occupancy import check_renderable
+    check_renderable(occupancy, net_coarse, False)
+    check_renderable(occupancy, net_fine, False)
+    if Nc < 3 or Nc > 256 or Nf < 0 or Nc + Nf > 512:
+        raise ValueError(f"hierarchical sampling needs 3 <= Nc <= 256 and Nc + Nf <= 512 (got Nc={Nc}, Nf={Nf})")
+    if occupancy.words.device != dev:
+        raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {dev}")
+    for name, t_, n in (("u_c", u_c, Nc), ("u_f", u_f, Nf)):
+        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
+            raise RuntimeError(f"{name} must be [B, {n}]")
+    code = _lib.precision_code(net_coarse.precision if precision is None else precision)
+    net_coarse.packed_weights(code)
+    net_fine.packed_weights(code)
+    flags = 0
+    if u_c is None and device_rng:
+        flags = _lib.FLAG_DEVICE_RNG
+    elif u_c is None:
+        u_c, pending_rng = reference_rand(B, Nc, dev)
+        pending_rng.finish()
+    if u_f is None and not device_rng:
+        u_f, pending_rng = reference_rand(B, Nf, dev)
+        pending_rng.finish()
+    return (code, None if u_c is None else u_c.contiguous(), flags, None if u_f is None else u_f.contiguous())
+
+
 def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *, u_c=None, u_f=None,
-                        precision=None, device_rng=False, seed=0, ray_id0=0):
+                        precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
     """Coarse + fine render (BASELINE config 4: 64 + 128 samples).  The reference
     only has the single-pass render_nerf (its CoarseNet / FineNet are empty
     classes), so this composition is new: a coarse render_nerf pass with Nc
@@ -492,9 +521,29 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
     of ``net_fine`` on the merged Nc+Nf positions (explicit ts).  Each pass is the
     pinned render_nerf; only the sampler in between is unpinned.
     Returns (fine 5-tuple, coarse 5-tuple, ts_fine).  Every arithmetic step runs in the library
-    (sample positions come out of the kernel); see render_hierarchical_view for the one-call form."""
+    (sample positions come out of the kernel); see render_hierarchical_view for the one-call form.
+
+    occupancy: ONE ``OccupancyGrid`` masks both passes: masked coarse pass -> sample_pdf on its
+    weights (exactly 0 at a dead sample; a ray with no live coarse sample gets uniform fine samples) -> masked fine pass
+    on the merged positions; each network sees live samples only, two host synchronisations per call, both passes at one
+    precision under one range guard.  Inference only (``torch.no_grad()``), default network shape only."""
     _lib.require_cuda_f32(rays, "rays")
     dev, B = rays.device, rays.size(0)
+    if occupancy is not None:
+        from .occupancy import render_masked_pair
+        if rays.dim() != 2 or rays.shape[1] != 6:
+            raise RuntimeError("rays must be [B, 6]")
+        Nc, Nf = int(Nc), int(Nf)
+        if torch.is_grad_enabled() and rays.requires_grad:
+            raise RuntimeError("the masked render (occupancy=) is inference only: call it under torch.no_grad()")
+        code, jit, flags, u_f = _masked_pair_args(occupancy, net_coarse, net_fine, B, Nc, Nf, u_c, u_f, precision, device_rng, dev)
+        rays = rays.detach().contiguous()
+        tb = _tbins(tn, tf, Nc, dev)
+        from .xyz import range_check_rays
+        range_check_rays(rays, jit, tb, flags, seed, ray_id0, Nc)
+        with torch.no_grad():
+            return render_masked_pair(occupancy, rays, net_coarse, net_fine, Nc, Nf, tb, jit, flags, u_f, device_rng, seed,
+                                      ray_id0, code)
     rays = rays.detach().contiguous()
     code = _lib.precision_code(net_coarse.precision if precision is None else precision)
     net_coarse.packed_weights(code)
@@ -527,18 +576,30 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
 
 
 def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
-                             ray0=0, n_rays=None, precision=None, device_rng=False, seed=0):
+                             ray0=0, n_rays=None, precision=None, device_rng=False, seed=0, occupancy=None):
     """BASELINE config 4 for one view (or its pixel range [ray0, ray0+n_rays)) in ONE library call:
     device ray generation -> coarse pass (Nc stratified samples) -> sample_pdf -> fine pass on the
     Nc+Nf merged positions -> clip(rgb,0,1)  (nerf_amd_render_hierarchical_forward: four launches,
     no torch arithmetic on the path).  Returns pixels [n,4] = [r,g,b,disparity] on the GPU.
     u_c [n,Nc] / u_f [n,Nf]: explicit uniforms for these pixels; default: the reference-style CPU
     draws torch.rand(n,Nc) then torch.rand(n,Nf); device_rng=True: counter RNG keyed by global pixel id.
-    Parity unpinned (no reference counterpart)."""
+    Parity unpinned (no reference counterpart).
+    occupancy: an ``OccupancyGrid`` for both passes -- device ray generation, then the composition of
+    ``render_hierarchical(..., occupancy=)``, then the clip (not one library call: two host reads, one per pass)."""
     import numpy as np
     dev = next(net_coarse.parameters()).device
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
     n = H * W - ray0 if n_rays is None else int(n_rays)
+    if occupancy is not None:
+        from .occupancy import render_masked_pair
+        Nc, Nf = int(Nc), int(Nf)
+        if device_rng:
+            u_c = u_f = None
+        code, jit, flags, u_f = _masked_pair_args(occupancy, net_coarse, net_fine, n, Nc, Nf, u_c, u_f, precision, device_rng, dev)
+        rays = generate_rays(pose, cam_params, dev, ray0, n)
+        with torch.no_grad():
+            return render_masked_pair(occupancy, rays, net_coarse, net_fine, Nc, Nf, _tbins(tn, tf, Nc, dev), jit, flags, u_f,
+                                      device_rng, seed, ray0, code, pixels=True)[0]
     code = _lib.precision_code(net_coarse.precision if precision is None else precision)
     flags = 0
     if device_rng:
