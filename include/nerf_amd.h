@@ -733,6 +733,58 @@ int nerf_amd_volume_render_masked_mse_backward_pdf(const float* raw_live, const 
                                                    float* d_raw_live, float* ts_out, int64_t capacity, int64_t B, int Nc,
                                                    int Nf, void* stream);
 
+/* ---- terminated render: early ray termination for the masked and dense inference renders (csrc/occupancy_terminate.hip) --
+ * Not in the reference.  tests/termination_model.py restates the semantics in numpy; DESIGN.md section 16.
+ *
+ * An occupancy grid removes the samples in front of a surface; termination removes those behind an opaque one.  Semantics:
+ *   - slabs: a ray's N samples are cut into slabs of S consecutive sample indices, S in {16, 32, 64} (a slab never straddles
+ *     a 64-sample chunk of the compositor); the last slab may be short; K = ceil(N / S).
+ *   - threshold: 0 < eps < 1.
+ *   - M0: the occupancy mask of the masked render above (every sample when there is no grid).
+ *   - before slab k the ray's transmittance T_k is formed: the transmittance entering the first sample of slab k over the
+ *     rows evaluated so far, in the compositor's arithmetic (the product scan of fl(fl(1 - alpha) + 1e-10) over the 64-chunk,
+ *     times the carry of the earlier chunks: bit for bit the T the masked compositor forms for that sample from the same
+ *     rows).  T_0 = 1.  The ray is TERMINATED from slab k on iff T_k < eps.  A NaN T_k is not terminated: termination never
+ *     hides a NaN.  Every factor is <= 1 in fp32, so T does not grow and termination is permanent; it is also permanent by
+ *     construction: a terminated ray evaluates nothing more and its T is frozen, T_j = T_k for j > k (the scan's product
+ *     tree is not associative to the last bit, so a re-formed T could differ from T_k in an ulp).
+ *   - evaluated mask: M* = M0 & (the slab of sample i is not terminated).
+ *   - result: the terminated render is BY DEFINITION the masked render above under M*: volume_render over all N samples with
+ *     the network's output replaced by (0, 0, 0, -inf) at every sample outside M*.  Nothing else about the arithmetic changes.
+ *   Consequences: each rgb channel differs from the un-terminated masked render by less than eps max|c| over the dropped
+ *   samples (their weights sum to less than the transmittance that reached them, < eps), acc by less than eps;
+ *   alpha = w = 0 exactly at a dropped sample; a ray that never terminates is bit for bit what it was.
+ *
+ * nerf_amd_termination_advance: one step of the slab loop, for the slab [s0, s1) just evaluated and the next slab [s1, s2).
+ *   The first call is (s0, s1, s2) = (0, 0, min(S, N)) with raw_slab = NULL; then (k S, min((k + 1) S, N), min((k + 2) S, N));
+ *   the call with s1 = s2 = N only retires the last slab.  Per ray (one wavefront):
+ *   1. retire: row offsets_slab[ray] + popcount(mask_slab bits below i) of raw_slab[rows_slab, 4] -- the network's output on
+ *      the slab's compacted points (nerf_amd_occupancy_points under mask_slab / offsets_slab, an earlier call's mask_next /
+ *      offsets_next) -- goes to row offsets0[ray] + popcount(M0 bits below i) of raw0[rows0, 4], the M0 layout.  The caller
+ *      pre-fills raw0 with (0, 0, 0, -inf); a row never written IS a dead sample, so after the last call
+ *      nerf_amd_volume_render_masked(_pixels)(raw0, mask0, offsets0) yields the defined result.  raw_slab = NULL (with
+ *      rows_slab = 0): nothing to retire (the first call, or a slab no ray had a live sample in).  No row is read or written
+ *      at or past rows_slab / rows0.
+ *   2. transmittance: T entering sample s1 from the rows of the current 64-chunk in raw0 (chunk start to s1) and the carry of
+ *      the earlier chunks (kept in `workspace` between calls); positions recomputed from (u, tbins, flags, seed, ray_id0) as the
+ *      masked compositor recomputes them, or read under NERF_AMD_TS_GIVEN.  T -> trans[B, K], column s1 / S (s1 < N).
+ *   3. select: mask_next[B, ceil(N / 64)] = M0 & [s1, s2) & !(T < eps), offsets_next[B + 1] its exclusive scan, and
+ *      totals (DEVICE int64[2]): [0] the live count of the next slab, [1] the live samples of M0 at or beyond s1 on rays
+ *      still alive.  The host stops when totals[1] is 0.
+ *   workspace: nerf_amd_termination_workspace_bytes(B) bytes, 16-aligned, ONE buffer kept through all calls of a render (the
+ *   first call initialises it).  mask_next / offsets_next must not be the buffers given as mask_slab / offsets_slab.
+ *   Checked on the host before any launch -- NERF_AMD_EINVAL: NULL or misaligned buffers, B < 0, N <= 0, negative row counts,
+ *   unknown flags or a jitter tensor missing, eps outside (0, 1) or NaN, S not 16, 32 or 64, slab bounds that are not the
+ *   multiples of S stated above (clipped at N) or are out of order, raw_slab with s0 = s1 or without its mask and offsets,
+ *   rows_slab > 0 without raw_slab; NERF_AMD_EUNSUP: N > 768 or B > 2^32.  B = 0: nothing is launched or written.
+ *   No atomics, fixed partitions: two runs write the same bytes. */
+int64_t nerf_amd_termination_workspace_bytes(int64_t B);
+int nerf_amd_termination_advance(const float* raw_slab, const uint64_t* mask_slab, const int64_t* offsets_slab, int64_t rows_slab,
+                                 const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
+                                 int64_t ray_id0, const uint64_t* mask0, const int64_t* offsets0, float* raw0, int64_t rows0,
+                                 float eps, int slab, int s0, int s1, int s2, float* trans, uint64_t* mask_next,
+                                 int64_t* offsets_next, int64_t* totals, void* workspace, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

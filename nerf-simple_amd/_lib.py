@@ -128,6 +128,9 @@ _SIGNATURES = {
     "nerf_amd_volume_render_masked": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                              _i32, _vp]),
     "nerf_amd_volume_render_masked_pixels": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_termination_workspace_bytes": (_i64, [_i64]),
+    "nerf_amd_termination_advance": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _i64,
+                                            ctypes.c_float, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_volume_render_masked_backward": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                       _vp, _i64, _i32, _vp]),
     "nerf_amd_occupancy_decay_max": (_i32, [_vp, _vp, ctypes.c_float, _i64, _vp]),

@@ -26,6 +26,13 @@ Training with a grid: ``TrainingOccupancyGrid`` (a grid that is refreshed from t
             occ.update(net, level=-1.75)
         train_step(net, opt, rays, gt, 64, device_rng=True, seed=step, occupancy=occ)
 
+Early ray termination (``EarlyTermination`` and ``render_terminated`` below): the samples hidden
+behind what a ray has already hit are not evaluated either.
+
+    term = EarlyTermination(eps=1e-3, slab=32)                           # no defaults: the caller states both
+    pixels = render_view(net, pose, cam_params, device_rng=True, occupancy=occ, terminate=term)
+    rgb, disp, alpha, acc, w = render_nerf(rays, net, 128, terminate=term)      # no grid: termination alone
+
 The coarse + fine pair through ONE grid (``render_masked_pair`` below: ``render_hierarchical[_view](..., occupancy=)``;
 ``training.train_step_hierarchical(..., occupancy=)`` / ``training.GraphedMaskedHierarchicalTrainStep``) -- DESIGN.md
 section 15.
@@ -352,6 +359,160 @@ def render_masked(occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, out
     m, stats, launch = _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels)
     occ.last_stats = stats
     if rays.size(0) == 0 or m.live == 0:
+        # nothing to evaluate: no network launch, hence nothing for the range guard to look at
+        return launch(code, None)
+    return guarded_launch([net], code, lambda code, packed: launch(code, packed[0]))
+
+
+SLABS = (16, 32, 64)                    # samples per slab: a slab never straddles a 64-sample chunk of the compositor
+
+
+class EarlyTermination:
+    """Early ray termination for the inference renders: ``render_nerf(..., terminate=term)`` /
+    ``render_view(..., terminate=term)``, with or without ``occupancy=``.  A ray's samples are evaluated in slabs of ``slab``
+    sample indices (16, 32 or 64); before each slab the ray's transmittance T over the rows evaluated so far is formed in
+    the compositor's arithmetic, and a ray with T < ``eps`` evaluates nothing more.  The result is the masked render under
+    the evaluated mask (include/nerf_amd.h, "terminated render"): each rgb channel moves by less than eps max|c| over the
+    dropped samples and acc by less than eps.  Neither argument has a default: what an eps costs in image quality and
+    which slab is fastest depend on the scene, so the caller states both.
+
+    After a render: ``last_stats`` (a plain dict: {'rays', 'samples', 'live', 'evaluated', 'terminated_rays', 'slabs_run',
+    'network_launches', 'host_reads'}; 'terminated_rays' = rays with T < eps at the last check, which comes back with the
+    loop's last host read; every figure describes the pass that produced the outputs -- after an fp16 overflow the repeat
+    with bf16 operands, whose counters start afresh), ``transmittance`` [B, K] (the T_k; column 0 is 1; columns the loop did
+    not reach repeat the last one formed) and ``evaluated_mask`` [B, ceil(N / 64)] int64 (the layout of ``MarkResult.mask``)."""
+
+    def __init__(self, eps, slab):
+        if isinstance(slab, bool) or not isinstance(slab, (int, np.integer)) or int(slab) not in SLABS:
+            raise ValueError(f"slab must be 16, 32 or 64 samples, got {slab!r}")
+        try:
+            e = np.float32(eps)
+        except (TypeError, ValueError):
+            raise ValueError(f"eps must be a number in (0, 1), got {eps!r}") from None
+        if not (e > 0 and e < 1):
+            raise ValueError(f"eps must lie in (0, 1) as a float32, got {eps!r}")
+        self.eps, self.slab = float(e), int(slab)
+        self.last_stats = None
+        self.transmittance = None
+        self.evaluated_mask = None
+
+
+_ALL_LIVE = {}
+
+
+def all_live_grid(device):
+    """The one-cell grid termination runs on when the caller has none: every sample is live (``outside='live'``)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device not in _ALL_LIVE:
+        _ALL_LIVE[device] = OccupancyGrid.from_mask(torch.ones((1, 1, 1), dtype=torch.bool, device=device), DEFAULT_BOUNDS,
+                                                    outside="live")
+    return _ALL_LIVE[device]
+
+
+def check_terminable(terminate, occupancy, net, rays_require_grad):
+    """The terminated render's preconditions (the masked render's, and an ``EarlyTermination``); raises before any jitter
+    is drawn."""
+    from .nets import Nerf
+    if not isinstance(terminate, EarlyTermination):
+        raise TypeError("terminate must be an EarlyTermination (utils/occupancy.py)")
+    if occupancy is not None:
+        return check_renderable(occupancy, net, rays_require_grad)
+    if not (isinstance(net, Nerf) and net._fused_ok()):
+        raise RuntimeError("the terminated render (terminate=) serves the default Nerf(10, 4, 256) only: other network sizes "
+                           "and foreign nets are not supported; render without terminate")
+    if torch.is_grad_enabled() and (rays_require_grad or any(p.requires_grad for p in net.parameters())):
+        raise RuntimeError("the terminated render (terminate=) is inference only: call it under torch.no_grad()")
+
+
+def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, outputs, pixels=False):
+    """The body of ``render_nerf(..., terminate=term)`` / ``render_view(..., terminate=term)``: ``render_masked`` with the
+    network run slab by slab.  mark (one host read of P'0) -> raw0 [P'0, 4] filled with (0, 0, 0, -inf) -> advance selects
+    slab 0 -> per slab: read the two counts (one host read), stop if nothing remains, emit the slab's points, the network on
+    them (nothing when the slab is empty), advance (retire the rows into raw0, T, select the next slab) -> the masked
+    compositor on (raw0, M0): at most K + 1 host reads.  ``occ`` None: the all-live grid."""
+    from .nets import guarded_launch
+    from .rendering import _per_sample
+    B, dev = rays.size(0), rays.device
+    if occ is None:
+        occ = all_live_grid(dev)
+    lib = _lib.lib()
+    S, K, W = term.slab, (N + term.slab - 1) // term.slab, (N + 63) // 64
+    m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N)          # M0; raises for N > MAX_N
+    trans = torch.ones((B, K), dtype=torch.float32, device=dev)
+    evaluated_mask = torch.zeros((B, W), dtype=torch.int64, device=dev)
+    stats = {"rays": B, "samples": B * N, "live": m.live, "evaluated": 0, "terminated_rays": 0, "slabs_run": 0,
+             "network_launches": 0, "host_reads": 1}
+    term.last_stats, term.transmittance, term.evaluated_mask = stats, trans, evaluated_mask
+    occ.last_stats = stats
+    masks = [torch.empty((B, W), dtype=torch.int64, device=dev) for _ in range(2)]
+    offs = [torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(2)]
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(lib.nerf_amd_termination_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+    dead_row = torch.tensor([0.0, 0.0, 0.0, -np.inf], dtype=torch.float32, device=dev) if B else None
+    head = (_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0))
+
+    def advance(raw, cur, rows, s0, s1, s2, raw0, st):
+        _lib.check(lib.nerf_amd_termination_advance(
+            _lib.ptr(raw), _lib.ptr(masks[cur]) if raw is not None else None, _lib.ptr(offs[cur]) if raw is not None else None,
+            rows, *head, _lib.ptr(m.mask), _lib.ptr(m.offsets), _lib.ptr(raw0), m.live, ctypes.c_float(term.eps), S, s0, s1, s2,
+            _lib.ptr(trans), _lib.ptr(masks[1 - cur]), _lib.ptr(offs[1 - cur]), _lib.ptr(totals), _lib.ptr(ws), B, N, st),
+            "nerf_amd_termination_advance")
+
+    def launch(code, image):
+        raw0 = None
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            if B:
+                raw0 = dead_row.repeat(max(m.live, 1), 1)
+                evaluated_mask.zero_()
+                # the counters of THIS pass (a repeat under the range guard starts afresh; the mark's read is kept)
+                stats.update(evaluated=0, terminated_rays=0, slabs_run=0, network_launches=0, host_reads=1)
+                cur = 1
+                advance(None, cur, 0, 0, 0, min(S, N), raw0, st)               # T_0 = 1, selects slab 0 into masks[0]
+                cur = 0
+                for k in range(K):
+                    # one host read per slab: the two counts and, with them, the rays terminated at this check (column k is
+                    # final: it was formed before slab k is evaluated)
+                    count, remaining, gone = torch.cat((totals, (trans[:, k] < term.eps).sum().view(1))).tolist()
+                    stats["host_reads"] += 1
+                    stats["terminated_rays"] = gone
+                    if remaining == 0:
+                        if k + 1 < K:
+                            trans[:, k + 1:] = trans[:, k:k + 1]
+                        break
+                    raw = None
+                    if count:
+                        pts = torch.empty((count, 6), dtype=torch.float32, device=dev)
+                        _lib.check(lib.nerf_amd_occupancy_points(*head, _lib.ptr(masks[cur]), _lib.ptr(offs[cur]), _lib.ptr(pts),
+                                                                 count, B, N, st), "nerf_amd_occupancy_points")
+                        raw = torch.empty((count, 4), dtype=torch.float32, device=dev)
+                        _lib.check(lib.nerf_amd_mlp_forward(_lib.ptr(pts), _lib.ptr(image), _lib.ptr(raw), count, code, st),
+                                   "nerf_amd_mlp_forward")
+                        stats["network_launches"] += 1
+                        stats["evaluated"] += count
+                        evaluated_mask.bitwise_or_(masks[cur])
+                    s1 = min(k * S + S, N)
+                    advance(raw, cur, count, k * S, s1, min(s1 + S, N), raw0, st)
+                    stats["slabs_run"] += 1
+                    cur = 1 - cur
+            chead = (_lib.ptr(raw0 if m.live else None), *head, _lib.ptr(m.mask), _lib.ptr(m.offsets))
+            if pixels:
+                px = torch.empty((B, 4), dtype=torch.float32, device=dev)
+                _lib.check(lib.nerf_amd_volume_render_masked_pixels(*chead, _lib.ptr(px), B, N, st),
+                           "nerf_amd_volume_render_masked_pixels")
+                return px
+            rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
+            disp = torch.empty((B,), dtype=torch.float32, device=dev)
+            acc = torch.empty((B,), dtype=torch.float32, device=dev)
+            alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
+            w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+            _lib.check(lib.nerf_amd_volume_render_masked(*chead, _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha), _lib.ptr(acc),
+                                                         _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
+        return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+
+    if B == 0 or m.live == 0:
         # nothing to evaluate: no network launch, hence nothing for the range guard to look at
         return launch(code, None)
     return guarded_launch([net], code, lambda code, packed: launch(code, packed[0]))

@@ -83,7 +83,7 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS):
 
 
 def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUTS,
-                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
+                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, terminate=None):
     """Stratified sampling along rays, NeRF query, compositing
     (reference utils/rendering.py:13-45).
 
@@ -97,6 +97,11 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     sample contributes exactly nothing (the masked render; one host synchronisation per call).  Inference only: a
     grad-enabled call on a trainable net or on rays that require grad raises RuntimeError (call it under
     ``torch.no_grad()``), and so do other network sizes and foreign nets -- nothing falls back to the dense render.
+
+    terminate: an ``EarlyTermination(eps, slab)`` (utils/occupancy.py) -- early ray termination: the samples are evaluated
+    slab by slab and a ray whose transmittance has fallen below eps evaluates nothing more (the masked render under the
+    evaluated mask; at most ceil(N / slab) + 1 host synchronisations).  With ``occupancy`` it runs on that grid, without one on
+    an all-live grid; the masked render's conditions hold either way.
     """
     _lib.require_cuda_f32(rays, "rays")
     if rays.dim() != 2 or rays.shape[1] != 6:
@@ -110,7 +115,10 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
 
     fused = isinstance(net, Nerf) and net._fused_ok()
     training = fused and torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in net.parameters()))
-    if occupancy is not None:
+    if terminate is not None:
+        from .occupancy import check_terminable
+        check_terminable(terminate, occupancy, net, rays_grad)
+    elif occupancy is not None:
         from .occupancy import check_renderable
         check_renderable(occupancy, net, rays_grad)
     # everything that can raise cheaply is checked BEFORE the jitter is drawn, so a failed call
@@ -143,11 +151,13 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     if pending_rng is not None and not fused:
         pending_rng.finish()                  # the net's own forward follows: the generator must be current
         pending_rng = None
-    if occupancy is not None:
-        from .occupancy import render_masked
+    if terminate is not None or occupancy is not None:
+        from .occupancy import render_masked, render_terminated
+        tb = None if ts is not None else _tbins(tn, tf, N, dev)
         try:
-            return render_masked(occupancy, rays, net, N, None if ts is not None else _tbins(tn, tf, N, dev), jit, flags,
-                                 seed, ray_id0, code, outputs)
+            if terminate is not None:
+                return render_terminated(terminate, occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
+            return render_masked(occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
         finally:
             if pending_rng is not None:
                 pending_rng.finish()
@@ -384,7 +394,7 @@ def generate_rays(pose, cam_params, device, ray0=0, n_rays=None):
 
 
 def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_rays=None,
-                precision=None, device_rng=False, seed=0, occupancy=None):
+                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None):
     """One view (or the pixel range [ray0, ray0+n_rays) of it) in ONE library
     call: device ray generation -> render_nerf -> clip(rgb,0,1), i.e. the body of
     the reference's per-image loop (utils/rendering.py:139-151) without the
@@ -394,10 +404,15 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     global pixel id.
     occupancy: an ``OccupancyGrid`` -- the masked render (device ray generation, then the stages of
     utils/occupancy.py); the same conditions as ``render_nerf(..., occupancy=)``: under ``torch.no_grad()``, default
-    network shape only."""
+    network shape only.
+    terminate: an ``EarlyTermination`` -- early ray termination as in ``render_nerf(..., terminate=)``, on ``occupancy`` or,
+    without one, on an all-live grid."""
     import numpy as np
     dev = next(net.parameters()).device
-    if occupancy is not None:
+    if terminate is not None:
+        from .occupancy import check_terminable
+        check_terminable(terminate, occupancy, net, False)
+    elif occupancy is not None:
         from .occupancy import check_renderable
         check_renderable(occupancy, net, False)
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
@@ -421,11 +436,14 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         jit, pending_rng = reference_rand(n, N, dev)
         pending_rng.finish()
     lib = _lib.lib()
-    if occupancy is not None:
-        from .occupancy import render_masked
+    if terminate is not None or occupancy is not None:
+        from .occupancy import render_masked, render_terminated
         if jit is not None and tuple(jit.shape) != (n, int(N)):
             raise RuntimeError("u must be [n_rays, N]")
         rays = generate_rays(pose, cam_params, dev, ray0, n)
+        if terminate is not None:
+            return render_terminated(terminate, occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
+                                     code, (), pixels=True)
         return render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0, code, (),
                              pixels=True)
     h_pose = np.zeros((3, 4), dtype=np.float32)
