@@ -52,6 +52,8 @@ extern "C" {
 
 /* flags of nerf_amd_render_forward / nerf_amd_mlp_forward_rays */
 #define NERF_AMD_TS_GIVEN   1u  /* `u` holds sample positions ts[B,N], not jitter */
+/* With NERF_AMD_TS_GIVEN `u` is required whatever the other flags are: every rays-mode entry point returns NERF_AMD_EINVAL
+ * for u == NULL then. */
 #define NERF_AMD_DEVICE_RNG 2u  /* `u` ignored (may be NULL): jitter from the counter RNG */
 #define NERF_AMD_SEED_IN_MEMORY 4u /* with NERF_AMD_DEVICE_RNG: `u` is the DEVICE ADDRESS of a uint64 that is added to
                                     * `seed` when the kernel runs -- a launch captured into a hipGraph is replayed with

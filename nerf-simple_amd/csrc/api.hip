@@ -1,8 +1,7 @@
 // api.hip -- the C ABI of libnerf_amd.so (include/nerf_amd.h): argument
 // checking, host-side introspection and the composition of the render path
 // out of the kernels in this directory.  No allocation, no host sync.
-#include "nerf_device.h"
-#include "../../include/nerf_amd.h"
+#include "api_checks.h"
 #include <math.h>
 
 using namespace nerf_layout;
@@ -90,19 +89,6 @@ inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool bad_precision(int p) { return p != NERF_AMD_F32 && p != NERF_AMD_BF16 && p != NERF_AMD_FP16; }
 inline bool bad_image(int p) { return bad_precision(p) && p != NERF_AMD_BF16_BWD; }
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-// the jitter arguments of every rays-mode entry point: explicit u / ts, the counter RNG, or the counter RNG with its
-// seed offset in device memory (then `u` is that address)
-inline bool bad_jitter(uint32_t flags, const float* u, const float* tbins) {
-    if (flags & ~(NERF_AMD_TS_GIVEN | NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return true;     // unknown bits
-    if (flags & NERF_AMD_SEED_IN_MEMORY) {
-        if (!(flags & NERF_AMD_DEVICE_RNG) || (flags & NERF_AMD_TS_GIVEN) || !u) return true;
-        if (reinterpret_cast<uintptr_t>(u) & 7) return true;                   // the kernels load it as one 64-bit word
-    } else if (!(flags & NERF_AMD_DEVICE_RNG) && !u) {
-        return true;
-    }
-    return !(flags & NERF_AMD_TS_GIVEN) && !tbins;
-}
-
 // the fused render kernels (sampling + MLP + compositing in one launch) serve rays of up to
 // FUSED_RENDER_MAX_N samples, in every precision
 inline bool fused_render(int precision, int N) { return !bad_precision(precision) && N <= FUSED_RENDER_MAX_N; }
@@ -136,13 +122,6 @@ int occ_rays(const float* rays, const float* u, const float* tbins, uint32_t fla
     if (N > nerf_amd_occ_max_n() || B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
     if (B > 0 && !rays) return NERF_AMD_EINVAL;
     return 0;
-}
-MlpArgs occ_args(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0, int64_t B,
-                 int N) {
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
-    return a;
 }
 }  // namespace
 
@@ -504,6 +483,7 @@ int nerf_amd_render_image_forward(const float* h_pose, int H, int W, float f, in
     if (n_rays < 0 || N <= 0 || bad_precision(precision)) return NERF_AMD_EINVAL;
     if (n_rays == 0) return 0;
     if (!workspace || !pixels || !packed) return NERF_AMD_EINVAL;
+    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;      // before the rays are generated: nothing is launched
     char* ws = reinterpret_cast<char*>(workspace);
     float* rays = reinterpret_cast<float*>(ws);
     int rc = nerf_amd_generate_rays(h_pose, H, W, f, ray0, n_rays, rays, stream);
@@ -755,7 +735,7 @@ int nerf_amd_select_rays(const uint32_t* draws, uint64_t seed, const uint64_t* s
     if (n >= (int64_t)(0xffffffffu / 20u)) return NERF_AMD_EUNSUP;      // torch.randperm switches algorithm there
     if (B == 0) return 0;
     if (!workspace || (rays_out && !table) || (gt_out && !colours)) return NERF_AMD_EINVAL;
-    if (((uintptr_t)table & 7) || ((uintptr_t)rays_out & 7) || ((uintptr_t)seed_mem & 7) || ((uintptr_t)workspace & 15)) return NERF_AMD_EINVAL;
+    if (misaligned(table, 8) || misaligned(rays_out, 8) || misaligned(seed_mem, 8) || misaligned(workspace, 16)) return NERF_AMD_EINVAL;
     return nerf_amd_launch_select_rays(draws, seed, reinterpret_cast<const unsigned long long*>(seed_mem), n, B, table, colours,
                                        rays_out, gt_out, reinterpret_cast<long long*>(ids_out), workspace, S(stream));
 }
@@ -832,7 +812,7 @@ int64_t nerf_amd_marching_cubes_workspace_bytes(int64_t nx, int64_t ny, int64_t 
 int nerf_amd_marching_cubes_count(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float level, void* workspace,
                                   int64_t* counts, void* stream) {
     if (bad_grid(nx, ny, nz) || !sigma || !workspace || !counts) return NERF_AMD_EINVAL;
-    if (((uintptr_t)workspace & 15) || ((uintptr_t)counts & 7)) return NERF_AMD_EINVAL;
+    if (misaligned(workspace, 16) || misaligned(counts, 8)) return NERF_AMD_EINVAL;
     return nerf_amd_launch_mc_count(sigma, nx, ny, nz, level, workspace, reinterpret_cast<long long*>(counts), S(stream));
 }
 
@@ -841,7 +821,7 @@ int nerf_amd_marching_cubes_emit(const float* sigma, int64_t nx, int64_t ny, int
                                  int64_t max_verts, int64_t max_faces, void* stream) {
     if (bad_grid(nx, ny, nz) || !sigma || !workspace || !h_lo || !h_step) return NERF_AMD_EINVAL;
     if (max_verts < 0 || max_faces < 0 || max_verts > INT32_MAX) return NERF_AMD_EINVAL;      // vertex numbers are int32
-    if ((max_verts > 0 && !verts) || (max_faces > 0 && !faces) || ((uintptr_t)workspace & 15)) return NERF_AMD_EINVAL;
+    if ((max_verts > 0 && !verts) || (max_faces > 0 && !faces) || misaligned(workspace, 16)) return NERF_AMD_EINVAL;
     return nerf_amd_launch_mc_emit(sigma, nx, ny, nz, level, h_lo, h_step, workspace, verts, normals, faces, max_verts, max_faces,
                                    S(stream));
 }
@@ -883,8 +863,8 @@ int nerf_amd_occupancy_mark(const float* rays, const float* u, const float* tbin
     if (rc) return rc;
     if (bad_grid(nx, ny, nz) || !bits || !h_lo || !h_inv_step || !offsets || !workspace) return NERF_AMD_EINVAL;
     if (B > 0 && !mask) return NERF_AMD_EINVAL;
-    if (((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)live & 7) || ((uintptr_t)workspace & 15)) return NERF_AMD_EINVAL;
-    const MlpArgs a = occ_args(rays, u, tbins, flags & ~NERF_AMD_OUTSIDE_EMPTY, seed, ray_id0, B, N);
+    if (misaligned(mask, 8) || misaligned(offsets, 8) || misaligned(live, 8) || misaligned(workspace, 16)) return NERF_AMD_EINVAL;
+    const MlpArgs a = rays_args(rays, u, tbins, flags & ~NERF_AMD_OUTSIDE_EMPTY, seed, ray_id0, B, N);
     return nerf_amd_launch_occ_mark(&a, bits, nx, ny, nz, h_lo, h_inv_step, (flags & NERF_AMD_OUTSIDE_EMPTY) ? 0 : 1,
                                     reinterpret_cast<unsigned long long*>(mask), reinterpret_cast<long long*>(offsets),
                                     reinterpret_cast<long long*>(live), workspace, B, S(stream));
@@ -897,8 +877,8 @@ int nerf_amd_occupancy_points(const float* rays, const float* u, const float* tb
     if (rc) return rc;
     if (max_points < 0) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
-    if (!mask || !offsets || (max_points > 0 && !pts) || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7)) return NERF_AMD_EINVAL;
-    const MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    if (!mask || !offsets || (max_points > 0 && !pts) || misaligned(mask, 8) || misaligned(offsets, 8)) return NERF_AMD_EINVAL;
+    const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
     return nerf_amd_launch_occ_emit(&a, reinterpret_cast<const unsigned long long*>(mask), reinterpret_cast<const long long*>(offsets),
                                     pts, max_points, B, S(stream));
 }
@@ -909,9 +889,9 @@ int nerf_amd_volume_render_masked(const float* raw_live, const float* rays, cons
     const int rc = occ_rays(rays, u, tbins, flags, B, N);
     if (rc) return rc;
     if (B == 0) return 0;
-    if (!mask || !offsets || !rgb || !disp || !acc || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)raw_live & 15))
+    if (!mask || !offsets || !rgb || !disp || !acc || misaligned(mask, 8) || misaligned(offsets, 8) || misaligned(raw_live, 16))
         return NERF_AMD_EINVAL;
-    MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
     a.rgb = rgb; a.disp = disp; a.alpha = alpha; a.acc = acc; a.w = w;
     return nerf_amd_launch_occ_composite(&a, reinterpret_cast<const unsigned long long*>(mask),
                                          reinterpret_cast<const long long*>(offsets), raw_live, B, S(stream));
@@ -923,10 +903,10 @@ int nerf_amd_volume_render_masked_pixels(const float* raw_live, const float* ray
     const int rc = occ_rays(rays, u, tbins, flags, B, N);
     if (rc) return rc;
     if (B == 0) return 0;
-    if (!mask || !offsets || !pixels || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)raw_live & 15) ||
-        ((uintptr_t)pixels & 15))
+    if (!mask || !offsets || !pixels || misaligned(mask, 8) || misaligned(offsets, 8) || misaligned(raw_live, 16) ||
+        misaligned(pixels, 16))
         return NERF_AMD_EINVAL;
-    MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
     a.pixels = pixels;
     return nerf_amd_launch_occ_composite(&a, reinterpret_cast<const unsigned long long*>(mask),
                                          reinterpret_cast<const long long*>(offsets), raw_live, B, S(stream));
@@ -941,10 +921,10 @@ int nerf_amd_volume_render_masked_backward(const float* raw_live, const float* r
     if (rc) return rc;
     if (N > nerf_amd_occ_train_max_n()) return NERF_AMD_EUNSUP;
     if (B == 0) return 0;
-    if (!mask || !offsets || ((uintptr_t)mask & 7) || ((uintptr_t)offsets & 7) || ((uintptr_t)raw_live & 15) ||
-        ((uintptr_t)d_raw_live & 15) || (!raw_live != !d_raw_live))
+    if (!mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8) || misaligned(raw_live, 16) ||
+        misaligned(d_raw_live, 16) || (!raw_live != !d_raw_live))
         return NERF_AMD_EINVAL;
-    const MlpArgs a = occ_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
     return nerf_amd_launch_occ_composite_backward(&a, reinterpret_cast<const unsigned long long*>(mask),
                                                   reinterpret_cast<const long long*>(offsets), raw_live, g_rgb, g_disp, g_alpha,
                                                   g_acc, g_w, d_raw_live, B, S(stream));

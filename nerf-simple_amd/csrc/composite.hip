@@ -13,7 +13,7 @@
 // 20 B read per sample (+8 B written when alpha / w are requested) and 20 B written per ray.
 // Not HBM-bound in practice: the exact-fp32 softplus / exp (ocml expf, log1pf) and the two scans
 // cost ~400 VALU instructions per 64 samples, which is what sets its 3.4 TB/s.
-#include "composite_device.h"
+#include "composite_backward_device.h"
 #include "sample_pdf_device.h"
 
 namespace {
@@ -44,13 +44,8 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_kernel(
 }
 
 // ---- backward ---------------------------------------------------------------
-// d loss / d nerf_outs[B,N,4] given the upstream gradients of the five outputs
-// (NULL = zero).  With G_i = dL/dw_i gathered from every consumer of w,
-//   dL/dc_i     = w_i * g_rgb
-//   dL/dalpha_i = G_i T_i - (1/f_i) * sum_{k>i} G_k w_k + g_alpha_i       (f = 1 - alpha + 1e-10)
-//   dL/dsigma_i = dL/dalpha_i * (1 - alpha_i) * delta_i * softplus'(sigma_i)
-// The suffix sum over k > i is a wave-level reverse scan; chunks of 64 samples
-// are walked forward once (recomputing alpha, T, w) and backward once.
+// d loss / d nerf_outs[B,N,4] given the upstream gradients of the five outputs (NULL = zero), or with the MSE loss
+// gradient formed in the kernel: the per-ray walk is composite_backward_ray (composite_backward_device.h).
 constexpr int MAX_CHUNKS = 8;          // N <= 512
 
 // The coarse training head (E > 0): the same kernel also places the fine pass's samples from the weights of its
@@ -66,22 +61,8 @@ struct PdfHead {
     long long ray_id0;
 };
 
-__device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& total) {
-    // inclusive suffix sum, then shift down by one lane
-    float incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float dn = __shfl_down(incl, off);
-        if (lane + off < 64) incl += dn;
-    }
-    total = __shfl(incl, 0);
-    float ex = __shfl_down(incl, 1);
-    if (lane == 63) ex = 0.f;
-    return ex;
-}
-
-// E = 0: the compositor's backward alone (N <= 512).  E > 0: the coarse training head, N = Nc <= 256 (four chunks)
-// and Nf new samples sorted E keys per lane.
+// E = 0: the compositor's backward alone (N <= 512), with the five upstream gradients or (mse_target != NULL) the MSE head.
+// E > 0: the coarse training head (MSE head only), N = Nc <= 256 (four chunks) and Nf new samples sorted E keys per lane.
 template <int E>
 __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel(
     const float* __restrict__ raw, const float* __restrict__ ts, const float* __restrict__ dirs,
@@ -97,14 +78,8 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
     if (ray >= B) return;
     const int lane = threadIdx.x & 63;
     const float* d = dirs + ray * dirs_stride;
-    float d0 = d[0], d1 = d[1], d2 = d[2];
-    if (normalize_dirs) {
-        const float n = norm3(d0, d1, d2);
-        d0 = __fdiv_rn(d0, n); d1 = __fdiv_rn(d1, n); d2 = __fdiv_rn(d2, n);
-    }
-    const float dnorm = norm3(d0, d1, d2);
-    const float* rts = ts + ray * N;
-    const f32x4* rraw = reinterpret_cast<const f32x4*>(raw) + ray * N;
+    const float dnorm = nerf_composite::unit_dir_norm(d[0], d[1], d[2], normalize_dirs != 0);
+    const nerf_composite::DenseSamples src{ts + ray * N, reinterpret_cast<const f32x4*>(raw) + ray * N};
     f32x4* rout = reinterpret_cast<f32x4*>(d_raw) + ray * N;
     if (N == 1) {
         // the reference composites an EMPTY sample axis at N == 1 (composite_device.h): no output depends on raw
@@ -114,106 +89,12 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
         }
         return;
     }
-
-    // forward sweep: per chunk keep alpha, T, fac, delta*softplus' and the colour
-    float al[CHUNKS], Tt[CHUNKS], fc[CHUNKS], ds[CHUNKS], tt[CHUNKS];
-    f32x4 cc[CHUNKS];
-    float carry = 1.0f, depth = 0.f, accw = 0.f;
-    float sr = 0.f, sg = 0.f, sb = 0.f;            // training form: the forward's rgb, for the loss gradient
-#pragma unroll
-    for (int ch = 0; ch < CHUNKS; ++ch) {
-        const int base = ch * 64;
-        al[ch] = 0.f; Tt[ch] = 0.f; fc[ch] = 1.f; ds[ch] = 0.f; tt[ch] = 0.f;
-        cc[ch] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (base < N) {
-            const int i = base + lane;
-            const bool valid = i < N;
-            float a = 0.f, fac = 1.0f;
-            if (valid) {
-                const float t = rts[i];
-                const f32x4 c = rraw[i];
-                float delta = (i == N - 1) ? 1e10f : sub_rn(rts[i + 1], t);
-                delta = mul_rn(delta, dnorm);
-                const float sigma = c[3];
-                const float z = expf(sigma);
-                const float sp = sigma > 20.f ? sigma : log1pf(z);
-                // softplus' as torch's backward forms it: z / (z + 1) keeps exp(sigma) down to the subnormals, where
-                // 1 / (1 + exp(-sigma)) is 0 from sigma = -88.7 on (a last sample's delta = 1e10 brings that back up)
-                const float spd = sigma > 20.f ? 1.0f : z / (z + 1.0f);
-                const float e = expf(mul_rn(-sp, delta));
-                a = sub_rn(1.0f, e);
-                fac = add_rn(sub_rn(1.0f, a), 1e-10f);
-                // e itself, not 1 - alpha: that recovers e to an absolute 2^-24, a relative 2^-24 / e on a nearly opaque sample
-                ds[ch] = e * delta * spd;       // d alpha / d sigma
-                tt[ch] = t; cc[ch] = c;
-            }
-            // the forward compositor's scan (composite_device.h): same tree, same rounded products
-            const float incl = nerf_composite::wave_scan_mul(fac);
-            const float excl = nerf_composite::dpp_move<0x138, 0xf>(1.0f, incl);          // wave_shr:1
-            al[ch] = a; fc[ch] = fac; Tt[ch] = mul_rn(carry, excl);
-            carry = mul_rn(carry, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63)));
-            if (valid) {
-                depth += a * Tt[ch] * tt[ch]; accw += a * Tt[ch];
-                // the same ops as the forward compositor (composite_device.h), so rgb_out equals its rgb
-                const float wt = mul_rn(a, Tt[ch]);
-                sr = __fmaf_rn(wt, cc[ch][0], sr); sg = __fmaf_rn(wt, cc[ch][1], sg); sb = __fmaf_rn(wt, cc[ch][2], sb);
-                if constexpr (E > 0) {      // the sampler's inputs: these positions and the forward compositor's weights
-                    s_pdf[wv].ts[i] = tt[ch];
-                    s_pdf_w[wv][i] = wt;
-                }
-            }
-        }
-    }
-    depth = wave_sum(depth); accw = wave_sum(accw);
-
-    // upstream gradients that reach every w_i of the ray
-    float gr = g_rgb ? g_rgb[ray * 3 + 0] : 0.f, gg = g_rgb ? g_rgb[ray * 3 + 1] : 0.f,
-          gb = g_rgb ? g_rgb[ray * 3 + 2] : 0.f;
-    if (mse_target) {
-        // loss = MSELoss(rgb, target) (train.py:52): d loss / d rgb = 2 (rgb - target) / (3 B), formed here
-        sr = nerf_composite::wave_total(sr); sg = nerf_composite::wave_total(sg); sb = nerf_composite::wave_total(sb);
-        gr = 2.0f * (sr - mse_target[ray * 3 + 0]) * mse_scale;
-        gg = 2.0f * (sg - mse_target[ray * 3 + 1]) * mse_scale;
-        gb = 2.0f * (sb - mse_target[ray * 3 + 2]) * mse_scale;
-        if (rgb_out && lane == 0) { rgb_out[ray * 3 + 0] = sr; rgb_out[ray * 3 + 1] = sg; rgb_out[ray * 3 + 2] = sb; }
-    }
-    float gdep = 0.f, gac = g_acc ? g_acc[ray] : 0.f;
-    if (g_disp) {
-        const float q = depth / accw;
-        if (q > 1e-10f) {                        // disp = 1/q there; the clamp branch has zero slope
-            const float dq = -g_disp[ray] / (q * q);
-            gdep = dq / accw;
-            gac += -dq * depth / (accw * accw);
-        }
-    }
-    // backward sweep over chunks, carrying sum_{k in later chunks} G_k w_k
-    float later = 0.f;
-#pragma unroll
-    for (int ch = CHUNKS - 1; ch >= 0; --ch) {
-        const int base = ch * 64;
-        if (base < N) {
-            const int i = base + lane;
-            const bool valid = i < N;
-            const float w = al[ch] * Tt[ch];
-            float G = 0.f;
-            if (valid) {
-                G = gr * cc[ch][0] + gg * cc[ch][1] + gb * cc[ch][2] + gdep * tt[ch] + gac;
-                if (g_w) G += g_w[ray * N + i];
-            }
-            float tot;
-            const float suffix = wave_suffix_excl(valid ? G * w : 0.f, lane, tot) + later;
-            later += tot;
-            if (valid) {
-                float dalpha = G * Tt[ch] - suffix / fc[ch];
-                if (g_alpha) dalpha += g_alpha[ray * N + i];
-                const f32x4 o = {w * gr, w * gg, w * gb, dalpha * ds[ch]};
-                rout[i] = o;
-            }
-        }
-    }
+    const nerf_composite::MseHead mse{mse_target, rgb_out, mse_scale};
     if constexpr (E > 0) {
+        nerf_composite::composite_backward_ray<CHUNKS>(src, mse, nerf_composite::PdfSink{s_pdf[wv].ts, s_pdf_w[wv]}, N, lane, dnorm,
+                                                       ray, rout);
         // the fine pass's positions from this ray's weights (nerf_amd_sample_pdf's body, same draws)
-        nerf_pdf::wave_lds_fence();
+        wave_lds_fence();
         unsigned long long seed = pdf.seed;
         if (pdf.seed_in_mem) {
             const unsigned long long v = *reinterpret_cast<const unsigned long long*>(pdf.u);
@@ -222,6 +103,11 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
         }
         nerf_pdf::sample_ray<E>(s_pdf[wv], s_pdf_w[wv], N, pdf.Nf, lane, pdf.u, pdf.device_rng != 0, seed, pdf.ray_id0, ray,
                                 pdf.ts_out + ray * (N + pdf.Nf));
+    } else if (mse_target) {
+        nerf_composite::composite_backward_ray<CHUNKS>(src, mse, nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
+    } else {
+        nerf_composite::composite_backward_ray<CHUNKS>(src, nerf_composite::FiveGrads{g_rgb, g_disp, g_alpha, g_acc, g_w},
+                                                       nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
     }
 }
 

@@ -1,0 +1,222 @@
+// composite_backward_device.h -- the per-ray backward walk of the compositor, shared by its four kernels:
+// composite_backward_kernel<E> (composite.hip, dense raw[B, N, 4]), occ_composite_backward_kernel (occupancy_train.hip,
+// masked), occ_head_capped_kernel (occupancy_graph.hip, masked under the capacity clamp, MSE head) and
+// occ_head_capped_pdf_kernel<E> (occupancy_hier.hip, the same with the fine pass's sampler behind it).
+//
+// d loss / d raw given the upstream gradients of the five outputs.  With G_i = dL/dw_i gathered from every consumer of w,
+//   dL/dc_i     = w_i * g_rgb
+//   dL/dalpha_i = G_i T_i - (1/f_i) * sum_{k>i} G_k w_k + g_alpha_i       (f = 1 - alpha + 1e-10)
+//   dL/dsigma_i = dL/dalpha_i * e_i * delta_i * softplus'(sigma_i)        (e = exp(-softplus(sigma) delta) = 1 - alpha)
+// ONE wavefront per ray, one sample per lane; chunks of 64 samples are walked forward once (recomputing alpha, T, w with the
+// forward compositor's ops, composite_device.h) and backward once, the suffix sum over k > i a wave-level reverse scan.
+//
+// Every floating-point operation is one explicitly rounded op (mul_rn / add_rn / sub_rn / __fmaf_rn / a division), as in
+// composite_device.h: the compiler has no contraction left to choose, so every caller writes the same bits from the same
+// samples.  The one fused pair is G T - suffix / f; everything else rounds separately.
+//
+// The three axes on which the callers differ are compile-time choices; a term a caller does not have is not computed.
+//   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd)
+//   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; MseHead: the loss gradient formed here)
+//   Sink -- where the forward sweep's weights go (NoSink; PdfSink: the sampler's LDS slice, sample_pdf_device.h)
+#pragma once
+#include "composite_device.h"
+
+namespace nerf_composite {
+
+// exclusive suffix sum over the 64 lanes (inclusive suffix sum, then shift down by one lane) and the wave's total
+__device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& total) {
+    float incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float dn = __shfl_down(incl, off);
+        if (lane + off < 64) incl = add_rn(incl, dn);
+    }
+    total = __shfl(incl, 0);
+    float ex = __shfl_down(incl, 1);
+    if (lane == 63) ex = 0.f;
+    return ex;
+}
+
+// ---- sample sources --------------------------------------------------------------------------------------------------------
+struct BwdSample {
+    float t, t_next;                   // t(i), t(i + 1) (0 at the last sample, whose delta is 1e10)
+    f32x4 c;                           // the network's output
+    int row;                           // the row of d_raw this sample writes, -1 = none
+};
+
+struct DenseSamples {                  // ts / raw in HBM, row = i
+    const float* ts;
+    const f32x4* raw;
+    __device__ __forceinline__ BwdSample chunk(int, int i, int, bool valid, int N) {
+        BwdSample s{0.f, 0.f, f32x4{0.f, 0.f, 0.f, 0.f}, -1};
+        if (valid) {
+            s.t = ts[i];
+            if (i + 1 < N) s.t_next = ts[i + 1];
+            s.c = raw[i];
+            s.row = i;
+        }
+        return s;
+    }
+};
+
+// positions in the wave's LDS slice, the network's output at rank = set mask bits of the ray below i.  A sample whose bit
+// is clear, or whose rank is not below n_kept, is (0, 0, 0, -inf): softplus' = 0, alpha = 0, w = 0, it receives nothing and
+// adds exact zeros to the suffix sums.  A capacity clamp lives in how the caller forms `raw` and `n_kept`.
+struct MaskedSamplesBwd {
+    const float* ts;                   // the ray's N positions (LDS)
+    const unsigned long long* m;       // the ray's mask words
+    const f32x4* raw;                  // the row of the ray's first kept sample
+    long long n_kept;
+    long long before = 0;              // set mask bits of this ray in earlier chunks
+    __device__ __forceinline__ BwdSample chunk(int ch, int i, int lane, bool valid, int N) {
+        const unsigned long long mw = m[ch];
+        BwdSample s{0.f, 0.f, f32x4{0.f, 0.f, 0.f, -__builtin_inff()}, -1};
+        if (valid) {
+            const long long rank = before + __popcll(mw & ((1ull << lane) - 1ull));
+            s.t = ts[i];
+            if (i + 1 < N) s.t_next = ts[i + 1];
+            if (((mw >> lane) & 1ull) && rank < n_kept) {
+                s.c = raw[rank];
+                s.row = (int)rank;
+            }
+        }
+        before += __popcll(mw);
+        return s;
+    }
+};
+
+// ---- upstream gradients ----------------------------------------------------------------------------------------------------
+struct FiveGrads {                     // of rgb[B,3], disp[B], alpha[B,N], acc[B], w[B,N]; NULL = zero
+    static constexpr bool MSE = false;
+    const float *g_rgb, *g_disp, *g_alpha, *g_acc, *g_w;
+};
+struct MseHead {                       // loss = MSELoss(rgb, target) (train.py:52): d loss / d rgb = 2 (rgb - target) scale
+    static constexpr bool MSE = true;
+    const float* target;               // [B,3]
+    float* rgb_out;                    // [B,3]: the forward compositor's rgb, or NULL
+    float scale;                       // 1 / (3 B)
+};
+
+// ---- weight sinks ----------------------------------------------------------------------------------------------------------
+struct NoSink {
+    __device__ __forceinline__ void put(int, float, float) const {}
+};
+struct PdfSink {                       // the sampler's inputs: the positions and the forward compositor's weights
+    float* ts;                         // NULL: the source's positions already are the sampler's
+    float* w;
+    __device__ __forceinline__ void put(int i, float t, float wt) const {
+        if (ts) ts[i] = t;
+        w[i] = wt;
+    }
+};
+
+// rout: row 0 of this ray in d_raw.  N >= 2 (the callers handle the reference's empty sample axis at N == 1), N <= 64 CHUNKS.
+template <int CHUNKS, class Src, class Up, class Sink>
+__device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, const Sink& sink, int N, int lane, float dnorm,
+                                                       long long ray, f32x4* rout) {
+    // forward sweep: per chunk keep alpha, T, fac, d alpha / d sigma, the colour and the row
+    float al[CHUNKS], Tt[CHUNKS], fc[CHUNKS], ds[CHUNKS], tt[CHUNKS];
+    f32x4 cc[CHUNKS];
+    int rk[CHUNKS];
+    float carry = 1.0f, depth = 0.f, accw = 0.f;
+    float sr = 0.f, sg = 0.f, sb = 0.f;            // MSE head: the forward's rgb, for the loss gradient
+#pragma unroll
+    for (int ch = 0; ch < CHUNKS; ++ch) {
+        const int base = ch * 64;
+        al[ch] = 0.f; Tt[ch] = 0.f; fc[ch] = 1.f; ds[ch] = 0.f; tt[ch] = 0.f;
+        cc[ch] = f32x4{0.f, 0.f, 0.f, 0.f};
+        rk[ch] = -1;
+        if (base < N) {
+            const int i = base + lane;
+            const bool valid = i < N;
+            const BwdSample s = src.chunk(ch, i, lane, valid, N);
+            float a = 0.f, fac = 1.0f;
+            if (valid) {
+                float delta = (i == N - 1) ? 1e10f : sub_rn(s.t_next, s.t);
+                delta = mul_rn(delta, dnorm);
+                const float sigma = s.c[3];
+                const float z = expf(sigma);
+                const float sp = sigma > 20.f ? sigma : log1pf(z);
+                // softplus' as torch's backward forms it: z / (z + 1) keeps exp(sigma) down to the subnormals, where
+                // 1 / (1 + exp(-sigma)) is 0 from sigma = -88.7 on (a last sample's delta = 1e10 brings that back up)
+                const float spd = sigma > 20.f ? 1.0f : __fdiv_rn(z, add_rn(z, 1.0f));
+                const float e = expf(mul_rn(-sp, delta));
+                a = sub_rn(1.0f, e);
+                fac = add_rn(sub_rn(1.0f, a), 1e-10f);
+                // e itself, not 1 - alpha: that recovers e to an absolute 2^-24, a relative 2^-24 / e on a nearly opaque sample
+                ds[ch] = mul_rn(mul_rn(e, delta), spd);
+                tt[ch] = s.t; cc[ch] = s.c; rk[ch] = s.row;
+            }
+            // the forward compositor's scan (composite_device.h): same tree, same rounded products
+            const float incl = wave_scan_mul(fac);
+            const float excl = dpp_move<0x138, 0xf>(1.0f, incl);          // wave_shr:1
+            al[ch] = a; fc[ch] = fac; Tt[ch] = mul_rn(carry, excl);
+            carry = mul_rn(carry, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63)));
+            if (valid) {
+                const float wt = mul_rn(a, Tt[ch]);
+                if constexpr (Up::MSE) {
+                    // the same ops as the forward compositor (composite_device.h), so rgb_out equals its rgb
+                    sr = __fmaf_rn(wt, cc[ch][0], sr); sg = __fmaf_rn(wt, cc[ch][1], sg); sb = __fmaf_rn(wt, cc[ch][2], sb);
+                } else {
+                    depth = add_rn(depth, mul_rn(wt, tt[ch])); accw = add_rn(accw, wt);
+                }
+                sink.put(i, tt[ch], rk[ch] >= 0 ? wt : 0.f);       // exactly 0 at a dead or over-capacity sample
+            }
+        }
+    }
+
+    // upstream gradients that reach every w_i of the ray
+    float gr, gg, gb, gdep = 0.f, gac = 0.f;
+    if constexpr (Up::MSE) {
+        sr = wave_total(sr); sg = wave_total(sg); sb = wave_total(sb);
+        gr = mul_rn(mul_rn(2.0f, sub_rn(sr, up.target[ray * 3 + 0])), up.scale);
+        gg = mul_rn(mul_rn(2.0f, sub_rn(sg, up.target[ray * 3 + 1])), up.scale);
+        gb = mul_rn(mul_rn(2.0f, sub_rn(sb, up.target[ray * 3 + 2])), up.scale);
+        if (up.rgb_out && lane == 0) { up.rgb_out[ray * 3 + 0] = sr; up.rgb_out[ray * 3 + 1] = sg; up.rgb_out[ray * 3 + 2] = sb; }
+    } else {
+        depth = wave_sum(depth); accw = wave_sum(accw);
+        gr = up.g_rgb ? up.g_rgb[ray * 3 + 0] : 0.f; gg = up.g_rgb ? up.g_rgb[ray * 3 + 1] : 0.f;
+        gb = up.g_rgb ? up.g_rgb[ray * 3 + 2] : 0.f;
+        gac = up.g_acc ? up.g_acc[ray] : 0.f;
+        if (up.g_disp) {
+            const float q = __fdiv_rn(depth, accw);
+            if (q > 1e-10f) {                        // disp = 1/q there; the clamp branch has zero slope
+                const float dq = __fdiv_rn(-up.g_disp[ray], mul_rn(q, q));
+                gdep = __fdiv_rn(dq, accw);
+                gac = add_rn(gac, __fdiv_rn(mul_rn(-dq, depth), mul_rn(accw, accw)));
+            }
+        }
+    }
+    // backward sweep over chunks, carrying sum_{k in later chunks} G_k w_k
+    float later = 0.f;
+#pragma unroll
+    for (int ch = CHUNKS - 1; ch >= 0; --ch) {
+        const int base = ch * 64;
+        if (base < N) {
+            const int i = base + lane;
+            const bool valid = i < N;
+            const float w = mul_rn(al[ch], Tt[ch]);
+            float G = 0.f;
+            if (valid) {
+                G = add_rn(add_rn(mul_rn(gr, cc[ch][0]), mul_rn(gg, cc[ch][1])), mul_rn(gb, cc[ch][2]));
+                if constexpr (!Up::MSE) {
+                    G = add_rn(add_rn(G, mul_rn(gdep, tt[ch])), gac);
+                    if (up.g_w) G = add_rn(G, up.g_w[ray * N + i]);
+                }
+            }
+            float tot;
+            const float suffix = add_rn(wave_suffix_excl(valid ? mul_rn(G, w) : 0.f, lane, tot), later);
+            later = add_rn(later, tot);
+            if (valid && rk[ch] >= 0) {
+                float dalpha = __fmaf_rn(G, Tt[ch], -__fdiv_rn(suffix, fc[ch]));
+                if constexpr (!Up::MSE) {
+                    if (up.g_alpha) dalpha = add_rn(dalpha, up.g_alpha[ray * N + i]);
+                }
+                const f32x4 o = {mul_rn(w, gr), mul_rn(w, gg), mul_rn(w, gb), mul_rn(dalpha, ds[ch])};
+                rout[rk[ch]] = o;
+            }
+        }
+    }
+}
+
+}  // namespace nerf_composite

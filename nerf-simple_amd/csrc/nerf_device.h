@@ -245,6 +245,12 @@ __device__ __forceinline__ void chunk_barrier() {
     asm volatile("" ::: "memory");            // nothing below is hoisted above the barrier
 }
 
+// one wave's LDS hand-over: what this wave has written, its other lanes may read (no workgroup barrier)
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_s_waitcnt(0xc07f);        // lgkmcnt(0): this wave's LDS writes are done
+    __builtin_amdgcn_wave_barrier();
+}
+
 // ---- LDS by byte address --------------------------------------------------------------
 // The kernels lay their dynamic LDS out by hand (LDS_* constants): base = a register, imm = a constant that lands in the
 // instruction's offset field.

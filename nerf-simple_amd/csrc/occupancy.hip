@@ -20,6 +20,7 @@
 //                                for a live sample and (0, 0, 0, -inf) for a dead one, which contributes exactly nothing.
 // Fixed partitions and hand-written scans, no atomics: every run writes the same bytes.
 #include "composite_device.h"
+#include "occ_scan_device.h"
 
 namespace {
 
@@ -38,11 +39,6 @@ struct OccGrid {
     float lo[3], inv_step[3];
     int outside_live;
 };
-
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);        // lgkmcnt(0): this wave's LDS writes are done
-    __builtin_amdgcn_wave_barrier();
-}
 
 // ---- bits from sigma ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void occ_bits_kernel(const float* __restrict__ sigma, long long nx, long long ny, long long nz,
@@ -119,28 +115,6 @@ __global__ __launch_bounds__(64 * OCC_RAYS_PER_BLOCK) void occ_mark_kernel(MlpAr
 }
 
 // ---- scan ----------------------------------------------------------------------------------------------------------------
-// exclusive scan of one value per thread over the workgroup (OCC_SCAN_THREADS), in thread order; also the block total
-__device__ __forceinline__ long long block_exclusive_scan(long long x, long long& total, long long* lds_waves) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) lds_waves[wave] = incl;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < OCC_SCAN_THREADS / 64; ++w) {
-        const long long t = lds_waves[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    return before + incl - x;
-}
-
 __global__ __launch_bounds__(OCC_SCAN_THREADS) void occ_block_sum_kernel(const int* __restrict__ counts, long long B,
                                                                          long long* __restrict__ blk) {
     __shared__ long long lds_waves[OCC_SCAN_THREADS / 64];
@@ -149,7 +123,7 @@ __global__ __launch_bounds__(OCC_SCAN_THREADS) void occ_block_sum_kernel(const i
     for (int r = 0; r < OCC_SCAN_PER_THREAD; ++r)
         if (base + r < B) s += counts[base + r];
     long long total;
-    (void)block_exclusive_scan(s, total, lds_waves);
+    (void)block_exclusive_scan<OCC_SCAN_THREADS>(s, total, lds_waves);
     if (threadIdx.x == 0) blk[blockIdx.x] = total;
 }
 
@@ -195,7 +169,7 @@ __global__ __launch_bounds__(OCC_SCAN_THREADS) void occ_offsets_kernel(const int
         s += c[r];
     }
     long long total;
-    long long p = blkoff[blockIdx.x] + block_exclusive_scan(s, total, lds_waves);
+    long long p = blkoff[blockIdx.x] + block_exclusive_scan<OCC_SCAN_THREADS>(s, total, lds_waves);
     for (int r = 0; r < OCC_SCAN_PER_THREAD; ++r) {
         if (base + r < B) offsets[base + r] = p;
         p += c[r];
@@ -210,22 +184,10 @@ __global__ __launch_bounds__(64 * OCC_RAYS_PER_BLOCK) void occ_emit_kernel(MlpAr
     const long long ray = (long long)blockIdx.x * OCC_RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= B) return;
     const int lane = threadIdx.x & 63;
-    long long out = offsets[ray];
-    if (offsets[ray + 1] == out) return;       // nothing live on this ray
-    const int words = (a.N + 63) >> 6;
-    for (int q = 0; q < words; ++q) {
-        const unsigned long long m = mask[ray * words + q];
-        const int i = q * 64 + lane;
-        if (((m >> lane) & 1ull) && i < a.N) {
-            const long long row = out + __popcll(m & ((1ull << lane) - 1ull));
-            if (row >= 0 && row < max_points) {            // never past the capacity the caller states
-                const PointIn pt = fetch_point_rays<true>(a, ray * a.N + i, RaySample{ray, i});
-                float* o = pts + row * 6;
-                o[0] = pt.x; o[1] = pt.y; o[2] = pt.z; o[3] = pt.d1; o[4] = pt.d2; o[5] = pt.d3;
-            }
-        }
-        out += __popcll(m);
-    }
+    const long long first = offsets[ray];
+    if (offsets[ray + 1] == first) return;     // nothing live on this ray
+    // never past the capacity the caller states
+    emit_ray_rows(a, mask + ray * ((a.N + 63) >> 6), pts, first, max_points, ray, lane);
 }
 
 // ---- masked composite ----------------------------------------------------------------------------------------------------

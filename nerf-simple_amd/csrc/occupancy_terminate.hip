@@ -18,9 +18,10 @@
 //                  still has beyond s1.
 //   term_block_sum_kernel / term_offsets_kernel -- exclusive scan of the counts into offsets_next[B + 1] and the two totals.
 // Fixed partitions, hand-written scans, no atomics: two runs write the same bytes.  The host wrapper below is the C ABI
-// itself: api.hip is not involved.
+// itself (argument rules: api_checks.h).
 #include "composite_device.h"
-#include "../../include/nerf_amd.h"
+#include "occ_scan_device.h"
+#include "api_checks.h"
 
 namespace {
 
@@ -131,29 +132,6 @@ __global__ __launch_bounds__(64 * TERM_RAYS_PER_BLOCK) void term_advance_kernel(
 }
 
 // ---- scan ----------------------------------------------------------------------------------------------------------------
-// exclusive scan of one value per thread over the workgroup, in thread order, and the block total (occupancy.hip's scheme)
-__device__ __forceinline__ long long term_block_scan(long long x, long long& total, long long* lds_waves) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    __syncthreads();                           // the slots may still be read from an earlier use
-    if (lane == 63) lds_waves[wave] = incl;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < TERM_SCAN_THREADS / 64; ++w) {
-        const long long v = lds_waves[w];
-        if (w < wave) before += v;
-        total += v;
-    }
-    return before + incl - x;
-}
-
 // blk[2 b], blk[2 b + 1]: the sums of cnt / rem over scan block b
 __global__ __launch_bounds__(TERM_SCAN_THREADS) void term_block_sum_kernel(const int* __restrict__ cnt, const int* __restrict__ rem,
                                                                            long long B, long long* __restrict__ blk) {
@@ -163,8 +141,8 @@ __global__ __launch_bounds__(TERM_SCAN_THREADS) void term_block_sum_kernel(const
     for (int k = 0; k < TERM_SCAN_PER_THREAD; ++k)
         if (base + k < B) { s += cnt[base + k]; r += rem[base + k]; }
     long long ts, tr;
-    (void)term_block_scan(s, ts, lds_waves);
-    (void)term_block_scan(r, tr, lds_waves);
+    (void)block_exclusive_scan<TERM_SCAN_THREADS>(s, ts, lds_waves);
+    (void)block_exclusive_scan<TERM_SCAN_THREADS>(r, tr, lds_waves);
     if (threadIdx.x == 0) { blk[2 * (long long)blockIdx.x] = ts; blk[2 * (long long)blockIdx.x + 1] = tr; }
 }
 
@@ -182,8 +160,8 @@ __global__ __launch_bounds__(TERM_SCAN_THREADS) void term_offsets_kernel(const i
         if (last) r += blk[2 * b + 1];
     }
     long long prefix, rem_total;
-    (void)term_block_scan(p, prefix, lds_waves);
-    (void)term_block_scan(r, rem_total, lds_waves);
+    (void)block_exclusive_scan<TERM_SCAN_THREADS>(p, prefix, lds_waves);
+    (void)block_exclusive_scan<TERM_SCAN_THREADS>(r, rem_total, lds_waves);
     const long long base = (long long)blockIdx.x * TERM_SCAN_ITEMS + (long long)threadIdx.x * TERM_SCAN_PER_THREAD;
     int c[TERM_SCAN_PER_THREAD];
     long long s = 0;
@@ -192,7 +170,7 @@ __global__ __launch_bounds__(TERM_SCAN_THREADS) void term_offsets_kernel(const i
         s += c[k];
     }
     long long total;
-    long long o = prefix + term_block_scan(s, total, lds_waves);
+    long long o = prefix + block_exclusive_scan<TERM_SCAN_THREADS>(s, total, lds_waves);
     for (int k = 0; k < TERM_SCAN_PER_THREAD; ++k) {
         if (base + k < B) offsets[base + k] = o;
         o += c[k];
@@ -218,8 +196,6 @@ TermWs term_ws(long long B) {
     return w;
 }
 
-inline bool term_misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 }  // namespace
 
 extern "C" int64_t nerf_amd_termination_workspace_bytes(int64_t B) {
@@ -234,15 +210,9 @@ extern "C" int nerf_amd_termination_advance(const float* raw_slab, const uint64_
                                             const int64_t* offsets0, float* raw0, int64_t rows0, float eps, int slab, int s0,
                                             int s1, int s2, float* trans, uint64_t* mask_next, int64_t* offsets_next,
                                             int64_t* totals, void* workspace, int64_t B, int N, void* stream) {
-    // the rays and jitter rules of the other masked stages, restated
+    // the rays and jitter rules of the other masked stages
     if (B < 0 || N <= 0 || rows_slab < 0 || rows0 < 0) return NERF_AMD_EINVAL;
-    if (flags & ~(NERF_AMD_TS_GIVEN | NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return NERF_AMD_EINVAL;
-    if (flags & NERF_AMD_SEED_IN_MEMORY) {
-        if (!(flags & NERF_AMD_DEVICE_RNG) || (flags & NERF_AMD_TS_GIVEN) || !u || term_misaligned(u, 8)) return NERF_AMD_EINVAL;
-    } else if (!(flags & NERF_AMD_DEVICE_RNG) && !u) {
-        return NERF_AMD_EINVAL;
-    }
-    if (!(flags & NERF_AMD_TS_GIVEN) && !tbins) return NERF_AMD_EINVAL;
+    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
     if (!(eps > 0.0f && eps < 1.0f)) return NERF_AMD_EINVAL;                    // also NaN
     if (slab != 16 && slab != 32 && slab != 64) return NERF_AMD_EINVAL;
     if (N > TERM_MAX_N || B > TERM_MAX_RAYS) return NERF_AMD_EUNSUP;
@@ -252,8 +222,8 @@ extern "C" int nerf_amd_termination_advance(const float* raw_slab, const uint64_
     if (s1 != clip((int64_t)s0 + slab) && !(s0 == 0 && s1 == 0)) return NERF_AMD_EINVAL;
     if (s2 != clip((int64_t)s1 + slab)) return NERF_AMD_EINVAL;
     if (raw_slab) {
-        if (s0 == s1 || !mask_slab || !offsets_slab || term_misaligned(raw_slab, 16) || term_misaligned(mask_slab, 8) ||
-            term_misaligned(offsets_slab, 8))
+        if (s0 == s1 || !mask_slab || !offsets_slab || misaligned(raw_slab, 16) || misaligned(mask_slab, 8) ||
+            misaligned(offsets_slab, 8))
             return NERF_AMD_EINVAL;
         if (mask_slab == mask_next || offsets_slab == offsets_next) return NERF_AMD_EINVAL;      // the scan is not in place
     } else if (rows_slab != 0) {
@@ -261,16 +231,14 @@ extern "C" int nerf_amd_termination_advance(const float* raw_slab, const uint64_
     }
     if (!mask0 || !offsets0 || !trans || !mask_next || !offsets_next || !totals || !workspace || (rows0 > 0 && !raw0))
         return NERF_AMD_EINVAL;
-    if (term_misaligned(mask0, 8) || term_misaligned(offsets0, 8) || term_misaligned(raw0, 16) || term_misaligned(trans, 4) ||
-        term_misaligned(mask_next, 8) || term_misaligned(offsets_next, 8) || term_misaligned(totals, 8) ||
-        term_misaligned(workspace, 16))
+    if (misaligned(mask0, 8) || misaligned(offsets0, 8) || misaligned(raw0, 16) || misaligned(trans, 4) ||
+        misaligned(mask_next, 8) || misaligned(offsets_next, 8) || misaligned(totals, 8) ||
+        misaligned(workspace, 16))
         return NERF_AMD_EINVAL;
     if (B > 0 && !rays) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
     (void)hipGetLastError();
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
     const TermWs w = term_ws(B);
     char* b = reinterpret_cast<char*>(workspace);
     TermArgs t;

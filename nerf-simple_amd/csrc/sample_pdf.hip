@@ -29,7 +29,7 @@ __global__ __launch_bounds__(64 * RPB) void sample_pdf_kernel(
     nerf_pdf::WaveLds<E>& s = s_wave[wv];
     const float* rts = ts + ray * Nc;
     for (int i = lane; i < Nc; i += 64) s.ts[i] = rts[i];
-    nerf_pdf::wave_lds_fence();
+    wave_lds_fence();
     nerf_pdf::sample_ray<E>(s, w + ray * Nc, Nc, Nf, lane, u, device_rng != 0, seed, ray_id0, ray, out + ray * (Nc + Nf));
 }
 

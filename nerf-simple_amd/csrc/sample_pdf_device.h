@@ -71,11 +71,6 @@ __device__ __forceinline__ void wave_bitonic_sort(float (&v)[E], int lane) {
     }
 }
 
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_s_waitcnt(0xc07f);                // lgkmcnt(0): this wave's LDS writes are done
-    __builtin_amdgcn_wave_barrier();
-}
-
 // One ray: s.ts[0..Nc) holds its coarse positions (written by this wave and fenced), rw[0..Nc) its weights (any
 // address space).  Jitter: u[ray * Nf + j], or with device_rng the counter RNG keyed (seed ^ RNG_KEY,
 // (ray_id0 + ray) * Nf + j) -- the caller resolves a seed held in device memory first.  Writes out[0..Nc+Nf).

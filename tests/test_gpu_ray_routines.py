@@ -233,6 +233,51 @@ def test_coarse_head_at_the_seams(dev, Nc, Nf):
     assert torch.equal(rgb, rgb_ref) and torch.equal(d_raw, d_ref) and torch.equal(ts_out, ts_ref)
 
 
+@pytest.mark.parametrize("N", [3, 64, 65, 256])
+def test_four_backward_kernels_write_the_same_bytes(dev, N):
+    """The compositor's backward walk is one routine (csrc/composite_backward_device.h): from the same raw and gt, under an
+    all-live mask, the dense MSE backward, the masked backward fed the g_rgb nerf_amd_mse_loss forms, the capped head at
+    C = B N and the capped pdf head at C = B N (Nf = 8) write the same d_raw bytes.  N: one partial chunk, one full chunk, a
+    chunk seam, and the pdf head's four-chunk limit."""
+    from nerf_simple_amd import _lib
+    lib, ptr = _lib.lib(), _lib.ptr
+    st = _lib.stream_ptr(dev)
+    B, Nf, TS_GIVEN = 5, 8, _lib.FLAG_TS_GIVEN
+    gen = torch.Generator().manual_seed(7000 + N)
+    raw = torch.randn(B, N, 4, generator=gen)
+    raw[..., 3] = 15.0 * raw[..., 3] + 7.5
+    ts = M.O.sample_ts(torch.rand(B, N, generator=gen))
+    rays, gt, u_f = torch.randn(B, 6, generator=gen), torch.rand(B, 3, generator=gen), torch.rand(B, Nf, generator=gen)
+    raw, ts, rays, gt, u_f = [x.contiguous().to(dev) for x in (raw, ts, rays, gt, u_f)]
+    i = torch.arange(((N + 63) // 64) * 64).view(-1, 64)
+    words = ((i < N).long() << (i % 64)).sum(1)                      # bit b of word q: sample 64 q + b exists
+    mask = words.expand(B, -1).contiguous().to(dev)
+    offsets = (torch.arange(B + 1, dtype=torch.int64) * N).to(dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    nan = lambda *shape: torch.full(shape, float("nan"), **f32)      # noqa: E731
+    rgb, d_dense = nan(B, 3), nan(B, N, 4)
+    _lib.check(lib.nerf_amd_volume_render_mse_backward(ptr(raw), ptr(ts), ptr(rays), ptr(gt), ptr(rgb), ptr(d_dense), B, N, st),
+               "nerf_amd_volume_render_mse_backward")
+    jit = (ptr(rays), ptr(ts), None, TS_GIVEN, 0, 0, ptr(mask), ptr(offsets))
+    loss, g_rgb, d_masked = nan(), nan(B, 3), nan(B * N, 4)
+    _lib.check(lib.nerf_amd_mse_loss(ptr(rgb), ptr(gt), ptr(loss), ptr(g_rgb), B * 3, st), "nerf_amd_mse_loss")
+    _lib.check(lib.nerf_amd_volume_render_masked_backward(ptr(raw), *jit, ptr(g_rgb), None, None, None, None, ptr(d_masked), B, N, st),
+               "nerf_amd_volume_render_masked_backward")
+    rgb_head, d_head = nan(B, 3), nan(B * N, 4)
+    _lib.check(lib.nerf_amd_volume_render_masked_mse_backward(ptr(raw), *jit, ptr(gt), ptr(rgb_head), ptr(d_head), B * N, B, N, st),
+               "nerf_amd_volume_render_masked_mse_backward")
+    rgb_pdf, d_pdf, ts_out = nan(B, 3), nan(B * N, 4), nan(B, N + Nf)
+    _lib.check(lib.nerf_amd_volume_render_masked_mse_backward_pdf(ptr(raw), *jit, ptr(gt), ptr(u_f), ptr(rgb_pdf), ptr(d_pdf),
+                                                                  ptr(ts_out), B * N, B, N, Nf, st),
+               "nerf_amd_volume_render_masked_mse_backward_pdf")
+    torch.cuda.synchronize(dev)
+    want = d_dense.view(torch.int32).view(B * N, 4)
+    assert torch.isfinite(d_dense).all() and (d_dense != 0).any()
+    assert torch.equal(rgb_head, rgb) and torch.equal(rgb_pdf, rgb)
+    for name, d in (("masked backward", d_masked), ("capped head", d_head), ("capped pdf head", d_pdf)):
+        assert torch.equal(d.view(torch.int32), want), name
+
+
 @pytest.mark.parametrize("case", M.pdf_cases(), ids=lambda c: c.id)
 def test_sample_pdf_per_ray(dev, case):
     """nerf_amd_sample_pdf with explicit u: ascending, the Nc coarse positions present bit for bit, and every ray without

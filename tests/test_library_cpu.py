@@ -266,6 +266,47 @@ def test_abi_argument_errors(lib):
     assert lib.nerf_amd_pinned_device_address(null) == EINVAL
 
 
+def test_ts_given_requires_u_at_every_rays_mode_entry_point(lib):
+    """With NERF_AMD_TS_GIVEN the kernels read the sample positions through `u` whatever the other flags say, so
+    flags = TS_GIVEN | DEVICE_RNG with u = NULL is NERF_AMD_EINVAL at every rays-mode entry point, before anything is
+    launched: every other pointer is a fake, 16-aligned address that is never dereferenced."""
+    EINVAL = -1
+    null, P, f = None, ctypes.c_void_p(0x1000), ctypes.c_float
+    F = 1 | 2                                     # NERF_AMD_TS_GIVEN | NERF_AMD_DEVICE_RNG
+    B, N = 4, 64
+    jit = (P, null, P, F, 0, 0)                   # rays, u, tbins, flags, seed, ray_id0
+    calls = {
+        "query_points": lambda: lib.nerf_amd_query_points(*jit, P, P, B, N, null),
+        "range_check": lambda: lib.nerf_amd_range_check(P, null, null, P, F, 0, 0, P, B, N, null),
+        "sample_encode": lambda: lib.nerf_amd_sample_encode(*jit, P, P, P, B, N, null),
+        "sample_encode_bf16": lambda: lib.nerf_amd_sample_encode_bf16(*jit, P, P, P, B, N, null),
+        "mlp_forward_rays": lambda: lib.nerf_amd_mlp_forward_rays(P, null, P, P, 1, F, 0, 0, P, P, B, N, null),
+        "mlp_forward_rays, N > 768": lambda: lib.nerf_amd_mlp_forward_rays(P, null, P, P, 1, F, 0, 0, P, P, B, 800, null),
+        "mlp_forward_train": lambda: lib.nerf_amd_mlp_forward_train(P, null, P, P, F, 0, 0, P, P, P, B, N, null),
+        "mlp_forward_train, e4m3": lambda: lib.nerf_amd_mlp_forward_train(P, null, P, P, F | 8, 0, 0, P, P, P, B, N, null),
+        "render_forward": lambda: lib.nerf_amd_render_forward(P, null, P, P, 1, F, 0, 0, P, P, P, P, P, P, B, N, null),
+        "render_forward, N > 768": lambda: lib.nerf_amd_render_forward(P, null, P, P, 1, F, 0, 0, P, P, P, P, P, P, B, 800, null),
+        "render_pixels_forward": lambda: lib.nerf_amd_render_pixels_forward(P, null, P, P, 1, F, 0, 0, P, P, B, N, null),
+        "render_pixels_forward, N > 768": lambda: lib.nerf_amd_render_pixels_forward(P, null, P, P, 1, F, 0, 0, P, P, B, 800, null),
+        "render_image_forward": lambda: lib.nerf_amd_render_image_forward(P, 8, 8, f(5.0), 0, 64, null, P, P, 1, F, 0, P, P, N, null),
+        "render_hierarchical_forward": lambda: lib.nerf_amd_render_hierarchical_forward(P, 8, 8, f(5.0), 0, 64, null, P, P, P, P, 1, F, 0,
+                                                                                        P, P, 16, 16, null),
+        "occupancy_mark": lambda: lib.nerf_amd_occupancy_mark(*jit, P, 9, 9, 9, P, P, P, P, P, P, B, N, null),
+        "occupancy_points": lambda: lib.nerf_amd_occupancy_points(*jit, P, P, P, 16, B, N, null),
+        "volume_render_masked": lambda: lib.nerf_amd_volume_render_masked(P, *jit, P, P, P, P, P, P, P, B, N, null),
+        "volume_render_masked_pixels": lambda: lib.nerf_amd_volume_render_masked_pixels(P, *jit, P, P, P, B, N, null),
+        "volume_render_masked_backward": lambda: lib.nerf_amd_volume_render_masked_backward(P, *jit, P, P, P, P, P, P, P, P, B, N, null),
+        "occupancy_points_capped": lambda: lib.nerf_amd_occupancy_points_capped(*jit, P, P, P, P, 8, B, N, null),
+        "volume_render_masked_mse_backward": lambda: lib.nerf_amd_volume_render_masked_mse_backward(P, *jit, P, P, P, P, P, 8, B, N, null),
+        "volume_render_masked_mse_backward_pdf": lambda: lib.nerf_amd_volume_render_masked_mse_backward_pdf(
+            P, *jit, P, P, P, P, P, P, P, 8, B, N, 64, null),
+        "termination_advance": lambda: lib.nerf_amd_termination_advance(null, null, null, 0, *jit, P, P, P, 16, f(1e-3), 64, 0, 0, N,
+                                                                        P, P, P, P, P, B, N, null),
+    }
+    for name, call in calls.items():
+        assert call() == EINVAL, name
+
+
 def test_jump_polynomial_on_the_host(lib):
     """nerf_amd_mt19937_jump_poly (C++, host): x^(624 q) mod phi equals tools/make_mt_jump.py's big-integer
     square-and-multiply for small and table-sized q, a wrong phi is refused, and the polynomial does what it is for:
