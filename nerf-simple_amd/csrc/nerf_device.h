@@ -432,10 +432,15 @@ __device__ __forceinline__ PointIn fetch_point_pts(const MlpArgs& a, long long p
 // x / (2 pi) as an unevaluated sum hi + lo (|lo| <= ulp(hi)/2): scaling by 2^k
 // is exact and fract(hi * 2^k) is exact, so the phase of sin(2^k x) keeps
 // ~1e-7 rad accuracy even at |2^k x| ~ 2300 rad.
+// |x| is limited to 2^100 first (one v_med3, nothing changes below that): from |x| ~ 4e36 on hi * 2^9 overflows, the
+// fraction of inf is NaN and so were the features, which have to stay finite with |f| <= 1 for every finite x -- their
+// value out there is noise, as the reference's sinf(2^k x) is.  Verified against float64 for |x| <= 4096
+// (tests/test_gpu_encoder_probe.py; DESIGN.md "Encoder probe").
 struct TwoF { float hi, lo; };
 __device__ __forceinline__ TwoF to_revolutions(float x) {
     const float C_HI = 0.15915494f;          // fl32(1/(2 pi))
     const float C_LO = 6.4206382e-09f;       // 1/(2 pi) - C_HI
+    x = __builtin_amdgcn_fmed3f(x, -0x1p100f, 0x1p100f);
     TwoF q;
     q.hi = mul_rn(x, C_HI);
     const float err = __fmaf_rn(x, C_HI, -q.hi);
@@ -450,7 +455,7 @@ __device__ __forceinline__ float enc_lane(TwoF q, int idx) {
     return __builtin_amdgcn_sinf(fr);
 }
 // sin / cos of (2 pi * 2^k * q) via the hardware v_sin/v_cos (argument in
-// revolutions).  Accuracy ~1e-6 abs: used by the bf16 path only.
+// revolutions).  Measured within 3.8e-7 of float64 for |x| <= 4096 (DESIGN.md "Encoder probe"): used by the bf16 path only.
 __device__ __forceinline__ void sincos_rev_fast(TwoF q, float scale, float& s, float& c) {
     const float f = __builtin_amdgcn_fractf(q.hi * scale) + q.lo * scale;
     s = __builtin_amdgcn_sinf(f);

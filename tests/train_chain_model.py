@@ -25,7 +25,8 @@ Encoder columns: layers 0, 5 (skip) and 9 (colour) also consume encoder features
 while the rows the products read come from nerf_amd_sample_encode_bf16; the two encoders differ by ~1e-6 before rounding, so
 a stored row can sit one bf16 step from what the forward used.  ``delta_enc = sum_k |w16_k| (ulp_bf16(x_k) + 2^-19)`` over
 the encoder columns is added to delta for those layers (zero for a weight set whose encoder columns are zero:
-``zero_encoder_columns``).
+``zero_encoder_columns``).  The in-register encoder itself is pinned elsewhere, feature by feature against float64:
+tests/test_gpu_encoder_probe.py (probe weight sets that turn single encoder columns into outputs).
 
 ``emulate_chain`` is a CPU emulation of the whole chain (bf16 round-to-nearest-even storage, fp32 sums in one of two orders)
 that produces the same buffers as the kernels; tests/test_train_chain_model_cpu.py runs it through the rule, unharmed and
