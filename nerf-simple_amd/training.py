@@ -677,6 +677,176 @@ class _StatusWatch:
         return hit
 
 
+class _CountsWatch:
+    """Asynchronous read-back of the graphed masked step's ``counts`` (int64[2] = {live, kept}), after _StatusWatch: ``push``
+    enqueues a 16-byte copy into pinned memory behind graph A, ``poll`` hands back the copies that have completed, oldest
+    first, as (step, live, kept) -- no host wait."""
+
+    def __init__(self, slots=4, width=2):
+        self.bufs = [torch.zeros(width, dtype=torch.int64).pin_memory() for _ in range(slots)]
+        self.pending = []                       # (event, slot, step)
+        self.k = 0
+
+    def push(self, counts, step):
+        if len(self.pending) >= len(self.bufs):
+            return                              # every slot still in flight: skip this sample
+        slot = self.k % len(self.bufs)
+        self.k += 1
+        self.bufs[slot].copy_(counts, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(counts.device))
+        self.pending.append((ev, slot, step))
+
+    def poll(self, wait=False):
+        done = []
+        while self.pending and (wait or self.pending[0][0].query()):
+            ev, slot, step = self.pending.pop(0)
+            if wait:
+                ev.synchronize()
+            done.append((step, *(int(v) for v in self.bufs[slot])))
+        return done
+
+
+def _capacity_points(capacity, total, what):
+    """A capacity argument as points: an int is a number of points, a float a fraction of ``total`` (GraphedMaskedTrainStep's
+    rule).  ``what`` names the argument in the messages."""
+    import math
+    import numbers
+    if isinstance(capacity, bool) or not isinstance(capacity, numbers.Real):
+        raise TypeError(f"{what} must be an int (points) or a float (fraction of the pass's samples)")
+    if isinstance(capacity, numbers.Integral):
+        C = int(capacity)
+    else:
+        if not 0.0 < capacity <= 1.0:
+            raise ValueError(f"a fractional {what} must lie in (0, 1], got {capacity!r}")
+        C = max(1, math.ceil(float(capacity) * total))
+    if not 1 <= C <= total:
+        raise ValueError(f"{what} must lie in [1, {total}] points, got {C}")
+    return C
+
+
+
+def _launch(name, *args):
+    """Enqueue one C entry point by name (its last argument is the stream); a refused launch raises."""
+    _lib.check(getattr(_lib.lib(), name)(*args), name)
+
+
+class _Pass:
+    """What ONE network pass of a graphed step owns, and how each of its stages is enqueued.
+    ``N`` samples per ray, network kernels on ``P`` points (``rows`` = the leading shape of raw / d_raw).  The stepper hands
+    it the rest before the first launch: ``net`` and its images ``fwd`` / ``bwd``, ``grads`` (its slice of the flat gradient
+    vector), ``loss`` (its loss slot) and ``jitter`` = (rays, jitter, tbins, flags, seed, ray_id0) as the kernels take them."""
+
+    def __init__(self, step, N, P, rows, e4m3=False):
+        lib, dev = _lib.lib(), step.dev
+        f32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
+        self.step, self.N, self.P, self.e4m3 = step, N, P, e4m3
+        self.raw, self.d_raw = torch.empty((*rows, 4), **f32), torch.empty((*rows, 4), **f32)
+        self.rgb = torch.empty((step.B, 3), **f32)
+        if e4m3:
+            self.acts = torch.empty(int(lib.nerf_amd_train_activation_bytes_e4m3(P)), **u8)
+            self.dys = torch.empty(int(lib.nerf_amd_train_gradient_bytes_e4m3(P)), **u8)
+            self.scratch8 = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_e4m3_bytes(P)), 16), **u8)
+        else:
+            nb = int(lib.nerf_amd_train_activation_bytes(P))
+            self.acts, self.dys = torch.empty(nb, **u8), torch.empty(nb, **u8)
+        self.posx = torch.empty((P, 64), dtype=torch.bfloat16, device=dev)
+        self.posd = torch.empty((P, 32), dtype=torch.bfloat16, device=dev)
+        self.scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), **u8)
+
+    def dx_chain(self, st):
+        ptr = _lib.ptr
+        _launch("nerf_amd_mlp_backward_e4m3" if self.e4m3 else "nerf_amd_mlp_backward",
+                ptr(self.d_raw), ptr(self.bwd), ptr(self.acts), ptr(self.dys), self.P, st)
+
+    def loss_and_begin(self, ss):
+        """The loss value, then the gradient slice's zero fill and the d_raw pack."""
+        ptr = _lib.ptr
+        _launch("nerf_amd_mse_loss", ptr(self.rgb), ptr(self.step.gt), ptr(self.loss), None, self.step.B * 3, ss)
+        _launch("nerf_amd_param_gradients_begin", ptr(self.d_raw), ptr(self.scratch), ptr(self.grads), self.P, ss)
+        if self.e4m3:        # the packed d_raw in the products' 8-bit form
+            _launch("nerf_amd_param_gradients_convert_e4m3", None, None, ptr(self.scratch), ptr(self.scratch8), self.P, 2, ss)
+
+    def finish(self, bucket, st):
+        """The dW products (all, or one bucket's) from the saved tensors in this pass's storage form."""
+        ptr = _lib.ptr
+        if self.e4m3:
+            _launch("nerf_amd_param_gradients_finish_e4m3", ptr(self.acts), ptr(self.dys), ptr(self.scratch8), ptr(self.grads),
+                    self.P, bucket, st)
+        else:
+            _launch("nerf_amd_param_gradients_finish_bucket", ptr(self.acts), ptr(self.dys), ptr(self.posx), ptr(self.posd),
+                    ptr(self.scratch), ptr(self.grads), self.P, bucket, st)
+
+
+class _DensePass(_Pass):
+    """All B x N samples: the forward samples the rays itself and writes the positions ``ts``."""
+
+    def __init__(self, step, N, e4m3=False):
+        super().__init__(step, N, step.B * N, (step.B, N), e4m3)
+        self.ts = torch.empty((step.B, N), dtype=torch.float32, device=step.dev)
+
+    def forward(self, st):
+        ptr, (rays, jit, tbins, flags, seed, rid) = _lib.ptr, self.jitter
+        _launch("nerf_amd_mlp_forward_train", rays, jit, tbins, ptr(self.fwd), flags | (_lib.FLAG_STORE_E4M3 if self.e4m3 else 0),
+                seed, rid, ptr(self.raw), ptr(self.ts), ptr(self.acts), self.step.B, self.N, st)
+
+    def head(self, st, pdf=None):
+        """Compositor + MSE gradient + compositor backward, one kernel; only rgb feeds the loss (train.py:52): disparity,
+        alpha, acc, w are not materialised.  ``pdf`` = (u_f, ts_f, Nf): sample_pdf on the weights in the same kernel (they
+        never reach HBM), which takes the seed in memory where the counter RNG leaves u_f empty."""
+        ptr, s, (rays, jit, _, flags, seed, rid) = _lib.ptr, self.step, self.jitter
+        if pdf is None:
+            _launch("nerf_amd_volume_render_mse_backward", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt), ptr(self.rgb),
+                    ptr(self.d_raw), s.B, self.N, st)
+        else:
+            u_f, ts_f, Nf = pdf
+            _launch("nerf_amd_volume_render_mse_backward_pdf", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt),
+                    jit if u_f is None else u_f, flags, seed, rid, ptr(self.rgb), ptr(self.d_raw), ts_f, s.B, self.N, Nf, st)
+
+    def encoder_rows(self, ss):
+        """At the sample positions the forward drew: ts = f(jitter) bit for bit (the same jitter arguments)."""
+        ptr = _lib.ptr
+        _launch("nerf_amd_sample_encode_bf16", *self.jitter, ptr(self.posx), ptr(self.posd), None, self.step.B, self.N, ss)
+        if self.e4m3:        # the encoder rows in the products' 8-bit form
+            _launch("nerf_amd_param_gradients_convert_e4m3", ptr(self.posx), ptr(self.posd), None, ptr(self.scratch8), self.P, 1, ss)
+
+
+class _MaskedPass(_Pass):
+    """The live samples of the stepper's occupancy grid, on a fixed capacity of P = C points: mark + scan, capped emit of
+    ``pts`` [C, 6] (``counts`` = {live, kept}), then the points-mode kernels; rows no live sample owns are inert."""
+
+    def __init__(self, step, N, C, counts):
+        super().__init__(step, N, C, (C,))
+        B, dev = step.B, step.dev
+        self.mask = torch.zeros((B, (N + 63) // 64), dtype=torch.int64, device=dev)
+        self.offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        self.pts, self.counts = torch.empty((C, 6), dtype=torch.float32, device=dev), counts
+
+    def forward(self, st):
+        import ctypes
+        ptr, s, (*head, flags, seed, rid) = _lib.ptr, self.step, self.jitter
+        R, lo, inv, outside = s._grid
+        _launch("nerf_amd_occupancy_mark", *head, flags | outside, seed, rid, ctypes.c_void_p(s._words_ptr), *R, lo, inv,
+                ptr(self.mask), ptr(self.offsets), None, ptr(s._mark_ws), s.B, self.N, st)
+        _launch("nerf_amd_occupancy_points_capped", *self.jitter, ptr(self.mask), ptr(self.offsets), ptr(self.pts),
+                ptr(self.counts), self.P, s.B, self.N, st)
+        _launch("nerf_amd_mlp_forward_train_points", ptr(self.pts), ptr(self.fwd), ptr(self.raw), ptr(self.acts), self.P, st)
+
+    def head(self, st, pdf=None):
+        """The masked head (masked compositor + MSE gradient + backward, one kernel); ``pdf`` as the dense pass's."""
+        ptr, s = _lib.ptr, self.step
+        args = (ptr(self.raw), *self.jitter, ptr(self.mask), ptr(self.offsets), ptr(s.gt))
+        if pdf is None:
+            _launch("nerf_amd_volume_render_masked_mse_backward", *args, ptr(self.rgb), ptr(self.d_raw), self.P, s.B, self.N, st)
+        else:
+            u_f, ts_f, Nf = pdf
+            _launch("nerf_amd_volume_render_masked_mse_backward_pdf", *args, u_f, ptr(self.rgb), ptr(self.d_raw), ts_f,
+                    self.P, s.B, self.N, Nf, st)
+
+    def encoder_rows(self, ss):
+        _launch("nerf_amd_encode_points_bf16", _lib.ptr(self.pts), _lib.ptr(self.posx), _lib.ptr(self.posd), self.P, ss)
+
+
 class GraphedTrainStep:
     """``train_step`` (reference train.py:47-57) for the fused bf16 path with every buffer
     allocated once and the launches captured into hipGraphs that are replayed per iteration:
@@ -686,6 +856,10 @@ class GraphedTrainStep:
                  value, the gradient zero fill and the d_raw pack on a parallel branch
                  (9 kernel nodes, all through the C ABI: no torch kernels, no memset node)
         graph B: Adam over the flat parameter vector -> re-pack the two MFMA weight images (one kernel)
+
+    This class holds the ONE launch sequence of graph A (``_forward_backward``) over ``passes``, the
+    network passes of an iteration; its subclasses choose the passes -- one or two (coarse and fine), each dense (B x N
+    samples) or masked (the live samples of an occupancy grid on a fixed capacity) -- and add their own bookkeeping.
 
     With a process group of more than one replica the flat gradient vector is averaged between graph A and graph B:
 
@@ -738,6 +912,10 @@ class GraphedTrainStep:
     (NaN / inf weights or inputs: a diverged run) -- the reference would show a NaN loss there.
     """
 
+    _samples = None              # samples per ray of each pass; None: the one pass of N samples
+    _capacities = None           # point capacity of each pass (masked passes through ``occupancy``); None: dense passes
+    _one_bucket = False          # the two-bucket exchange exists for the dense single step only
+
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
                  device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16"):
         from . import parallel
@@ -767,15 +945,16 @@ class GraphedTrainStep:
             if int(table.shape[0]) < self.B:
                 raise RuntimeError(f"a batch of {self.B} rays from a table of {int(table.shape[0])}")
         lib = _lib.lib()
-        B, N_, P = self.B, self.N, self.B * self.N
+        B = self.B
         f32 = dict(dtype=torch.float32, device=dev)
         self.rays = torch.zeros((B, 6), **f32)
         self.rays[:, 5] = -1.0                      # a valid direction: the capture warm-up runs on these buffers
         self.gt = torch.zeros((B, 3), **f32)
-        self.u = torch.zeros((B, N_), **f32)
-        self._alloc_pass_buffers(tn, tf)
+        self.u = torch.zeros((B, self.N), **f32)
         self.grads = torch.zeros(optimizer.flat.numel(), **f32)
         self.loss = torch.zeros((), **f32)
+        self.hyper = torch.zeros(8, **f32)                 # [lr, b1, b2, eps, 1-b1^t, sqrt(1-b2^t), seed offset (int64)]
+        self._alloc_pass_buffers(tn, tf)
         self._ids_next = torch.zeros((B,), dtype=torch.int64, device=dev)      # rays_from: rows of the table (see ray_ids)
         self._ids_cur, self._ids_step, self._primed_for = torch.zeros_like(self._ids_next), -1, -1
         self._select_ws = torch.empty(max(int(lib.nerf_amd_select_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
@@ -786,7 +965,6 @@ class GraphedTrainStep:
         for b in (1, 2):
             _lib.check(lib.nerf_amd_grad_bucket_range(b, ctypes.byref(first), ctypes.byref(count)), "nerf_amd_grad_bucket_range")
             self.buckets.append(self.grads[first.value:first.value + count.value])
-        self.hyper = torch.zeros(8, **f32)                 # [lr, b1, b2, eps, 1-b1^t, sqrt(1-b2^t), seed offset (int64)]
         self._ring = _HyperRing(dev)
         self._side = torch.cuda.Stream(dev)
         # parameters' .grad are views of the flat gradient vector, as after the eager fused backward
@@ -805,104 +983,113 @@ class GraphedTrainStep:
             raise RuntimeError("the optimizer belongs to another module")
         _check_fused_trainable(net.precision)
 
+    @property
+    def _seed_mem(self):
+        """The address of this step's seed offset inside the hyper vector (int64 at float slot 6): what a launch with
+        NERF_AMD_SEED_IN_MEMORY takes in place of its jitter tensor, and nerf_amd_select_rays as its step counter."""
+        import ctypes
+        return ctypes.c_void_p(self.hyper.data_ptr() + 24)
+
     def _alloc_pass_buffers(self, tn, tf):
-        """The buffers of the one forward / backward pass: sample bins, raw / ts, saved activations, encoder rows, d_raw."""
+        """``passes`` with their buffers, each pass's module, gradient slice, loss slot and jitter arguments.  A pair
+        (coarse, fine) shares ONE jitter draw: ``u`` [B, Nc+Nf] of the reference stream, whose first B*Nc values are
+        torch.rand(B,Nc) = ``u_c`` and the rest torch.rand(B,Nf) = ``u_f`` -- the same numbers as the two draws in a row."""
         from .utils.rendering import _tbins
-        lib, dev = _lib.lib(), self.dev
-        B, N_, P = self.B, self.N, self.B * self.N
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.tbins = _tbins(tn, tf, N_, dev)
-        self._first_N, self._first_u = N_, self.u          # the stratified pass: what the range check looks at
-        self.raw = torch.empty((B, N_, 4), **f32)
-        self.ts = torch.empty((B, N_), **f32)
-        if self._e4m3:
-            self.acts = torch.empty(int(lib.nerf_amd_train_activation_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
-            self.dys = torch.empty(int(lib.nerf_amd_train_gradient_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
-            self.scratch8 = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_e4m3_bytes(P)), 16), dtype=torch.uint8, device=dev)
+        lib, dev, ptr, B = _lib.lib(), self.dev, _lib.ptr, self.B
+        samples = self._samples or (self.N,)
+        pair = len(samples) == 2
+        self.tbins = _tbins(tn, tf, samples[0], dev)
+        if self._capacities is not None:
+            from .utils.mesh import _host_f32x3
+            occ = self.occupancy
+            self._mark_ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+            self._counts = torch.zeros(2 * len(samples), dtype=torch.int64, device=dev)       # {live, kept} per pass
+            # the grid as the graph sees it: the words' address, the axes as HOST floats, the outside policy
+            self._grid = (tuple(occ.resolution), _host_f32x3(occ.lo), _host_f32x3(occ.inv_step),
+                          _lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
+            self.passes = [_MaskedPass(self, N_, C, self._counts[2 * k:2 * k + 2])
+                           for k, (N_, C) in enumerate(zip(samples, self._capacities))]
         else:
-            nb = int(lib.nerf_amd_train_activation_bytes(P))
-            self.acts = torch.empty(nb, dtype=torch.uint8, device=dev)
-            self.dys = torch.empty(nb, dtype=torch.uint8, device=dev)
-        self.posx = torch.empty((P, 64), dtype=torch.bfloat16, device=dev)
-        self.posd = torch.empty((P, 32), dtype=torch.bfloat16, device=dev)
-        self.rgb = torch.empty((B, 3), **f32)
-        self.d_raw = torch.empty((B, N_, 4), **f32)
-        self.scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8,
-                                   device=dev)
+            self.passes = [_DensePass(self, N_, self._e4m3) for N_ in samples]
+        # the stratified pass: the buffer, or the counter RNG with this step's seed offset read from device memory
+        if self.device_rng:
+            jitter = (ptr(self.rays), self._seed_mem, ptr(self.tbins), _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY,
+                      self.seed, self.ray_id0)
+        else:
+            jitter = (ptr(self.rays), ptr(self.u), ptr(self.tbins), 0, 0, 0)
+        self.passes[0].jitter = jitter
+        if pair:
+            Nc, Nf = samples[0], samples[1] - samples[0]
+            flat_u = self.u.view(-1)
+            self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, Nf)
+            self.losses = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.ts_f = torch.empty((B, samples[1]), dtype=torch.float32, device=dev)     # the coarse head's output:
+            self.passes[1].jitter = (ptr(self.rays), ptr(self.ts_f), None, _lib.FLAG_TS_GIVEN, 0, 0)   # the fine positions
+            self._pdf = (None if self.device_rng else ptr(self.u_f), ptr(self.ts_f), Nf)
+        off = 0
+        for k, (p, net) in enumerate(zip(self.passes, self.opt.nets or (self.net,))):
+            n = sum(q.numel() for q in net.parameters())
+            p.net, p.grads, p.loss = net, self.grads[off:off + n], self.losses[k] if pair else self.loss
+            off += n
+        if not pair:         # a single pass's buffers are the stepper's own attributes (bench.py, tools and tests read them)
+            for name in ("raw", "ts", "acts", "dys", "posx", "posd", "rgb", "d_raw", "scratch", "scratch8", "pts", "mask",
+                         "offsets"):
+                if hasattr(self.passes[0], name):
+                    setattr(self, name, getattr(self.passes[0], name))
 
     # ---- the two launch sequences --------------------------------------------------
     def _forward_backward(self, bucket=0):
-        """Main branch: forward -> compositing + MSE gradient + compositing backward -> dX chain -> dW (all products,
-        or with ``bucket`` = 1 only those of the late layers: _head_gradients adds the rest).
-        Side branch (ONE fork / join inside the captured graph, behind the compositor and beside the dX chain): the encoder
-        rows of the dW products, loss value, gradient-vector zero fill, d_raw pack, (8-bit form: the narrow operands'
-        conversion,) and the next step's batch selection."""
-        lib, B, N_, P = _lib.lib(), self.B, self.N, self.B * self.N
-        packed = self.net.packed_weights(_lib.BF16)
-        image = self.net.packed_weights(_lib.BF16_BWD)
-        ck, ptr = _lib.check, _lib.ptr
+        """The one forward / backward sequence of every graphed step:
+
+            hyper fetch -> per pass: forward -> head                                                     (main)
+            -> fork -> per pass: dX chain  ||  side: per pass encoder rows; per pass loss + dW begin;
+                                               [loss sum]; [the next batch's selection]
+            -> join -> per pass: dW finish (all products, or with ``bucket`` = 1 only those of the late layers:
+                                            _head_gradients adds the rest)
+
+        ONE fork / join inside the captured graph, behind the last head and beside the dX chains."""
         main = torch.cuda.current_stream(self.dev)
         side = self._side
         st, ss = ctypes_stream(main), ctypes_stream(side)
         # first node: this step's scalars (Adam's, the jitter seed offset) from the pinned host ring into `hyper`
         self._ring.fetch(self.hyper, self.dev)
-        if self.device_rng:
-            # counter RNG; `u` = the address of this step's seed offset inside the hyper vector (int64 at float slot 6)
-            import ctypes
-            jit = ctypes.c_void_p(self.hyper.data_ptr() + 24)
-            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
-        else:
-            jit, flags, seed, rid = ptr(self.u), 0, 0, 0
-        ck(lib.nerf_amd_mlp_forward_train(ptr(self.rays), jit, ptr(self.tbins), ptr(packed),
-                                          flags | (_lib.FLAG_STORE_E4M3 if self._e4m3 else 0), seed, rid,
-                                          ptr(self.raw), ptr(self.ts), ptr(self.acts), B, N_, st),
-           "nerf_amd_mlp_forward_train")
-        # only rgb feeds the loss (train.py:52): disparity, alpha, acc, w are not materialised
-        ck(lib.nerf_amd_volume_render_mse_backward(ptr(self.raw), ptr(self.ts), ptr(self.rays), ptr(self.gt), ptr(self.rgb),
-                                                   ptr(self.d_raw), B, N_, st), "nerf_amd_volume_render_mse_backward")
+        for p in self.passes[:-1]:
+            p.forward(st)
+            self._coarse_head(p, st)                # writes ts_f, which the next pass's forward (and mark) reads
+        self.passes[-1].forward(st)
+        self.passes[-1].head(st)
         fork = torch.cuda.Event()
-        fork.record(main)                           # behind the compositor: what the side branch needs (rgb, d_raw) is final
-        backward = lib.nerf_amd_mlp_backward_e4m3 if self._e4m3 else lib.nerf_amd_mlp_backward
-        ck(backward(ptr(self.d_raw), ptr(image), ptr(self.acts), ptr(self.dys), P, st), "nerf_amd_mlp_backward")
+        fork.record(main)                           # behind the last head: what the side branch needs (rgb, d_raw, ts_f, pts) is final
+        for p in self.passes:
+            p.dx_chain(st)
         side.wait_event(fork)
         # The side branch carries everything the dW products need besides dY -- and nothing else runs beside the forward:
         # a kernel enqueued next to a persistent kernel that fills every CU either delays its start (~10 us per branch at a
-        # replayed graph's root) or crawls beside it and slows the compositor behind it.  Order: the encoder rows read
-        # this step's rays and jitter, so they come before the selection overwrites the batch.
-        # same sample positions as the forward drew them: ts = f(jitter) bit for bit (the same flags / u / seed / tbins)
-        ck(lib.nerf_amd_sample_encode_bf16(ptr(self.rays), jit, ptr(self.tbins), flags, seed, rid,
-                                           ptr(self.posx), ptr(self.posd), None, B, N_, ss),
-           "nerf_amd_sample_encode_bf16")
-        if self._e4m3:       # the encoder rows in the products' 8-bit form
-            ck(lib.nerf_amd_param_gradients_convert_e4m3(ptr(self.posx), ptr(self.posd), None, ptr(self.scratch8), P, 1, ss),
-               "nerf_amd_param_gradients_convert_e4m3")
-        ck(lib.nerf_amd_mse_loss(ptr(self.rgb), ptr(self.gt), ptr(self.loss), None, B * 3, ss), "nerf_amd_mse_loss")
-        ck(lib.nerf_amd_param_gradients_begin(ptr(self.d_raw), ptr(self.scratch), ptr(self.grads), P, ss),
-           "nerf_amd_param_gradients_begin")
-        if self._e4m3:       # the packed d_raw likewise
-            ck(lib.nerf_amd_param_gradients_convert_e4m3(None, None, ptr(self.scratch), ptr(self.scratch8), P, 2, ss),
-               "nerf_amd_param_gradients_convert_e4m3")
+        # replayed graph's root) or crawls beside it and slows the compositor behind it.  Order: the encoder rows of a
+        # dense pass read this step's rays and jitter, so they come before the selection overwrites the batch.
+        for p in self.passes:
+            p.encoder_rows(ss)
+        for p in self.passes:
+            p.loss_and_begin(ss)
+        if len(self.passes) == 2:
+            with torch.cuda.stream(side):
+                torch.add(self.losses[0], self.losses[1], out=self.loss)       # the total, MSE(rgb_c) + MSE(rgb_f)
         if self.rays_from is not None and self.device_rng:
             # rg.select + the colour gather (train.py:47-49) for the NEXT step, beside the dX chain: this step's rays and
-            # colours have been read for the last time (encoder rows, forward, compositor, loss), and the selection depends
-            # on the step counter only (device memory: every replay selects the batch of step + 1), never on the weights --
-            # so the first lines of the next iteration cost the step nothing.  step() primes the first batch.
-            import ctypes
-            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
+            # colours have been read for the last time (forward or mark + emit, heads on the main branch in front of the
+            # fork; encoder rows and losses here), and the selection depends on the step counter only (device memory: every
+            # replay selects the batch of step + 1), never on the weights -- so the first lines of the next iteration cost
+            # the step nothing.  step() primes the first batch.
+            self.rays_from.launch(self.select_mode, self.B, None, self._select_seed(1), self._seed_mem,
                                   self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
         main.wait_stream(side)
-        self._finish(bucket, st)
+        for p in self.passes:
+            p.finish(bucket, st)
 
-    def _finish(self, bucket, st):
-        """The dW products (all, or one bucket's) from the saved tensors in this step's storage form."""
-        lib, ptr, P = _lib.lib(), _lib.ptr, self.B * self.N
-        if self._e4m3:
-            _lib.check(lib.nerf_amd_param_gradients_finish_e4m3(ptr(self.acts), ptr(self.dys), ptr(self.scratch8), ptr(self.grads),
-                                                                P, bucket, st), "nerf_amd_param_gradients_finish_e4m3")
-        else:
-            _lib.check(lib.nerf_amd_param_gradients_finish_bucket(ptr(self.acts), ptr(self.dys), ptr(self.posx), ptr(self.posd),
-                                                                  ptr(self.scratch), ptr(self.grads), P, bucket, st),
-                       "nerf_amd_param_gradients_finish_bucket")
+    def _coarse_head(self, c, st):
+        """rgb_c, d_raw_c and the fine positions ts_f from the coarse weights, which never reach HBM: one launch.
+        ``_pdf`` = (u_f, ts_f, Nf) as pointers; the coarse jitter arguments are ``c.jitter``."""
+        c.head(st, self._pdf)
 
     def _select_seed(self, offset=0):
         """The seed argument of nerf_amd_select_rays for the batch ``offset`` steps after the one the step counter in
@@ -930,7 +1117,8 @@ class GraphedTrainStep:
 
     def _head_gradients(self):
         """The second launch of the bucketed form: the products of layers_0.* (bucket 2)."""
-        self._finish(2, _lib.stream_ptr(self.dev))
+        for p in self.passes:
+            p.finish(2, _lib.stream_ptr(self.dev))
 
     def _update(self):
         lib, opt = _lib.lib(), self.opt
@@ -957,7 +1145,8 @@ class GraphedTrainStep:
             side.wait_stream(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(side):                       # warm-up outside capture (lazy inits)
                 self._forward_backward()
-                self._head_gradients()
+                if not self._one_bucket:
+                    self._head_gradients()
             torch.cuda.current_stream(self.dev).wait_stream(side)
             torch.cuda.synchronize(self.dev)
             self.graph_a = torch.cuda.CUDAGraph()
@@ -996,10 +1185,12 @@ class GraphedTrainStep:
             self._own_images_of(net, flat, bufs, force)
 
     def _bind_images(self):
-        """(module, its slice of the optimizer's flat vector, (forward image, backward image)) per trained module."""
-        self._packed_fwd = self.net.packed_weights(_lib.BF16)
-        self._packed_bwd = self.net.packed_weights(_lib.BF16_BWD)
-        self._images = [(self.net, self.opt.flat, (self._packed_fwd, self._packed_bwd))]
+        """(module, its slice of the optimizer's flat vector, (forward image, backward image)) per pass."""
+        self._images = []
+        for p, flat in zip(self.passes, self.opt.slices if self.opt.nets else (self.opt.flat,)):
+            p.fwd, p.bwd = p.net.packed_weights(_lib.BF16), p.net.packed_weights(_lib.BF16_BWD)
+            self._images.append((p.net, flat, (p.fwd, p.bwd)))
+        self._packed_fwd, self._packed_bwd = self._images[0][2]
 
     def _own_images_of(self, net, flat, bufs, force):
         from .utils.nets import _Packed
@@ -1140,12 +1331,9 @@ class GraphedTrainStep:
     def _range_check(self):
         """The reference's |x| > 1 warning on the stratified pass's first / last samples (the finer passes lie between)."""
         from .utils.xyz import range_check_rays
-        if self.device_rng:
-            import ctypes
-            range_check_rays(self.rays, ctypes.c_void_p(self.hyper.data_ptr() + 24), self.tbins,
-                             _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0, self._first_N)
-        else:
-            range_check_rays(self.rays, self._first_u, self.tbins, 0, 0, 0, self._first_N)
+        first = self.passes[0]
+        _, jit, _, flags, seed, rid = first.jitter
+        range_check_rays(self.rays, jit, self.tbins, flags, seed, rid, first.N)
 
     def reset_timing(self):
         """Forget the exchange events recorded so far (warm-up steps: the first collective creates the communicator)."""
@@ -1164,39 +1352,90 @@ class GraphedTrainStep:
         return span, exposed
 
 
-class _CountsWatch:
-    """Asynchronous read-back of the graphed masked step's ``counts`` (int64[2] = {live, kept}), after _StatusWatch: ``push``
-    enqueues a 16-byte copy into pinned memory behind graph A, ``poll`` hands back the copies that have completed, oldest
-    first, as (step, live, kept) -- no host wait."""
+class _MaskedSteps:
+    """What the two masked steppers share (listed in front of their stepper base): the refusals, the grid and the capacities,
+    and the overflow report -- ``counts`` on the device is int64 {live, kept} per pass, copied back every ``check_every``
+    steps without waiting."""
 
-    def __init__(self, slots=4, width=2):
-        self.bufs = [torch.zeros(width, dtype=torch.int64).pin_memory() for _ in range(slots)]
-        self.pending = []                       # (event, slot, step)
-        self.k = 0
+    _one_bucket = True
 
-    def push(self, counts, step):
-        if len(self.pending) >= len(self.bufs):
-            return                              # every slot still in flight: skip this sample
-        slot = self.k % len(self.bufs)
-        self.k += 1
-        self.bufs[slot].copy_(counts, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(counts.device))
-        self.pending.append((ev, slot, step))
+    def _refuse(self, storage, buckets):
+        name = type(self).__name__
+        if storage != "bf16":
+            raise ValueError(f"{name} keeps its operands in bf16: storage={storage!r} is not supported")
+        if buckets != 1:
+            raise ValueError(f"{name} exchanges its gradients in one bucket: buckets must be 1")
 
-    def poll(self, wait=False):
-        done = []
-        while self.pending and (wait or self.pending[0][0].query()):
-            ev, slot, step = self.pending.pop(0)
-            if wait:
-                ev.synchronize()
-            done.append((step, *(int(v) for v in self.bufs[slot])))
-        return done
+    def _bind_grid(self, nets, samples, B, optimizer, occupancy, capacity):
+        """Checks the modules, the grid and the capacity argument (one value, or a pair (C_c, C_f) for two passes) in this
+        order and, if nothing raised, keeps them."""
+        from .utils import occupancy as occ_mod
+        for net, N_ in zip(nets, samples):
+            occ_mod.check_trainable(occupancy, net, torch.empty(0), N_)
+        self._check_modules(nets[0] if len(nets) == 1 else nets, optimizer)
+        if len(nets) == 1:
+            self._capacities = (_capacity_points(capacity, B * samples[0], "capacity"),)
+        else:
+            if isinstance(capacity, (str, bytes)) or not hasattr(capacity, "__len__") or len(capacity) != 2:
+                raise TypeError("capacity must be a pair (C_c, C_f), each an int (points) or a float (fraction of the pass's samples)")
+            self._capacities = tuple(_capacity_points(c, B * N_, f"the {w} capacity")
+                                     for c, N_, w in zip(capacity, samples, ("coarse", "fine")))
+        if occupancy.words.device != optimizer.flat.device:
+            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the module on {optimizer.flat.device}")
+        self.occupancy = occupancy
+        self._words_ptr = occupancy.words.data_ptr()
+        self._counts_watch = _CountsWatch(width=2 * len(nets))
+        self.last_stats, self.overflow_steps = None, 0
+
+    def _range_check(self):
+        """Runs behind graph A on every ``check_every``-th step: the reference's |x| > 1 warning on the points the networks
+        were asked about (the pad point is in range), and the copy of ``counts`` the overflow report reads."""
+        from .utils.xyz import range_check_values
+        for p in self.passes:
+            range_check_values(p.pts)
+        self._counts_watch.push(self._counts, self.opt.step_count)
+
+    def _stats(self, step, values):
+        per = [{"samples": self.B * p.N, "live": values[2 * k], "kept": values[2 * k + 1], "capacity": p.P}
+               for k, p in enumerate(self.passes)]
+        return {"step": step, **per[0]} if len(per) == 1 else {"step": step, "coarse": per[0], "fine": per[1]}
+
+    def _note(self, done, stacklevel):
+        import warnings
+        for step, *values in done:
+            self.last_stats = s = self._stats(step, values)
+            per = {None: s} if "live" in s else {name: s[name] for name in ("coarse", "fine")}
+            over = {name: q for name, q in per.items() if q["live"] > q["capacity"]}
+            if not over:
+                continue
+            self.overflow_steps += 1
+            if None in over:
+                what = (f"step {step} had {s['live']} live samples for a capacity of {s['capacity']} points; the last "
+                        f"{s['live'] - s['kept']} (ray-major order) were treated as dead")
+            else:
+                what = f"step {step}: " + "; ".join(
+                    f"the {name} pass had {q['live']} live samples for a capacity of {q['capacity']} points, the last "
+                    f"{q['live'] - q['kept']} (ray-major order) were treated as dead" for name, q in over.items())
+            warnings.warn(f"{type(self).__name__}: {what}.  Build a stepper with a larger capacity.", RuntimeWarning,
+                          stacklevel=stacklevel)
+
+    def counts(self):
+        """The report of the latest step in the shape of ``last_stats``, read now (synchronises); pending reports are
+        delivered first."""
+        self._note(self._counts_watch.poll(wait=True), 3)
+        return self._stats(self.opt.step_count, [int(v) for v in self._counts.cpu()])
+
+    def _watch_grid(self):
+        """First thing in ``step``: the grid is still the captured one; completed overflow reports are delivered."""
+        if self.occupancy.words.data_ptr() != self._words_ptr:
+            raise RuntimeError("the occupancy grid's words tensor was replaced: its address is baked into the captured graph "
+                               f"(TrainingOccupancyGrid.update writes in place); build a new {type(self).__name__}")
+        self._note(self._counts_watch.poll(), 4)
 
 
-class GraphedMaskedTrainStep(GraphedTrainStep):
-    """``train_step(..., occupancy=)`` as captured hipGraphs, on GraphedTrainStep's machinery (hyper
-    ring, status watch, ``rays_from`` selection, exchange, capture) -- DESIGN.md section 14.  The live count P' of a batch
+class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
+    """``train_step(..., occupancy=)`` as captured hipGraphs: GraphedTrainStep with its one pass
+    masked -- DESIGN.md section 14.  The live count P' of a batch
     never reaches the host on the step's path: the graph is captured for a fixed point ``capacity`` C (an int number of
     points, or a float fraction of n_rays * N; NO default -- what is safe depends on the scene and the grid), every network
     kernel runs on exactly C points, and the rows no live sample owns are inert (include/nerf_amd.h: pad points in,
@@ -1205,8 +1444,7 @@ class GraphedMaskedTrainStep(GraphedTrainStep):
         graph A: hyper fetch -> mark + scan (nerf_amd_occupancy_mark) -> capped emit (nerf_amd_occupancy_points_capped:
                  pts[C, 6], counts) -> training forward on the C points -> masked head (compositor + MSE gradient +
                  compositor backward, ONE kernel: nerf_amd_volume_render_masked_mse_backward) -> dX chain -> dW products;
-                 the encoder rows, the loss value, the zero fill / d_raw pack and (``rays_from`` with ``device_rng``) the
-                 next batch's selection on the one side branch beside the dX chain
+                 the side branch beside the dX chain is GraphedTrainStep's
         graph B and the all-reduce seam: GraphedTrainStep's, unchanged (one exchange bucket).
 
     With P' <= C the step is the eager masked step.  With P' > C (an overflow) the live samples of global rank >= C -- the
@@ -1223,158 +1461,32 @@ class GraphedMaskedTrainStep(GraphedTrainStep):
 
     def __init__(self, net, optimizer, n_rays, N, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
                  ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
-        from .utils import occupancy as occ_mod
-        if storage != "bf16":
-            raise ValueError(f"GraphedMaskedTrainStep keeps its operands in bf16: storage={storage!r} is not supported")
-        if buckets != 1:
-            raise ValueError("GraphedMaskedTrainStep exchanges its gradients in one bucket: buckets must be 1")
+        self._refuse(storage, buckets)
         B, N_ = int(n_rays), int(N)
         if B < 1 or N_ < 1:
             raise ValueError(f"GraphedMaskedTrainStep needs n_rays >= 1 and N >= 1 (got {n_rays}, {N})")
-        occ_mod.check_trainable(occupancy, net, torch.empty(0), N_)
-        self._check_modules(net, optimizer)
-        import math
-        import numbers
-        if isinstance(capacity, bool) or not isinstance(capacity, numbers.Real):
-            raise TypeError("capacity must be an int (points) or a float (fraction of n_rays * N)")
-        if isinstance(capacity, numbers.Integral):
-            C = int(capacity)
-        else:
-            if not 0.0 < capacity <= 1.0:
-                raise ValueError(f"a fractional capacity must lie in (0, 1], got {capacity!r}")
-            C = max(1, math.ceil(float(capacity) * B * N_))
-        if not 1 <= C <= B * N_:
-            raise ValueError(f"capacity must lie in [1, n_rays * N = {B * N_}] points, got {C}")
-        if occupancy.words.device != optimizer.flat.device:
-            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the module on {optimizer.flat.device}")
-        self.occupancy, self.capacity = occupancy, int(C)
-        self._words_ptr = occupancy.words.data_ptr()
-        self._counts_watch = _CountsWatch()
-        self.last_stats, self.overflow_steps = None, 0
+        self._bind_grid((net,), (N_,), B, optimizer, occupancy, capacity)
+        self.capacity = self._capacities[0]
         super().__init__(net, optimizer, B, N_, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed, ray_id0=ray_id0,
                          check_every=check_every, rays_from=rays_from, select_mode=select_mode)
 
-    def _alloc_pass_buffers(self, tn, tf):
-        from .utils.mesh import _host_f32x3
-        from .utils.rendering import _tbins
-        lib, dev, occ = _lib.lib(), self.dev, self.occupancy
-        B, N_, C = self.B, self.N, self.capacity
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.tbins = _tbins(tn, tf, N_, dev)
-        self.mask = torch.zeros((B, (N_ + 63) // 64), dtype=torch.int64, device=dev)
-        self.offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-        self._mark_ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
-        self._counts = torch.zeros(2, dtype=torch.int64, device=dev)
-        # the grid as the graph sees it: the words' address, the axes as HOST floats, the outside policy
-        self._grid = (tuple(occ.resolution), _host_f32x3(occ.lo), _host_f32x3(occ.inv_step),
-                      _lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-        self.pts = torch.empty((C, 6), **f32)
-        self.raw = torch.empty((C, 4), **f32)
-        nb = int(lib.nerf_amd_train_activation_bytes(C))
-        self.acts = torch.empty(nb, dtype=torch.uint8, device=dev)
-        self.dys = torch.empty(nb, dtype=torch.uint8, device=dev)
-        self.posx = torch.empty((C, 64), dtype=torch.bfloat16, device=dev)
-        self.posd = torch.empty((C, 32), dtype=torch.bfloat16, device=dev)
-        self.rgb = torch.empty((B, 3), **f32)
-        self.d_raw = torch.empty((C, 4), **f32)
-        self.scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(C)), 16), dtype=torch.uint8, device=dev)
-
-    def _forward_backward(self, bucket=0):
-        import ctypes
-        lib, B, N_, C = _lib.lib(), self.B, self.N, self.capacity
-        packed = self.net.packed_weights(_lib.BF16)
-        image = self.net.packed_weights(_lib.BF16_BWD)
-        ck, ptr = _lib.check, _lib.ptr
-        main = torch.cuda.current_stream(self.dev)
-        side = self._side
-        st, ss = ctypes_stream(main), ctypes_stream(side)
-        self._ring.fetch(self.hyper, self.dev)
-        if self.device_rng:
-            jit = ctypes.c_void_p(self.hyper.data_ptr() + 24)
-            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
-        else:
-            jit, flags, seed, rid = ptr(self.u), 0, 0, 0
-        R, lo, inv, outside = self._grid
-        head = (ptr(self.rays), jit, ptr(self.tbins))
-        ck(lib.nerf_amd_occupancy_mark(*head, flags | outside, seed, rid, ctypes.c_void_p(self._words_ptr), *R, lo, inv,
-                                       ptr(self.mask), ptr(self.offsets), None, ptr(self._mark_ws), B, N_, st),
-           "nerf_amd_occupancy_mark")
-        ck(lib.nerf_amd_occupancy_points_capped(*head, flags, seed, rid, ptr(self.mask), ptr(self.offsets), ptr(self.pts),
-                                                ptr(self._counts), C, B, N_, st), "nerf_amd_occupancy_points_capped")
-        ck(lib.nerf_amd_mlp_forward_train_points(ptr(self.pts), ptr(packed), ptr(self.raw), ptr(self.acts), C, st),
-           "nerf_amd_mlp_forward_train_points")
-        ck(lib.nerf_amd_volume_render_masked_mse_backward(ptr(self.raw), *head, flags, seed, rid, ptr(self.mask), ptr(self.offsets),
-                                                          ptr(self.gt), ptr(self.rgb), ptr(self.d_raw), C, B, N_, st),
-           "nerf_amd_volume_render_masked_mse_backward")
-        fork = torch.cuda.Event()
-        fork.record(main)                           # behind the head: rgb, d_raw (and pts) are final
-        ck(lib.nerf_amd_mlp_backward(ptr(self.d_raw), ptr(image), ptr(self.acts), ptr(self.dys), C, st), "nerf_amd_mlp_backward")
-        side.wait_event(fork)
-        # the side branch as GraphedTrainStep's: what the dW products need besides dY, then the next batch (rays and gt
-        # have been read for the last time: mark, emit, head on the main branch in front of the fork, the loss here)
-        ck(lib.nerf_amd_encode_points_bf16(ptr(self.pts), ptr(self.posx), ptr(self.posd), C, ss), "nerf_amd_encode_points_bf16")
-        ck(lib.nerf_amd_mse_loss(ptr(self.rgb), ptr(self.gt), ptr(self.loss), None, B * 3, ss), "nerf_amd_mse_loss")
-        ck(lib.nerf_amd_param_gradients_begin(ptr(self.d_raw), ptr(self.scratch), ptr(self.grads), C, ss),
-           "nerf_amd_param_gradients_begin")
-        if self.rays_from is not None and self.device_rng:
-            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
-                                  self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
-        main.wait_stream(side)
-        self._finish(bucket, st)
-
-    def _finish(self, bucket, st):
-        lib, ptr, C = _lib.lib(), _lib.ptr, self.capacity
-        _lib.check(lib.nerf_amd_param_gradients_finish_bucket(ptr(self.acts), ptr(self.dys), ptr(self.posx), ptr(self.posd),
-                                                              ptr(self.scratch), ptr(self.grads), C, bucket, st),
-                   "nerf_amd_param_gradients_finish_bucket")
-
-    def _head_gradients(self):
-        pass                                         # one exchange bucket: graph A forms every product
-
-    def _range_check(self):
-        """Runs behind graph A on every ``check_every``-th step: the reference's |x| > 1 warning on the points the network
-        was asked about (the pad point is in range), and the copy of ``counts`` the overflow report reads."""
-        from .utils.xyz import range_check_values
-        range_check_values(self.pts)
-        self._counts_watch.push(self._counts, self.opt.step_count)
-
-    def _note(self, done):
-        import warnings
-        for step, live, kept in done:
-            self.last_stats = {"step": step, "samples": self.B * self.N, "live": live, "kept": kept, "capacity": self.capacity}
-            if live > self.capacity:
-                self.overflow_steps += 1
-                warnings.warn(f"GraphedMaskedTrainStep: step {step} had {live} live samples for a capacity of {self.capacity} "
-                              f"points; the last {live - kept} (ray-major order) were treated as dead.  Build a stepper with "
-                              "a larger capacity.", RuntimeWarning, stacklevel=3)
-
-    def counts(self):
-        """{'step', 'samples', 'live', 'kept', 'capacity'} of the latest step, read now (synchronises); pending reports
-        are delivered first."""
-        self._note(self._counts_watch.poll(wait=True))
-        live, kept = (int(v) for v in self._counts.cpu())
-        return {"step": self.opt.step_count, "samples": self.B * self.N, "live": live, "kept": kept, "capacity": self.capacity}
-
     def step(self, rays=None, gt=None, u=None, decay=1.0):
-        if self.occupancy.words.data_ptr() != self._words_ptr:
-            raise RuntimeError("the occupancy grid's words tensor was replaced: its address is baked into the captured graph "
-                               "(TrainingOccupancyGrid.update writes in place); build a new GraphedMaskedTrainStep")
-        self._note(self._counts_watch.poll())
+        self._watch_grid()
         return super().step(rays, gt, u=u, decay=decay)
 
     __call__ = step
 
 
 class GraphedHierarchicalTrainStep(GraphedTrainStep):
-    """``train_step_hierarchical`` for the fused bf16 path as captured hipGraphs, on GraphedTrainStep's machinery (hyper
-    ring, status watch, ``rays_from`` selection in both jitter modes, exchange, capture):
+    """``train_step_hierarchical`` for the fused bf16 path as captured hipGraphs: GraphedTrainStep with two dense passes,
+    coarse and fine (hyper ring, status watch, ``rays_from`` selection in both jitter modes, exchange, capture: inherited):
 
         graph A: hyper fetch -> coarse training forward (Nc stratified samples) -> coarse head (compositor + MSE gradient
                  + compositor backward + sample_pdf on the coarse weights, ONE kernel:
                  nerf_amd_volume_render_mse_backward_pdf, writes ts_f) -> fine training forward on ts_f (Nc+Nf samples,
                  NERF_AMD_TS_GIVEN) -> fine compositor + MSE gradient + backward -> both dX chains -> both sets of dW
-                 products into ONE combined gradient vector (coarse first, the optimizer's order); the encoder rows, the two
-                 loss values, the zero fill and both d_raw packs on the single side branch
+                 products into ONE combined gradient vector (coarse first, the optimizer's order); GraphedTrainStep's side
+                 branch with both passes' launches and the sum of the two loss values on it
         graph B: one Adam launch over both networks' flat vector -> re-pack of both networks' training images
 
     ``optimizer`` must be ``optim.FusedAdam([net_c, net_f])``.  Jitter as in GraphedTrainStep: default the reference-style
@@ -1384,12 +1496,15 @@ class GraphedHierarchicalTrainStep(GraphedTrainStep):
     ``losses`` holds [coarse, fine]; ``net_c`` / ``net_f`` are the two modules, ``net`` = ``nets`` the pair (as
     ``FusedAdam([net_c, net_f]).net``).  bf16 storage, one exchange bucket."""
 
+    _one_bucket = True
+
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc=64, Nf=128, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
                  ray_id0=0, check_every=16, rays_from=None, select_mode="train"):
         _check_pair(net_c, net_f, Nc, Nf, None)
         self.net_c, self.net_f, self.Nc, self.Nf = net_c, net_f, int(Nc), int(Nf)
         # ``net`` / ``nets`` are the pair, as FusedAdam([net_c, net_f]).net / .nets hold it
         self.nets = (net_c, net_f)
+        self._samples = (self.Nc, self.Nc + self.Nf)
         super().__init__(self.nets, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng,
                          seed=seed, ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
 
@@ -1400,96 +1515,6 @@ class GraphedHierarchicalTrainStep(GraphedTrainStep):
         if optimizer.nets is None or len(optimizer.nets) != 2 or optimizer.nets[0] is not net[0] or optimizer.nets[1] is not net[1]:
             raise RuntimeError("the optimizer is not FusedAdam([net_c, net_f]) of this pair")
         _check_fused_trainable(net[0].precision)
-
-    def _alloc_pass_buffers(self, tn, tf):
-        from .utils.rendering import _tbins
-        lib, dev = _lib.lib(), self.dev
-        B, Nc, M = self.B, self.Nc, self.Nc + self.Nf
-        f32 = dict(dtype=torch.float32, device=dev)
-        # self.u [B, Nc+Nf] is ONE draw of the reference stream: its first B*Nc values are torch.rand(B,Nc), the rest
-        # torch.rand(B,Nf) -- the same numbers as the two draws in a row
-        flat_u = self.u.view(-1)
-        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, self.Nf)
-        self.tbins = _tbins(tn, tf, Nc, dev)
-        self._first_N, self._first_u = Nc, self.u_c
-        self.losses = torch.zeros(2, **f32)
-        self.passes = []
-        for N_ in (Nc, M):
-            P = B * N_
-            nb = int(lib.nerf_amd_train_activation_bytes(P))
-            self.passes.append(dict(
-                N=N_, P=P, raw=torch.empty((B, N_, 4), **f32), ts=torch.empty((B, N_), **f32),
-                acts=torch.empty(nb, dtype=torch.uint8, device=dev), dys=torch.empty(nb, dtype=torch.uint8, device=dev),
-                posx=torch.empty((P, 64), dtype=torch.bfloat16, device=dev), posd=torch.empty((P, 32), dtype=torch.bfloat16, device=dev),
-                rgb=torch.empty((B, 3), **f32), d_raw=torch.empty((B, N_, 4), **f32),
-                scratch=torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8, device=dev)))
-        self.ts_f = torch.empty((B, M), **f32)          # the coarse head's output: the fine pass's positions
-
-    def _bind_images(self):
-        n = self.opt.slices
-        self._images = [(m, sl, (m.packed_weights(_lib.BF16), m.packed_weights(_lib.BF16_BWD)))
-                        for m, sl in zip((self.net_c, self.net_f), n)]
-        self._packed_fwd, self._packed_bwd = self._images[0][2]
-
-    def _forward_backward(self, bucket=0):
-        lib, B, Nc, Nf = _lib.lib(), self.B, self.Nc, self.Nf
-        ck, ptr = _lib.check, _lib.ptr
-        c, f = self.passes
-        (_, _, (fwd_c, bwd_c)), (_, _, (fwd_f, bwd_f)) = self._images
-        main = torch.cuda.current_stream(self.dev)
-        side = self._side
-        st, ss = ctypes_stream(main), ctypes_stream(side)
-        self._ring.fetch(self.hyper, self.dev)
-        if self.device_rng:
-            import ctypes
-            jit_c = jit_f = ctypes.c_void_p(self.hyper.data_ptr() + 24)
-            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
-        else:
-            jit_c, jit_f, flags, seed, rid = ptr(self.u_c), ptr(self.u_f), 0, 0, 0
-        ck(lib.nerf_amd_mlp_forward_train(ptr(self.rays), jit_c, ptr(self.tbins), ptr(fwd_c), flags, seed, rid,
-                                          ptr(c["raw"]), ptr(c["ts"]), ptr(c["acts"]), B, Nc, st), "nerf_amd_mlp_forward_train")
-        self._coarse_head(c, jit_f, flags, seed, rid, st)
-        ck(lib.nerf_amd_mlp_forward_train(ptr(self.rays), ptr(self.ts_f), None, ptr(fwd_f), _lib.FLAG_TS_GIVEN, 0, 0,
-                                          ptr(f["raw"]), ptr(f["ts"]), ptr(f["acts"]), B, Nc + Nf, st), "nerf_amd_mlp_forward_train")
-        ck(lib.nerf_amd_volume_render_mse_backward(ptr(f["raw"]), ptr(f["ts"]), ptr(self.rays), ptr(self.gt), ptr(f["rgb"]),
-                                                   ptr(f["d_raw"]), B, Nc + Nf, st), "nerf_amd_volume_render_mse_backward")
-        fork = torch.cuda.Event()
-        fork.record(main)                           # both heads done: rgb / d_raw of both passes and ts_f are final
-        for p, image in ((c, bwd_c), (f, bwd_f)):
-            ck(lib.nerf_amd_mlp_backward(ptr(p["d_raw"]), ptr(image), ptr(p["acts"]), ptr(p["dys"]), p["P"], st),
-               "nerf_amd_mlp_backward")
-        side.wait_event(fork)
-        n = self.opt.slices[0].numel()
-        grads = (self.grads[:n], self.grads[n:])
-        ck(lib.nerf_amd_sample_encode_bf16(ptr(self.rays), jit_c, ptr(self.tbins), flags, seed, rid,
-                                           ptr(c["posx"]), ptr(c["posd"]), None, B, Nc, ss), "nerf_amd_sample_encode_bf16")
-        ck(lib.nerf_amd_sample_encode_bf16(ptr(self.rays), ptr(self.ts_f), None, _lib.FLAG_TS_GIVEN, 0, 0,
-                                           ptr(f["posx"]), ptr(f["posd"]), None, B, Nc + Nf, ss), "nerf_amd_sample_encode_bf16")
-        for k, (p, g) in enumerate(zip((c, f), grads)):
-            ck(lib.nerf_amd_mse_loss(ptr(p["rgb"]), ptr(self.gt), ptr(self.losses[k]), None, B * 3, ss), "nerf_amd_mse_loss")
-            ck(lib.nerf_amd_param_gradients_begin(ptr(p["d_raw"]), ptr(p["scratch"]), ptr(g), p["P"], ss),
-               "nerf_amd_param_gradients_begin")
-        with torch.cuda.stream(side):
-            torch.add(self.losses[0], self.losses[1], out=self.loss)       # the total, MSE(rgb_c) + MSE(rgb_f)
-        if self.rays_from is not None and self.device_rng:
-            import ctypes        # the next step's batch, beside the dX chains (GraphedTrainStep._forward_backward)
-            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
-                                  self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
-        main.wait_stream(side)
-        for p, g in zip((c, f), grads):
-            ck(lib.nerf_amd_param_gradients_finish_bucket(ptr(p["acts"]), ptr(p["dys"]), ptr(p["posx"]), ptr(p["posd"]),
-                                                          ptr(p["scratch"]), ptr(g), p["P"], 0, st),
-               "nerf_amd_param_gradients_finish_bucket")
-
-    def _coarse_head(self, c, jit_f, flags, seed, rid, st):
-        """rgb_c, d_raw_c and the fine positions ts_f from the coarse weights, which never reach HBM: one launch."""
-        _lib.check(_lib.lib().nerf_amd_volume_render_mse_backward_pdf(
-            _lib.ptr(c["raw"]), _lib.ptr(c["ts"]), _lib.ptr(self.rays), _lib.ptr(self.gt), jit_f, flags, seed, rid,
-            _lib.ptr(c["rgb"]), _lib.ptr(c["d_raw"]), _lib.ptr(self.ts_f), self.B, self.Nc, self.Nf, st),
-            "nerf_amd_volume_render_mse_backward_pdf")
-
-    def _head_gradients(self):
-        pass                                         # one exchange bucket: graph A forms every product
 
     def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
         if (u_c is None) != (u_f is None):
@@ -1509,25 +1534,7 @@ class GraphedHierarchicalTrainStep(GraphedTrainStep):
     __call__ = step
 
 
-def _capacity_points(capacity, total, what):
-    """A capacity argument as points: an int is a number of points, a float a fraction of ``total`` (GraphedMaskedTrainStep's
-    rule).  ``what`` names the argument in the messages."""
-    import math
-    import numbers
-    if isinstance(capacity, bool) or not isinstance(capacity, numbers.Real):
-        raise TypeError(f"{what} must be an int (points) or a float (fraction of the pass's samples)")
-    if isinstance(capacity, numbers.Integral):
-        C = int(capacity)
-    else:
-        if not 0.0 < capacity <= 1.0:
-            raise ValueError(f"a fractional {what} must lie in (0, 1], got {capacity!r}")
-        C = max(1, math.ceil(float(capacity) * total))
-    if not 1 <= C <= total:
-        raise ValueError(f"{what} must lie in [1, {total}] points, got {C}")
-    return C
-
-
-class GraphedMaskedHierarchicalTrainStep(GraphedHierarchicalTrainStep):
+class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainStep):
     """``train_step_hierarchical(..., occupancy=)`` as captured hipGraphs: GraphedHierarchicalTrainStep's
     pair (one FusedAdam([net_c, net_f]), one combined gradient vector, the ``u_c`` / ``u_f`` jitter) with each pass run as
     GraphedMaskedTrainStep runs its one -- on a fixed point capacity, the live counts never reaching the host.
@@ -1536,9 +1543,8 @@ class GraphedMaskedHierarchicalTrainStep(GraphedHierarchicalTrainStep):
                  -> masked coarse head (masked compositor + MSE gradient + backward + sample_pdf on its weights, ONE kernel:
                  nerf_amd_volume_render_masked_mse_backward_pdf, writes ts_f) -> mark + scan with NERF_AMD_TS_GIVEN on ts_f
                  -> capped emit (C_f points) -> fine training forward -> fused masked head (NERF_AMD_TS_GIVEN) -> both dX
-                 chains -> both sets of dW products into the combined gradient vector, coarse first; both encoder-row
-                 launches, the two loss values and their sum, both zero fills / d_raw packs and (``rays_from`` with
-                 ``device_rng``) the next batch's selection on the one side branch beside the dX chains
+                 chains -> both sets of dW products into the combined gradient vector, coarse first; the side branch as
+                 GraphedHierarchicalTrainStep's
         graph B and the all-reduce seam: inherited (one exchange bucket; ``group`` is handed through unchanged).
 
     ``capacity`` = (C_c, C_f): each an int (points) or a float (fraction of n_rays * Nc, of n_rays * (Nc + Nf)); NO default.
@@ -1555,161 +1561,18 @@ class GraphedMaskedHierarchicalTrainStep(GraphedHierarchicalTrainStep):
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc, Nf, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
                  seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
-        from .utils import occupancy as occ_mod
-        name = type(self).__name__
-        if storage != "bf16":
-            raise ValueError(f"{name} keeps its operands in bf16: storage={storage!r} is not supported")
-        if buckets != 1:
-            raise ValueError(f"{name} exchanges its gradients in one bucket: buckets must be 1")
+        self._refuse(storage, buckets)
         _check_pair(net_c, net_f, Nc, Nf, None)
         B, Nc_, Nf_ = int(n_rays), int(Nc), int(Nf)
         if B < 1:
-            raise ValueError(f"{name} needs n_rays >= 1 (got {n_rays})")
-        occ_mod.check_trainable(occupancy, net_c, torch.empty(0), Nc_)
-        occ_mod.check_trainable(occupancy, net_f, torch.empty(0), Nc_ + Nf_)
-        self._check_modules((net_c, net_f), optimizer)
-        if isinstance(capacity, (str, bytes)) or not hasattr(capacity, "__len__") or len(capacity) != 2:
-            raise TypeError("capacity must be a pair (C_c, C_f), each an int (points) or a float (fraction of the pass's samples)")
-        self.capacity = (_capacity_points(capacity[0], B * Nc_, "the coarse capacity"),
-                         _capacity_points(capacity[1], B * (Nc_ + Nf_), "the fine capacity"))
-        if occupancy.words.device != optimizer.flat.device:
-            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the module on {optimizer.flat.device}")
-        self.occupancy = occupancy
-        self._words_ptr = occupancy.words.data_ptr()
-        self._counts_watch = _CountsWatch(width=4)
-        self.last_stats, self.overflow_steps = None, 0
+            raise ValueError(f"{type(self).__name__} needs n_rays >= 1 (got {n_rays})")
+        self._bind_grid((net_c, net_f), (Nc_, Nc_ + Nf_), B, optimizer, occupancy, capacity)
+        self.capacity = self._capacities
         super().__init__(net_c, net_f, optimizer, B, Nc_, Nf_, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
                          ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
 
-    def _alloc_pass_buffers(self, tn, tf):
-        from .utils.mesh import _host_f32x3
-        from .utils.rendering import _tbins
-        lib, dev, occ = _lib.lib(), self.dev, self.occupancy
-        B, Nc, M = self.B, self.Nc, self.Nc + self.Nf
-        f32 = dict(dtype=torch.float32, device=dev)
-        flat_u = self.u.view(-1)                         # ONE draw [B, Nc+Nf]: rand(B,Nc) then rand(B,Nf), as the dense pair
-        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, self.Nf)
-        self.tbins = _tbins(tn, tf, Nc, dev)
-        self._first_N, self._first_u = Nc, self.u_c
-        self.losses = torch.zeros(2, **f32)
-        self._mark_ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
-        self._counts = torch.zeros(4, dtype=torch.int64, device=dev)
-        self._grid = (tuple(occ.resolution), _host_f32x3(occ.lo), _host_f32x3(occ.inv_step),
-                      _lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-        self.passes = []
-        for k, (N_, C) in enumerate(zip((Nc, M), self.capacity)):
-            nb = int(lib.nerf_amd_train_activation_bytes(C))
-            self.passes.append(dict(
-                N=N_, C=C, mask=torch.zeros((B, (N_ + 63) // 64), dtype=torch.int64, device=dev),
-                offsets=torch.zeros(B + 1, dtype=torch.int64, device=dev), counts=self._counts[2 * k:2 * k + 2],
-                pts=torch.empty((C, 6), **f32), raw=torch.empty((C, 4), **f32),
-                acts=torch.empty(nb, dtype=torch.uint8, device=dev), dys=torch.empty(nb, dtype=torch.uint8, device=dev),
-                posx=torch.empty((C, 64), dtype=torch.bfloat16, device=dev), posd=torch.empty((C, 32), dtype=torch.bfloat16, device=dev),
-                rgb=torch.empty((B, 3), **f32), d_raw=torch.empty((C, 4), **f32),
-                scratch=torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(C)), 16), dtype=torch.uint8, device=dev)))
-        self.ts_f = torch.empty((B, M), **f32)          # the masked coarse head's output: the fine pass's positions
-
-    def _forward_backward(self, bucket=0):
-        import ctypes
-        lib, B, Nc, Nf = _lib.lib(), self.B, self.Nc, self.Nf
-        ck, ptr = _lib.check, _lib.ptr
-        c, f = self.passes
-        (_, _, (fwd_c, bwd_c)), (_, _, (fwd_f, bwd_f)) = self._images
-        main = torch.cuda.current_stream(self.dev)
-        side = self._side
-        st, ss = ctypes_stream(main), ctypes_stream(side)
-        self._ring.fetch(self.hyper, self.dev)
-        if self.device_rng:
-            jit_c, jit_f = ctypes.c_void_p(self.hyper.data_ptr() + 24), None
-            flags, seed, rid = _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0
-        else:
-            jit_c, jit_f, flags, seed, rid = ptr(self.u_c), ptr(self.u_f), 0, 0, 0
-        R, lo, inv, outside = self._grid
-        words = ctypes.c_void_p(self._words_ptr)
-        # (rays, jitter, tbins, flags, seed, ray_id0) of each pass: the coarse jitter; the fine positions as given
-        heads = (((ptr(self.rays), jit_c, ptr(self.tbins)), (flags, seed, rid)),
-                 ((ptr(self.rays), ptr(self.ts_f), None), (_lib.FLAG_TS_GIVEN, 0, 0)))
-        for p, image, (head, (fl, sd, ri)) in zip((c, f), (fwd_c, fwd_f), heads):
-            ck(lib.nerf_amd_occupancy_mark(*head, fl | outside, sd, ri, words, *R, lo, inv, ptr(p["mask"]), ptr(p["offsets"]), None,
-                                           ptr(self._mark_ws), B, p["N"], st), "nerf_amd_occupancy_mark")
-            ck(lib.nerf_amd_occupancy_points_capped(*head, fl, sd, ri, ptr(p["mask"]), ptr(p["offsets"]), ptr(p["pts"]),
-                                                    ptr(p["counts"]), p["C"], B, p["N"], st), "nerf_amd_occupancy_points_capped")
-            ck(lib.nerf_amd_mlp_forward_train_points(ptr(p["pts"]), ptr(image), ptr(p["raw"]), ptr(p["acts"]), p["C"], st),
-               "nerf_amd_mlp_forward_train_points")
-            if p is c:        # rgb_c, d_raw_c and ts_f: the fine pass's mark depends on it, so it is produced inside the graph
-                ck(lib.nerf_amd_volume_render_masked_mse_backward_pdf(
-                    ptr(p["raw"]), *head, fl, sd, ri, ptr(p["mask"]), ptr(p["offsets"]), ptr(self.gt), jit_f, ptr(p["rgb"]),
-                    ptr(p["d_raw"]), ptr(self.ts_f), p["C"], B, Nc, Nf, st), "nerf_amd_volume_render_masked_mse_backward_pdf")
-            else:
-                ck(lib.nerf_amd_volume_render_masked_mse_backward(
-                    ptr(p["raw"]), *head, fl, sd, ri, ptr(p["mask"]), ptr(p["offsets"]), ptr(self.gt), ptr(p["rgb"]),
-                    ptr(p["d_raw"]), p["C"], B, p["N"], st), "nerf_amd_volume_render_masked_mse_backward")
-        fork = torch.cuda.Event()
-        fork.record(main)                           # both heads done: rgb / d_raw / pts of both passes are final
-        for p, image in ((c, bwd_c), (f, bwd_f)):
-            ck(lib.nerf_amd_mlp_backward(ptr(p["d_raw"]), ptr(image), ptr(p["acts"]), ptr(p["dys"]), p["C"], st),
-               "nerf_amd_mlp_backward")
-        side.wait_event(fork)
-        n = self.opt.slices[0].numel()
-        grads = (self.grads[:n], self.grads[n:])
-        for p in (c, f):
-            ck(lib.nerf_amd_encode_points_bf16(ptr(p["pts"]), ptr(p["posx"]), ptr(p["posd"]), p["C"], ss),
-               "nerf_amd_encode_points_bf16")
-        for k, (p, g) in enumerate(zip((c, f), grads)):
-            ck(lib.nerf_amd_mse_loss(ptr(p["rgb"]), ptr(self.gt), ptr(self.losses[k]), None, B * 3, ss), "nerf_amd_mse_loss")
-            ck(lib.nerf_amd_param_gradients_begin(ptr(p["d_raw"]), ptr(p["scratch"]), ptr(g), p["C"], ss),
-               "nerf_amd_param_gradients_begin")
-        with torch.cuda.stream(side):
-            torch.add(self.losses[0], self.losses[1], out=self.loss)       # the total, MSE(rgb_c) + MSE(rgb_f)
-        if self.rays_from is not None and self.device_rng:
-            # the next step's batch, beside the dX chains: rays and gt have been read for the last time (marks, emits and
-            # heads on the main branch in front of the fork, the losses here)
-            self.rays_from.launch(self.select_mode, B, None, self._select_seed(1), ctypes.c_void_p(self.hyper.data_ptr() + 24),
-                                  self.rays, self.gt, self._ids_next, stream=ss, workspace=self._select_ws)
-        main.wait_stream(side)
-        for p, g in zip((c, f), grads):
-            ck(lib.nerf_amd_param_gradients_finish_bucket(ptr(p["acts"]), ptr(p["dys"]), ptr(p["posx"]), ptr(p["posd"]),
-                                                          ptr(p["scratch"]), ptr(g), p["C"], 0, st),
-               "nerf_amd_param_gradients_finish_bucket")
-
-    def _range_check(self):
-        """Behind graph A on every ``check_every``-th step: the reference's |x| > 1 warning on the points both networks were
-        asked about (the pad point is in range), and the copy of ``counts`` the overflow report reads."""
-        from .utils.xyz import range_check_values
-        for p in self.passes:
-            range_check_values(p["pts"])
-        self._counts_watch.push(self._counts, self.opt.step_count)
-
-    def _stats(self, step, values):
-        out = {"step": step}
-        for k, name in enumerate(("coarse", "fine")):
-            out[name] = {"samples": self.B * self.passes[k]["N"], "live": values[2 * k], "kept": values[2 * k + 1],
-                         "capacity": self.capacity[k]}
-        return out
-
-    def _note(self, done):
-        import warnings
-        for step, *values in done:
-            self.last_stats = self._stats(step, values)
-            over = [(name, s) for name, s in list(self.last_stats.items())[1:] if s["live"] > s["capacity"]]
-            if over:
-                self.overflow_steps += 1
-                what = "; ".join(f"the {name} pass had {s['live']} live samples for a capacity of {s['capacity']} points, the last "
-                                 f"{s['live'] - s['kept']} (ray-major order) were treated as dead" for name, s in over)
-                warnings.warn(f"{type(self).__name__}: step {step}: {what}.  Build a stepper with a larger capacity.",
-                              RuntimeWarning, stacklevel=3)
-
-    def counts(self):
-        """{'step', 'coarse': {'samples', 'live', 'kept', 'capacity'}, 'fine': {...}} of the latest step, read now
-        (synchronises); pending reports are delivered first."""
-        self._note(self._counts_watch.poll(wait=True))
-        return self._stats(self.opt.step_count, [int(v) for v in self._counts.cpu()])
-
     def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
-        if self.occupancy.words.data_ptr() != self._words_ptr:
-            raise RuntimeError("the occupancy grid's words tensor was replaced: its address is baked into the captured graph "
-                               f"(TrainingOccupancyGrid.update writes in place); build a new {type(self).__name__}")
-        self._note(self._counts_watch.poll())
+        self._watch_grid()
         return super().step(rays, gt, u_c=u_c, u_f=u_f, decay=decay)
 
     __call__ = step

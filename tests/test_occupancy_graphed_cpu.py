@@ -141,6 +141,47 @@ def test_python_surface():
     assert callable(cls.counts) and callable(cls.step)
 
 
+# capacity argument at n_rays * N = 100 -> points, or the exception: what BOTH spellings gave while GraphedMaskedTrainStep
+# still carried its own copy of the rule (recorded there, before the copy went)
+CAPACITY_CASES = [(7, 7), (1, 1), (100, 100), (0, ValueError), (-3, ValueError), (101, ValueError), (0.25, 25), (0.999, 100),
+                  (1.0, 100), (1e-9, 1), (0.0, ValueError), (-0.5, ValueError), (1.5, ValueError), (2.0, ValueError),
+                  (float("nan"), ValueError), (True, TypeError), (False, TypeError), (None, TypeError), ("half", TypeError),
+                  ((1, 2), TypeError), (np.int64(7), 7), (np.float32(0.5), 50)]
+
+
+def test_capacity_rule_is_capacity_points(monkeypatch):
+    """GraphedMaskedTrainStep's capacity rule and training._capacity_points are one function: the constructor hands its
+    argument to it with n_rays * N as the total, and every case raises or returns the same under both spellings.  No GPU: a
+    grid on another device than the optimizer's vector stops the constructor right behind the capacity."""
+    from nerf_simple_amd import training
+    from nerf_simple_amd.optim import FusedAdam
+    from nerf_simple_amd.utils.nets import Nerf
+    from nerf_simple_amd.utils.occupancy import OccupancyGrid
+    net = Nerf(precision="bf16")
+    opt = object.__new__(FusedAdam)
+    opt.net, opt.flat = net, torch.zeros(1)
+    occ = object.__new__(OccupancyGrid)
+    occ.words = torch.zeros(1, device="meta")
+    real, seen = training._capacity_points, []
+
+    def spy(capacity, total, what):
+        seen.append((total, real(capacity, total, what)))
+        return seen[-1][1]
+    monkeypatch.setattr(training, "_capacity_points", spy)
+    for capacity, want in CAPACITY_CASES:
+        del seen[:]
+        if isinstance(want, type):
+            with pytest.raises(want):
+                real(capacity, 100, "capacity")
+            with pytest.raises(want):
+                training.GraphedMaskedTrainStep(net, opt, 10, 10, occ, capacity)
+        else:
+            assert real(capacity, 100, "capacity") == want, capacity
+            with pytest.raises(RuntimeError, match="lives on"):
+                training.GraphedMaskedTrainStep(net, opt, 10, 10, occ, capacity)
+            assert seen == [(100, want)], (capacity, seen)
+
+
 def test_new_kernels_pass_the_static_isa_checks():
     """tools/check_vmcnt.py on csrc/occupancy_graph.hip: no counted vmcnt wait is short, no wide store has its data
     registers overwritten by the next instruction, and no kernel uses an atomic (every row is written by exactly one lane)."""

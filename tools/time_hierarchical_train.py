@@ -30,16 +30,17 @@ class ComposedHead(GraphedHierarchicalTrainStep):
         self._w = torch.empty((self.B, self.Nc), **f32)
         self._junk = [torch.empty(s_, **f32) for s_ in ((self.B, 3), (self.B,), (self.B, self.Nc), (self.B,))]
 
-    def _coarse_head(self, c, jit_f, flags, seed, rid, st):
+    def _coarse_head(self, c, st):
         lib, ptr, B, Nc = _lib.lib(), _lib.ptr, self.B, self.Nc
-        _lib.check(lib.nerf_amd_volume_render_mse_backward(ptr(c["raw"]), ptr(c["ts"]), ptr(self.rays), ptr(self.gt), ptr(c["rgb"]),
-                                                           ptr(c["d_raw"]), B, Nc, st), "nerf_amd_volume_render_mse_backward")
+        (jit_f, ts_f, Nf), (_, _, _, flags, seed, rid) = self._pdf, c.jitter
+        _lib.check(lib.nerf_amd_volume_render_mse_backward(ptr(c.raw), ptr(c.ts), ptr(self.rays), ptr(self.gt), ptr(c.rgb),
+                                                           ptr(c.d_raw), B, Nc, st), "nerf_amd_volume_render_mse_backward")
         rgb, disp, alpha, acc = self._junk
-        _lib.check(lib.nerf_amd_volume_render_rays(ptr(c["raw"]), ptr(c["ts"]), ptr(self.rays), ptr(rgb), ptr(disp), ptr(alpha),
+        _lib.check(lib.nerf_amd_volume_render_rays(ptr(c.raw), ptr(c.ts), ptr(self.rays), ptr(rgb), ptr(disp), ptr(alpha),
                                                    ptr(acc), ptr(self._w), B, Nc, st), "nerf_amd_volume_render_rays")
         # nerf_amd_sample_pdf takes its seed as an argument only: the seed-in-memory form is the fused head's
-        _lib.check(lib.nerf_amd_sample_pdf(ptr(c["ts"]), ptr(self._w), jit_f if not flags else None, flags & _lib.FLAG_DEVICE_RNG,
-                                           seed, rid, ptr(self.ts_f), B, Nc, self.Nf, st), "nerf_amd_sample_pdf")
+        _lib.check(lib.nerf_amd_sample_pdf(ptr(c.ts), ptr(self._w), jit_f if not flags else None, flags & _lib.FLAG_DEVICE_RNG,
+                                           seed, rid, ts_f, B, Nc, Nf, st), "nerf_amd_sample_pdf")
 
 
 def make(cls, dev, B, Nc, Nf, device_rng):
