@@ -9,6 +9,7 @@
 //   m = b1 m + (1-b1) g ;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 #include "nerf_device.h"
+#include "launchers.h"
 
 namespace {
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

@@ -2,93 +2,15 @@
 // checking, host-side introspection and the composition of the render path
 // out of the kernels in this directory.  No allocation, no host sync.
 #include "api_checks.h"
+#include "launchers.h"
 #include <math.h>
 
 using namespace nerf_layout;
-
-extern "C" {
-int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
-int nerf_amd_launch_pack_train(const float*, void*, void*, hipStream_t);
-int nerf_amd_launch_composite_mse_backward(const float*, const float*, const float*, const float*, float*, float*, long long,
-                                           int, hipStream_t);
-int nerf_amd_launch_composite_mse_backward_pdf(const float*, const float*, const float*, const float*, float*, float*,
-                                               const float*, float*, long long, int, int, unsigned long long, long long, int,
-                                               int, hipStream_t);
-int nerf_amd_launch_param_gradients_begin(const float*, void*, float*, long long, hipStream_t);
-int nerf_amd_launch_param_gradients_finish(const void*, const void*, const void*, const void*, const void*, float*, long long,
-                                           int, hipStream_t);
-int nerf_amd_launch_query_points(const MlpArgs*, float*, hipStream_t);
-int nerf_amd_launch_gamma(const float*, long long, float*, long long, int, hipStream_t);
-int nerf_amd_launch_posenc(const float*, float*, float*, long long, int, int, hipStream_t);
-int nerf_amd_launch_composite(const float*, const float*, const float*, long long, float*, float*,
-                              float*, float*, float*, long long, int, int, float*, hipStream_t);
-int nerf_amd_launch_sample_pdf(const float*, const float*, const float*, float*, long long, int, int,
-                               unsigned long long, long long, int, hipStream_t);
-int nerf_amd_launch_generate_rays(const float*, int, int, float, long long, long long, float*, hipStream_t);
-int nerf_amd_launch_composite_backward(const float*, const float*, const float*, long long, const float*,
-                                       const float*, const float*, const float*, const float*, float*,
-                                       long long, int, int, hipStream_t);
-int nerf_amd_launch_mse_loss(const float*, const float*, float*, float*, long long, hipStream_t);
-int nerf_amd_launch_sample_encode(const MlpArgs*, float*, float*, hipStream_t);
-int nerf_amd_launch_mlp_f32(const MlpArgs*, int, hipStream_t);
-int nerf_amd_launch_mlp_bf16_16(const MlpArgs*, int, hipStream_t);
-int nerf_amd_launch_mlp_f16_16(const MlpArgs*, int, hipStream_t);
-int nerf_amd_launch_mlp_backward(const float*, const void*, const void*, void*, long long, int, hipStream_t);
-int nerf_amd_launch_param_gradients_finish_e4m3(const void*, const void*, const void*, float*, long long, int, hipStream_t);
-int nerf_amd_launch_param_gradients_convert_e4m3(const void*, const void*, const void*, void*, long long, int, hipStream_t);
-long long nerf_amd_f8_scratch_bytes(long long);
-int nerf_amd_launch_mt19937_uniform(const uint32_t*, int, float*, long long, uint32_t*, hipStream_t);
-int nerf_amd_launch_mt19937_uniform_par(const uint32_t*, int, float*, long long, uint32_t*, const uint32_t*, int, long long,
-                                        uint32_t*, hipStream_t);
-int nerf_amd_launch_range_check(const MlpArgs*, long long, unsigned*, hipStream_t);
-int nerf_amd_launch_mt19937_raw(const uint32_t*, int, uint32_t*, long long, uint32_t*, hipStream_t);
-int nerf_amd_launch_mt19937_uniform_after(const uint32_t*, const uint32_t*, int, int, float*, long long, uint32_t*, long long, uint32_t*,
-                                          hipStream_t);
-int nerf_amd_launch_mt19937_advance(const uint32_t*, const uint32_t*, uint32_t*, hipStream_t);
-int nerf_amd_launch_select_rays(const uint32_t*, unsigned long long, const unsigned long long*, long long, long long, const float*,
-                                const float*, float*, float*, long long*, void*, hipStream_t);
-int nerf_amd_host_mt19937_jump_poly(long long, const uint32_t*, uint32_t*);
-int nerf_amd_launch_adam_hyper(float*, const float*, float*, float*, long long, const float*, hipStream_t);
-int nerf_amd_launch_hyper_fetch(const float*, int, float*, unsigned*, hipStream_t);
-int nerf_amd_launch_linear_f32(const float*, long long, long long, const float*, const float*, long long, long long, const float*,
-                               float*, long long, long long, long long, long long, int, hipStream_t);
-int nerf_amd_launch_adam(float*, const float*, float*, float*, long long, float, float, float, float, float, float,
-                         hipStream_t);
-int nerf_amd_launch_sample_encode_bf16(const MlpArgs*, void*, void*, hipStream_t);
-int nerf_amd_launch_param_gradients(const float*, const void*, const void*, const void*, const void*, void*, float*,
-                                    long long, hipStream_t);
-int nerf_amd_launch_input_gradients(const void*, const float*, const float*, const float*, const float*, float*, float*,
-                                    long long, int, hipStream_t);
-int nerf_amd_launch_query_points_backward(const float*, const float*, const float*, float*, long long, int, hipStream_t);
-int nerf_amd_launch_gamma_backward(const float*, long long, const float*, float*, long long, int, hipStream_t);
-int nerf_amd_launch_posenc_backward(const float*, const float*, const float*, float*, long long, int, int, hipStream_t);
-int nerf_amd_launch_density_bf16(const DensityArgs*, hipStream_t);
-int nerf_amd_launch_density_f16(const DensityArgs*, hipStream_t);
-int nerf_amd_launch_grid_points(const DensityArgs*, long long, long long, float*, hipStream_t);
-long long nerf_amd_mc_workspace_bytes(long long);
-int nerf_amd_launch_mc_count(const float*, long long, long long, long long, float, void*, long long*, hipStream_t);
-int nerf_amd_launch_mc_emit(const float*, long long, long long, long long, float, const float*, const float*, void*, float*, float*,
-                            int*, long long, long long, hipStream_t);
-int nerf_amd_occ_max_n(void);
-int nerf_amd_occ_max_dilate(void);
-long long nerf_amd_occ_workspace_bytes(long long);
-int nerf_amd_launch_occ_bits(const float*, long long, long long, long long, float, int, unsigned*, hipStream_t);
-int nerf_amd_launch_occ_pack(const unsigned char*, long long, long long, long long, unsigned*, hipStream_t);
-int nerf_amd_launch_occ_mark(const MlpArgs*, const unsigned*, long long, long long, long long, const float*, const float*, int,
-                             unsigned long long*, long long*, long long*, void*, long long, hipStream_t);
-int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const long long*, float*, long long, long long, hipStream_t);
-int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
-int nerf_amd_occ_train_max_n(void);
-int nerf_amd_launch_occ_composite_backward(const MlpArgs*, const unsigned long long*, const long long*, const float*, const float*,
-                                           const float*, const float*, const float*, const float*, float*, long long, hipStream_t);
-int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
-}
 
 namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool bad_precision(int p) { return p != NERF_AMD_F32 && p != NERF_AMD_BF16 && p != NERF_AMD_FP16; }
 inline bool bad_image(int p) { return bad_precision(p) && p != NERF_AMD_BF16_BWD; }
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 // the fused render kernels (sampling + MLP + compositing in one launch) serve rays of up to
 // FUSED_RENDER_MAX_N samples, in every precision
 inline bool fused_render(int precision, int N) { return !bad_precision(precision) && N <= FUSED_RENDER_MAX_N; }
@@ -113,15 +35,62 @@ inline DensityArgs grid_args(const float* h_lo, const float* h_step, int64_t nx,
 int launch_density(const DensityArgs& a, int precision, hipStream_t s) {
     return precision == NERF_AMD_FP16 ? nerf_amd_launch_density_f16(&a, s) : nerf_amd_launch_density_bf16(&a, s);
 }
-// the rays, jitter and sizes every stage of the masked render takes (the mark / emit / composite kernels form the sample
-// positions themselves): 0 = go on, otherwise the code to return
-constexpr int64_t OCC_MAX_RAYS = 1ll << 32;
+// the masked render's stages (the mark / emit / composite kernels form the sample positions themselves)
 int occ_rays(const float* rays, const float* u, const float* tbins, uint32_t flags, int64_t B, int N) {
-    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
-    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-    if (N > nerf_amd_occ_max_n() || B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
-    if (B > 0 && !rays) return NERF_AMD_EINVAL;
-    return 0;
+    return masked_rays_check(rays, u, tbins, flags, B, N, N > MASKED_MAX_N);
+}
+
+// ---- workspace layouts: the *_workspace_bytes function and the entry point that carves the buffer read the same struct ----
+struct RenderWs {                      // the two-launch render: raw[B,N,4] at 0, ts[B,N]; nothing on the fused path
+    int64_t off_ts, bytes;
+};
+RenderWs render_ws(int precision, int64_t B, int N) {
+    if (fused_render(precision, N)) return {0, 0};
+    const int64_t raw = align256(B * N * 16);
+    return {raw, raw + align256(B * N * 4)};
+}
+struct ImageWs {                       // rays[n,6] at 0, then the render's own workspace
+    int64_t off_render, bytes;
+};
+ImageWs image_ws(int precision, int64_t n_rays, int N) {
+    const int64_t rays = align256(n_rays * 24);
+    return {rays, rays + render_ws(precision, n_rays, N).bytes};
+}
+struct HierWs {                        // rays[n,6] at 0, ts_c[n,Nc], w_c[n,Nc], ts_f[n,Nc+Nf]
+    int64_t off_ts_c, off_w_c, off_ts_f, bytes;
+};
+HierWs hier_ws(int64_t n_rays, int Nc, int Nf) {
+    HierWs w;
+    w.off_ts_c = align256(n_rays * 24);
+    w.off_w_c = w.off_ts_c + align256(n_rays * Nc * 4);
+    w.off_ts_f = w.off_w_c + align256(n_rays * Nc * 4);
+    w.bytes = w.off_ts_f + align256(n_rays * (int64_t)(Nc + Nf) * 4);
+    return w;
+}
+
+// ---- the render of a batch of rays: every render entry point ends here --------------------------------------------------
+struct RenderOut {                     // rgb / disp / acc (alpha and w on request), or pixels
+    float *rgb, *disp, *alpha, *acc, *w, *pixels;
+};
+// `a`: rays_args + packed.  One fused launch (sampling + MLP + compositing) up to FUSED_RENDER_MAX_N samples; beyond, the
+// MLP leaves raw / ts in the workspace (render_ws) and the compositor reads them.
+int render_rays(MlpArgs a, const RenderOut& out, int precision, void* workspace, hipStream_t s) {
+    const bool fused = fused_render(precision, a.N);
+    if (!fused && !workspace) return NERF_AMD_EINVAL;
+    if (!a.rays || !a.packed) return NERF_AMD_EINVAL;
+    if (bad_jitter(a.flags, a.u, a.tbins)) return NERF_AMD_EINVAL;
+    if (fused) {
+        a.rgb = out.rgb; a.disp = out.disp; a.alpha = out.alpha; a.acc = out.acc; a.w = out.w; a.pixels = out.pixels;
+        return launch_mlp(a, 1, precision, s);
+    }
+    const int64_t B = a.P / a.N;
+    a.raw = reinterpret_cast<float*>(workspace);
+    a.ts_out = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + render_ws(precision, B, a.N).off_ts);
+    const int rc = launch_mlp(a, 1, precision, s);
+    if (rc) return rc;
+    // dirs = rays[:,3:] normalised inside the kernel (utils/rendering.py:37,43)
+    return nerf_amd_launch_composite(a.raw, a.ts_out, a.rays + 3, 6, out.rgb, out.disp, out.alpha, out.acc, out.w, B, a.N, 1,
+                                     out.pixels, s);
 }
 }  // namespace
 
@@ -150,16 +119,12 @@ int nerf_amd_grad_bucket_range(int bucket, int64_t* first, int64_t* count) {
 
 int64_t nerf_amd_render_image_workspace_bytes(int precision, int64_t n_rays, int N) {
     if (n_rays < 0 || N <= 0 || bad_precision(precision)) return NERF_AMD_EINVAL;
-    // rays[n,6] (+ raw[n,N,4] + ts[n,N] on the two-launch path)
-    if (fused_render(precision, N)) return align_up(n_rays * 24, 256);
-    return align_up(n_rays * 24, 256) + align_up(n_rays * N * 16, 256) + align_up(n_rays * N * 4, 256);
+    return image_ws(precision, n_rays, N).bytes;
 }
 
 int64_t nerf_amd_render_workspace_bytes(int precision, int64_t B, int N) {
     if (B < 0 || N <= 0 || bad_precision(precision)) return NERF_AMD_EINVAL;
-    if (fused_render(precision, N)) return 0;
-    // raw[B,N,4] + ts[B,N]
-    return align_up(B * N * 16, 256) + align_up(B * N * 4, 256);
+    return render_ws(precision, B, N).bytes;
 }
 
 int nerf_amd_layout_src_col(int precision, int layer, int kstep, int half, int elem) {
@@ -275,9 +240,8 @@ int nerf_amd_query_points(const float* rays, const float* u, const float* tbins,
     if (B == 0) return 0;
     if (!rays || !query_pts) return NERF_AMD_EINVAL;
     if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins; a.ts_out = ts;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.ts_out = ts;
     return nerf_amd_launch_query_points(&a, query_pts, S(stream));
 }
 
@@ -291,8 +255,7 @@ int nerf_amd_range_check(const float* rays, const float* pts, const float* u, co
     } else {
         if (!rays || N <= 0) return NERF_AMD_EINVAL;
         if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-        a.rays = rays; a.u = u; a.tbins = tbins;
-        a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+        a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
     }
     return nerf_amd_launch_range_check(&a, B, word, S(stream));
 }
@@ -338,7 +301,7 @@ int nerf_amd_volume_render_rays_backward(const float* raw, const float* ts, cons
                                          const float* g_w, float* d_raw, int64_t B, int N, void* stream) {
     if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
-    if (N > 512) return NERF_AMD_EUNSUP;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !d_raw) return NERF_AMD_EINVAL;
     return nerf_amd_launch_composite_backward(raw, ts, rays + 3, 6, g_rgb, g_disp, g_alpha, g_acc, g_w, d_raw, B, N, 1,
                                               S(stream));
@@ -348,7 +311,7 @@ int nerf_amd_volume_render_mse_backward(const float* raw, const float* ts, const
                                        float* rgb, float* d_raw, int64_t B, int N, void* stream) {
     if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
-    if (N > 512) return NERF_AMD_EUNSUP;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
     return nerf_amd_launch_composite_mse_backward(raw, ts, rays, target, rgb, d_raw, B, N, S(stream));
 }
@@ -366,7 +329,7 @@ int nerf_amd_volume_render_mse_backward_pdf(const float* raw, const float* ts, c
         return NERF_AMD_EINVAL;
     }
     if (B == 0) return 0;
-    if (Nc < 3 || Nc > 256 || Nc + Nf > 512) return NERF_AMD_EUNSUP;
+    if (nerf_pdf::unsupported_sizes(Nc, Nf)) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !d_raw || !ts_out) return NERF_AMD_EINVAL;
     return nerf_amd_launch_composite_mse_backward_pdf(raw, ts, rays, target, rgb, d_raw, u, ts_out, B, Nc, Nf, seed, ray_id0,
                                                       (flags & NERF_AMD_DEVICE_RNG) ? 1 : 0,
@@ -384,7 +347,7 @@ int nerf_amd_volume_render_backward(const float* raw, const float* ts, const flo
                                     void* stream) {
     if (B < 0 || N <= 0 || dirs_stride < 3) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
-    if (N > 512) return NERF_AMD_EUNSUP;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !dirs || !d_raw) return NERF_AMD_EINVAL;
     return nerf_amd_launch_composite_backward(raw, ts, dirs, dirs_stride, g_rgb, g_disp, g_alpha, g_acc, g_w,
                                               d_raw, B, N, 0, S(stream));
@@ -397,9 +360,8 @@ int nerf_amd_sample_encode(const float* rays, const float* u, const float* tbins
     if (B == 0) return 0;
     if (!rays || !posx || !posd) return NERF_AMD_EINVAL;
     if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins; a.ts_out = ts;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.ts_out = ts;
     return nerf_amd_launch_sample_encode(&a, posx, posd, S(stream));
 }
 
@@ -410,9 +372,8 @@ int nerf_amd_mlp_forward_rays(const float* rays, const float* u, const float* tb
     if (B == 0) return 0;
     if (!rays || !packed || !raw) return NERF_AMD_EINVAL;
     if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins; a.packed = packed; a.raw = raw; a.ts_out = ts;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.packed = packed; a.raw = raw; a.ts_out = ts;
     return launch_mlp(a, 1, precision, S(stream));
 }
 
@@ -423,23 +384,9 @@ int nerf_amd_render_forward(const float* rays, const float* u, const float* tbin
     if (B < 0 || N <= 0 || bad_precision(precision)) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
     if (!rgb || !disp || !acc) return NERF_AMD_EINVAL;
-    if (fused_render(precision, N)) {
-        if (!rays || !packed) return NERF_AMD_EINVAL;
-        if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-        MlpArgs a{};
-        a.rays = rays; a.u = u; a.tbins = tbins; a.packed = packed;
-        a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
-        a.rgb = rgb; a.disp = disp; a.alpha = alpha; a.acc = acc; a.w = w;
-        return launch_mlp(a, 1, precision, S(stream));
-    }
-    if (!workspace) return NERF_AMD_EINVAL;
-    float* raw = reinterpret_cast<float*>(workspace);
-    float* ts = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_up(B * N * 16, 256));
-    int rc = nerf_amd_mlp_forward_rays(rays, u, tbins, packed, precision, flags, seed, ray_id0, raw, ts, B, N,
-                                       stream);
-    if (rc) return rc;
-    // dirs = rays[:,3:] normalised inside the kernel (utils/rendering.py:37,43)
-    return nerf_amd_launch_composite(raw, ts, rays + 3, 6, rgb, disp, alpha, acc, w, B, N, 1, nullptr, S(stream));
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.packed = packed;
+    return render_rays(a, RenderOut{rgb, disp, alpha, acc, w, nullptr}, precision, workspace, S(stream));
 }
 
 int nerf_amd_render_pixels_forward(const float* rays, const float* u, const float* tbins, void* packed,
@@ -448,23 +395,9 @@ int nerf_amd_render_pixels_forward(const float* rays, const float* u, const floa
     if (B < 0 || N <= 0 || bad_precision(precision)) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
     if (!pixels) return NERF_AMD_EINVAL;
-    if (fused_render(precision, N)) {
-        if (!rays || !packed) return NERF_AMD_EINVAL;
-        if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-        MlpArgs a{};
-        a.rays = rays; a.u = u; a.tbins = tbins; a.packed = packed;
-        a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
-        a.pixels = pixels;
-        return launch_mlp(a, 1, precision, S(stream));
-    }
-    if (!workspace) return NERF_AMD_EINVAL;
-    float* raw = reinterpret_cast<float*>(workspace);
-    float* ts = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_up(B * N * 16, 256));
-    int rc = nerf_amd_mlp_forward_rays(rays, u, tbins, packed, precision, flags, seed, ray_id0, raw, ts, B, N,
-                                       stream);
-    if (rc) return rc;
-    return nerf_amd_launch_composite(raw, ts, rays + 3, 6, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, 1,
-                                     pixels, S(stream));
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.packed = packed;
+    return render_rays(a, RenderOut{nullptr, nullptr, nullptr, nullptr, nullptr, pixels}, precision, workspace, S(stream));
 }
 
 int nerf_amd_generate_rays(const float* h_pose, int H, int W, float f, int64_t ray0, int64_t n_rays,
@@ -486,18 +419,18 @@ int nerf_amd_render_image_forward(const float* h_pose, int H, int W, float f, in
     if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;      // before the rays are generated: nothing is launched
     char* ws = reinterpret_cast<char*>(workspace);
     float* rays = reinterpret_cast<float*>(ws);
-    int rc = nerf_amd_generate_rays(h_pose, H, W, f, ray0, n_rays, rays, stream);
+    const int rc = nerf_amd_generate_rays(h_pose, H, W, f, ray0, n_rays, rays, stream);
     if (rc) return rc;
     // jitter is keyed by the GLOBAL pixel id, so the image does not depend on how it is sharded
     return nerf_amd_render_pixels_forward(rays, u, tbins, packed, precision, flags, seed, ray0, pixels,
-                                          ws + align_up(n_rays * 24, 256), n_rays, N, stream);
+                                          ws + image_ws(precision, n_rays, N).off_render, n_rays, N, stream);
 }
 
 int nerf_amd_sample_pdf(const float* ts, const float* w, const float* u, uint32_t flags, uint64_t seed,
                         int64_t ray_id0, float* ts_out, int64_t B, int Nc, int Nf, void* stream) {
     if (B < 0 || Nc <= 0 || Nf < 0) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
-    if (Nc < 3 || Nc > 256 || Nc + Nf > 512) return NERF_AMD_EUNSUP;
+    if (nerf_pdf::unsupported_sizes(Nc, Nf)) return NERF_AMD_EUNSUP;
     if (!ts || !w || !ts_out) return NERF_AMD_EINVAL;
     if (flags & ~NERF_AMD_DEVICE_RNG) return NERF_AMD_EINVAL;
     if (!(flags & NERF_AMD_DEVICE_RNG) && !u && Nf > 0) return NERF_AMD_EINVAL;
@@ -507,8 +440,7 @@ int nerf_amd_sample_pdf(const float* ts, const float* w, const float* u, uint32_
 
 int64_t nerf_amd_render_hierarchical_workspace_bytes(int64_t n_rays, int Nc, int Nf) {
     if (n_rays < 0 || Nc <= 0 || Nf < 0) return NERF_AMD_EINVAL;
-    // rays[n,6] + ts_c[n,Nc] + w_c[n,Nc] + ts_f[n,Nc+Nf]
-    return align_up(n_rays * 24, 256) + 2 * align_up(n_rays * Nc * 4, 256) + align_up(n_rays * (int64_t)(Nc + Nf) * 4, 256);
+    return hier_ws(n_rays, Nc, Nf).bytes;
 }
 
 int nerf_amd_render_hierarchical_forward(const float* h_pose, int H, int W, float f, int64_t ray0, int64_t n_rays,
@@ -517,26 +449,23 @@ int nerf_amd_render_hierarchical_forward(const float* h_pose, int H, int W, floa
                                          uint64_t seed, float* pixels, void* workspace, int Nc, int Nf, void* stream) {
     if (n_rays < 0 || Nc <= 0 || Nf < 0 || bad_precision(precision)) return NERF_AMD_EINVAL;
     if (n_rays == 0) return 0;
-    if (Nc < 3 || Nc > 256 || Nc + Nf > 512 || !fused_render(precision, Nc + Nf)) return NERF_AMD_EUNSUP;
+    if (nerf_pdf::unsupported_sizes(Nc, Nf) || !fused_render(precision, Nc + Nf)) return NERF_AMD_EUNSUP;
     if (!workspace || !pixels || !packed_c || !packed_f || !tbins_c) return NERF_AMD_EINVAL;
     // explicit jitter for both passes, or the counter RNG with its seed in the argument: the seed-in-memory form would
     // need u_c to be that address, which this entry point does not offer (the coarse kernel would dereference it)
     if (flags & ~NERF_AMD_DEVICE_RNG) return NERF_AMD_EINVAL;
     if (!(flags & NERF_AMD_DEVICE_RNG) && (!u_c || (!u_f && Nf > 0))) return NERF_AMD_EINVAL;
     char* ws = reinterpret_cast<char*>(workspace);
+    const HierWs l = hier_ws(n_rays, Nc, Nf);
     float* rays = reinterpret_cast<float*>(ws);
-    ws += align_up(n_rays * 24, 256);
-    float* ts_c = reinterpret_cast<float*>(ws);
-    ws += align_up(n_rays * Nc * 4, 256);
-    float* w_c = reinterpret_cast<float*>(ws);
-    ws += align_up(n_rays * Nc * 4, 256);
-    float* ts_f = reinterpret_cast<float*>(ws);
+    float* ts_c = reinterpret_cast<float*>(ws + l.off_ts_c);
+    float* w_c = reinterpret_cast<float*>(ws + l.off_w_c);
+    float* ts_f = reinterpret_cast<float*>(ws + l.off_ts_f);
     int rc = nerf_amd_generate_rays(h_pose, H, W, f, ray0, n_rays, rays, stream);
     if (rc) return rc;
     // coarse pass: one fused launch that leaves only what the sampler needs (positions and weights)
-    MlpArgs a{};
-    a.rays = rays; a.u = u_c; a.tbins = tbins_c; a.packed = packed_c; a.ts_out = ts_c; a.w = w_c;
-    a.P = n_rays * (int64_t)Nc; a.N = Nc; a.flags = flags; a.seed = seed; a.ray_id0 = ray0;
+    MlpArgs a = rays_args(rays, u_c, tbins_c, flags, seed, ray0, n_rays, Nc);
+    a.packed = packed_c; a.ts_out = ts_c; a.w = w_c;
     rc = launch_mlp(a, 1, precision, S(stream));
     if (rc) return rc;
     rc = nerf_amd_launch_sample_pdf(ts_c, w_c, u_f, ts_f, n_rays, Nc, Nf, seed, ray0,
@@ -559,9 +488,8 @@ int nerf_amd_mlp_forward_train(const float* rays, const float* u, const float* t
     if (!rays || !packed || !raw || !acts) return NERF_AMD_EINVAL;
     if (bad_jitter(flags & ~NERF_AMD_STORE_E4M3, u, tbins)) return NERF_AMD_EINVAL;
     static_assert(NERF_AMD_STORE_E4M3 == NERF_FLAG_STORE_E4M3, "the flag travels to the kernel as it is");
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins; a.packed = packed; a.raw = raw; a.ts_out = ts; a.acts = acts;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.packed = packed; a.raw = raw; a.ts_out = ts; a.acts = acts;
     return nerf_amd_launch_mlp_bf16_16(&a, 1, S(stream));
 }
 
@@ -629,9 +557,8 @@ int nerf_amd_sample_encode_bf16(const float* rays, const float* u, const float* 
     if (B == 0) return 0;
     if (!rays || !posx64 || !posd32) return NERF_AMD_EINVAL;
     if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-    MlpArgs a{};
-    a.rays = rays; a.u = u; a.tbins = tbins; a.ts_out = ts;
-    a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
+    MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    a.ts_out = ts;
     return nerf_amd_launch_sample_encode_bf16(&a, posx64, posd32, S(stream));
 }
 
@@ -726,7 +653,7 @@ int nerf_amd_mt19937_uniform_after(const uint32_t* state624, const uint32_t* pol
                                                  S(stream));
 }
 
-int64_t nerf_amd_select_workspace_bytes(int64_t B) { return B < 0 ? NERF_AMD_EINVAL : align_up(B * 12 + 16, 256); }
+int64_t nerf_amd_select_workspace_bytes(int64_t B) { return B < 0 ? NERF_AMD_EINVAL : align256(B * 12 + 16); }
 
 int nerf_amd_select_rays(const uint32_t* draws, uint64_t seed, const uint64_t* seed_mem, int64_t n, int64_t B,
                          const float* table, const float* colours, float* rays_out, float* gt_out, int64_t* ids_out,
@@ -846,13 +773,13 @@ int nerf_amd_occupancy_from_mask(const uint8_t* cells, int64_t nx, int64_t ny, i
 
 int64_t nerf_amd_occupancy_mask_words(int64_t B, int N) {
     if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
-    if (N > nerf_amd_occ_max_n() || B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (N > MASKED_MAX_N || B > MASKED_MAX_RAYS) return NERF_AMD_EUNSUP;
     return B * (((int64_t)N + 63) / 64);
 }
 
 int64_t nerf_amd_occupancy_workspace_bytes(int64_t B) {
     if (B < 0) return NERF_AMD_EINVAL;
-    if (B > OCC_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (B > MASKED_MAX_RAYS) return NERF_AMD_EUNSUP;
     return nerf_amd_occ_workspace_bytes(B);
 }
 
@@ -919,7 +846,7 @@ int nerf_amd_volume_render_masked_backward(const float* raw_live, const float* r
                                            const float* g_acc, const float* g_w, float* d_raw_live, int64_t B, int N, void* stream) {
     const int rc = occ_rays(rays, u, tbins, flags, B, N);
     if (rc) return rc;
-    if (N > nerf_amd_occ_train_max_n()) return NERF_AMD_EUNSUP;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (B == 0) return 0;
     if (!mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8) || misaligned(raw_live, 16) ||
         misaligned(d_raw_live, 16) || (!raw_live != !d_raw_live))

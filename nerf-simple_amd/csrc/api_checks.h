@@ -1,15 +1,27 @@
 // api_checks.h -- host-side argument rules shared by the sources that implement the C ABI (include/nerf_amd.h): api.hip and
 // the self-contained entry points in occupancy_graph.hip, occupancy_hier.hip and occupancy_terminate.hip.  Host code only.
+// Each limit and each rule that more than one entry point applies is stated here once (the limits a kernel's static sizes
+// depend on: nerf_layout.h, sample_pdf_device.h); an entry point chooses the ORDER in which it applies them, and that order
+// is part of the ABI (tests/test_abi_refusals_cpu.py).
 #pragma once
 #include "nerf_device.h"
+#include "sample_pdf_device.h"
 #include "../../include/nerf_amd.h"
+
+using nerf_layout::align256;
+using nerf_layout::COMPOSITE_BWD_MAX_N;          // N of the four compositor backward entry points and the capped heads
+using nerf_layout::MASKED_MAX_N;                 // N of the masked render and of ray termination
+constexpr int64_t MASKED_MAX_RAYS = 1ll << 32;   // B of every masked, capped and terminated entry point
+// the sampler's merged positions feed the fine pass: its fused render and its compositor backward
+static_assert(nerf_pdf::MAXM <= nerf_layout::FUSED_RENDER_MAX_N && nerf_pdf::MAXM <= COMPOSITE_BWD_MAX_N, "fine pass sizes");
 
 inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 // the jitter arguments of every rays-mode entry point: explicit u / ts, the counter RNG, or the counter RNG with its seed
 // offset in device memory (then `u` is that address).  With TS_GIVEN the kernels read the positions through `u` whatever
 // the other flags say, so `u` is required then.
-inline bool bad_jitter(uint32_t flags, const float* u, const float* tbins) {
+// (`used`: emitted whether or not every call is inlined, so the library's symbol table does not depend on the inliner)
+__attribute__((used)) inline bool bad_jitter(uint32_t flags, const float* u, const float* tbins) {
     if (flags & ~(NERF_AMD_TS_GIVEN | NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return true;     // unknown bits
     if (flags & NERF_AMD_SEED_IN_MEMORY) {
         if (!(flags & NERF_AMD_DEVICE_RNG) || (flags & NERF_AMD_TS_GIVEN) || !u) return true;
@@ -27,4 +39,23 @@ inline MlpArgs rays_args(const float* rays, const float* u, const float* tbins, 
     a.rays = rays; a.u = u; a.tbins = tbins;
     a.P = B * (int64_t)N; a.N = N; a.flags = flags; a.seed = seed; a.ray_id0 = ray_id0;
     return a;
+}
+
+// the rays, jitter and sizes every stage of the masked render takes (the kernels form the sample positions themselves):
+// 0 = go on, otherwise the code to return.  `unsupported_n` is the entry point's own size rule (N > MASKED_MAX_N,
+// N > COMPOSITE_BWD_MAX_N, nerf_pdf::unsupported_sizes): NERF_AMD_EUNSUP comes after the jitter rule and before the rays.
+inline int masked_rays_check(const float* rays, const float* u, const float* tbins, uint32_t flags, int64_t B, int N,
+                             bool unsupported_n) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
+    if (unsupported_n || B > MASKED_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (B > 0 && !rays) return NERF_AMD_EINVAL;
+    return 0;
+}
+
+// a capped entry point (fixed capacity of C live points): 1 <= C <= B N, so B >= 1; the mask and its offsets
+inline int capped_check(const uint64_t* mask, const int64_t* offsets, int64_t C, int64_t B, int N) {
+    if (C > B * (int64_t)N) return NERF_AMD_EINVAL;
+    if (!mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8)) return NERF_AMD_EINVAL;
+    return 0;
 }

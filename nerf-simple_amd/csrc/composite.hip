@@ -14,6 +14,7 @@
 // Not HBM-bound in practice: the exact-fp32 softplus / exp (ocml expf, log1pf) and the two scans
 // cost ~400 VALU instructions per 64 samples, which is what sets its 3.4 TB/s.
 #include "composite_backward_device.h"
+#include "launchers.h"
 #include "sample_pdf_device.h"
 
 namespace {
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_kernel(
 // ---- backward ---------------------------------------------------------------
 // d loss / d nerf_outs[B,N,4] given the upstream gradients of the five outputs (NULL = zero), or with the MSE loss
 // gradient formed in the kernel: the per-ray walk is composite_backward_ray (composite_backward_device.h).
-constexpr int MAX_CHUNKS = 8;          // N <= 512
+constexpr int MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;          // N <= 512
 
 // The coarse training head (E > 0): the same kernel also places the fine pass's samples from the weights of its
 // forward sweep (sample_pdf_device.h).  The weights go from registers to the wave's LDS slice with the positions; the
@@ -142,7 +143,7 @@ extern "C" int nerf_amd_launch_composite_backward(const float* raw, const float*
                                                   long long B, int N, int normalize_dirs, hipStream_t stream) {
     (void)hipGetLastError();
     if (B == 0) return 0;
-    if (N > 64 * MAX_CHUNKS) return -2;
+    if (N > nerf_layout::COMPOSITE_BWD_MAX_N) return -2;
     const long long blocks = (B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
     hipLaunchKernelGGL(composite_backward_kernel<0>, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
                        raw, ts, dirs, dirs_stride, g_rgb, g_disp, g_alpha, g_acc, g_w, d_raw, B, N,
@@ -156,7 +157,7 @@ extern "C" int nerf_amd_launch_composite_mse_backward(const float* raw, const fl
                                                       int N, hipStream_t stream) {
     (void)hipGetLastError();
     if (B == 0) return 0;
-    if (N > 64 * MAX_CHUNKS) return -2;
+    if (N > nerf_layout::COMPOSITE_BWD_MAX_N) return -2;
     const long long blocks = (B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
     hipLaunchKernelGGL(composite_backward_kernel<0>, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
                        raw, ts, rays + 3, 6ll, nullptr, nullptr, nullptr, nullptr, nullptr, d_raw, B, N, 1,
@@ -172,7 +173,7 @@ extern "C" int nerf_amd_launch_composite_mse_backward_pdf(const float* raw, cons
                                                           hipStream_t stream) {
     (void)hipGetLastError();
     if (B == 0) return 0;
-    if (Nc < 3 || Nc > nerf_pdf::MAXC || Nf < 0 || Nc + Nf > nerf_pdf::MAXM) return -2;
+    if (Nf < 0 || nerf_pdf::unsupported_sizes(Nc, Nf)) return -2;
     const dim3 grid((unsigned)((B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
     const PdfHead pdf{u, ts_out, Nf, device_rng, seed_in_mem, seed, ray_id0};
     const float scale = 1.0f / (3.0f * (float)B);

@@ -16,6 +16,7 @@
 // Inputs: explicit points (any row stride >= 3) or grid point p of an [Rx, Ry, Rz] grid (C order, z fastest) with
 // coordinates x_a(i) = fl(lo_a + fl(i s_a)), formed here -- no input buffer.
 #include "nerf_device.h"
+#include "launchers.h"
 
 using namespace nerf_layout;
 

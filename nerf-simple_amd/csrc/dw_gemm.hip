@@ -26,6 +26,7 @@
 // HBM-bound by design: every dY / X byte is read once per product (~11.5 KB per
 // point in all); 128 FLOP per byte.
 #include "nerf_device.h"
+#include "launchers.h"
 
 using namespace nerf_layout;
 

@@ -20,6 +20,7 @@
 //   * db = A^T . 1: one more MFMA per wave and slab against a fragment of ones.
 // HBM-bound by design at half the bytes of the bf16 form: (M + N) bytes per point and product.
 #include "nerf_device.h"
+#include "launchers.h"
 
 using namespace nerf_layout;
 
@@ -320,7 +321,6 @@ __global__ __launch_bounds__(256) void rows_to_e4m3_kernel(const __bf16* __restr
 }  // namespace
 
 // scratch_f8: the narrow operands in the 8-bit form, nerf_amd_f8_scratch_bytes(P): posx (64) | posd (32) | dsr (16)
-static long long align256(long long v) { return (v + 255) / 256 * 256; }
 extern "C" long long nerf_amd_f8_scratch_bytes(long long P) {
     return align256(f8_narrow_bytes(64, P)) + align256(f8_narrow_bytes(32, P)) + align256(f8_narrow_bytes(16, P));
 }

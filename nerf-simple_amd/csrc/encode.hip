@@ -9,6 +9,7 @@
 // the exactly-scaled argument 2^i * x (a power-of-two product is exact in fp32,
 // as it is in the reference), so results track torch-CPU to ~1 ulp.
 #include "nerf_device.h"
+#include "launchers.h"
 
 namespace {
 

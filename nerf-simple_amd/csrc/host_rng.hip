@@ -22,6 +22,7 @@
 // stream; long draws are cut into segments whose start states come from jump-ahead (below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "launchers.h"
 
 namespace {
 

@@ -18,6 +18,7 @@
 // MFMA k order, a fixed butterfly over the four lane groups, samples of a ray in index order), so two launches on the
 // same inputs give identical bits.
 #include "nerf_device.h"
+#include "launchers.h"
 
 using namespace nerf_layout;
 

@@ -1,0 +1,89 @@
+// launchers.h -- every function one source of this directory defines and another calls: the kernel launchers
+// (nerf_amd_launch_*) and the few host helpers beside them.  api.hip calls them; the source that defines one includes this
+// header too, so a definition whose parameter list drifts from the declaration its callers see is a compile error
+// (C linkage would otherwise link it and pass garbage to a launch).  No .hip file declares a function of another file.
+// A launcher returns 0, a hipError_t, or -2 for a size its kernel does not serve (api.hip refuses those first).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+struct MlpArgs;          // nerf_device.h
+struct DensityArgs;
+
+extern "C" {
+int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
+int nerf_amd_launch_pack_train(const float*, void*, void*, hipStream_t);
+int nerf_amd_launch_composite_mse_backward(const float*, const float*, const float*, const float*, float*, float*, long long,
+                                           int, hipStream_t);
+int nerf_amd_launch_composite_mse_backward_pdf(const float*, const float*, const float*, const float*, float*, float*,
+                                               const float*, float*, long long, int, int, unsigned long long, long long, int,
+                                               int, hipStream_t);
+int nerf_amd_launch_param_gradients_begin(const float*, void*, float*, long long, hipStream_t);
+int nerf_amd_launch_param_gradients_finish(const void*, const void*, const void*, const void*, const void*, float*, long long,
+                                           int, hipStream_t);
+int nerf_amd_launch_query_points(const MlpArgs*, float*, hipStream_t);
+int nerf_amd_launch_gamma(const float*, long long, float*, long long, int, hipStream_t);
+int nerf_amd_launch_posenc(const float*, float*, float*, long long, int, int, hipStream_t);
+int nerf_amd_launch_composite(const float*, const float*, const float*, long long, float*, float*,
+                              float*, float*, float*, long long, int, int, float*, hipStream_t);
+int nerf_amd_launch_sample_pdf(const float*, const float*, const float*, float*, long long, int, int,
+                               unsigned long long, long long, int, hipStream_t);
+int nerf_amd_launch_generate_rays(const float*, int, int, float, long long, long long, float*, hipStream_t);
+int nerf_amd_launch_composite_backward(const float*, const float*, const float*, long long, const float*,
+                                       const float*, const float*, const float*, const float*, float*,
+                                       long long, int, int, hipStream_t);
+int nerf_amd_launch_mse_loss(const float*, const float*, float*, float*, long long, hipStream_t);
+int nerf_amd_launch_sample_encode(const MlpArgs*, float*, float*, hipStream_t);
+int nerf_amd_launch_mlp_f32(const MlpArgs*, int, hipStream_t);
+int nerf_amd_launch_mlp_bf16_16(const MlpArgs*, int, hipStream_t);
+int nerf_amd_launch_mlp_f16_16(const MlpArgs*, int, hipStream_t);
+int nerf_amd_launch_mlp_backward(const float*, const void*, const void*, void*, long long, int, hipStream_t);
+int nerf_amd_launch_param_gradients_finish_e4m3(const void*, const void*, const void*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_param_gradients_convert_e4m3(const void*, const void*, const void*, void*, long long, int, hipStream_t);
+long long nerf_amd_f8_scratch_bytes(long long);
+int nerf_amd_launch_mt19937_uniform(const uint32_t*, int, float*, long long, uint32_t*, hipStream_t);
+int nerf_amd_launch_mt19937_uniform_par(const uint32_t*, int, float*, long long, uint32_t*, const uint32_t*, int, long long,
+                                        uint32_t*, hipStream_t);
+int nerf_amd_launch_range_check(const MlpArgs*, long long, unsigned*, hipStream_t);
+int nerf_amd_launch_mt19937_raw(const uint32_t*, int, uint32_t*, long long, uint32_t*, hipStream_t);
+int nerf_amd_launch_mt19937_uniform_after(const uint32_t*, const uint32_t*, int, int, float*, long long, uint32_t*, long long, uint32_t*,
+                                          hipStream_t);
+int nerf_amd_launch_mt19937_advance(const uint32_t*, const uint32_t*, uint32_t*, hipStream_t);
+int nerf_amd_launch_select_rays(const uint32_t*, unsigned long long, const unsigned long long*, long long, long long, const float*,
+                                const float*, float*, float*, long long*, void*, hipStream_t);
+int nerf_amd_host_mt19937_jump_poly(long long, const uint32_t*, uint32_t*);
+int nerf_amd_launch_adam_hyper(float*, const float*, float*, float*, long long, const float*, hipStream_t);
+int nerf_amd_launch_hyper_fetch(const float*, int, float*, unsigned*, hipStream_t);
+int nerf_amd_launch_linear_f32(const float*, long long, long long, const float*, const float*, long long, long long, const float*,
+                               float*, long long, long long, long long, long long, int, hipStream_t);
+int nerf_amd_launch_adam(float*, const float*, float*, float*, long long, float, float, float, float, float, float,
+                         hipStream_t);
+int nerf_amd_launch_sample_encode_bf16(const MlpArgs*, void*, void*, hipStream_t);
+int nerf_amd_launch_param_gradients(const float*, const void*, const void*, const void*, const void*, void*, float*,
+                                    long long, hipStream_t);
+int nerf_amd_launch_input_gradients(const void*, const float*, const float*, const float*, const float*, float*, float*,
+                                    long long, int, hipStream_t);
+int nerf_amd_launch_query_points_backward(const float*, const float*, const float*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_gamma_backward(const float*, long long, const float*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_posenc_backward(const float*, const float*, const float*, float*, long long, int, int, hipStream_t);
+int nerf_amd_launch_density_bf16(const DensityArgs*, hipStream_t);
+int nerf_amd_launch_density_f16(const DensityArgs*, hipStream_t);
+int nerf_amd_launch_grid_points(const DensityArgs*, long long, long long, float*, hipStream_t);
+long long nerf_amd_mc_workspace_bytes(long long);
+int nerf_amd_launch_mc_count(const float*, long long, long long, long long, float, void*, long long*, hipStream_t);
+int nerf_amd_launch_mc_emit(const float*, long long, long long, long long, float, const float*, const float*, void*, float*, float*,
+                            int*, long long, long long, hipStream_t);
+int nerf_amd_occ_max_n(void);
+int nerf_amd_occ_max_dilate(void);
+long long nerf_amd_occ_workspace_bytes(long long);
+int nerf_amd_launch_occ_bits(const float*, long long, long long, long long, float, int, unsigned*, hipStream_t);
+int nerf_amd_launch_occ_pack(const unsigned char*, long long, long long, long long, unsigned*, hipStream_t);
+int nerf_amd_launch_occ_mark(const MlpArgs*, const unsigned*, long long, long long, long long, const float*, const float*, int,
+                             unsigned long long*, long long*, long long*, void*, long long, hipStream_t);
+int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const long long*, float*, long long, long long, hipStream_t);
+int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
+int nerf_amd_occ_train_max_n(void);
+int nerf_amd_launch_occ_composite_backward(const MlpArgs*, const unsigned long long*, const long long*, const float*, const float*,
+                                           const float*, const float*, const float*, const float*, float*, long long, hipStream_t);
+int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
+}

@@ -15,6 +15,7 @@
 // fetched into registers under the current step's MFMAs), loads coalesced along whichever index is contiguous.  Long reductions with few output tiles (dW: K = number of points) are split over blockIdx.z and
 // summed with float atomics.
 #include "nerf_device.h"
+#include "launchers.h"
 
 namespace {
 

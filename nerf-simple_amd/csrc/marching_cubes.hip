@@ -16,6 +16,7 @@
 //          mc_face_kernel   -- triangles, whose corners look their vertex numbers up in the workspace.
 // Hand-written scans, fixed block partition, no atomics: the output is the same bytes on every run.
 #include "nerf_device.h"
+#include "launchers.h"
 #include "mc_tables.h"
 
 namespace {
@@ -284,7 +285,7 @@ struct McWs {
     long long nblk, off_blk, off_off, off_first, off_mask, bytes;
 };
 McWs mc_ws(long long n) {
-    auto up = [](long long x) { return (x + 255) / 256 * 256; };
+    constexpr auto up = nerf_layout::align256;
     McWs w;
     w.nblk = (n + MC_ITEMS - 1) / MC_ITEMS;
     w.off_blk = 0;

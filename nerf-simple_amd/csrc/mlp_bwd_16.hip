@@ -18,6 +18,7 @@
 // L2 -> LDS by LDS-DMA exactly as in the forward.  HBM-bound by construction:
 // 0.3 KB of mask bits read and ~5 KB of dY written per point.
 #include "nerf_device.h"
+#include "launchers.h"
 #include <utility>
 
 using namespace nerf_layout;

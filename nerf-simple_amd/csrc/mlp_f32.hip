@@ -15,6 +15,7 @@
 //     composite.hip uses, so the pixels are bit-identical to the two-launch path).
 // Peak for this path is the fp32 MFMA rate, 157.3 TFLOP/s (1/16 of bf16).
 #include "composite_device.h"
+#include "launchers.h"
 #include <utility>
 
 using namespace nerf_layout;

@@ -41,6 +41,16 @@ constexpr int PARAM_COUNT = 595844;
 // largest samples-per-ray the fused render kernel composites in its LDS ring (mlp_bf16_16.hip);
 // longer rays take the two-launch path (MLP -> raw/ts in HBM -> composite.hip)
 constexpr int FUSED_RENDER_MAX_N = 768;
+// Limits that a kernel's static sizes and the host's argument checks (api_checks.h) both come from:
+// samples per ray of the masked render and of ray termination (occupancy.hip: the masked compositor's LDS row; the mask
+// layout) -- the fused render's own limit, so a masked render serves whatever the dense one does in one launch
+constexpr int MASKED_MAX_N = FUSED_RENDER_MAX_N;
+// samples per ray of every compositor backward (composite.hip, occupancy_train.hip, occupancy_graph.hip): the sweep
+// holds a ray in COMPOSITE_BWD_MAX_CHUNKS registers per lane (composite_backward_device.h)
+constexpr int COMPOSITE_BWD_MAX_CHUNKS = 8;
+constexpr int COMPOSITE_BWD_MAX_N = 64 * COMPOSITE_BWD_MAX_CHUNKS;
+// every workspace and scratch layout places its buffers on 256-byte boundaries
+NL_HD constexpr long long align256(long long v) { return (v + 255) / 256 * 256; }
 
 // offsets of the 24 tensors inside the flat fp32 parameter vector
 // (PARAM_SPECS order of utils/synthetic.py == state_dict order of the reference)
@@ -324,7 +334,7 @@ NL_HD constexpr long long f8_elem_offset(int L, long long p, int f, long long P)
 NL_HD constexpr long long f8_scale_layer_stride(long long P) { return act_tiles(P) * (ACT_TILE_PTS / 32) * F8_SCALE_BYTES_PER_BLOCK; }
 NL_HD constexpr long long f8_scale_offset_bytes(int L, long long P) { return 10 * f8_layer_stride(P) + (long long)L * f8_scale_layer_stride(P); }
 NL_HD constexpr long long f8_data_bytes(long long P) { return 10 * f8_layer_stride(P) + 10 * f8_scale_layer_stride(P); }   // dY buffer
-NL_HD constexpr long long f8_mask_region_offset(long long P) { return (f8_data_bytes(P) + 255) / 256 * 256; }
+NL_HD constexpr long long f8_mask_region_offset(long long P) { return align256(f8_data_bytes(P)); }
 NL_HD constexpr long long f8_mask_offset_bytes(int L, long long tile, int dword, long long P) {
     return f8_mask_region_offset(P) + (((long long)L * mask_tiles(P) + tile) * 4 + dword) * 2048;
 }

@@ -20,12 +20,13 @@
 //                                for a live sample and (0, 0, 0, -inf) for a dead one, which contributes exactly nothing.
 // Fixed partitions and hand-written scans, no atomics: every run writes the same bytes.
 #include "composite_device.h"
+#include "launchers.h"
 #include "occ_scan_device.h"
 
 namespace {
 
 constexpr int OCC_RAYS_PER_BLOCK = 4;
-constexpr int OCC_MAX_N = 768;                 // samples per ray (the fused render's own limit, nerf_layout.h)
+constexpr int OCC_MAX_N = nerf_layout::MASKED_MAX_N;      // samples per ray (the fused render's own limit, nerf_layout.h)
 constexpr int OCC_MAX_DILATE = 15;             // 33 + 2 d grid points along z feed one word: one per lane
 constexpr int OCC_SCAN_THREADS = 256;
 constexpr int OCC_SCAN_PER_THREAD = 8;
@@ -234,7 +235,7 @@ struct OccWs {
     long long nblk, off_counts, off_blk, off_blkoff, bytes;
 };
 OccWs occ_ws(long long B) {
-    auto up = [](long long x) { return (x + 255) / 256 * 256; };
+    constexpr auto up = nerf_layout::align256;
     OccWs w;
     w.nblk = (B + OCC_SCAN_ITEMS - 1) / OCC_SCAN_ITEMS;
     w.off_counts = 0;

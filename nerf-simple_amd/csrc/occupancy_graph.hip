@@ -22,9 +22,8 @@ namespace {
 
 constexpr int OCCG_RAYS_PER_BLOCK = 4;
 constexpr int OCCG_THREADS = 64 * OCCG_RAYS_PER_BLOCK;
-constexpr int OCCG_MAX_CHUNKS = 8;             // N <= 512: the masked compositor backward's limit
-constexpr int OCCG_MAX_N = 64 * OCCG_MAX_CHUNKS;
-constexpr long long OCCG_MAX_RAYS = 1ll << 32;
+constexpr int OCCG_MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;      // N <= 512: the masked compositor backward's limit
+constexpr int OCCG_MAX_N = COMPOSITE_BWD_MAX_N;
 
 __device__ __forceinline__ long long occg_min(long long a, long long b) { return a < b ? a : b; }
 
@@ -95,12 +94,9 @@ __global__ __launch_bounds__(OCCG_THREADS) void occ_head_capped_kernel(
 // what both entry points share: 0 = go on, otherwise the code to return.  1 <= C <= B N, so B >= 1.
 int occg_check(const float* rays, const float* u, const float* tbins, uint32_t flags, const uint64_t* mask, const int64_t* offsets,
                int64_t C, int64_t B, int N) {
-    if (B < 0 || N <= 0 || C < 1) return NERF_AMD_EINVAL;
-    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
-    if (N > OCCG_MAX_N || B > OCCG_MAX_RAYS) return NERF_AMD_EUNSUP;
-    if (C > B * (int64_t)N) return NERF_AMD_EINVAL;
-    if (!rays || !mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8)) return NERF_AMD_EINVAL;
-    return 0;
+    if (C < 1) return NERF_AMD_EINVAL;
+    const int rc = masked_rays_check(rays, u, tbins, flags, B, N, N > OCCG_MAX_N);
+    return rc ? rc : capped_check(mask, offsets, C, B, N);
 }
 
 }  // namespace

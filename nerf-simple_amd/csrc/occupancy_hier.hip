@@ -23,7 +23,6 @@ namespace {
 constexpr int OCCH_RAYS_PER_BLOCK = 4;
 constexpr int OCCH_THREADS = 64 * OCCH_RAYS_PER_BLOCK;
 constexpr int OCCH_CHUNKS = nerf_pdf::MAXC / 64;
-constexpr long long OCCH_MAX_RAYS = 1ll << 32;
 
 __device__ __forceinline__ long long occh_min(long long a, long long b) { return a < b ? a : b; }
 
@@ -87,12 +86,11 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward_pdf(const float* raw_l
                                                               const float* u_f, float* rgb, float* d_raw_live, float* ts_out,
                                                               int64_t capacity, int64_t B, int Nc, int Nf, void* stream) {
     // the rules of the two section-14 entry points (occupancy_graph.hip), with the sampler's limits
-    if (B < 0 || Nc <= 0 || Nf < 0 || capacity < 1) return NERF_AMD_EINVAL;
-    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
+    if (Nf < 0 || capacity < 1) return NERF_AMD_EINVAL;
     if (!(flags & NERF_AMD_DEVICE_RNG) && !u_f && Nf > 0) return NERF_AMD_EINVAL;
-    if (Nc < 3 || Nc > nerf_pdf::MAXC || Nc + Nf > nerf_pdf::MAXM || B > OCCH_MAX_RAYS) return NERF_AMD_EUNSUP;
-    if (capacity > B * (int64_t)Nc) return NERF_AMD_EINVAL;
-    if (!rays || !mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8)) return NERF_AMD_EINVAL;
+    int rc = masked_rays_check(rays, u, tbins, flags, B, Nc, nerf_pdf::unsupported_sizes(Nc, Nf));
+    if (!rc) rc = capped_check(mask, offsets, capacity, B, Nc);
+    if (rc) return rc;
     if (!raw_live || !gt || !rgb || !d_raw_live || !ts_out || misaligned(raw_live, 16) || misaligned(d_raw_live, 16) ||
         misaligned(gt, 4) || misaligned(rgb, 4) || misaligned(ts_out, 4) || misaligned(u_f, 4))
         return NERF_AMD_EINVAL;

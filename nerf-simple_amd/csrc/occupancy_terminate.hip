@@ -26,8 +26,6 @@
 namespace {
 
 constexpr int TERM_RAYS_PER_BLOCK = 4;
-constexpr int TERM_MAX_N = 768;                // the mask layout's and the masked compositor's limit
-constexpr long long TERM_MAX_RAYS = 1ll << 32;
 constexpr int TERM_SCAN_THREADS = 256;
 constexpr int TERM_SCAN_PER_THREAD = 8;
 constexpr long long TERM_SCAN_ITEMS = (long long)TERM_SCAN_THREADS * TERM_SCAN_PER_THREAD;      // rays per scan block
@@ -186,7 +184,7 @@ struct TermWs {
     long long nblk, off_cnt, off_rem, off_blk, bytes;      // the carries are the first B floats
 };
 TermWs term_ws(long long B) {
-    auto up = [](long long x) { return (x + 255) / 256 * 256; };
+    constexpr auto up = align256;
     TermWs w;
     w.nblk = (B + TERM_SCAN_ITEMS - 1) / TERM_SCAN_ITEMS;
     w.off_cnt = up(B * 4);
@@ -200,7 +198,7 @@ TermWs term_ws(long long B) {
 
 extern "C" int64_t nerf_amd_termination_workspace_bytes(int64_t B) {
     if (B < 0) return NERF_AMD_EINVAL;
-    if (B > TERM_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (B > MASKED_MAX_RAYS) return NERF_AMD_EUNSUP;
     return term_ws(B).bytes;
 }
 
@@ -210,12 +208,12 @@ extern "C" int nerf_amd_termination_advance(const float* raw_slab, const uint64_
                                             const int64_t* offsets0, float* raw0, int64_t rows0, float eps, int slab, int s0,
                                             int s1, int s2, float* trans, uint64_t* mask_next, int64_t* offsets_next,
                                             int64_t* totals, void* workspace, int64_t B, int N, void* stream) {
-    // the rays and jitter rules of the other masked stages
-    if (B < 0 || N <= 0 || rows_slab < 0 || rows0 < 0) return NERF_AMD_EINVAL;
-    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
+    if (rows_slab < 0 || rows0 < 0) return NERF_AMD_EINVAL;
     if (!(eps > 0.0f && eps < 1.0f)) return NERF_AMD_EINVAL;                    // also NaN
     if (slab != 16 && slab != 32 && slab != 64) return NERF_AMD_EINVAL;
-    if (N > TERM_MAX_N || B > TERM_MAX_RAYS) return NERF_AMD_EUNSUP;
+    // the rays and jitter rules of the other masked stages; N: the mask layout's and the masked compositor's limit
+    const int rc = masked_rays_check(rays, u, tbins, flags, B, N, N > MASKED_MAX_N);
+    if (rc) return rc;
     // the slabs: (0, 0, min(S, N)) at first, then (k S, min((k + 1) S, N), min((k + 2) S, N))
     auto clip = [N](int64_t x) { return (int)(x < N ? x : N); };
     if (s0 < 0 || s0 > s1 || s1 > s2 || s2 > N || s0 % slab != 0) return NERF_AMD_EINVAL;
@@ -235,7 +233,6 @@ extern "C" int nerf_amd_termination_advance(const float* raw_slab, const uint64_
         misaligned(mask_next, 8) || misaligned(offsets_next, 8) || misaligned(totals, 8) ||
         misaligned(workspace, 16))
         return NERF_AMD_EINVAL;
-    if (B > 0 && !rays) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
     (void)hipGetLastError();
     const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);

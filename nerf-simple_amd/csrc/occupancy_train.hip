@@ -10,12 +10,13 @@
 //       bit for bit.  No atomics: row offsets[ray] + rank is written by exactly one lane.
 //   occ_decay_max_kernel -- state = max(fl(state decay), softplus(sigma_now)), softplus as the compositor's.
 #include "composite_backward_device.h"
+#include "launchers.h"
 
 namespace {
 
 constexpr int OCCT_RAYS_PER_BLOCK = 4;
-constexpr int OCCT_MAX_CHUNKS = 8;             // N <= 512, the dense backward's limit
-constexpr int OCCT_MAX_N = 64 * OCCT_MAX_CHUNKS;
+constexpr int OCCT_MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;      // N <= 512, the dense backward's limit
+constexpr int OCCT_MAX_N = nerf_layout::COMPOSITE_BWD_MAX_N;
 
 __global__ __launch_bounds__(64 * OCCT_RAYS_PER_BLOCK) void occ_composite_backward_kernel(
     MlpArgs a, const unsigned long long* __restrict__ mask, const long long* __restrict__ offsets,

@@ -2,6 +2,7 @@
 // MFMA-fragment-ordered weight images streamed by the fused kernels.
 // Runs once per parameter update; one thread per packed element.
 #include "nerf_device.h"
+#include "launchers.h"
 
 using namespace nerf_layout;
 

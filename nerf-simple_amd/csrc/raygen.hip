@@ -8,6 +8,7 @@
 //
 // HBM-bound and tiny: 24 B written per ray, nothing read.
 #include "nerf_device.h"
+#include "launchers.h"
 
 namespace {
 

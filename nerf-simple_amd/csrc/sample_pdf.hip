@@ -10,6 +10,7 @@
 // slots through LDS: 45 stages x 8 exchanges per lane, 26 us per ray; the register sort is ~6x faster.
 // Nc <= 256, Nf <= 512, Nc + Nf <= 512.
 #include "sample_pdf_device.h"
+#include "launchers.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ extern "C" int nerf_amd_launch_sample_pdf(const float* ts, const float* w, const
                                           long long ray_id0, int device_rng, hipStream_t stream) {
     (void)hipGetLastError();
     if (B == 0) return 0;
-    if (Nc < 3 || Nc > MAXC || Nf < 0 || Nc + Nf > MAXM) return -2;
+    if (Nf < 0 || nerf_pdf::unsupported_sizes(Nc, Nf)) return -2;
     const dim3 grid((unsigned)((B + RPB - 1) / RPB)), block(64 * RPB);
     // keys per lane of the register sort: ceil_pow2(Nf) / 64 (nerf_pdf::keys_per_lane)
     if (Nf <= 64) hipLaunchKernelGGL(sample_pdf_kernel<1>, grid, block, 0, stream, ts, w, u, out, B, Nc, Nf, seed, ray_id0, device_rng);

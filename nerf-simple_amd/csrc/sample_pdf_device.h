@@ -23,6 +23,8 @@ namespace nerf_pdf {
 
 constexpr int MAXC = 256;
 constexpr int MAXM = 512;
+// the sizes the sampler serves, for Nc > 0 and Nf >= 0: the one statement of the rule, for the launchers and the C ABI
+__host__ __device__ constexpr bool unsupported_sizes(int Nc, int Nf) { return Nc < 3 || Nc > MAXC || Nc + Nf > MAXM; }
 constexpr unsigned long long RNG_KEY = 0x9e3779b97f4a7c15ull;     // the sampler's counter-RNG key: seed ^ RNG_KEY
 
 // keys per lane of the register sort for Nf new samples: ceil_pow2(Nf) / 64 (1, 2, 4 or 8)

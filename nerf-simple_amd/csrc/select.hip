@@ -31,6 +31,7 @@
 #include <string.h>
 #include <vector>
 #include "nerf_device.h"
+#include "launchers.h"
 
 namespace {
 

@@ -317,7 +317,7 @@ def sample_positions(rays, jit, tbins, flags, seed, ray_id0, N):
 def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels):
     """mark + emit of one masked pass, now (one host read) -> (MarkResult, stats, launch); ``launch(code, image)`` enqueues
     the network on the live points and the masked compositor and returns the 5-tuple, or pixels [B, 4]."""
-    from .rendering import _per_sample
+    from .rendering import _five_outputs, _per_sample
     B, dev = rays.size(0), rays.device
     lib = _lib.lib()
     m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N)
@@ -340,11 +340,7 @@ def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels
                 _lib.check(lib.nerf_amd_volume_render_masked_pixels(*head, _lib.ptr(px), B, N, st),
                            "nerf_amd_volume_render_masked_pixels")
                 return px
-            rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-            disp = torch.empty((B,), dtype=torch.float32, device=dev)
-            acc = torch.empty((B,), dtype=torch.float32, device=dev)
-            alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
-            w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+            rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
             _lib.check(lib.nerf_amd_volume_render_masked(*head, _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha), _lib.ptr(acc),
                                                          _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
         return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
@@ -433,7 +429,7 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
     them (nothing when the slab is empty), advance (retire the rows into raw0, T, select the next slab) -> the masked
     compositor on (raw0, M0): at most K + 1 host reads.  ``occ`` None: the all-live grid."""
     from .nets import guarded_launch
-    from .rendering import _per_sample
+    from .rendering import _five_outputs, _per_sample
     B, dev = rays.size(0), rays.device
     if occ is None:
         occ = all_live_grid(dev)
@@ -503,11 +499,7 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
                 _lib.check(lib.nerf_amd_volume_render_masked_pixels(*chead, _lib.ptr(px), B, N, st),
                            "nerf_amd_volume_render_masked_pixels")
                 return px
-            rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-            disp = torch.empty((B,), dtype=torch.float32, device=dev)
-            acc = torch.empty((B,), dtype=torch.float32, device=dev)
-            alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
-            w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+            rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
             _lib.check(lib.nerf_amd_volume_render_masked(*chead, _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha), _lib.ptr(acc),
                                                          _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
         return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)

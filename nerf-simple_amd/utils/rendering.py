@@ -52,6 +52,15 @@ def _per_sample(t_, N):
     return t_ if (t_ is None or N != 1) else t_[:, :0]
 
 
+def _five_outputs(B, N, outputs, dev):
+    """Uninitialised buffers for (rgb [B,3], disp [B], alpha [B,N], acc [B], w [B,N]); alpha / w only when
+    `outputs` names them, else None (the kernels skip a NULL output)."""
+    def buf(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    rgb, disp, acc = buf(B, 3), buf(B), buf(B)
+    return rgb, disp, buf(B, N) if "alpha" in outputs else None, acc, buf(B, N) if "w" in outputs else None
+
+
 def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS):
     """nerf_outs [B,N,4], ts [B,N], dirs [B,3] -> (rgb [B,3], disp [B], alpha [B,N],
     acc [B], w [B,N])  (reference utils/rendering.py:47-85).  The second output is
@@ -69,11 +78,7 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS):
         return volume_render_autograd(nerf_outs, ts, dirs)
     dev = nerf_outs.device
     raw, ts, dirs = nerf_outs.detach().contiguous(), ts.detach().contiguous(), dirs.detach().contiguous()
-    rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((B,), dtype=torch.float32, device=dev)
-    acc = torch.empty((B,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
-    w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+    rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().nerf_amd_volume_render(
             _lib.ptr(raw), _lib.ptr(ts), _lib.ptr(dirs), 3, _lib.ptr(rgb), _lib.ptr(disp),
@@ -175,11 +180,7 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
 
     def launch(code, packed):
         lib = _lib.lib()
-        rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        disp = torch.empty((B,), dtype=torch.float32, device=dev)
-        acc = torch.empty((B,), dtype=torch.float32, device=dev)
-        alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
-        w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+        rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
         nws = int(lib.nerf_amd_render_workspace_bytes(code, B, N))        # 0: the fused one-launch render
         ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
         with torch.cuda.device(dev):
@@ -217,11 +218,7 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0):
         from ..training import _VolumeRender
         return _VolumeRender.apply(out, ts, rays, True)
     out = out.detach().contiguous()
-    rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-    disp = torch.empty((B,), dtype=torch.float32, device=dev)
-    acc = torch.empty((B,), dtype=torch.float32, device=dev)
-    alpha = torch.empty((B, N), dtype=torch.float32, device=dev) if "alpha" in outputs else None
-    w = torch.empty((B, N), dtype=torch.float32, device=dev) if "w" in outputs else None
+    rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.nerf_amd_volume_render_rays(_lib.ptr(out), _lib.ptr(ts), _lib.ptr(rays), _lib.ptr(rgb), _lib.ptr(disp),
                                                    _lib.ptr(alpha), _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)),

@@ -38,6 +38,65 @@ def test_header_symbols_exported(lib):
     assert sorted(_lib.EXPORTS) == syms
 
 
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+             "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
+
+
+def header_prototypes():
+    """{name: (result type, [argument type, ...])} of every prototype in include/nerf_amd.h, as C type names with the
+    qualifiers and parameter names dropped ("float*", "int64_t", ...)."""
+    text = open(HEADER).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*$", " ", text, flags=re.M)           # preprocessor lines, continued ones too
+    text = text.replace('extern "C"', ";").replace("{", ";").replace("}", ";")
+
+    def ctype(decl, named):
+        words = decl.replace("*", " * ").split()
+        words = [w for w in words if w != "const"]
+        if named and words[-1] != "*":
+            words = words[:-1]                                  # the parameter's name
+        return "".join(words)
+
+    protos = {}
+    for stmt in text.split(";"):
+        m = re.fullmatch(r"\s*(.+?)\b(nerf_amd_[a-z0-9_]+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if not m:
+            assert "nerf_amd_" not in stmt, stmt
+            continue
+        params = m.group(3).strip()
+        args = [] if params == "void" else [ctype(p, True) for p in params.split(",")]
+        assert m.group(2) not in protos, m.group(2)
+        protos[m.group(2)] = (ctype(m.group(1), False), args)
+    return protos
+
+
+def test_ctypes_table_matches_the_header():
+    """Every row of _lib._SIGNATURES is the header's prototype: result type, arity and each argument type.  A pointer is
+    c_void_p (or a typed ctypes pointer to what the header points at); the scalars map by C_SCALARS.  A row with c_int
+    where the header says int64_t would load, pass every name check and corrupt the arguments behind it."""
+    from nerf_simple_amd import _lib
+    protos = header_prototypes()
+    assert sorted(protos) == sorted(_lib._SIGNATURES) and len(protos) >= 90
+
+    def matches(have, want):
+        if want.endswith("*"):
+            if have is ctypes.c_void_p:
+                return True
+            pointee = C_SCALARS.get(want[:-1])
+            return pointee is not None and have is ctypes.POINTER(pointee)
+        return have is C_SCALARS[want]
+
+    for name, (res, args) in protos.items():
+        have_res, have_args = _lib._SIGNATURES[name]
+        assert matches(have_res, res), (name, "result", res, have_res)
+        assert len(have_args) == len(args), (name, "arity", len(args), len(have_args))
+        for i, (h, w) in enumerate(zip(have_args, args)):
+            assert matches(h, w), (name, "argument", i, w, h)
+    # the parser reads what it is given: one wrong scalar width is seen
+    assert not matches(ctypes.c_int, "int64_t") and not matches(ctypes.c_int64, "int") and not matches(ctypes.c_void_p, "int64_t")
+
+
 def test_introspection(lib):
     assert lib.nerf_amd_abi_version() == 5
     assert lib.nerf_amd_param_count() == 595844

@@ -43,7 +43,6 @@ ts = torch.empty(B, N, device=dev)
 pixels = torch.empty(B, 4, device=dev)
 tb = torch.linspace(2, 6, N + 1).to(dev)
 u_buf = torch.rand(B, N, device=dev)
-vp, i64, i32, u32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64
 
 
 class Variant:
@@ -59,13 +58,10 @@ class Variant:
         self.precision = _lib.precision_code(parts[-1])
         self.name = spec
         h = ctypes.CDLL(os.path.abspath(self.path))
-        h.nerf_amd_packed_bytes.restype, h.nerf_amd_packed_bytes.argtypes = i64, [i32]
-        h.nerf_amd_pack_weights.restype, h.nerf_amd_pack_weights.argtypes = i32, [vp, vp, i32, vp]
-        h.nerf_amd_mlp_forward_rays.restype = i32
-        h.nerf_amd_mlp_forward_rays.argtypes = [vp, vp, vp, vp, i32, u32, u64, i64, vp, vp, i64, i32, vp]
-        if self.fused:
-            h.nerf_amd_render_pixels_forward.restype = i32
-            h.nerf_amd_render_pixels_forward.argtypes = [vp, vp, vp, vp, i32, u32, u64, i64, vp, vp, i64, i32, vp]
+        # every build compared here has the in-tree header's prototypes: the binding's table (checked against the header)
+        fused = ("nerf_amd_render_pixels_forward",) if self.fused else ()
+        for fn in ("nerf_amd_packed_bytes", "nerf_amd_pack_weights", "nerf_amd_mlp_forward_rays") + fused:
+            getattr(h, fn).restype, getattr(h, fn).argtypes = _lib._SIGNATURES[fn]
         self.h = h
         self.packed = torch.empty(h.nerf_amd_packed_bytes(self.precision), dtype=torch.uint8, device=dev)
         _lib.check(h.nerf_amd_pack_weights(_lib.ptr(flat), _lib.ptr(self.packed), self.precision,
