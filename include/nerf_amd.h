@@ -795,6 +795,42 @@ int nerf_amd_termination_advance(const float* raw_slab, const uint64_t* mask_sla
                                  float eps, int slab, int s0, int s1, int s2, float* trans, uint64_t* mask_next,
                                  int64_t* offsets_next, int64_t* totals, void* workspace, int64_t B, int N, void* stream);
 
+/* ---- grid-guided fine sampling: importance samples from a sigma volume (csrc/guided_sample.hip) --------------------------
+ * Not in the reference.  tests/guided_model.py restates the look-up and the composition in numpy; DESIGN.md section 21.
+ *
+ * The hierarchical path places its Nf fine samples from the weights of a coarse NETWORK.  Here the weights come from a sigma
+ * VOLUME on a grid instead (nerf_amd_density_grid's output): Nc table look-ups per ray in place of Nc network evaluations.
+ * The guided sample placement is BY DEFINITION this composition of existing entry points plus one exact table look-up:
+ *   1. coarse positions: ts_c[B, Nc] and the points o + d t are those of nerf_amd_query_points for (u, tbins, flags, seed,
+ *      ray_id0).  Every jitter mode is accepted: explicit u, NERF_AMD_TS_GIVEN, NERF_AMD_DEVICE_RNG, and
+ *      NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY.
+ *   2. look-up: V[nx, ny, nz] is fp32 in C order (z fastest) and holds raw sigma at the grid points of the density grid's
+ *      axes, exactly what nerf_amd_density_grid writes.  The cell of a point is the occupancy rule above, op for op: per axis
+ *      c = floor(fl(fl(x - lo) * inv_step)), h_lo[3] and h_inv_step[3] HOST floats.  A point is OUTSIDE when !(0 <= c < n - 1)
+ *      on any axis; a NaN coordinate is outside.  The value inside is the maximum over the cell's 8 corners V[cx + a, cy + b,
+ *      cz + c], a, b, c in {0, 1}; the maximum starts from -inf and skips NaN corners.  The value outside, or in a cell whose
+ *      8 corners are all NaN, is -inf.  There is no rounding anywhere in the look-up, and a NaN in the volume never reaches
+ *      the sampler.
+ *   3. weights: w_c[B, Nc] is the `w` output of nerf_amd_volume_render_rays on raw = (0, 0, 0, value), ts_c and rays.  The
+ *      compositor's softplus applies, so a value of -inf gives alpha = w = 0 exactly.
+ *   4. sampler: ts_out[B, Nc + Nf] = nerf_amd_sample_pdf(ts_c, w_c, u_f, ...): u_f[B, Nf], or with NERF_AMD_DEVICE_RNG that
+ *      entry point's own key (seed, ray_id0).  With NERF_AMD_SEED_IN_MEMORY the 64-bit offset at `u` is added to the seed of
+ *      both draws, exactly as nerf_amd_volume_render_mse_backward_pdf does.  A ray with all-zero weights gets the sampler's
+ *      uniform placement: that is the defined result, not an error.
+ * The guided render is the existing render with NERF_AMD_TS_GIVEN on ts_out; the guided training loss is MSE(rgb, gt) of ONE
+ * network on those positions, and ts_out carries no gradient.
+ *
+ * nerf_amd_sample_pdf_volume: one launch, one wavefront per ray; w_c stays in LDS unless asked for.  sigma_c[B, Nc] (the
+ *   look-up's values) and w_c[B, Nc] are optional outputs (NULL: not written); ts_out does not depend on them.
+ *   Checked on the host before any launch, in this order -- NERF_AMD_EINVAL: Nf < 0, B < 0, Nc <= 0, unknown flags or a jitter
+ *   tensor missing; NERF_AMD_EUNSUP: Nc < 3, Nc > 256, Nc + Nf > 512, B > 2^32; NERF_AMD_EINVAL: an axis < 2, no u_f without
+ *   the counter RNG when Nf > 0; B = 0: nothing is launched or written; NERF_AMD_EINVAL: a NULL rays, sigma_volume, h_lo,
+ *   h_inv_step or ts_out, or a device buffer not aligned to 4 bytes.  No atomics: two runs write the same bytes. */
+int nerf_amd_sample_pdf_volume(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
+                               int64_t ray_id0, const float* sigma_volume, int64_t nx, int64_t ny, int64_t nz,
+                               const float* h_lo, const float* h_inv_step, const float* u_f, float* ts_out, float* sigma_c,
+                               float* w_c, int64_t B, int Nc, int Nf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

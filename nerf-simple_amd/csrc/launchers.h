@@ -28,6 +28,8 @@ int nerf_amd_launch_composite(const float*, const float*, const float*, long lon
                               float*, float*, float*, long long, int, int, float*, hipStream_t);
 int nerf_amd_launch_sample_pdf(const float*, const float*, const float*, float*, long long, int, int,
                                unsigned long long, long long, int, hipStream_t);
+int nerf_amd_launch_sample_pdf_volume(const MlpArgs*, const float*, long long, long long, long long, const float*, const float*,
+                                      const float*, float*, float*, float*, int, hipStream_t);
 int nerf_amd_launch_generate_rays(const float*, int, int, float, long long, long long, float*, hipStream_t);
 int nerf_amd_launch_composite_backward(const float*, const float*, const float*, long long, const float*,
                                        const float*, const float*, const float*, const float*, float*,

@@ -595,6 +595,50 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
 
 
 # --------------------------------------------------------------------------
+# grid-guided fine sampling: ONE network, its Nf new samples placed from a sigma volume
+# --------------------------------------------------------------------------
+def _check_guided(net, proposal, precision=None):
+    """The guided steps' limits, checked before anything is drawn or launched."""
+    from .utils.nets import Nerf
+    from .utils.proposal import ProposalVolume
+    if not isinstance(proposal, ProposalVolume):
+        raise TypeError("proposal must be a ProposalVolume (utils/proposal.py)")
+    if not (isinstance(net, Nerf) and net._fused_ok()):
+        raise RuntimeError("guided sampling serves the default Nerf(10, 4, 256) only: other network sizes and foreign nets "
+                           "are not supported; nothing falls back")
+    return _lib.precision_code(net.precision if precision is None else precision)
+
+
+def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, ts_c=None, u_f=None, decay=1.0,
+                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0):
+    """One optimisation step of ONE network on grid-guided positions: ts = ``proposal.sample(rays, Nc, Nf, ...)`` (a
+    ``ProposalVolume``, utils/proposal.py: no network evaluation, no gradient) -> zero_grad -> render_nerf with gradients on those
+    Nc + Nf positions -> MSE(rgb, gt) -> backward -> [grad all-reduce] -> optimizer.step -> lr *= decay.  The loss is that of
+    the existing eager step on the same explicit ``ts``, bit for bit; nothing of ``proposal`` receives a gradient.
+    Jitter as ``ProposalVolume.sample`` (default: render_hierarchical's draws, torch.rand(B,Nc) then torch.rand(B,Nf) from
+    torch's CPU generator).  Refreshing the volume (``proposal.update(net)``) is the caller's schedule.
+    Returns the detached loss; ``.ts`` on it holds the positions."""
+    from . import parallel
+    _check_guided(net, proposal, precision)
+    proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng)         # before any draw: a refused call changes nothing
+    ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+    rays = rays.detach().contiguous()
+    optimizer.zero_grad(set_to_none=True)
+    outs, _ = _render_train_with_ts(rays, net, int(Nc) + int(Nf), tn, tf, ts, _lib.FLAG_TS_GIVEN,
+                                    net.precision if precision is None else precision, seed, ray_id0)
+    loss = mse_loss(outs[0], gt)
+    loss.backward()
+    parallel.allreduce_gradients(net.parameters(), group=group)
+    optimizer.step()
+    if decay != 1.0:
+        for pg in optimizer.param_groups:
+            pg["lr"] = pg["lr"] * decay
+    out = loss.detach()
+    out.ts = ts
+    return out
+
+
+# --------------------------------------------------------------------------
 # the same step as ONE captured hipGraph (launch-bound at 4096-ray batches)
 # --------------------------------------------------------------------------
 class _HyperRing:
@@ -1041,7 +1085,7 @@ class GraphedTrainStep:
     def _forward_backward(self, bucket=0):
         """The one forward / backward sequence of every graphed step:
 
-            hyper fetch -> per pass: forward -> head                                                     (main)
+            hyper fetch -> [_before_forward: a subclass's own launches] -> per pass: forward -> head     (main)
             -> fork -> per pass: dX chain  ||  side: per pass encoder rows; per pass loss + dW begin;
                                                [loss sum]; [the next batch's selection]
             -> join -> per pass: dW finish (all products, or with ``bucket`` = 1 only those of the late layers:
@@ -1053,6 +1097,7 @@ class GraphedTrainStep:
         st, ss = ctypes_stream(main), ctypes_stream(side)
         # first node: this step's scalars (Adam's, the jitter seed offset) from the pinned host ring into `hyper`
         self._ring.fetch(self.hyper, self.dev)
+        self._before_forward(st)
         for p in self.passes[:-1]:
             p.forward(st)
             self._coarse_head(p, st)                # writes ts_f, which the next pass's forward (and mark) reads
@@ -1085,6 +1130,9 @@ class GraphedTrainStep:
         main.wait_stream(side)
         for p in self.passes:
             p.finish(bucket, st)
+
+    def _before_forward(self, st):
+        """What a stepper enqueues between the hyper fetch and the first forward, on the main branch: nothing here."""
 
     def _coarse_head(self, c, st):
         """rgb_c, d_raw_c and the fine positions ts_f from the coarse weights, which never reach HBM: one launch.
@@ -1574,5 +1622,89 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
     def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
         self._watch_grid()
         return super().step(rays, gt, u_c=u_c, u_f=u_f, decay=decay)
+
+    __call__ = step
+
+
+class GraphedGuidedTrainStep(GraphedTrainStep):
+    """``train_step_guided`` as captured hipGraphs: GraphedTrainStep with its one dense pass at
+    N = Nc + Nf under NERF_AMD_TS_GIVEN, and ONE more node in graph A:
+
+        graph A: hyper fetch -> guided sampler (nerf_amd_sample_pdf_volume: coarse positions, look-up in the proposal's sigma
+                 volume, weights, sample_pdf; writes ``ts_f`` [B, Nc+Nf]) -> training forward on ts_f -> head -> ...: the rest
+                 is GraphedTrainStep's, and so are graph B, the exchange seam, ``rays_from`` and ``check_every``.
+
+    ``proposal``: a ``ProposalVolume`` on the module's device.  The address of its ``sigma`` is baked into the graph (``step``
+    raises if the tensor was replaced); ``ProposalVolume.update`` writes in place, so an update between two replays simply
+    takes effect.  Jitter: default the reference-style CPU draws torch.rand(B,Nc) then torch.rand(B,Nf) (one draw of
+    B*(Nc+Nf) from the same stream, continued on the device), or ``step(..., u_c=, u_f=)``; ``device_rng=True`` keys both draws
+    by seed + step, read from device memory (the eager step's values with ``seed=seed + k`` at step k).
+    ``optimizer`` is ``optim.FusedAdam(net)``: one network, one Adam launch.  bf16 storage, one exchange bucket."""
+
+    _one_bucket = True
+
+    def __init__(self, net, optimizer, n_rays, Nc, Nf, proposal, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+        from .utils.proposal import check_sizes
+        _MaskedSteps._refuse(self, storage, buckets)
+        _check_guided(net, proposal)
+        self.Nc, self.Nf = check_sizes(Nc, Nf)
+        if int(n_rays) < 1:
+            raise ValueError(f"GraphedGuidedTrainStep needs n_rays >= 1 (got {n_rays})")
+        self._check_modules(net, optimizer)
+        if proposal.sigma.device != optimizer.flat.device:
+            raise RuntimeError(f"the proposal volume lives on {proposal.sigma.device}, the module on {optimizer.flat.device}")
+        proposal.check(torch.empty((0, 6), dtype=torch.float32, device=proposal.sigma.device), self.Nc, self.Nf)
+        self.proposal, self._sigma_ptr = proposal, proposal.sigma.data_ptr()
+        super().__init__(net, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        """The dense pass reads given positions: ``ts_f``, which the sampler writes.  ``u`` [B, Nc+Nf] of the reference
+        stream is the pair's: its first B*Nc values are torch.rand(B,Nc) = ``u_c``, the rest torch.rand(B,Nf) = ``u_f``."""
+        from .utils.rendering import _tbins
+        super()._alloc_pass_buffers(tn, tf)
+        ptr, B, Nc, Nf, dev = _lib.ptr, self.B, self.Nc, self.Nf, self.dev
+        self.tbins = _tbins(tn, tf, Nc, dev)                        # of the COARSE positions, the only ones drawn from bins
+        flat_u = self.u.view(-1)
+        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, Nf)
+        self.ts_f = torch.empty((B, Nc + Nf), dtype=torch.float32, device=dev)
+        if self.device_rng:
+            self._coarse_jitter = (ptr(self.rays), self._seed_mem, ptr(self.tbins),
+                                   _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY, self.seed, self.ray_id0)
+        else:
+            self._coarse_jitter = (ptr(self.rays), ptr(self.u_c), ptr(self.tbins), 0, 0, 0)
+        self.passes[0].jitter = (ptr(self.rays), ptr(self.ts_f), None, _lib.FLAG_TS_GIVEN, 0, 0)
+
+    def _before_forward(self, st):
+        import ctypes
+        p = self.proposal
+        _launch("nerf_amd_sample_pdf_volume", *self._coarse_jitter, ctypes.c_void_p(self._sigma_ptr), *p.resolution, p._h_lo,
+                p._h_inv_step, None if self.device_rng else _lib.ptr(self.u_f), _lib.ptr(self.ts_f), None, None, self.B, self.Nc,
+                self.Nf, st)
+
+    def _range_check(self):
+        """The reference's |x| > 1 warning on the coarse positions' first / last samples (the new ones lie between)."""
+        from .utils.xyz import range_check_rays
+        _, jit, _, flags, seed, rid = self._coarse_jitter
+        range_check_rays(self.rays, jit, self.tbins, flags, seed, rid, self.Nc)
+
+    def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
+        if self.proposal.sigma.data_ptr() != self._sigma_ptr:
+            raise RuntimeError("the proposal's sigma tensor was replaced: its address is baked into the captured graph "
+                               "(ProposalVolume.update writes in place); build a new GraphedGuidedTrainStep")
+        if (u_c is None) != (u_f is None):
+            raise RuntimeError("step(): u_c and u_f come together (or neither)")
+        u = None
+        if u_c is not None:
+            if tuple(u_c.shape) != tuple(self.u_c.shape) or tuple(u_f.shape) != tuple(self.u_f.shape):
+                raise RuntimeError(f"u_c / u_f must be {tuple(self.u_c.shape)} / {tuple(self.u_f.shape)}")
+            if self.device_rng:
+                raise RuntimeError("this GraphedGuidedTrainStep draws its jitter on the device (device_rng=True): "
+                                   "u_c / u_f must be None")
+            self.u_c.copy_(u_c, non_blocking=True)
+            self.u_f.copy_(u_f, non_blocking=True)
+            u = self.u
+        return super().step(rays, gt, u=u, decay=decay)
 
     __call__ = step

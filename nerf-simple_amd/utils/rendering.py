@@ -660,3 +660,56 @@ def render_hierarchical_sharded(net_coarse, net_fine, pose, cam_params, Nc=64, N
                                      u_c=None if u_c is None else u_c[lo:hi], u_f=None if u_f is None else u_f[lo:hi],
                                      **kw)
     return parallel.gather_pixels(shard, n, group)
+
+
+def _check_guided(net, proposal):
+    from .proposal import ProposalVolume
+    if not isinstance(proposal, ProposalVolume):
+        raise TypeError("proposal must be a ProposalVolume (utils/proposal.py)")
+    if not (isinstance(net, Nerf) and net._fused_ok()):
+        raise RuntimeError("guided sampling serves the default Nerf(10, 4, 256) only: other network sizes and foreign nets "
+                           "are not supported; nothing falls back")
+
+
+def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=None, u_f=None, outputs=ALL_OUTPUTS,
+                  precision=None, device_rng=False, seed=0, ray_id0=0):
+    """Grid-guided render: ONE network on Nc + Nf positions per ray, the Nf new ones placed by
+    ``proposal`` (a ``ProposalVolume``, utils/proposal.py) from its sigma volume instead of by a coarse network.  It is
+    ``render_nerf(rays, net, Nc + Nf, ts=proposal.sample(rays, Nc, Nf, ...))``; jitter arguments as ``ProposalVolume.sample``
+    (default: ``render_hierarchical``'s two CPU draws).  Returns render_nerf's five outputs plus ts [B, Nc + Nf].  Default
+    network shape only; no gradients to the rays; no host synchronisation beyond the fp16 range guard's."""
+    _check_guided(net, proposal)
+    B, Nc, Nf = proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng)
+    if not (torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())):
+        net.packed_weights(_lib.precision_code(net.precision if precision is None else precision))     # errors before the draws
+    ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+    return render_nerf(rays, net, Nc + Nf, tn, tf, ts=ts, outputs=outputs, precision=precision) + (ts,)
+
+
+def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, u_f=None, ray0=0, n_rays=None,
+                       precision=None, device_rng=False, seed=0):
+    """One view (or its pixel range [ray0, ray0 + n_rays)) through the grid-guided render: device ray generation ->
+    ``proposal.sample`` (counter RNG keyed by global pixel id with device_rng=True) -> the fused render on the given
+    positions -> clip(rgb, 0, 1).  Returns pixels [n, 4] = [r, g, b, disparity] on the GPU.  u_c [n, Nc] / u_f [n, Nf]:
+    explicit uniforms for these pixels; default: the CPU draws torch.rand(n, Nc) then torch.rand(n, Nf)."""
+    _check_guided(net, proposal)
+    dev = next(net.parameters()).device
+    n = int(cam_params[0]) * int(cam_params[1]) - ray0 if n_rays is None else int(n_rays)
+    code = _lib.precision_code(net.precision if precision is None else precision)
+    net.packed_weights(code)
+    rays = generate_rays(pose, cam_params, dev, ray0, n)
+    ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray0)
+    N, lib = ts.size(1), _lib.lib()
+
+    def launch(code, packed):
+        pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        nws = int(lib.nerf_amd_render_workspace_bytes(code, n, N))
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_render_pixels_forward(
+                _lib.ptr(rays), _lib.ptr(ts), None, _lib.ptr(packed[0]), code, _lib.FLAG_TS_GIVEN, int(seed), int(ray0),
+                _lib.ptr(pixels), _lib.ptr(ws), n, N, _lib.stream_ptr(dev)), "nerf_amd_render_pixels_forward")
+        return pixels
+
+    with torch.no_grad():
+        return guarded_launch([net], code, launch)
