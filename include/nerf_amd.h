@@ -831,6 +831,57 @@ int nerf_amd_sample_pdf_volume(const float* rays, const float* u, const float* t
                                const float* h_lo, const float* h_inv_step, const float* u_f, float* ts_out, float* sigma_c,
                                float* w_c, int64_t B, int Nc, int Nf, void* stream);
 
+/* ---- background colour and sigma noise for the dense training path ----------------------------------------------------
+ * Two controls every NeRF trainer offers and the reference does not (white_bkgd and raw_noise_std elsewhere; the noise is the
+ * reference's own `## TODO add gaussian noise regularizer`, utils/rendering.py:63).  Dense single-network path only.
+ *
+ * nerf_amd_sigma_noise: raw[B,N,4] -> out[B,N,4] (out may be raw): the colours are copied, sigma' = sigma + std z goes in
+ *   column 3 (two rounded ops; it replaces sigma in front of the softplus, utils/rendering.py:63-64, d sigma' / d sigma = 1).
+ *   z = sqrt(-2 ln u1) cos(2 pi u2) is a standard normal from the counter RNG whatever the jitter source is: key =
+ *   (seed + offset) ^ NOISE_KEY -- a key of its own, apart from the jitter's, the sampler's and the ray selection's --
+ *   where offset is 0, or with flags = NERF_AMD_SEED_IN_MEMORY the uint64 at the DEVICE ADDRESS seed_mem (8-byte aligned;
+ *   a node of a replayed graph: step k draws what seed + k draws); sample (ray_id0 + ray) N + i owns the counters
+ *   2 s and 2 s + 1, so the noise does not depend on how the rays are batched or sharded.  u1 in (0, 1] from the top 24
+ *   bits of the first word plus one, u2 in [0, 1) from the second.  std == 0: out = raw, no noise code runs.
+ *   NERF_AMD_EINVAL: B < 0, N <= 0; std < 0 or not finite; any other flag; NERF_AMD_SEED_IN_MEMORY with a NULL or
+ *   misaligned seed_mem -- in this order, all before the empty problem (B == 0: nothing is launched) and the pointers.
+ *   A training control: the inference renders do not take it. */
+int nerf_amd_sigma_noise(const float* raw, float* out, float std, uint32_t flags, uint64_t seed, const uint64_t* seed_mem,
+                         int64_t ray_id0, int64_t B, int N, void* stream);
+
+/* nerf_amd_background_blend: a background colour behind the volume, applied to a ray's composited rgb[B,3] and acc[B]:
+ *   rgb_bg[c] = rgb[c] + (1 - acc) bg[c], the subtraction, the product and the sum each rounded on its own (no fma), so the
+ *   torch fp32 expression rgb + (1 - acc) * bg has the same bits.  bg: one colour [3] (bg_stride = 0) or one per ray [B,3]
+ *   (bg_stride = 3, in floats); it carries no gradient.  Outputs, either may be NULL (not both): rgb_out[B,3] = rgb_bg and
+ *   pixels[B,4] = [clip(rgb_bg, 0, 1), disp] -- the clip comes after the blend and passes NaN through, as the compositor's
+ *   does (utils/rendering.py:103-105); disp[B] is read for pixels only.  disp, alpha, acc and w are what they were.  At
+ *   N == 1 (rgb = acc = 0) rgb_bg = bg exactly.
+ * nerf_amd_background_blend_backward: g_rgb passes through; g_acc[B] = -((g0 bg0 + g1 bg1) + g2 bg2) from g = g_rgb_bg[B,3],
+ *   every product and sum rounded on its own, in that order.  g_acc is WRITTEN, not accumulated: the caller adds its own
+ *   term and hands the sum to nerf_amd_volume_render_rays_backward.
+ * Both: NERF_AMD_EINVAL for B < 0, then for bg_stride not in {0, 3}; B == 0 launches nothing; then NERF_AMD_EINVAL for a
+ *   missing pointer. */
+int nerf_amd_background_blend(const float* rgb, const float* acc, const float* disp, const float* bg, int64_t bg_stride,
+                              float* rgb_out, float* pixels, int64_t B, void* stream);
+int nerf_amd_background_blend_backward(const float* g_rgb_bg, const float* bg, int64_t bg_stride, float* g_acc, int64_t B,
+                                       void* stream);
+
+/* nerf_amd_volume_render_mse_backward_bg: the training head with both controls, ONE launch.  By definition, bit for bit
+ *   (tests/test_gpu_background.py), it is the composition
+ *     nerf_amd_sigma_noise (std, flags, seed, seed_mem, ray_id0)          (the regulariser of utils/rendering.py:63)
+ *     -> nerf_amd_volume_render_rays (rgb, acc) -> nerf_amd_background_blend
+ *     -> g = 2 (rgb_bg - target) / (3 B), as nerf_amd_volume_render_mse_backward forms it
+ *     -> nerf_amd_background_blend_backward -> nerf_amd_volume_render_rays_backward (g_rgb = g, g_acc)
+ *   raw, ts, rays, target[B,3] -> rgb[B,3] = rgb_bg (may be NULL; nerf_amd_mse_loss on it is the step's loss) and
+ *   d_raw[B,N,4].  Each sample's noise is generated once, as its chunk is loaded.  bg == NULL: no background (bg_stride is
+ *   still checked); std == 0: no noise; with both it IS nerf_amd_volume_render_mse_backward.  N <= 512 (NERF_AMD_EUNSUP
+ *   beyond); at N == 1 rgb = bg (0 without one) and d_raw = 0.  Rules in order: sizes; the noise arguments as in
+ *   nerf_amd_sigma_noise; bg_stride; B == 0; the size limit; the pointers. */
+int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, const float* rays, const float* target,
+                                           const float* bg, int64_t bg_stride, float std, uint32_t flags, uint64_t seed,
+                                           const uint64_t* seed_mem, int64_t ray_id0, float* rgb, float* d_raw, int64_t B, int N,
+                                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,11 @@ _SIGNATURES = {
                                           _i64, _i32, _i32, _vp]),
     "nerf_amd_volume_render_mse_backward_pdf": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _i64,
                                                        _i32, _i32, _vp]),
+    "nerf_amd_sigma_noise": (_i32, [_vp, _vp, ctypes.c_float, _u32, _u64, _vp, _i64, _i64, _i32, _vp]),
+    "nerf_amd_background_blend": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "nerf_amd_background_blend_backward": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "nerf_amd_volume_render_mse_backward_bg": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_float, _u32, _u64, _vp, _i64,
+                                                      _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_render_hierarchical_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "nerf_amd_render_hierarchical_forward": (_i32, [_vp, _i32, _i32, ctypes.c_float, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
                                                     _i32, _u32, _u64, _vp, _vp, _i32, _i32, _vp]),

@@ -336,6 +336,51 @@ int nerf_amd_volume_render_mse_backward_pdf(const float* raw, const float* ts, c
                                                       (flags & NERF_AMD_SEED_IN_MEMORY) ? 1 : 0, S(stream));
 }
 
+// Order of the rules of the four entry points below: sizes; the noise arguments (api_checks.h bad_sigma_noise); the background's
+// stride; the empty problem; the size limit (NERF_AMD_EUNSUP); the pointers.
+int nerf_amd_sigma_noise(const float* raw, float* out, float std, uint32_t flags, uint64_t seed, const uint64_t* seed_mem,
+                         int64_t ray_id0, int64_t B, int N, void* stream) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_sigma_noise(std, flags, seed_mem)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (!raw || !out) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_sigma_noise(raw, out, std, seed, (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
+                                       ray_id0, B, N, S(stream));
+}
+
+int nerf_amd_background_blend(const float* rgb, const float* acc, const float* disp, const float* bg, int64_t bg_stride,
+                              float* rgb_out, float* pixels, int64_t B, void* stream) {
+    if (B < 0) return NERF_AMD_EINVAL;
+    if (bad_bg_stride(bg_stride)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (!rgb || !acc || !bg || (!rgb_out && !pixels) || (pixels && !disp)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_background_blend(rgb, acc, disp, bg, bg_stride, rgb_out, pixels, B, S(stream));
+}
+
+int nerf_amd_background_blend_backward(const float* g_rgb_bg, const float* bg, int64_t bg_stride, float* g_acc, int64_t B,
+                                       void* stream) {
+    if (B < 0) return NERF_AMD_EINVAL;
+    if (bad_bg_stride(bg_stride)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (!g_rgb_bg || !bg || !g_acc) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_background_blend_backward(g_rgb_bg, bg, bg_stride, g_acc, B, S(stream));
+}
+
+int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, const float* rays, const float* target,
+                                           const float* bg, int64_t bg_stride, float std, uint32_t flags, uint64_t seed,
+                                           const uint64_t* seed_mem, int64_t ray_id0, float* rgb, float* d_raw, int64_t B, int N,
+                                           void* stream) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_sigma_noise(std, flags, seed_mem)) return NERF_AMD_EINVAL;
+    if (bad_bg_stride(bg_stride)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
+    if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_composite_mse_backward_bg(raw, ts, rays, target, bg, bg_stride, std, seed,
+                                                     (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
+                                                     ray_id0, rgb, d_raw, B, N, S(stream));
+}
+
 int nerf_amd_mse_loss(const float* pred, const float* target, float* loss, float* g_pred, int64_t n, void* stream) {
     if (n <= 0 || !pred || !target || !loss) return NERF_AMD_EINVAL;
     return nerf_amd_launch_mse_loss(pred, target, loss, g_pred, n, S(stream));

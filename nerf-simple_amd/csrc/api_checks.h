@@ -32,6 +32,17 @@ __attribute__((used)) inline bool bad_jitter(uint32_t flags, const float* u, con
     return !(flags & NERF_AMD_TS_GIVEN) && !tbins;
 }
 
+// the sigma-noise arguments (nerf_amd_sigma_noise, nerf_amd_volume_render_mse_backward_bg): std finite and >= 0; the only flag
+// is NERF_AMD_SEED_IN_MEMORY, and with it `seed_mem` is the 8-byte aligned device address of the step offset (without it
+// `seed_mem` is not looked at).  Applied whatever std is: std == 0 launches no noise code but the call is still checked.
+inline bool bad_sigma_noise(float std, uint32_t flags, const uint64_t* seed_mem) {
+    if (!(std >= 0.f) || std > 3.402823466e38f) return true;                   // negative, NaN, inf
+    if (flags & ~NERF_AMD_SEED_IN_MEMORY) return true;
+    return (flags & NERF_AMD_SEED_IN_MEMORY) && (!seed_mem || misaligned(seed_mem, 8));
+}
+// a background: one colour (stride 0) or one per ray (stride 3), in floats; looked at whether or not `bg` is given
+inline bool bad_bg_stride(int64_t bg_stride) { return bg_stride != 0 && bg_stride != 3; }
+
 // the rays and jitter of a rays-mode launch whose kernels form the sample positions themselves
 inline MlpArgs rays_args(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0,
                          int64_t B, int N) {

@@ -16,7 +16,8 @@
 //
 // The three axes on which the callers differ are compile-time choices; a term a caller does not have is not computed.
 //   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd)
-//   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; MseHead: the loss gradient formed here)
+//   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; MseHead: the loss gradient formed here;
+//           BgMseHead: the same behind a background colour, whose gradient to acc reaches every w_i)
 //   Sink -- where the forward sweep's weights go (NoSink; PdfSink: the sampler's LDS slice, sample_pdf_device.h)
 #pragma once
 #include "composite_device.h"
@@ -97,6 +98,21 @@ struct MseHead {                       // loss = MSELoss(rgb, target) (train.py:
     float scale;                       // 1 / (3 B)
 };
 
+// The MSE head behind a background colour: rgb_bg = rgb + (1 - acc) bg (two rounded ops per channel, no fma), loss =
+// MSELoss(rgb_bg, target).  By definition the chain  compositor (rgb, acc) -> blend -> 2 (rgb_bg - target) scale -> the
+// blend's backward (g_rgb passes through, g_acc = -((g0 bg0 + g1 bg1) + g2 bg2)) -> compositor backward (g_rgb, g_acc),
+// bit for bit: acc is summed with the forward compositor's ops, g_acc joins G_i where FiveGrads adds gac.
+struct BgMseHead {
+    static constexpr bool MSE = true;
+    const float* target;               // [B,3]
+    float* rgb_out;                    // [B,3]: rgb_bg, or NULL
+    float scale;                       // 1 / (3 B)
+    const float* bg;                   // one colour [3] (bg_stride 0) or one per ray [B,3] (bg_stride 3); no gradient
+    long long bg_stride;
+};
+template <class Up> inline constexpr bool behind_background = false;
+template <> inline constexpr bool behind_background<BgMseHead> = true;
+
 // ---- weight sinks ----------------------------------------------------------------------------------------------------------
 struct NoSink {
     __device__ __forceinline__ void put(int, float, float) const {}
@@ -120,6 +136,7 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
     int rk[CHUNKS];
     float carry = 1.0f, depth = 0.f, accw = 0.f;
     float sr = 0.f, sg = 0.f, sb = 0.f;            // MSE head: the forward's rgb, for the loss gradient
+    float sa = 0.f;                                // ... behind a background: the forward's acc
 #pragma unroll
     for (int ch = 0; ch < CHUNKS; ++ch) {
         const int base = ch * 64;
@@ -157,6 +174,7 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
                 if constexpr (Up::MSE) {
                     // the same ops as the forward compositor (composite_device.h), so rgb_out equals its rgb
                     sr = __fmaf_rn(wt, cc[ch][0], sr); sg = __fmaf_rn(wt, cc[ch][1], sg); sb = __fmaf_rn(wt, cc[ch][2], sb);
+                    if constexpr (behind_background<Up>) sa = add_rn(sa, wt);
                 } else {
                     depth = add_rn(depth, mul_rn(wt, tt[ch])); accw = add_rn(accw, wt);
                 }
@@ -169,9 +187,17 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
     float gr, gg, gb, gdep = 0.f, gac = 0.f;
     if constexpr (Up::MSE) {
         sr = wave_total(sr); sg = wave_total(sg); sb = wave_total(sb);
+        float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+        if constexpr (behind_background<Up>) {     // sr, sg, sb become rgb_bg: the loss's prediction and the rgb output
+            const float* bg = up.bg + ray * up.bg_stride;
+            b0 = bg[0]; b1 = bg[1]; b2 = bg[2];
+            const float through = sub_rn(1.0f, wave_total(sa));
+            sr = add_rn(sr, mul_rn(through, b0)); sg = add_rn(sg, mul_rn(through, b1)); sb = add_rn(sb, mul_rn(through, b2));
+        }
         gr = mul_rn(mul_rn(2.0f, sub_rn(sr, up.target[ray * 3 + 0])), up.scale);
         gg = mul_rn(mul_rn(2.0f, sub_rn(sg, up.target[ray * 3 + 1])), up.scale);
         gb = mul_rn(mul_rn(2.0f, sub_rn(sb, up.target[ray * 3 + 2])), up.scale);
+        if constexpr (behind_background<Up>) gac = -add_rn(add_rn(mul_rn(gr, b0), mul_rn(gg, b1)), mul_rn(gb, b2));
         if (up.rgb_out && lane == 0) { up.rgb_out[ray * 3 + 0] = sr; up.rgb_out[ray * 3 + 1] = sg; up.rgb_out[ray * 3 + 2] = sb; }
     } else {
         depth = wave_sum(depth); accw = wave_sum(accw);
@@ -199,6 +225,7 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
             float G = 0.f;
             if (valid) {
                 G = add_rn(add_rn(mul_rn(gr, cc[ch][0]), mul_rn(gg, cc[ch][1])), mul_rn(gb, cc[ch][2]));
+                if constexpr (behind_background<Up>) G = add_rn(G, gac);
                 if constexpr (!Up::MSE) {
                     G = add_rn(add_rn(G, mul_rn(gdep, tt[ch])), gac);
                     if (up.g_w) G = add_rn(G, up.g_w[ray * N + i]);

@@ -88,4 +88,12 @@ int nerf_amd_occ_train_max_n(void);
 int nerf_amd_launch_occ_composite_backward(const MlpArgs*, const unsigned long long*, const long long*, const float*, const float*,
                                            const float*, const float*, const float*, const float*, float*, long long, hipStream_t);
 int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
+int nerf_amd_launch_sigma_noise(const float*, float*, float, unsigned long long, const unsigned long long*, long long, long long,
+                                int, hipStream_t);
+int nerf_amd_launch_background_blend(const float*, const float*, const float*, const float*, long long, float*, float*,
+                                     long long, hipStream_t);
+int nerf_amd_launch_background_blend_backward(const float*, const float*, long long, float*, long long, hipStream_t);
+int nerf_amd_launch_composite_mse_backward_bg(const float*, const float*, const float*, const float*, const float*, long long,
+                                              float, unsigned long long, const unsigned long long*, long long, float*, float*,
+                                              long long, int, hipStream_t);
 }

@@ -26,6 +26,9 @@ constexpr int MAXM = 512;
 // the sizes the sampler serves, for Nc > 0 and Nf >= 0: the one statement of the rule, for the launchers and the C ABI
 __host__ __device__ constexpr bool unsupported_sizes(int Nc, int Nf) { return Nc < 3 || Nc > MAXC || Nc + Nf > MAXM; }
 constexpr unsigned long long RNG_KEY = 0x9e3779b97f4a7c15ull;     // the sampler's counter-RNG key: seed ^ RNG_KEY
+// the sigma-noise regulariser's key ("noise:v1"): noise_seed ^ NOISE_KEY (sigma_noise_device.h); apart from RNG_KEY, from the
+// ray selection's key (select.hip SEL_KEY) and from the stratified jitter's, which is the bare seed
+constexpr unsigned long long NOISE_KEY = 0x6e6f6973653a7631ull;
 
 // keys per lane of the register sort for Nf new samples: ceil_pow2(Nf) / 64 (1, 2, 4 or 8)
 __host__ __device__ constexpr int keys_per_lane(int Nf) { return Nf <= 64 ? 1 : Nf <= 128 ? 2 : Nf <= 256 ? 4 : 8; }

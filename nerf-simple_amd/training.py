@@ -147,6 +147,67 @@ def volume_render_autograd(nerf_outs, ts, dirs):
 
 
 # --------------------------------------------------------------------------
+# the two training controls around the dense compositor
+# --------------------------------------------------------------------------
+class _SigmaNoise(torch.autograd.Function):
+    """raw [B,N,4] -> the same with sigma' = sigma + std z in column 3 (nerf_amd_sigma_noise; the reference's
+    `## TODO add gaussian noise regularizer`, utils/rendering.py:63).  d sigma' / d sigma = 1: the backward is the identity."""
+
+    @staticmethod
+    def forward(ctx, raw, std, noise_seed, ray_id0):
+        B, N = raw.shape[0], raw.shape[1]
+        dev = raw.device
+        raw = raw.contiguous()
+        out = torch.empty_like(raw)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_sigma_noise(_lib.ptr(raw), _lib.ptr(out), float(std), 0, int(noise_seed) & (2 ** 64 - 1),
+                                                       None, int(ray_id0), B, N, _lib.stream_ptr(dev)), "nerf_amd_sigma_noise")
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None, None
+
+
+class _Background(torch.autograd.Function):
+    """(rgb [B,3], acc [B]) -> rgb_bg = rgb + (1 - acc) bg (nerf_amd_background_blend); backward: g_rgb passes through,
+    g_acc from nerf_amd_background_blend_backward -- autograd adds it to whatever else reaches acc, and the sum enters
+    the compositor's backward, which already takes g_acc.  ``bg`` [3] (stride 0) or [B,3] (stride 3) carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, rgb, acc, bg, stride):
+        from .utils.rendering import _blend
+        rgb, acc = rgb.contiguous(), acc.contiguous()
+        ctx.save_for_backward(bg)
+        ctx.stride = stride
+        return _blend(rgb, acc, None, bg, stride)
+
+    @staticmethod
+    def backward(ctx, g):
+        (bg,) = ctx.saved_tensors
+        g = g.contiguous().float()
+        B, dev = g.shape[0], g.device
+        g_acc = torch.empty((B,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_background_blend_backward(_lib.ptr(g), _lib.ptr(bg), ctx.stride, _lib.ptr(g_acc), B,
+                                                                     _lib.stream_ptr(dev)), "nerf_amd_background_blend_backward")
+        return g, g_acc, None, None
+
+
+def composite_with_controls(raw, ts, dirs, from_rays, controls, ray_id0=0):
+    """_VolumeRender with the training controls around it.  ``controls`` = (bg, stride, sigma_noise, noise_seed) or None."""
+    if controls is None:
+        return _VolumeRender.apply(raw, ts, dirs, from_rays)
+    bg, stride, std, noise_seed = controls
+    if std:
+        raw = _SigmaNoise.apply(raw, std, noise_seed, ray_id0)
+    out = _VolumeRender.apply(raw, ts, dirs, from_rays)
+    if bg is not None:
+        out = (_Background.apply(out[0], out[3], bg, stride),) + tuple(out[1:])
+    return out
+
+
+# --------------------------------------------------------------------------
 # fused dense layers: HIP forward (saving activations) + HIP dX chain + HIP dW
 # --------------------------------------------------------------------------
 def ctypes_stream(stream):
@@ -285,9 +346,10 @@ def nerf_forward_autograd(net, v, precision):
     return raw.reshape(-1, 4)
 
 
-def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0):
+def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0, controls=None):
     """render_nerf (reference utils/rendering.py:13-45) with gradients to the
-    parameters of ``net`` and, when ``rays`` requires grad, to the rays; returns the same 5-tuple."""
+    parameters of ``net`` and, when ``rays`` requires grad, to the rays; returns the same 5-tuple.
+    ``controls``: the background / sigma noise of ``composite_with_controls``, None = neither."""
     from .utils.rendering import _tbins
     if _lib.precision_code(precision) == _lib.F32:
         # exact fp32: the reference's own composition (sampling -> net.forward -> volume_render), each stage a HIP kernel
@@ -299,12 +361,12 @@ def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_
             def forward(q):
                 return generic_mlp.forward(net, q)
 
-        return _render_generic(rays, _Exact, N, tn, tf, jit, flags, ALL_OUTPUTS, seed, ray_id0)
+        return _render_generic(rays, _Exact, N, tn, tf, jit, flags, ALL_OUTPUTS, seed, ray_id0, controls)
     dev = rays.device
     params = [p for _, p in net.named_parameters()]
     raw, ts = _FusedDense.apply(net, rays, jit, _tbins(tn, tf, N, dev), flags, seed, ray_id0, N, None, *params)
     # the compositor's |d_hat| factor carries no gradient (|d_hat| == 1): the rays enter it detached
-    return _VolumeRender.apply(raw, ts, rays.detach(), True)
+    return composite_with_controls(raw, ts, rays.detach(), True, controls, ray_id0)
 
 
 # --------------------------------------------------------------------------
@@ -431,16 +493,21 @@ def lr_decay_factor(lr_init, lr_final, num_iters):
 
 
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
-               precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
+               precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, background=None, sigma_noise=0.0,
+               noise_seed=0):
     """zero_grad -> render_nerf -> MSELoss(rgb, gt) -> backward -> [grad all-reduce]
     -> optimizer.step -> lr *= decay.  Returns the (detached) loss.
     Only ``rgb`` feeds the loss, as in the reference (train.py:52).
     The dense layers train in bf16 whatever the module's inference precision ('bf16' or 'fp16');
     precision 'fp32' trains exactly, layer by layer in fp32 (utils/generic_mlp.py): slow, and the reference's numbers.
     occupancy: an ``OccupancyGrid`` -- the render is ``render_nerf_masked`` (the network sees the live samples only; one
-    host synchronisation per step); everything else is the same step."""
+    host synchronisation per step); everything else is the same step.
+    background, sigma_noise, noise_seed: ``render_nerf``'s -- the loss is MSELoss(rgb + (1 - acc) background, gt) and the raw
+    density carries Gaussian noise of that standard deviation (counter RNG keyed by ``noise_seed``: pass a new one per step).
+    Dense path only: with ``occupancy`` either raises RuntimeError before anything is drawn or launched."""
     from . import parallel
-    from .utils.rendering import render_nerf
+    from .utils.rendering import render_nerf, _refuse_controls
+    _refuse_controls(background, sigma_noise, occupancy=occupancy)
     if occupancy is not None:
         from .utils.occupancy import check_trainable
         check_trainable(occupancy, net, rays, N, precision)      # before zero_grad: a refused call changes nothing
@@ -449,8 +516,11 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
         rgb, _, _, _, _ = render_nerf_masked(rays, net, N, occupancy, tn, tf, u=u, device_rng=device_rng, seed=seed,
                                              ray_id0=ray_id0)
     else:
+        kw = {}
+        if background is not None or sigma_noise:          # off by default: a call without them is the call it was
+            kw = dict(background=background, sigma_noise=sigma_noise, noise_seed=noise_seed)
         rgb, _, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
-                                      device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+                                      device_rng=device_rng, seed=seed, ray_id0=ray_id0, **kw)
     loss = mse_loss(rgb, gt)
     loss.backward()
     parallel.allreduce_gradients(net.parameters(), group=group)
@@ -839,7 +909,13 @@ class _DensePass(_Pass):
         alpha, acc, w are not materialised.  ``pdf`` = (u_f, ts_f, Nf): sample_pdf on the weights in the same kernel (they
         never reach HBM), which takes the seed in memory where the counter RNG leaves u_f empty."""
         ptr, s, (rays, jit, _, flags, seed, rid) = _lib.ptr, self.step, self.jitter
-        if pdf is None:
+        if pdf is None and s._controls:
+            # the same head behind the stepper's background and / or with noise on sigma; the noise key is noise_seed + the
+            # step's offset in memory, whatever the jitter source is
+            _launch("nerf_amd_volume_render_mse_backward_bg", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt), ptr(s.background),
+                    s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, s.noise_seed & (2 ** 64 - 1), s._seed_mem, s.ray_id0,
+                    ptr(self.rgb), ptr(self.d_raw), s.B, self.N, st)
+        elif pdf is None:
             _launch("nerf_amd_volume_render_mse_backward", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt), ptr(self.rgb),
                     ptr(self.d_raw), s.B, self.N, st)
         else:
@@ -951,19 +1027,38 @@ class GraphedTrainStep:
     outputs, the loss and d_raw are bit for bit those of the default; the gradients carry the operands' 8-bit rounding,
     inside the same criterion (a fraction of the reference's own minibatch deviation; tests/test_gpu_storage.py).
 
+    ``background`` (a colour [3] or one per ray [n_rays, 3]) and ``sigma_noise`` (a standard deviation): the head is
+    nerf_amd_volume_render_mse_backward_bg, still one launch -- the loss is MSELoss(rgb + (1 - acc) background, gt) and the
+    raw density carries Gaussian noise (the reference's open TODO, utils/rendering.py:63).  The background lives in the
+    device buffer ``stepper.background``, which the caller may overwrite IN PLACE between replays.  The noise is always the
+    counter RNG, with either jitter source: step k (1-based) draws with ``noise_seed`` + k, the step count read from device
+    memory -- the eager equivalent is ``train_step(..., noise_seed=noise_seed + k)``.  ``sigma_noise`` is fixed at capture
+    and ``stepper.sigma_noise`` is read-only: a schedule on it is a recapture (a new GraphedTrainStep).  Both work with
+    ``storage='e4m3'`` and ``buckets=2``: the head sits in front of both.  The dense single step only: the masked,
+    hierarchical and guided steppers do not take them.
+
     ``check_every`` (default 16, 0 = never): every so many steps the forward's range flag is copied back without
     waiting; a later ``step`` raises FloatingPointError once such a copy shows non-finite values inside the network
     (NaN / inf weights or inputs: a diverged run) -- the reference would show a NaN loss there.
     """
 
+    _controls = False            # a background or sigma noise in the head (the dense single step only)
+    background, _bg_stride, _sigma_noise, noise_seed = None, 0, 0.0, 0
     _samples = None              # samples per ray of each pass; None: the one pass of N samples
     _capacities = None           # point capacity of each pass (masked passes through ``occupancy``); None: dense passes
     _one_bucket = False          # the two-bucket exchange exists for the dense single step only
 
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
-                 device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16"):
+                 device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16",
+                 background=None, sigma_noise=0.0, noise_seed=0):
         from . import parallel
+        from .utils.rendering import _background_arg, _check_sigma_noise
         self._check_modules(net, optimizer)
+        self._sigma_noise, self.noise_seed = _check_sigma_noise(sigma_noise), int(noise_seed)
+        if background is not None:           # this object's own buffer: the captured head reads it at every replay
+            bg, self._bg_stride = _background_arg(background, int(n_rays), optimizer.flat.device)
+            self.background = bg.clone()
+        self._controls = self.background is not None or self._sigma_noise > 0
         self.net, self.opt, self.group = net, optimizer, group
         if buckets not in (1, 2):
             raise ValueError("buckets must be 1 (one all-reduce between the two graphs, the default) or 2 (overlapped)")
@@ -1026,6 +1121,11 @@ class GraphedTrainStep:
         if optimizer.net is not net:
             raise RuntimeError("the optimizer belongs to another module")
         _check_fused_trainable(net.precision)
+
+    @property
+    def sigma_noise(self):
+        """The standard deviation captured into the head (read-only: a schedule is a new GraphedTrainStep)."""
+        return self._sigma_noise
 
     @property
     def _seed_mem(self):

@@ -61,10 +61,56 @@ def _five_outputs(B, N, outputs, dev):
     return rgb, disp, buf(B, N) if "alpha" in outputs else None, acc, buf(B, N) if "w" in outputs else None
 
 
-def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS):
+# ---- the two training controls of the dense path: a background colour and noise on the raw density -------------------------
+def _background_arg(background, B, dev):
+    """``background`` as the kernels take it: (fp32 contiguous tensor on ``dev``, stride) -- one colour [3] (stride 0) or one
+    per ray [B,3] (stride 3).  A sequence of three numbers is a colour.  It carries no gradient."""
+    if not torch.is_tensor(background):
+        background = torch.tensor([float(x) for x in background], dtype=torch.float32)
+    bg = background.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(bg.shape) == (3,):
+        return bg, 0
+    if tuple(bg.shape) == (B, 3):
+        return bg, 3
+    raise RuntimeError(f"background must be one colour [3] or one per ray [{B}, 3], got {tuple(bg.shape)}")
+
+
+def _check_sigma_noise(sigma_noise):
+    import math
+    std = float(sigma_noise)
+    if not (std >= 0.0) or math.isinf(std):
+        raise ValueError(f"sigma_noise is a standard deviation: finite and >= 0, got {sigma_noise!r}")
+    return std
+
+
+def _refuse_controls(background, sigma_noise, **paths):
+    """The masked and terminated renders know neither control: refused before any launch and any RNG draw."""
+    if background is None and not sigma_noise:
+        return
+    for name, v in paths.items():
+        if v is not None:
+            raise RuntimeError(f"background / sigma_noise serve the dense path only: not with {name}= (render without them, "
+                               "or without the grid)")
+
+
+def _blend(rgb, acc, disp, bg, stride, pixels=False):
+    """rgb + (1 - acc) bg through nerf_amd_background_blend: rgb_bg [B,3], or pixels [B,4] = [clip(rgb_bg, 0, 1), disp]."""
+    B, dev = rgb.shape[0], rgb.device
+    out = torch.empty((B, 4 if pixels else 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nerf_amd_background_blend(
+            _lib.ptr(rgb), _lib.ptr(acc), _lib.ptr(disp) if pixels else None, _lib.ptr(bg), stride,
+            None if pixels else _lib.ptr(out), _lib.ptr(out) if pixels else None, B, _lib.stream_ptr(dev)),
+            "nerf_amd_background_blend")
+    return out
+
+
+def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS, background=None):
     """nerf_outs [B,N,4], ts [B,N], dirs [B,3] -> (rgb [B,3], disp [B], alpha [B,N],
     acc [B], w [B,N])  (reference utils/rendering.py:47-85).  The second output is
-    disparity; acc == 0 yields NaN there, as in the reference."""
+    disparity; acc == 0 yields NaN there, as in the reference.
+    background: a colour [3] or one per ray [B,3] behind the volume -- rgb becomes rgb + (1 - acc) background (fp32, each
+    operation rounded on its own); the other four outputs are what they were."""
     _lib.require_cuda_f32(nerf_outs, "nerf_outs")
     _lib.require_cuda_f32(ts, "ts")
     _lib.require_cuda_f32(dirs, "dirs")
@@ -73,9 +119,11 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS):
     B, N = nerf_outs.shape[0], nerf_outs.shape[1]
     if tuple(ts.shape) != (B, N) or tuple(dirs.shape) != (B, 3):
         raise RuntimeError("ts must be [B, N] and dirs [B, 3]")
+    bg = None if background is None else _background_arg(background, B, nerf_outs.device)
     if torch.is_grad_enabled() and nerf_outs.requires_grad:
-        from ..training import volume_render_autograd
-        return volume_render_autograd(nerf_outs, ts, dirs)
+        from ..training import _Background, volume_render_autograd
+        out = volume_render_autograd(nerf_outs, ts, dirs)
+        return out if bg is None else (_Background.apply(out[0], out[3], *bg),) + tuple(out[1:])
     dev = nerf_outs.device
     raw, ts, dirs = nerf_outs.detach().contiguous(), ts.detach().contiguous(), dirs.detach().contiguous()
     rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
@@ -84,11 +132,14 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS):
             _lib.ptr(raw), _lib.ptr(ts), _lib.ptr(dirs), 3, _lib.ptr(rgb), _lib.ptr(disp),
             _lib.ptr(alpha), _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)),
             "nerf_amd_volume_render")
+    if bg is not None:
+        rgb = _blend(rgb, acc, None, *bg)
     return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
 
 
 def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUTS,
-                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, terminate=None):
+                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, terminate=None,
+                background=None, sigma_noise=0.0, noise_seed=0):
     """Stratified sampling along rays, NeRF query, compositing
     (reference utils/rendering.py:13-45).
 
@@ -107,12 +158,27 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     slab by slab and a ray whose transmittance has fallen below eps evaluates nothing more (the masked render under the
     evaluated mask; at most ceil(N / slab) + 1 host synchronisations).  With ``occupancy`` it runs on that grid, without one on
     an all-live grid; the masked render's conditions hold either way.
+
+    background: a colour [3] (or one per ray [B,3]) behind the volume: rgb becomes rgb + (1 - acc) background, fp32 with
+    every operation rounded on its own; disp, alpha, acc and w are what they were, and the background carries no gradient.
+    sigma_noise: standard deviation of Gaussian noise added to the raw density in front of the softplus (the reference's
+    open ``## TODO add gaussian noise regularizer``, utils/rendering.py:63) -- a REGULARISER: a call that does not train
+    (no_grad, a frozen net and rays without grad) raises RuntimeError.  The noise comes from the counter RNG keyed by
+    ``noise_seed`` and the global sample id (``ray_id0``), whatever the jitter source; pass a new ``noise_seed`` per step.
+    Both serve the dense path only: with ``occupancy`` or ``terminate`` they raise RuntimeError before anything is drawn
+    or launched.
     """
+    _refuse_controls(background, sigma_noise, occupancy=occupancy, terminate=terminate)
+    std = _check_sigma_noise(sigma_noise) if sigma_noise else 0.0
     _lib.require_cuda_f32(rays, "rays")
     if rays.dim() != 2 or rays.shape[1] != 6:
         raise RuntimeError("rays must be [B, 6]")
     B, N = rays.size(0), int(N)
     dev = rays.device
+    controls = None
+    if background is not None or sigma_noise:
+        bg = (None, 0) if background is None else _background_arg(background, B, dev)
+        controls = (*bg, std, int(noise_seed))
     # d loss / d rays (utils/rendering.py:31-40 is differentiable in the rays): autograd runs even for a frozen net
     rays_grad = torch.is_grad_enabled() and rays.requires_grad
     rays_in = rays.contiguous() if rays_grad else None
@@ -120,6 +186,12 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
 
     fused = isinstance(net, Nerf) and net._fused_ok()
     training = fused and torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in net.parameters()))
+    if controls is not None and controls[2] > 0:
+        trains = training or (not fused and torch.is_grad_enabled() and (
+            rays_grad or any(p.requires_grad for p in getattr(net, "parameters", lambda: ())())))
+        if not trains:
+            raise RuntimeError("sigma_noise is a training regulariser, not a render option: this call trains nothing (no_grad, "
+                               "or no parameter and no ray requires grad)")
     if terminate is not None:
         from .occupancy import check_terminable
         check_terminable(terminate, occupancy, net, rays_grad)
@@ -171,12 +243,12 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
         try:
             return render_nerf_autograd(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags,
                                         net.precision if precision is None else precision,
-                                        seed, ray_id0)
+                                        seed, ray_id0, *(() if controls is None else (controls,)))
         finally:
             if pending_rng is not None:
                 pending_rng.finish()          # the forward is enqueued behind the generator kernel: only that is awaited
     if not fused:
-        return _render_generic(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0)
+        return _render_generic(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, controls)
 
     def launch(code, packed):
         lib = _lib.lib()
@@ -188,6 +260,8 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
                 _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)), _lib.ptr(packed[0]), code,
                 flags, int(seed), int(ray_id0), _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha),
                 _lib.ptr(acc), _lib.ptr(w), _lib.ptr(ws), B, N, _lib.stream_ptr(dev)), "nerf_amd_render_forward")
+        if controls is not None:              # the same one-launch render, then the blend (acc is always among the outputs)
+            rgb = _blend(rgb, acc, None, controls[0], controls[1])
         return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
 
     try:
@@ -200,7 +274,7 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
 render_rays = render_nerf      # the name BASELINE.json uses for the same function
 
 
-def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0):
+def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, controls=None):
     """Any other net object: sampling and query-point assembly in one HIP kernel (nerf_amd_query_points =
     utils/rendering.py:24-40; the same jitter sources as the fused path, counter RNG included), the net's own
     forward exactly as the reference calls it (:41), compositing by the HIP kernel with the directions taken
@@ -215,14 +289,18 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0):
     lib = _lib.lib()
     out = net.forward(q).reshape(B, N, 4).float()
     if torch.is_grad_enabled() and out.requires_grad:
-        from ..training import _VolumeRender
-        return _VolumeRender.apply(out, ts, rays, True)
+        from ..training import composite_with_controls
+        return composite_with_controls(out, ts, rays, True, controls, ray_id0)
+    if controls is not None and controls[2] > 0:
+        raise RuntimeError("sigma_noise is a training regulariser: the net's output carries no gradient")
     out = out.detach().contiguous()
     rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.nerf_amd_volume_render_rays(_lib.ptr(out), _lib.ptr(ts), _lib.ptr(rays), _lib.ptr(rgb), _lib.ptr(disp),
                                                    _lib.ptr(alpha), _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)),
                    "nerf_amd_volume_render_rays")
+    if controls is not None:
+        rgb = _blend(rgb, acc, None, controls[0], controls[1])
     return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
 
 
@@ -271,6 +349,10 @@ def _render_batched(rays, net, batch_size, N, tn, tf, u, progress, id_base=0, **
     n = rays.size(0)
     rgb = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
     disp = torch.empty((n,), dtype=torch.float32, device=rays.device)
+    background = kw.pop("background", None)          # one colour, or one per ray of this table: its rows follow the batches
+    per_ray = torch.is_tensor(background) and background.dim() == 2
+    if per_ray and background.shape[0] != n:
+        raise RuntimeError(f"background must be one colour [3] or one per ray [{n}, 3], got {tuple(background.shape)}")
     if isinstance(net, Nerf) and net._fused_ok() and rays.is_cuda and 0 < n and N <= _FUSED_MAX_N:
         # The reference's batch_size bounds the [batch, N, ...] tensors of its per-sample path.  The fused render keeps
         # nothing per sample in HBM and its pixels do not depend on how the rays are batched (jitter rows follow the rays;
@@ -292,6 +374,8 @@ def _render_batched(rays, net, batch_size, N, tn, tf, u, progress, id_base=0, **
             for k, s in enumerate(tqdm(starts) if progress else starts):
                 e = min(s + batch_size, n)
                 uk = ahead.batch(k) if ahead is not None else (None if u is None else u[s:e])
+                if background is not None:
+                    kw["background"] = background[s:e] if per_ray else background
                 r, d, _, _, _ = render_nerf(rays[s:e], net, N, tn, tf, u=uk,
                                             outputs=("rgb", "disp", "acc"), ray_id0=id_base + s, **kw)
                 rgb[s:e] = torch.clip(r, 0., 1.)
@@ -391,7 +475,7 @@ def generate_rays(pose, cam_params, device, ray0=0, n_rays=None):
 
 
 def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_rays=None,
-                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None):
+                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None, background=None):
     """One view (or the pixel range [ray0, ray0+n_rays) of it) in ONE library
     call: device ray generation -> render_nerf -> clip(rgb,0,1), i.e. the body of
     the reference's per-image loop (utils/rendering.py:139-151) without the
@@ -403,8 +487,12 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     utils/occupancy.py); the same conditions as ``render_nerf(..., occupancy=)``: under ``torch.no_grad()``, default
     network shape only.
     terminate: an ``EarlyTermination`` -- early ray termination as in ``render_nerf(..., terminate=)``, on ``occupancy`` or,
-    without one, on an all-live grid."""
+    without one, on an all-live grid.
+    background: a colour [3] (or one per pixel of the range, [n,3]) behind the volume: pixels = [clip(rgb + (1 - acc)
+    background, 0, 1), disparity], the clip behind the blend.  Device ray generation, nerf_amd_render_forward for rgb, disp
+    and acc, then one small blend launch (without a background: the one call it was).  Not with occupancy / terminate."""
     import numpy as np
+    _refuse_controls(background, 0.0, occupancy=occupancy, terminate=terminate)
     dev = next(net.parameters()).device
     if terminate is not None:
         from .occupancy import check_terminable
@@ -420,8 +508,10 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         rays = generate_rays(pose, cam_params, dev, ray0, n)
         with torch.no_grad():
             rgb, disp, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, outputs=("rgb", "disp", "acc"),
-                                             device_rng=device_rng, seed=seed, ray_id0=ray0)
+                                             device_rng=device_rng, seed=seed, ray_id0=ray0,
+                                             **({} if background is None else {"background": background}))
         return torch.cat([rgb.clamp(0., 1.), disp[:, None]], dim=1)
+    bg = None if background is None else _background_arg(background, n, dev)
     code = _lib.precision_code(net.precision if precision is None else precision)
     net.packed_weights(code)
     flags, jit = 0, None
@@ -446,6 +536,23 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     h_pose = np.zeros((3, 4), dtype=np.float32)
     h_pose[:] = np.asarray(pose, dtype=np.float32)[:3, :4]
 
+    def launch_bg(code, packed):
+        rgb, disp, _, acc, _ = _five_outputs(n, int(N), (), dev)
+        nws = int(lib.nerf_amd_render_workspace_bytes(code, n, int(N)))
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.nerf_amd_render_forward(
+                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)), _lib.ptr(packed[0]), code, flags, int(seed),
+                int(ray0), _lib.ptr(rgb), _lib.ptr(disp), None, _lib.ptr(acc), None, _lib.ptr(ws), n, int(N),
+                _lib.stream_ptr(dev)), "nerf_amd_render_forward")
+        return _blend(rgb, acc, disp, *bg, pixels=True)
+
+    if bg is not None:
+        if jit is not None and tuple(jit.shape) != (n, int(N)):
+            raise RuntimeError("u must be [n_rays, N]")
+        rays = generate_rays(pose, cam_params, dev, ray0, n)
+        return guarded_launch([net], code, launch_bg)
+
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
         ws = torch.empty(max(int(lib.nerf_amd_render_image_workspace_bytes(code, n, N)), 256), dtype=torch.uint8, device=dev)
@@ -467,6 +574,9 @@ def render_view_sharded(net, pose, cam_params, *, group=None, **kw):
     n = int(cam_params[0]) * int(cam_params[1])
     lo, hi = parallel.shard_range(n, rank, world)
     u = kw.pop("u", None)
+    bg = kw.get("background")
+    if torch.is_tensor(bg) and bg.dim() == 2:            # one colour per pixel of the view: this rank's rows
+        kw["background"] = bg[lo:hi]
     shard = render_view(net, pose, cam_params, ray0=lo, n_rays=hi - lo,
                         u=None if u is None else u[lo:hi], **kw)
     return parallel.gather_pixels(shard, n, group)
