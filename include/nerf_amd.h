@@ -831,6 +831,48 @@ int nerf_amd_sample_pdf_volume(const float* rays, const float* u, const float* t
                                const float* h_lo, const float* h_inv_step, const float* u_f, float* ts_out, float* sigma_c,
                                float* w_c, int64_t B, int Nc, int Nf, void* stream);
 
+/* ---- masked guided placement: guided sampling through an occupancy grid (csrc/guided_masked.hip) -------------------------
+ * Not in the reference.  tests/guided_masked_model.py restates it in numpy; DESIGN.md section 24.
+ *
+ * The guided sampler does not know the occupancy grid: left alone it places fine samples in cells the masked render then
+ * discards.  The masked guided placement looks at the grid twice -- at the coarse samples in front of the weights, and at the
+ * merged positions.  For (rays, u, tbins, flags, seed, ray_id0), a sigma volume V, an occupancy grid G with its outside policy
+ * and u_f it is BY DEFINITION, bit for bit, this chain of existing entry points:
+ *   1. ts_c[B, Nc] and the points: nerf_amd_query_points.
+ *   2. value_i: the look-up of the guided placement above (maximum over the 8 corners of the point's cell in V, NaN corners
+ *      skipped, -inf outside).
+ *   3. mask_c: nerf_amd_occupancy_mark on the same coarse jitter through G (the jitter flags, plus NERF_AMD_OUTSIDE_EMPTY when
+ *      given); value_i := -inf where the bit is clear -- the rule of the masked pair: the sampler sees weights that are exactly
+ *      0 at a dead sample.
+ *   4. w_c: the `w` output of nerf_amd_volume_render_rays on raw = (0, 0, 0, value).
+ *   5. ts_out[B, Nc + Nf] = nerf_amd_sample_pdf(ts_c, w_c, u_f, ...) under the sampler's key; with NERF_AMD_SEED_IN_MEMORY the
+ *      64-bit offset at `u` is added to the seed of both draws, as in the guided placement.
+ *   6. mask[B, ceil((Nc + Nf) / 64)], offsets[B + 1], live = offsets[B]: nerf_amd_occupancy_mark with NERF_AMD_TS_GIVEN on
+ *      ts_out, through the same G and policy.
+ * Hence: an all-live grid gives nerf_amd_sample_pdf_volume's ts_out and a full mask; a ray with no live coarse sample gets the
+ * sampler's uniform placement; a new sample may still land in a dead cell (the sampler's 1e-5 floor, a bin that straddles a
+ * boundary) and is then simply masked; V and G may differ in resolution and bounds.  The masked guided render and training
+ * step are the existing masked render / masked step with NERF_AMD_TS_GIVEN on ts_out under this mask and these offsets.
+ *
+ * nerf_amd_sample_pdf_volume_masked: the placement kernel (one wavefront per ray) followed by the mark's three scan kernels.
+ *   flags: the jitter flags (NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY included), plus NERF_AMD_OUTSIDE_EMPTY.
+ *   sigma_volume[vx, vy, vz] with v_lo[3], v_inv_step[3]; bits of the grid of (gx, gy, gz) grid points with g_lo[3],
+ *   g_inv_step[3]: the four axis arrays are HOST floats.  Optional outputs (NULL: not written): sigma_c[B, Nc], the value AFTER
+ *   step 3; w_c[B, Nc]; live, a DEVICE int64.  workspace: nerf_amd_occupancy_workspace_bytes(B) bytes, 16-byte aligned.
+ *   Checked on the host before any launch, in this order -- nerf_amd_sample_pdf_volume's rules (NERF_AMD_EINVAL: Nf < 0, B < 0,
+ *   Nc <= 0, unknown flags or a jitter tensor missing; NERF_AMD_EUNSUP: Nc < 3, Nc > 256, Nc + Nf > 512, B > 2^32;
+ *   NERF_AMD_EINVAL: a volume axis < 2, no u_f without the counter RNG when Nf > 0); NERF_AMD_EINVAL: a grid axis < 2; B = 0:
+ *   returns 0, and offsets[0] = 0 (*live = 0) is written as nerf_amd_occupancy_mark writes it at B = 0 when offsets and
+ *   workspace are given and aligned; NERF_AMD_EINVAL: a NULL rays, sigma_volume, v_lo, v_inv_step, bits, g_lo, g_inv_step,
+ *   ts_out, mask, offsets or workspace, or a buffer not aligned (mask, offsets, live: 8 bytes; workspace: 16; the rest: 4).
+ *   No atomics: two runs write the same bytes. */
+int nerf_amd_sample_pdf_volume_masked(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
+                                      int64_t ray_id0, const float* sigma_volume, int64_t vx, int64_t vy, int64_t vz,
+                                      const float* v_lo, const float* v_inv_step, const uint32_t* bits, int64_t gx, int64_t gy,
+                                      int64_t gz, const float* g_lo, const float* g_inv_step, const float* u_f, float* ts_out,
+                                      float* sigma_c, float* w_c, uint64_t* mask, int64_t* offsets, int64_t* live,
+                                      void* workspace, int64_t B, int Nc, int Nf, void* stream);
+
 /* ---- background colour and sigma noise for the dense training path ----------------------------------------------------
  * Two controls every NeRF trainer offers and the reference does not (white_bkgd and raw_noise_std elsewhere; the noise is the
  * reference's own `## TODO add gaussian noise regularizer`, utils/rendering.py:63).  Dense single-network path only.

@@ -69,6 +69,9 @@ _SIGNATURES = {
     "nerf_amd_sample_pdf": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _i64, _i32, _i32, _vp]),
     "nerf_amd_sample_pdf_volume": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _i64, _i32, _i32, _vp]),
+    "nerf_amd_sample_pdf_volume_masked": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _i64, _i64, _i64, _vp, _vp,
+                                                 _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _i64, _i32, _i32, _vp]),
     "nerf_amd_volume_render_mse_backward_pdf": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _i64,
                                                        _i32, _i32, _vp]),
     "nerf_amd_sigma_noise": (_i32, [_vp, _vp, ctypes.c_float, _u32, _u64, _vp, _i64, _i64, _i32, _vp]),

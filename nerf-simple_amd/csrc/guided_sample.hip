@@ -3,10 +3,10 @@
 //
 // One kernel joins four shared device routines, none of them copied or edited.  One wavefront per ray:
 //   positions: the Nc coarse samples as every render forms them (nerf_device.h: fetch_point_rays) -> the wave's WaveLds::ts;
-//   look-up:   the cell of each point by the occupancy rule (occupancy.hip: floor(fl(fl(x - lo) inv_step)), outside when
-//              !(0 <= c < n - 1) or NaN) and the maximum of the cell's 8 corners of V[nx, ny, nz], from -inf, NaN corners
-//              skipped; -inf outside.  No arithmetic on the values: the look-up is exact.  8 plain loads per sample through
-//              the read-only path; a 128^3 volume (8 MiB) stays in L2 / MALL;
+//   look-up:   volume_value (sigma_volume_device.h): the cell of each point by the occupancy rule (occ_grid_device.h:
+//              floor(fl(fl(x - lo) inv_step)), outside when !(0 <= c < n - 1) or NaN) and the maximum of the cell's 8 corners
+//              of V[nx, ny, nz], from -inf, NaN corners skipped; -inf outside.  No arithmetic on the values: the look-up is
+//              exact.  8 plain loads per sample through the read-only path; a 128^3 volume (8 MiB) stays in L2 / MALL;
 //   weights:   composite_ray (composite_device.h) over raw = (0, 0, 0, value): its `w` output is pointed at the wave's own LDS
 //              slice (ray index 0, every other output NULL), so the bits are composite_ray's and w never reaches HBM;
 //   sampler:   nerf_pdf::sample_ray (sample_pdf_device.h) on those positions and weights.
@@ -14,6 +14,7 @@
 // rules: api_checks.h).
 #include "composite_device.h"
 #include "sample_pdf_device.h"
+#include "sigma_volume_device.h"
 #include "api_checks.h"
 #include "launchers.h"
 
@@ -21,40 +22,6 @@ namespace {
 
 constexpr int GUIDED_RAYS_PER_BLOCK = 4;
 using nerf_pdf::MAXC;
-
-struct SigmaVolume {                           // V[n0, n1, n2], C order
-    long long n[3];
-    float lo[3], inv_step[3];
-};
-
-// the look-up of one point: max over the 8 corners of its cell, NaN corners skipped; -inf outside the grid
-__device__ __forceinline__ float volume_value(const SigmaVolume& g, const float* __restrict__ vol, float x, float y, float z) {
-    const float p[3] = {x, y, z};
-    long long c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float f = floorf(mul_rn(sub_rn(p[a], g.lo[a]), g.inv_step[a]));
-        if (!(f >= 0.f && f < (float)(g.n[a] - 1))) return -__builtin_inff();       // also NaN
-        c[a] = (long long)f;
-        if (c[a] < 0 || c[a] > g.n[a] - 2) return -__builtin_inff();               // (float)(n - 1) may round up: never past the volume
-    }
-    const float* base = vol + (c[0] * g.n[1] + c[1]) * g.n[2] + c[2];
-    const long long sy = g.n[2], sx = g.n[1] * g.n[2];
-    float m = -__builtin_inff();
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float v = base[(k >> 2) * sx + ((k >> 1) & 1) * sy + (k & 1)];
-        if (v > m) m = v;                      // false for a NaN corner
-    }
-    return m;
-}
-
-struct VolumeSamples {                         // the ray's positions and looked-up values (LDS)
-    const float* ts;
-    const float* sigma;
-    __device__ __forceinline__ float t(int i) const { return ts[i]; }
-    __device__ __forceinline__ f32x4 c(int i) const { return f32x4{0.f, 0.f, 0.f, sigma[i]}; }
-};
 
 template <int E>
 __global__ __launch_bounds__(64 * GUIDED_RAYS_PER_BLOCK) void guided_sample_kernel(
@@ -101,9 +68,7 @@ extern "C" int nerf_amd_launch_sample_pdf_volume(const MlpArgs* args, const floa
     const long long B = args->P / Nc;
     if (B == 0) return 0;
     if (Nf < 0 || nerf_pdf::unsupported_sizes(Nc, Nf) || nx < 2 || ny < 2 || nz < 2) return -2;
-    SigmaVolume g;
-    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = h_lo[a]; g.inv_step[a] = h_inv_step[a]; }
+    const SigmaVolume g = sigma_volume_args(nx, ny, nz, h_lo, h_inv_step);
     const dim3 grid((unsigned)((B + GUIDED_RAYS_PER_BLOCK - 1) / GUIDED_RAYS_PER_BLOCK)), block(64 * GUIDED_RAYS_PER_BLOCK);
     // keys per lane of the register sort: ceil_pow2(Nf) / 64 (nerf_pdf::keys_per_lane)
     switch (nerf_pdf::keys_per_lane(Nf)) {

@@ -30,6 +30,10 @@ int nerf_amd_launch_sample_pdf(const float*, const float*, const float*, float*,
                                unsigned long long, long long, int, hipStream_t);
 int nerf_amd_launch_sample_pdf_volume(const MlpArgs*, const float*, long long, long long, long long, const float*, const float*,
                                       const float*, float*, float*, float*, int, hipStream_t);
+int nerf_amd_launch_sample_pdf_volume_masked(const MlpArgs*, const float*, long long, long long, long long, const float*,
+                                             const float*, const unsigned*, long long, long long, long long, const float*,
+                                             const float*, int, const float*, float*, float*, float*, unsigned long long*,
+                                             long long*, long long*, void*, int, hipStream_t);
 int nerf_amd_launch_generate_rays(const float*, int, int, float, long long, long long, float*, hipStream_t);
 int nerf_amd_launch_composite_backward(const float*, const float*, const float*, long long, const float*,
                                        const float*, const float*, const float*, const float*, float*,
@@ -82,6 +86,7 @@ int nerf_amd_launch_occ_bits(const float*, long long, long long, long long, floa
 int nerf_amd_launch_occ_pack(const unsigned char*, long long, long long, long long, unsigned*, hipStream_t);
 int nerf_amd_launch_occ_mark(const MlpArgs*, const unsigned*, long long, long long, long long, const float*, const float*, int,
                              unsigned long long*, long long*, long long*, void*, long long, hipStream_t);
+int nerf_amd_launch_occ_scan(void*, long long*, long long*, long long, hipStream_t);
 int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const long long*, float*, long long, long long, hipStream_t);
 int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
 int nerf_amd_occ_train_max_n(void);

@@ -21,6 +21,7 @@
 // Fixed partitions and hand-written scans, no atomics: every run writes the same bytes.
 #include "composite_device.h"
 #include "launchers.h"
+#include "occ_grid_device.h"
 #include "occ_scan_device.h"
 
 namespace {
@@ -32,14 +33,6 @@ constexpr int OCC_SCAN_THREADS = 256;
 constexpr int OCC_SCAN_PER_THREAD = 8;
 constexpr long long OCC_SCAN_ITEMS = (long long)OCC_SCAN_THREADS * OCC_SCAN_PER_THREAD;      // rays per scan block
 constexpr int OCC_TOP_THREADS = 1024;
-
-struct OccGrid {
-    const unsigned* bits;
-    int cells[3];                              // cells per axis
-    long long wz;                              // words per z row
-    float lo[3], inv_step[3];
-    int outside_live;
-};
 
 // ---- bits from sigma ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void occ_bits_kernel(const float* __restrict__ sigma, long long nx, long long ny, long long nz,
@@ -80,19 +73,6 @@ __global__ __launch_bounds__(256) void occ_pack_kernel(const unsigned char* __re
 }
 
 // ---- mark ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool sample_live(const OccGrid& g, float x, float y, float z) {
-    const float v[3] = {x, y, z};
-    long long c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float f = floorf(mul_rn(sub_rn(v[a], g.lo[a]), g.inv_step[a]));
-        if (!(f >= 0.f && f < (float)g.cells[a])) return g.outside_live != 0;       // also NaN
-        c[a] = (long long)f;
-    }
-    const unsigned word = g.bits[(c[0] * g.cells[1] + c[1]) * g.wz + (c[2] >> 5)];
-    return (word >> (c[2] & 31)) & 1u;
-}
-
 __global__ __launch_bounds__(64 * OCC_RAYS_PER_BLOCK) void occ_mark_kernel(MlpArgs a, OccGrid g,
                                                                            unsigned long long* __restrict__ mask,
                                                                            int* __restrict__ counts, long long B) {
@@ -238,7 +218,7 @@ OccWs occ_ws(long long B) {
     constexpr auto up = nerf_layout::align256;
     OccWs w;
     w.nblk = (B + OCC_SCAN_ITEMS - 1) / OCC_SCAN_ITEMS;
-    w.off_counts = 0;
+    w.off_counts = 0;                          // occ_ws_counts (occ_grid_device.h)
     w.off_blk = up(B * 4);
     w.off_blkoff = w.off_blk + up(w.nblk * 8);
     w.bytes = w.off_blkoff + up(w.nblk * 8);
@@ -269,34 +249,37 @@ extern "C" int nerf_amd_launch_occ_pack(const unsigned char* cells, long long cx
     return (int)hipGetLastError();
 }
 
-extern "C" int nerf_amd_launch_occ_mark(const MlpArgs* args, const unsigned* bits, long long nx, long long ny, long long nz,
-                                        const float* h_lo, const float* h_inv_step, int outside_live, unsigned long long* mask,
-                                        long long* offsets, long long* live, void* ws, long long B, hipStream_t stream) {
-    (void)hipGetLastError();
-    OccGrid g;
-    g.bits = bits;
-    g.cells[0] = (int)(nx - 1); g.cells[1] = (int)(ny - 1); g.cells[2] = (int)(nz - 1);
-    g.wz = (nz - 1 + 31) >> 5;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = h_lo[a]; g.inv_step[a] = h_inv_step[a]; }
-    g.outside_live = outside_live;
+// the exclusive scan of the rays' live counts (int[B] at the head of `ws`, occ_ws_counts) into offsets[B + 1]; the total goes
+// to offsets[B] and, when given, to *live.  Enqueued behind the kernel that wrote the counts: the mark below, or the masked
+// guided sampler (guided_masked.hip).
+extern "C" int nerf_amd_launch_occ_scan(void* ws, long long* offsets, long long* live, long long B, hipStream_t stream) {
     const OccWs w = occ_ws(B);
     char* b = reinterpret_cast<char*>(ws);
     int* counts = reinterpret_cast<int*>(b + w.off_counts);
     long long* blk = reinterpret_cast<long long*>(b + w.off_blk);
     long long* blkoff = reinterpret_cast<long long*>(b + w.off_blkoff);
-    if (B > 0) {
-        const long long blocks = (B + OCC_RAYS_PER_BLOCK - 1) / OCC_RAYS_PER_BLOCK;
-        hipLaunchKernelGGL(occ_mark_kernel, dim3((unsigned)blocks), dim3(64 * OCC_RAYS_PER_BLOCK), 0, stream, *args, g, mask,
-                           counts, B);
+    if (B > 0)
         hipLaunchKernelGGL(occ_block_sum_kernel, dim3((unsigned)w.nblk), dim3(OCC_SCAN_THREADS), 0, stream, (const int*)counts, B,
                            blk);
-    }
     hipLaunchKernelGGL(occ_scan_blocks_kernel, dim3(1), dim3(OCC_TOP_THREADS), 0, stream, (const long long*)blk, w.nblk, blkoff,
                        offsets + B, live);
     if (B > 0)
         hipLaunchKernelGGL(occ_offsets_kernel, dim3((unsigned)w.nblk), dim3(OCC_SCAN_THREADS), 0, stream, (const int*)counts, B,
                            (const long long*)blkoff, offsets);
     return (int)hipGetLastError();
+}
+
+extern "C" int nerf_amd_launch_occ_mark(const MlpArgs* args, const unsigned* bits, long long nx, long long ny, long long nz,
+                                        const float* h_lo, const float* h_inv_step, int outside_live, unsigned long long* mask,
+                                        long long* offsets, long long* live, void* ws, long long B, hipStream_t stream) {
+    (void)hipGetLastError();
+    const OccGrid g = occ_grid_args(bits, nx, ny, nz, h_lo, h_inv_step, outside_live);
+    if (B > 0) {
+        const long long blocks = (B + OCC_RAYS_PER_BLOCK - 1) / OCC_RAYS_PER_BLOCK;
+        hipLaunchKernelGGL(occ_mark_kernel, dim3((unsigned)blocks), dim3(64 * OCC_RAYS_PER_BLOCK), 0, stream, *args, g, mask,
+                           occ_ws_counts(ws), B);
+    }
+    return nerf_amd_launch_occ_scan(ws, offsets, live, B, stream);
 }
 
 extern "C" int nerf_amd_launch_occ_emit(const MlpArgs* args, const unsigned long long* mask, const long long* offsets, float* pts,

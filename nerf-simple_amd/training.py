@@ -431,6 +431,29 @@ class _ZeroParamGrads(torch.autograd.Function):
         return tuple(torch.zeros_like(p) for p in ctx.like)
 
 
+def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, mark=None):
+    """The stages of ``render_nerf_masked`` once rays and jitter are settled: mark (or ``mark``, the ready MarkResult of these
+    positions: the masked guided placement produces it with them) -> emit -> training forward on the live points -> masked
+    compositor, with gradients.  Sets ``occupancy.last_stats``."""
+    from .utils import occupancy as occ_mod
+    B = rays.size(0)
+    m = occ_mod._mark(occupancy, rays, jit, tbins, flags, seed, ray_id0, N) if mark is None else mark
+    pts = occ_mod._points(m, rays, jit, tbins, flags, seed, ray_id0)
+    stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
+    occupancy.last_stats = stats
+    params = [p for _, p in net.named_parameters()]
+    if m.live:
+        # the reference's |x| > 1 warning, on the points the network is asked about (lazily, as Nerf.forward does)
+        from .utils.xyz import range_check_values
+        range_check_values(pts)
+        raw_live, _ = _FusedDense.apply(net, None, None, None, 0, 0, 0, 1, pts, *params)
+        raw_live = raw_live.reshape(-1, 4)
+        stats["network_launches"] = 1
+    else:
+        raw_live = _ZeroParamGrads.apply(*params)
+    return _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+
+
 def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0,
                        return_ts=False):
     """``render_nerf`` through an occupancy grid WITH gradients to the parameters of ``net``: the network is evaluated
@@ -460,21 +483,7 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     try:
         rays = rays.detach().contiguous()
         tbins = None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, N, dev)
-        m = occ_mod._mark(occupancy, rays, jit, tbins, flags, seed, ray_id0, N)
-        pts = occ_mod._points(m, rays, jit, tbins, flags, seed, ray_id0)
-        stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
-        occupancy.last_stats = stats
-        params = [p for _, p in net.named_parameters()]
-        if m.live:
-            # the reference's |x| > 1 warning, on the points the network is asked about (lazily, as Nerf.forward does)
-            from .utils.xyz import range_check_values
-            range_check_values(pts)
-            raw_live, _ = _FusedDense.apply(net, None, None, None, 0, 0, 0, 1, pts, *params)
-            raw_live = raw_live.reshape(-1, 4)
-            stats["network_launches"] = 1
-        else:
-            raw_live = _ZeroParamGrads.apply(*params)
-        out = _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+        out = _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0)
         if return_ts:
             return out, occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
         return out
@@ -680,22 +689,40 @@ def _check_guided(net, proposal, precision=None):
 
 
 def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, ts_c=None, u_f=None, decay=1.0,
-                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0):
+                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
     """One optimisation step of ONE network on grid-guided positions: ts = ``proposal.sample(rays, Nc, Nf, ...)`` (a
     ``ProposalVolume``, utils/proposal.py: no network evaluation, no gradient) -> zero_grad -> render_nerf with gradients on those
     Nc + Nf positions -> MSE(rgb, gt) -> backward -> [grad all-reduce] -> optimizer.step -> lr *= decay.  The loss is that of
     the existing eager step on the same explicit ``ts``, bit for bit; nothing of ``proposal`` receives a gradient.
     Jitter as ``ProposalVolume.sample`` (default: render_hierarchical's draws, torch.rand(B,Nc) then torch.rand(B,Nf) from
     torch's CPU generator).  Refreshing the volume (``proposal.update(net)``) is the caller's schedule.
-    Returns the detached loss; ``.ts`` on it holds the positions."""
+    Returns the detached loss; ``.ts`` on it holds the positions.
+
+    occupancy: an ``OccupancyGrid`` -- the masked guided step: the masked guided placement (dead coarse
+    samples weigh nothing; the merged positions come back marked, one host read) -> the stages of ``render_nerf_masked`` on
+    those positions under that mark, which is not formed again.  The loss is that of ``render_nerf_masked(rays, net, Nc + Nf,
+    occupancy, ts=ts)``, bit for bit; refused as that function refuses (precision='fp32', other network sizes, foreign nets),
+    before anything is drawn."""
     from . import parallel
     _check_guided(net, proposal, precision)
-    proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng)         # before any draw: a refused call changes nothing
-    ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
-    rays = rays.detach().contiguous()
-    optimizer.zero_grad(set_to_none=True)
-    outs, _ = _render_train_with_ts(rays, net, int(Nc) + int(Nf), tn, tf, ts, _lib.FLAG_TS_GIVEN,
-                                    net.precision if precision is None else precision, seed, ray_id0)
+    if occupancy is not None:
+        from .utils import occupancy as occ_mod
+        occ_mod.check_trainable(occupancy, net, rays, int(Nc) + int(Nf), precision)
+    proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)   # before any draw: a refused call changes nothing
+    if occupancy is not None:
+        net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
+        rays = rays.detach().contiguous()
+        ts, mark = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
+                                   ray_id0=ray_id0, occupancy=occupancy, return_mark=True)
+        optimizer.zero_grad(set_to_none=True)
+        outs = _masked_outputs(rays, net, int(Nc) + int(Nf), occupancy, None, ts, _lib.FLAG_TS_GIVEN, 0, 0, mark=mark)
+    else:
+        ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
+                             ray_id0=ray_id0)
+        rays = rays.detach().contiguous()
+        optimizer.zero_grad(set_to_none=True)
+        outs, _ = _render_train_with_ts(rays, net, int(Nc) + int(Nf), tn, tf, ts, _lib.FLAG_TS_GIVEN,
+                                        net.precision if precision is None else precision, seed, ray_id0)
     loss = mse_loss(outs[0], gt)
     loss.backward()
     parallel.allreduce_gradients(net.parameters(), group=group)
@@ -967,6 +994,17 @@ class _MaskedPass(_Pass):
         _launch("nerf_amd_encode_points_bf16", _lib.ptr(self.pts), _lib.ptr(self.posx), _lib.ptr(self.posd), self.P, ss)
 
 
+class _MarkedPass(_MaskedPass):
+    """A masked pass whose ``mask`` / ``offsets`` the stepper's own launch in front of it has written (the masked guided
+    placement, which marks the positions it places): capped emit, then the points-mode kernels -- no mark of its own."""
+
+    def forward(self, st):
+        ptr = _lib.ptr
+        _launch("nerf_amd_occupancy_points_capped", *self.jitter, ptr(self.mask), ptr(self.offsets), ptr(self.pts),
+                ptr(self.counts), self.P, self.step.B, self.N, st)
+        _launch("nerf_amd_mlp_forward_train_points", ptr(self.pts), ptr(self.fwd), ptr(self.raw), ptr(self.acts), self.P, st)
+
+
 class GraphedTrainStep:
     """``train_step`` (reference train.py:47-57) for the fused bf16 path with every buffer
     allocated once and the launches captured into hipGraphs that are replayed per iteration:
@@ -1047,6 +1085,7 @@ class GraphedTrainStep:
     _samples = None              # samples per ray of each pass; None: the one pass of N samples
     _capacities = None           # point capacity of each pass (masked passes through ``occupancy``); None: dense passes
     _one_bucket = False          # the two-bucket exchange exists for the dense single step only
+    _masked_pass_type = _MaskedPass      # what a masked pass is: with its own mark, or behind a launch that marks (_MarkedPass)
 
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
                  device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16",
@@ -1151,7 +1190,7 @@ class GraphedTrainStep:
             # the grid as the graph sees it: the words' address, the axes as HOST floats, the outside policy
             self._grid = (tuple(occ.resolution), _host_f32x3(occ.lo), _host_f32x3(occ.inv_step),
                           _lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-            self.passes = [_MaskedPass(self, N_, C, self._counts[2 * k:2 * k + 2])
+            self.passes = [self._masked_pass_type(self, N_, C, self._counts[2 * k:2 * k + 2])
                            for k, (N_, C) in enumerate(zip(samples, self._capacities))]
         else:
             self.passes = [_DensePass(self, N_, self._e4m3) for N_ in samples]
@@ -1806,5 +1845,58 @@ class GraphedGuidedTrainStep(GraphedTrainStep):
             self.u_f.copy_(u_f, non_blocking=True)
             u = self.u
         return super().step(rays, gt, u=u, decay=decay)
+
+    __call__ = step
+
+
+class GraphedMaskedGuidedTrainStep(_MaskedSteps, GraphedGuidedTrainStep):
+    """``train_step_guided(..., occupancy=)`` as captured hipGraphs: GraphedGuidedTrainStep with its one
+    pass masked on a fixed point capacity, as GraphedMaskedTrainStep runs its one -- the cheapest step this package has: one
+    network, its samples gathered where the volume says the surface is, empty space never evaluated.
+
+        graph A: hyper fetch -> masked guided placement (nerf_amd_sample_pdf_volume_masked: coarse positions, look-up in the
+                 proposal's sigma volume, dead coarse samples weighed 0, sample_pdf, mark + scan of the merged positions; writes
+                 ``ts_f`` [B, Nc+Nf], ``mask``, ``offsets``) -> capped emit on ts_f (nerf_amd_occupancy_points_capped: pts[C, 6],
+                 counts) -> training forward on the C points -> masked head (nerf_amd_volume_render_masked_mse_backward under
+                 NERF_AMD_TS_GIVEN) -> dX chain -> dW products; the side branch beside the dX chain is GraphedTrainStep's.
+                 nerf_amd_occupancy_mark is not launched: the placement marks what it places.
+        graph B and the all-reduce seam: GraphedTrainStep's, unchanged (one exchange bucket).
+
+    ``capacity``: points, or a fraction of n_rays * (Nc + Nf); NO default.  Overflow, ``counts()``, ``last_stats``,
+    ``overflow_steps`` and the RuntimeWarning are GraphedMaskedTrainStep's; jitter, ``step(rays, gt, u_c=, u_f=)`` and
+    ``rays_from`` are GraphedGuidedTrainStep's.  The addresses of ``occupancy.words`` and ``proposal.sigma`` are baked into
+    the graph (``step`` raises if either tensor was replaced); ``TrainingOccupancyGrid.update`` and ``ProposalVolume.update``
+    write in place, so an update between two replays simply takes effect.  With P' <= C at step k the step is the eager
+    ``train_step_guided(..., occupancy=, device_rng=True, seed=seed + k)``.  bf16 storage, the default network."""
+
+    _masked_pass_type = _MarkedPass
+
+    def __init__(self, net, optimizer, n_rays, Nc, Nf, proposal, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
+                 seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+        from .utils.proposal import check_sizes
+        self._refuse(storage, buckets)
+        _check_guided(net, proposal)
+        Nc_, Nf_ = check_sizes(Nc, Nf)
+        B = int(n_rays)
+        if B < 1:
+            raise ValueError(f"{type(self).__name__} needs n_rays >= 1 (got {n_rays})")
+        self._bind_grid((net,), (Nc_ + Nf_,), B, optimizer, occupancy, capacity)
+        self.capacity = self._capacities[0]
+        super().__init__(net, optimizer, B, Nc_, Nf_, proposal, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+
+    def _before_forward(self, st):
+        import ctypes
+        p, m, ptr = self.proposal, self.passes[0], _lib.ptr
+        R, lo, inv, outside = self._grid
+        rays, jit, tbins, flags, seed, rid = self._coarse_jitter
+        _launch("nerf_amd_sample_pdf_volume_masked", rays, jit, tbins, flags | outside, seed, rid,
+                ctypes.c_void_p(self._sigma_ptr), *p.resolution, p._h_lo, p._h_inv_step, ctypes.c_void_p(self._words_ptr), *R, lo,
+                inv, None if self.device_rng else ptr(self.u_f), ptr(self.ts_f), None, None, ptr(m.mask), ptr(m.offsets), None,
+                ptr(self._mark_ws), self.B, self.Nc, self.Nf, st)
+
+    def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
+        self._watch_grid()
+        return super().step(rays, gt, u_c=u_c, u_f=u_f, decay=decay)
 
     __call__ = step

@@ -314,13 +314,14 @@ def sample_positions(rays, jit, tbins, flags, seed, ray_id0, N):
     return _query_points(rays, jit, tbins, flags, seed, ray_id0, N)[1]
 
 
-def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels):
+def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels, mark=None):
     """mark + emit of one masked pass, now (one host read) -> (MarkResult, stats, launch); ``launch(code, image)`` enqueues
-    the network on the live points and the masked compositor and returns the 5-tuple, or pixels [B, 4]."""
+    the network on the live points and the masked compositor and returns the 5-tuple, or pixels [B, 4].  ``mark``: the
+    ready MarkResult of these positions (the masked guided placement produces it with them): no mark is launched."""
     from .rendering import _five_outputs, _per_sample
     B, dev = rays.size(0), rays.device
     lib = _lib.lib()
-    m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N)
+    m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N) if mark is None else mark
     pts = _points(m, rays, jit, tbins, flags, seed, ray_id0)
     stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
 
@@ -351,8 +352,20 @@ def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels
 def render_masked(occ, rays, net, N, tbins, jit, flags, seed, ray_id0, code, outputs, pixels=False):
     """The body of ``render_nerf(..., occupancy=occ)`` / ``render_view(..., occupancy=occ)`` once rays, jitter and
     precision are settled.  Returns the 5-tuple, or pixels [B, 4] with ``pixels=True``."""
+    return _render_pass(occ, rays, net, code, _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels))
+
+
+def _render_marked(occ, rays, net, ts, mark, code, outputs, pixels=False):
+    """``render_masked`` on given positions ``ts`` [B, N] whose MarkResult through ``occ`` is already there (the masked guided
+    placement, ``ProposalVolume.sample(..., occupancy=occ, return_mark=True)``): emit, network, masked compositor."""
+    N = ts.size(1)
+    return _render_pass(occ, rays, net, code,
+                        _masked_pass(occ, rays, N, None, ts, _lib.FLAG_TS_GIVEN, 0, 0, outputs, pixels, mark=mark))
+
+
+def _render_pass(occ, rays, net, code, masked_pass):
     from .nets import guarded_launch
-    m, stats, launch = _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels)
+    m, stats, launch = masked_pass
     occ.last_stats = stats
     if rays.size(0) == 0 or m.live == 0:
         # nothing to evaluate: no network launch, hence nothing for the range guard to look at

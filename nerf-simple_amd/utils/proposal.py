@@ -12,6 +12,10 @@ skipped), the compositor's weights of raw = (0, 0, 0, value), and ``sample_pdf``
 definition it equals nerf_amd_query_points -> look-up -> nerf_amd_volume_render_rays -> nerf_amd_sample_pdf bit for bit;
 tests/guided_model.py restates the look-up and the composition in numpy.  The positions carry no gradient.
 
+With ``occupancy=`` (an ``OccupancyGrid``) the sampler is the masked guided placement (csrc/guided_masked.hip, DESIGN.md
+section 24): dead coarse samples weigh nothing and the merged positions come back marked, so ``render_guided``,
+``render_guided_view`` and ``train_step_guided`` evaluate the network at the live ones only.
+
 There is no default for the resolution or for how often ``update`` runs: the caller states both.
 """
 import numpy as np
@@ -103,8 +107,25 @@ class ProposalVolume:
                 *self.resolution, self._h_lo, self._h_inv_step, _lib.ptr(u_f), _lib.ptr(ts_out), _lib.ptr(sigma_c),
                 _lib.ptr(w_c), B, Nc, Nf, _lib.stream_ptr(dev)), "nerf_amd_sample_pdf_volume")
 
-    def check(self, rays, Nc, Nf, u_c=None, ts_c=None, u_f=None, device_rng=False):
+    def _launch_masked(self, occ, rays, jit, tbins, flags, seed, ray_id0, u_f, ts_out, sigma_c, w_c, mask, offsets, live, ws,
+                       B, Nc, Nf):
+        """Enqueue nerf_amd_sample_pdf_volume_masked (placement + mark + scan through ``occ``) likewise."""
+        dev = self.sigma.device
+        mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_sample_pdf_volume_masked(
+                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), mflags, int(seed), int(ray_id0), _lib.ptr(self.sigma),
+                *self.resolution, self._h_lo, self._h_inv_step, _lib.ptr(occ.words), *occ.resolution, _host_f32x3(occ.lo),
+                _host_f32x3(occ.inv_step), _lib.ptr(u_f), _lib.ptr(ts_out), _lib.ptr(sigma_c), _lib.ptr(w_c), _lib.ptr(mask),
+                _lib.ptr(offsets), _lib.ptr(live), _lib.ptr(ws), B, Nc, Nf, _lib.stream_ptr(dev)),
+                "nerf_amd_sample_pdf_volume_masked")
+
+    def check(self, rays, Nc, Nf, u_c=None, ts_c=None, u_f=None, device_rng=False, *, occupancy=None):
         """The preconditions of ``sample``; raises before any jitter is drawn.  -> (B, Nc, Nf)"""
+        if occupancy is not None:
+            from .occupancy import OccupancyGrid
+            if not isinstance(occupancy, OccupancyGrid):
+                raise TypeError("occupancy must be an OccupancyGrid (utils/occupancy.py)")
         Nc, Nf = check_sizes(Nc, Nf)
         _lib.require_cuda_f32(rays, "rays")
         if rays.dim() != 2 or rays.shape[1] != 6:
@@ -126,20 +147,31 @@ class ProposalVolume:
         for name, t_, n in (("u_c", u_c, Nc), ("ts_c", ts_c, Nc), ("u_f", u_f, Nf)):
             if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
                 raise RuntimeError(f"{name} must be [B, {n}]")
+        if occupancy is not None and occupancy.words.device != rays.device:
+            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {rays.device}")
         return B, Nc, Nf
 
     def sample(self, rays, Nc, Nf, tn=2, tf=6, *, u_c=None, ts_c=None, u_f=None, device_rng=False, seed=0, ray_id0=0,
-               return_weights=False):
+               return_weights=False, occupancy=None, return_mark=False):
         """ts [B, Nc + Nf]: the Nc coarse positions of ``render_nerf`` for these jitter arguments merged with Nf importance
         samples of the volume's weights, sorted.  Coarse jitter: ``u_c`` [B, Nc] / ``ts_c`` [B, Nc] explicit, or
         ``device_rng=True`` (counter RNG keyed by ``seed``, ``ray_id0``); fine jitter: ``u_f`` [B, Nf], or the counter RNG
         with ``device_rng=True`` (``sample_pdf``'s key).  Default: ``render_hierarchical``'s draws, ``torch.rand(B, Nc)`` then
         ``torch.rand(B, Nf)`` from torch's CPU generator, continued on the device.  return_weights: also the looked-up
         values and the weights, (ts, sigma_c [B, Nc], w_c [B, Nc]).  No host synchronisation; every refusal happens before
-        anything is drawn."""
+        anything is drawn.
+
+        occupancy: an ``OccupancyGrid`` -- the masked guided placement (one entry point,
+        nerf_amd_sample_pdf_volume_masked): a coarse sample in a dead cell of the grid weighs exactly 0, so the new samples
+        gather in live cells, and the merged positions are marked through the same grid.  ``sigma_c`` is then the value
+        after that masking (-inf at a dead coarse sample).  return_mark (needs ``occupancy``): the ``MarkResult`` of the
+        merged positions (utils/occupancy.py) comes back as the last element; reading its live count is the call's one host
+        synchronisation."""
         from .host_rng import reference_rand
         from .rendering import _tbins
-        B, Nc, Nf = self.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng)
+        if return_mark and occupancy is None:
+            raise ValueError("return_mark=True needs an occupancy grid")
+        B, Nc, Nf = self.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)
         dev = rays.device
         rays = rays.detach().contiguous()
         flags, jit = 0, None
@@ -162,5 +194,17 @@ class ProposalVolume:
         if return_weights:
             sigma_c = torch.empty((B, Nc), dtype=torch.float32, device=dev)
             w_c = torch.empty((B, Nc), dtype=torch.float32, device=dev)
-        self._launch(rays, jit, tbins, flags, seed, ray_id0, u_f, ts, sigma_c, w_c, B, Nc, Nf)
-        return (ts, sigma_c, w_c) if return_weights else ts
+        if occupancy is None:
+            self._launch(rays, jit, tbins, flags, seed, ray_id0, u_f, ts, sigma_c, w_c, B, Nc, Nf)
+            return (ts, sigma_c, w_c) if return_weights else ts
+        from .occupancy import MarkResult
+        N = Nc + Nf
+        mask = torch.empty((B, (N + 63) // 64), dtype=torch.int64, device=dev)
+        offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        ws = torch.empty(max(int(_lib.lib().nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+        self._launch_masked(occupancy, rays, jit, tbins, flags, seed, ray_id0, u_f, ts, sigma_c, w_c, mask, offsets, None, ws,
+                            B, Nc, Nf)
+        out = (ts, sigma_c, w_c) if return_weights else (ts,)
+        if return_mark:
+            out += (MarkResult(mask, offsets, int(offsets[B]), B, N),)          # the one host synchronisation
+        return out if len(out) > 1 else ts

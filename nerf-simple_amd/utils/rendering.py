@@ -782,13 +782,22 @@ def _check_guided(net, proposal):
 
 
 def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=None, u_f=None, outputs=ALL_OUTPUTS,
-                  precision=None, device_rng=False, seed=0, ray_id0=0):
+                  precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
     """Grid-guided render: ONE network on Nc + Nf positions per ray, the Nf new ones placed by
     ``proposal`` (a ``ProposalVolume``, utils/proposal.py) from its sigma volume instead of by a coarse network.  It is
     ``render_nerf(rays, net, Nc + Nf, ts=proposal.sample(rays, Nc, Nf, ...))``; jitter arguments as ``ProposalVolume.sample``
     (default: ``render_hierarchical``'s two CPU draws).  Returns render_nerf's five outputs plus ts [B, Nc + Nf].  Default
-    network shape only; no gradients to the rays; no host synchronisation beyond the fp16 range guard's."""
+    network shape only; no gradients to the rays; no host synchronisation beyond the fp16 range guard's.
+
+    occupancy: an ``OccupancyGrid`` -- the masked guided render: the masked guided placement (dead
+    coarse samples weigh nothing; the merged positions come back marked) and the masked render on those positions under
+    that mark, which is not formed a second time.  By definition ``render_nerf(rays, net, Nc + Nf, ts=ts, occupancy=occupancy)``
+    on the placement's ``ts``; inference only (call it under ``torch.no_grad()``), one host synchronisation, sets
+    ``occupancy.last_stats``."""
     _check_guided(net, proposal)
+    if occupancy is not None:
+        return _render_guided_masked(rays, net, Nc, Nf, proposal, tn, tf, u_c, ts_c, u_f, outputs, precision, device_rng, seed,
+                                     ray_id0, occupancy)
     B, Nc, Nf = proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng)
     if not (torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())):
         net.packed_weights(_lib.precision_code(net.precision if precision is None else precision))     # errors before the draws
@@ -796,18 +805,49 @@ def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=Non
     return render_nerf(rays, net, Nc + Nf, tn, tf, ts=ts, outputs=outputs, precision=precision) + (ts,)
 
 
+def _render_guided_masked(rays, net, Nc, Nf, proposal, tn, tf, u_c, ts_c, u_f, outputs, precision, device_rng, seed, ray_id0,
+                          occupancy):
+    """The body of ``render_guided(..., occupancy=)``: render_nerf's masked branch on the placement's positions and mark."""
+    from .occupancy import check_renderable, _render_marked
+    from .xyz import range_check_rays
+    check_renderable(occupancy, net, torch.is_tensor(rays) and rays.requires_grad)
+    proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)
+    code = _lib.precision_code(net.precision if precision is None else precision)
+    net.packed_weights(code)                      # errors before the draws
+    with torch.no_grad():
+        rays = rays.detach().contiguous()
+        ts, mark = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
+                                   ray_id0=ray_id0, occupancy=occupancy, return_mark=True)
+        range_check_rays(rays, ts, None, _lib.FLAG_TS_GIVEN, 0, 0, ts.size(1))
+        return _render_marked(occupancy, rays, net, ts, mark, code, outputs) + (ts,)
+
+
 def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, u_f=None, ray0=0, n_rays=None,
-                       precision=None, device_rng=False, seed=0):
+                       precision=None, device_rng=False, seed=0, occupancy=None):
     """One view (or its pixel range [ray0, ray0 + n_rays)) through the grid-guided render: device ray generation ->
     ``proposal.sample`` (counter RNG keyed by global pixel id with device_rng=True) -> the fused render on the given
     positions -> clip(rgb, 0, 1).  Returns pixels [n, 4] = [r, g, b, disparity] on the GPU.  u_c [n, Nc] / u_f [n, Nf]:
-    explicit uniforms for these pixels; default: the CPU draws torch.rand(n, Nc) then torch.rand(n, Nf)."""
+    explicit uniforms for these pixels; default: the CPU draws torch.rand(n, Nc) then torch.rand(n, Nf).
+
+    occupancy: an ``OccupancyGrid`` -- device ray generation -> the masked guided placement -> the
+    masked render's pixel head (nerf_amd_volume_render_masked_pixels) on its positions under its mark; under
+    ``torch.no_grad()``, one host synchronisation."""
     _check_guided(net, proposal)
+    if occupancy is not None:
+        from .occupancy import check_renderable
+        check_renderable(occupancy, net, False)
     dev = next(net.parameters()).device
     n = int(cam_params[0]) * int(cam_params[1]) - ray0 if n_rays is None else int(n_rays)
     code = _lib.precision_code(net.precision if precision is None else precision)
     net.packed_weights(code)
     rays = generate_rays(pose, cam_params, dev, ray0, n)
+    if occupancy is not None:
+        # the masked guided placement -> the masked render's pixel head on its positions under its mark (section 24)
+        from .occupancy import _render_marked
+        with torch.no_grad():
+            ts, mark = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray0,
+                                       occupancy=occupancy, return_mark=True)
+            return _render_marked(occupancy, rays, net, ts, mark, code, (), pixels=True)
     ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray0)
     N, lib = ts.size(1), _lib.lib()
 
