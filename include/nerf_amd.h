@@ -924,6 +924,47 @@ int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, co
                                            const uint64_t* seed_mem, int64_t ray_id0, float* rgb, float* d_raw, int64_t B, int N,
                                            void* stream);
 
+/* ---- distortion loss for the dense training path -------------------------------------------------------------------------
+ * mip-NeRF 360's regulariser on a ray's compositing weights (the w of utils/rendering.py:68), which pulls them together into
+ * one compact interval.  For one ray with positions t_0 <= ... <= t_{N-1} and the far plane t_far:
+ *     delta_i = t_{i+1} - t_i (i < N - 1), delta_{N-1} = max(t_far - t_{N-1}, 0)     (the compositor's 1e10, clipped)
+ *     m_i     = t_i + delta_i / 2
+ *     D       = 2 sum_i w_i sum_{j<i} w_j (m_i - m_j) + (1/3) sum_i w_i^2 delta_i
+ *     dD/dw_i = 2 [ sum_{j<i} w_j (m_i - m_j) + sum_{j>i} w_j (m_j - m_i) ] + (2/3) w_i delta_i
+ * This ORDERED form is the definition; it equals sum_ij w_i w_j |m_i - m_j| + (1/3) sum w_i^2 delta_i on nondecreasing
+ * positions, which every sampler here produces and nothing checks.  Positions carry no gradient.  O(N) per ray: one
+ * wavefront per ray, prefix and suffix sums of w and w m (m centred on t_0), every operation rounded on its own; no atomics:
+ * every run writes the same bytes.  A sample with w_i == 0 contributes exact zeros; a NaN weight stays inside its ray.
+ *
+ * nerf_amd_distortion_loss: ts[B,N], w[B,N] -> loss_ray[B] = coef D and g_w[B,N] = coef dD/dw; either output may be NULL (not
+ *   both).  A training step's term is lambda / (B (tf - tn)) sum_rays D: coef = lambda / (B (tf - tn)) formed in double and
+ *   rounded once, t_far = tf (mip-NeRF 360's normalised distance: D is homogeneous of degree 1 in t).  N == 1 is the
+ *   reference's empty sample axis: loss_ray = 0, g_w = 0.  N <= 512.
+ *   Rules in order: NERF_AMD_EINVAL for B < 0 or N <= 0; for t_far or coef not finite or coef < 0; B == 0 launches nothing;
+ *   NERF_AMD_EUNSUP for N > 512 (or B > 2^32); NERF_AMD_EINVAL for a missing pointer. */
+int nerf_amd_distortion_loss(const float* ts, const float* w, float t_far, float coef, float* loss_ray, float* g_w, int64_t B,
+                             int N, void* stream);
+
+/* nerf_amd_sum_f32: out[0] = the sum of x[n], one workgroup and a fixed summation order (as nerf_amd_mse_loss): the same bits
+ *   from run to run.  The step's distortion term from loss_ray.  NERF_AMD_EINVAL for n <= 0 or a missing pointer. */
+int nerf_amd_sum_f32(const float* x, float* out, int64_t n, void* stream);
+
+/* nerf_amd_volume_render_mse_backward_dist: the training head with the distortion term, ONE launch.  By definition, bit for
+ *   bit (tests/test_gpu_distortion.py), it is the composition
+ *     nerf_amd_sigma_noise (std, flags, seed, seed_mem, ray_id0)
+ *     -> nerf_amd_volume_render_rays (rgb, acc, w) -> nerf_amd_distortion_loss (t_far, coef) on that w: loss_ray, g_w
+ *     -> nerf_amd_background_blend -> g = 2 (rgb_bg - target) / (3 B) -> nerf_amd_background_blend_backward
+ *     -> nerf_amd_volume_render_rays_backward (g_rgb = g, g_acc, g_w)
+ *   so d_raw[B,N,4] is the gradient of MSELoss(rgb_bg, target) + sum_rays coef D.  rgb[B,3] = rgb_bg and loss_ray[B] may be
+ *   NULL.  bg == NULL: no background (bg_stride is still checked); std == 0: no noise; with both it is the plain chain.
+ *   coef == 0: rgb and d_raw are nerf_amd_volume_render_mse_backward_bg's and loss_ray is all zeros.  N <= 512; at N == 1
+ *   rgb = bg (0 without one), loss_ray = 0 and d_raw = 0.  Rules in order: sizes; the noise arguments as in
+ *   nerf_amd_sigma_noise; bg_stride; t_far and coef as in nerf_amd_distortion_loss; B == 0; the size limit; the pointers. */
+int nerf_amd_volume_render_mse_backward_dist(const float* raw, const float* ts, const float* rays, const float* target,
+                                             const float* bg, int64_t bg_stride, float std, uint32_t flags, uint64_t seed,
+                                             const uint64_t* seed_mem, int64_t ray_id0, float t_far, float coef, float* rgb,
+                                             float* loss_ray, float* d_raw, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

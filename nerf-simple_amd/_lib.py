@@ -79,6 +79,10 @@ _SIGNATURES = {
     "nerf_amd_background_blend_backward": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "nerf_amd_volume_render_mse_backward_bg": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_float, _u32, _u64, _vp, _i64,
                                                       _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_distortion_loss": (_i32, [_vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _i64, _i32, _vp]),
+    "nerf_amd_sum_f32": (_i32, [_vp, _vp, _i64, _vp]),
+    "nerf_amd_volume_render_mse_backward_dist": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_float, _u32, _u64, _vp, _i64,
+                                                        ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_render_hierarchical_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "nerf_amd_render_hierarchical_forward": (_i32, [_vp, _i32, _i32, ctypes.c_float, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
                                                     _i32, _u32, _u64, _vp, _vp, _i32, _i32, _vp]),

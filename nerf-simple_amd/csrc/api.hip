@@ -381,6 +381,39 @@ int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, co
                                                      ray_id0, rgb, d_raw, B, N, S(stream));
 }
 
+// The distortion term (composite_dist.hip).  Order of the rules: sizes; [the noise arguments; the background's stride;] the
+// term's scalars (api_checks.h bad_distortion); the empty problem; the size limit (NERF_AMD_EUNSUP); the pointers.
+int nerf_amd_distortion_loss(const float* ts, const float* w, float t_far, float coef, float* loss_ray, float* g_w, int64_t B,
+                             int N, void* stream) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_distortion(t_far, coef)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (N > COMPOSITE_BWD_MAX_N || B > MASKED_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (!ts || !w || (!loss_ray && !g_w)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_distortion_loss(ts, w, t_far, coef, loss_ray, g_w, B, N, S(stream));
+}
+
+int nerf_amd_sum_f32(const float* x, float* out, int64_t n, void* stream) {
+    if (n <= 0 || !x || !out) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_sum_f32(x, out, n, S(stream));
+}
+
+int nerf_amd_volume_render_mse_backward_dist(const float* raw, const float* ts, const float* rays, const float* target,
+                                             const float* bg, int64_t bg_stride, float std, uint32_t flags, uint64_t seed,
+                                             const uint64_t* seed_mem, int64_t ray_id0, float t_far, float coef, float* rgb,
+                                             float* loss_ray, float* d_raw, int64_t B, int N, void* stream) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_sigma_noise(std, flags, seed_mem)) return NERF_AMD_EINVAL;
+    if (bad_bg_stride(bg_stride)) return NERF_AMD_EINVAL;
+    if (bad_distortion(t_far, coef)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
+    if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_composite_mse_backward_dist(raw, ts, rays, target, bg, bg_stride, std, seed,
+                                                       (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
+                                                       ray_id0, t_far, coef, rgb, loss_ray, d_raw, B, N, S(stream));
+}
+
 int nerf_amd_mse_loss(const float* pred, const float* target, float* loss, float* g_pred, int64_t n, void* stream) {
     if (n <= 0 || !pred || !target || !loss) return NERF_AMD_EINVAL;
     return nerf_amd_launch_mse_loss(pred, target, loss, g_pred, n, S(stream));

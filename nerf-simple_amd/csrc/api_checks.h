@@ -40,6 +40,12 @@ inline bool bad_sigma_noise(float std, uint32_t flags, const uint64_t* seed_mem)
     if (flags & ~NERF_AMD_SEED_IN_MEMORY) return true;
     return (flags & NERF_AMD_SEED_IN_MEMORY) && (!seed_mem || misaligned(seed_mem, 8));
 }
+// the distortion term's scalars (nerf_amd_distortion_loss, nerf_amd_volume_render_mse_backward_dist): the far plane finite,
+// the coefficient finite and >= 0 (0 switches the term off: its gradient and loss values are zeros)
+inline bool bad_distortion(float t_far, float coef) {
+    if (!(coef >= 0.f) || coef > 3.402823466e38f) return true;                 // negative, NaN, inf
+    return !(t_far >= -3.402823466e38f && t_far <= 3.402823466e38f);
+}
 // a background: one colour (stride 0) or one per ray (stride 3), in floats; looked at whether or not `bg` is given
 inline bool bad_bg_stride(int64_t bg_stride) { return bg_stride != 0 && bg_stride != 3; }
 

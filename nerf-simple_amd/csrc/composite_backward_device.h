@@ -17,7 +17,8 @@
 // The three axes on which the callers differ are compile-time choices; a term a caller does not have is not computed.
 //   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd)
 //   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; MseHead: the loss gradient formed here;
-//           BgMseHead: the same behind a background colour, whose gradient to acc reaches every w_i)
+//           BgMseHead: the same behind a background colour, whose gradient to acc reaches every w_i; DistMseHead: the same
+//           with the distortion loss of the ray's weights beside the MSE, whose gradient joins G_i where FiveGrads adds g_w)
 //   Sink -- where the forward sweep's weights go (NoSink; PdfSink: the sampler's LDS slice, sample_pdf_device.h)
 #pragma once
 #include "composite_device.h"
@@ -37,6 +38,10 @@ __device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& tota
     if (lane == 63) ex = 0.f;
     return ex;
 }
+
+}  // namespace nerf_composite
+#include "composite_dist_device.h"      // distortion_ray: the distortion loss of a ray's weights (uses wave_suffix_excl)
+namespace nerf_composite {
 
 // ---- sample sources --------------------------------------------------------------------------------------------------------
 struct BwdSample {
@@ -112,6 +117,24 @@ struct BgMseHead {
 };
 template <class Up> inline constexpr bool behind_background = false;
 template <> inline constexpr bool behind_background<BgMseHead> = true;
+
+// The MSE head with the distortion term beside it: loss = MSELoss(rgb_bg, target) + sum_rays coef D(w, t) (composite_dist_device.h).
+// By definition the chain  compositor (rgb, acc, w) -> nerf_amd_distortion_loss on that w (loss_ray, g_w) -> [blend] -> the MSE
+// gradient -> [the blend's backward] -> compositor backward (g_rgb, g_acc, g_w), bit for bit: G_i = (rgb terms + g_acc) + g_w_i.
+template <bool BG>
+struct DistMseHead {
+    static constexpr bool MSE = true;
+    const float* target;               // [B,3]
+    float* rgb_out;                    // [B,3]: rgb_bg (rgb without a background), or NULL
+    float scale;                       // 1 / (3 B)
+    const float* bg;                   // as BgMseHead's; not looked at without BG
+    long long bg_stride;
+    float t_far, coef;                 // the last sample's interval ends at t_far; coef = lambda / (B (tf - tn))
+    float* loss_ray;                   // [B]: coef D of each ray, or NULL
+};
+template <> inline constexpr bool behind_background<DistMseHead<true>> = true;
+template <class Up> inline constexpr bool with_distortion = false;
+template <bool BG> inline constexpr bool with_distortion<DistMseHead<BG>> = true;
 
 // ---- weight sinks ----------------------------------------------------------------------------------------------------------
 struct NoSink {
@@ -213,6 +236,15 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
             }
         }
     }
+    // the distortion term on the forward sweep's weights: its gradient to every w_i, and the ray's loss value
+    [[maybe_unused]] float gw[with_distortion<Up> ? CHUNKS : 1];
+    if constexpr (with_distortion<Up>) {
+        float wv[CHUNKS];
+#pragma unroll
+        for (int ch = 0; ch < CHUNKS; ++ch) wv[ch] = (ch * 64 + lane < N) ? mul_rn(al[ch], Tt[ch]) : 0.f;
+        const float dist = distortion_ray<CHUNKS>(tt, wv, N, lane, up.t_far, up.coef, gw);
+        if (up.loss_ray && lane == 0) up.loss_ray[ray] = dist;
+    }
     // backward sweep over chunks, carrying sum_{k in later chunks} G_k w_k
     float later = 0.f;
 #pragma unroll
@@ -226,6 +258,7 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
             if (valid) {
                 G = add_rn(add_rn(mul_rn(gr, cc[ch][0]), mul_rn(gg, cc[ch][1])), mul_rn(gb, cc[ch][2]));
                 if constexpr (behind_background<Up>) G = add_rn(G, gac);
+                if constexpr (with_distortion<Up>) G = add_rn(G, gw[ch]);
                 if constexpr (!Up::MSE) {
                     G = add_rn(add_rn(G, mul_rn(gdep, tt[ch])), gac);
                     if (up.g_w) G = add_rn(G, up.g_w[ray * N + i]);

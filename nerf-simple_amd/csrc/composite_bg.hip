@@ -63,20 +63,7 @@ __global__ __launch_bounds__(256) void background_blend_backward_kernel(const fl
     g_acc[ray] = -add_rn(add_rn(mul_rn(g[ray * 3 + 0], b[0]), mul_rn(g[ray * 3 + 1], b[1])), mul_rn(g[ray * 3 + 2], b[2]));
 }
 
-// ---- the training head -----------------------------------------------------------------------------------------------------
-// DenseSamples with the shared noise routine applied to sigma as a chunk is loaded: the forward sweep keeps sigma'-derived
-// values per chunk and the backward sweep reuses them, so each sample's noise is generated once.
-struct NoisySamples {
-    nerf_composite::DenseSamples dense;
-    float std;
-    unsigned long long key, sample0;       // sample0 = (ray_id0 + ray) N
-    __device__ __forceinline__ nerf_composite::BwdSample chunk(int ch, int i, int lane, bool valid, int N) {
-        nerf_composite::BwdSample s = dense.chunk(ch, i, lane, valid, N);
-        if (valid) s.c[3] = nerf_noise::noisy_sigma(s.c[3], std, key, sample0 + (unsigned long long)i);
-        return s;
-    }
-};
-
+// ---- the training head (its noisy sample source: sigma_noise_device.h NoisySamples) ---------------------------------------
 // NOISE: sigma' in front of the softplus; BG: the loss sits behind the blend.  (false, false) is composite_backward_kernel<0>
 // with the MSE head (composite.hip) and is not instantiated here.
 template <bool NOISE, bool BG>
@@ -112,7 +99,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_bg_head_kernel(
         }
     };
     if constexpr (NOISE) {
-        run(NoisySamples{dense, std, nerf_noise::noise_key(seed, seed_mem), (unsigned long long)((ray_id0 + ray) * N)});
+        run(nerf_noise::NoisySamples{dense, std, nerf_noise::noise_key(seed, seed_mem), (unsigned long long)((ray_id0 + ray) * N)});
     } else {
         run(dense);
     }

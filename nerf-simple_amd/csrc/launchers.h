@@ -101,4 +101,9 @@ int nerf_amd_launch_background_blend_backward(const float*, const float*, long l
 int nerf_amd_launch_composite_mse_backward_bg(const float*, const float*, const float*, const float*, const float*, long long,
                                               float, unsigned long long, const unsigned long long*, long long, float*, float*,
                                               long long, int, hipStream_t);
+int nerf_amd_launch_distortion_loss(const float*, const float*, float, float, float*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_sum_f32(const float*, float*, long long, hipStream_t);
+int nerf_amd_launch_composite_mse_backward_dist(const float*, const float*, const float*, const float*, const float*, long long,
+                                                float, unsigned long long, const unsigned long long*, long long, float, float,
+                                                float*, float*, float*, long long, int, hipStream_t);
 }

@@ -14,6 +14,7 @@
 //   z  = mul_rn(sqrt_rn(mul_rn(-2, logf(u1))), cospif(mul_rn(2, u2)))      (2 u2 is exact: cos(2 pi u2) with no rounded 2 pi)
 // |z| <= sqrt(2 * 24 ln 2) = 5.77; u1 = 1 gives z = +-0.
 #pragma once
+#include "composite_backward_device.h"
 #include "sample_pdf_device.h"
 
 namespace nerf_noise {
@@ -43,5 +44,19 @@ __device__ __forceinline__ float standard_normal(unsigned long long key, unsigne
 __device__ __forceinline__ float noisy_sigma(float sigma, float std, unsigned long long key, unsigned long long sample) {
     return add_rn(sigma, mul_rn(std, standard_normal(key, sample)));
 }
+
+// DenseSamples with the routine above applied to sigma as a chunk is loaded, for the training heads (composite_bg.hip,
+// composite_dist.hip): the forward sweep keeps sigma'-derived values per chunk and the backward sweep reuses them, so each
+// sample's noise is generated once.
+struct NoisySamples {
+    nerf_composite::DenseSamples dense;
+    float std;
+    unsigned long long key, sample0;       // sample0 = (ray_id0 + ray) N
+    __device__ __forceinline__ nerf_composite::BwdSample chunk(int ch, int i, int lane, bool valid, int N) {
+        nerf_composite::BwdSample s = dense.chunk(ch, i, lane, valid, N);
+        if (valid) s.c[3] = noisy_sigma(s.c[3], std, key, sample0 + (unsigned long long)i);
+        return s;
+    }
+};
 
 }  // namespace nerf_noise

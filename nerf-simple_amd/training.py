@@ -9,6 +9,7 @@ behind the C ABI, torch supplies tensors, streams, autograd bookkeeping and the 
   sigma -> alpha compositing, forward               nerf_amd_volume_render
   MSE loss and its gradient                         nerf_amd_mse_loss
   compositing, backward (suffix-sum scan)           nerf_amd_volume_render_backward
+  distortion loss on the weights (distortion=)      nerf_amd_distortion_loss + nerf_amd_sum_f32
   dense layers, backward dX chain (on-chip)         nerf_amd_mlp_backward
   dense layers, dW = dY^T X and db = sum dY         nerf_amd_param_gradients (one split-K launch for
                                                     all 14 products into ONE flat gradient vector)
@@ -197,14 +198,115 @@ class _Background(torch.autograd.Function):
 def composite_with_controls(raw, ts, dirs, from_rays, controls, ray_id0=0):
     """_VolumeRender with the training controls around it.  ``controls`` = (bg, stride, sigma_noise, noise_seed) or None."""
     if controls is None:
-        return _VolumeRender.apply(raw, ts, dirs, from_rays)
+        out = _VolumeRender.apply(raw, ts, dirs, from_rays)
+        out[4].ts = ts                # the positions the weights belong to: what a distortion term on w needs beside it
+        return out
     bg, stride, std, noise_seed = controls
     if std:
         raw = _SigmaNoise.apply(raw, std, noise_seed, ray_id0)
     out = _VolumeRender.apply(raw, ts, dirs, from_rays)
+    out[4].ts = ts
     if bg is not None:
         out = (_Background.apply(out[0], out[3], bg, stride),) + tuple(out[1:])
     return out
+
+
+# --------------------------------------------------------------------------
+# the distortion loss on the compositor's weights (DESIGN.md section 25)
+# --------------------------------------------------------------------------
+def _check_distortion(distortion):
+    """``distortion=`` as a weight: a finite float >= 0 (0 = off), else ValueError."""
+    import math
+    lam = float(distortion)
+    if not (lam >= 0.0) or math.isinf(lam):
+        raise ValueError(f"distortion is the weight of the distortion loss: finite and >= 0, got {distortion!r}")
+    return lam
+
+
+def _refuse_distortion(lam, **paths):
+    """The masked, hierarchical and sharded paths do not know the term: refused before any launch and any RNG draw."""
+    if not lam:
+        return
+    for name, v in paths.items():
+        if v is not None:
+            raise RuntimeError(f"distortion serves the dense and guided steps only: not with {name} (train without the term, "
+                               "or on the dense path)")
+
+
+def _distortion_launch(w, ts, t_far, coef, want_loss, want_grad):
+    """nerf_amd_distortion_loss on w [B,N], ts [B,N]: (coef D per ray [B], coef dD/dw [B,N]); the reference's empty sample
+    axis (w [B,0] at N == 1) has D = 0 and no gradient."""
+    _lib.require_cuda_f32(w, "w")
+    _lib.require_cuda_f32(ts, "ts")
+    B, dev = ts.shape[0], ts.device
+    if w.dim() != 2 or ts.dim() != 2 or w.shape[0] != B or (tuple(w.shape) != tuple(ts.shape) and not (w.shape[1] == 0 and ts.shape[1] == 1)):
+        raise RuntimeError(f"distortion loss: w {tuple(w.shape)} and ts {tuple(ts.shape)} must both be [B, N]")
+    if w.shape[1] == 0:
+        return torch.zeros((B,), dtype=torch.float32, device=dev), torch.zeros_like(w)
+    w, ts = w.contiguous(), ts.contiguous()
+    loss_ray = torch.empty((B,), dtype=torch.float32, device=dev) if want_loss else None
+    g_w = torch.empty_like(w) if want_grad else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nerf_amd_distortion_loss(_lib.ptr(ts), _lib.ptr(w), float(t_far), float(coef), _lib.ptr(loss_ray),
+                                                       _lib.ptr(g_w), B, w.shape[1], _lib.stream_ptr(dev)),
+                   "nerf_amd_distortion_loss")
+    return loss_ray, g_w
+
+
+class _DistortionRays(torch.autograd.Function):
+    """w [B,N] -> coef D per ray [B] through nerf_amd_distortion_loss, which writes coef dD/dw in the same launch."""
+
+    @staticmethod
+    def forward(ctx, w, ts, t_far, coef):
+        loss_ray, g_w = _distortion_launch(w, ts, t_far, coef, True, True)
+        ctx.save_for_backward(g_w)
+        return loss_ray
+
+    @staticmethod
+    def backward(ctx, g):
+        (g_w,) = ctx.saved_tensors
+        return g_w * g[:, None], None, None, None
+
+
+class _DistortionTerm(torch.autograd.Function):
+    """w [B,N] -> the step's scalar term sum_rays coef D: nerf_amd_distortion_loss, then nerf_amd_sum_f32 on its per-ray values
+    (one workgroup, fixed order) -- the two launches a graphed step's head and side branch make of it."""
+
+    @staticmethod
+    def forward(ctx, w, ts, t_far, coef):
+        loss_ray, g_w = _distortion_launch(w, ts, t_far, coef, True, True)
+        dev = loss_ray.device
+        term = torch.zeros((), dtype=torch.float32, device=dev)
+        if loss_ray.numel():
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().nerf_amd_sum_f32(_lib.ptr(loss_ray), _lib.ptr(term), loss_ray.numel(), _lib.stream_ptr(dev)),
+                           "nerf_amd_sum_f32")
+        ctx.save_for_backward(g_w)
+        return term
+
+    @staticmethod
+    def backward(ctx, g):
+        (g_w,) = ctx.saved_tensors
+        return g_w * g, None, None, None
+
+
+def distortion_loss(w, ts, tn=2, tf=6):
+    """mip-NeRF 360's distortion loss of each ray's compositing weights ``w`` [B,N] at the positions ``ts`` [B,N] (nondecreasing
+    along a ray; they carry no gradient), on the normalised distance: D / (tf - tn) per ray, [B], differentiable in ``w``.
+    Sample i owns [t_i, t_{i+1}], the last one [t_{N-1}, tf] (include/nerf_amd.h nerf_amd_distortion_loss); O(N) per ray."""
+    return _DistortionRays.apply(w, ts.detach(), float(tf), 1.0 / (float(tf) - float(tn)))
+
+
+def _distortion_coef(lam, B, tn, tf):
+    """lambda / (B (tf - tn)) in float64; the launch rounds it to fp32 once."""
+    return float(lam) / (float(B) * (float(tf) - float(tn)))
+
+
+def _distortion_term(w, ts, lam, tn, tf):
+    """lambda / (B (tf - tn)) sum_rays D as a 0-d tensor, differentiable in ``w``."""
+    if ts is None:
+        raise RuntimeError("distortion: this render did not hand back its sample positions (the net does not train)")
+    return _DistortionTerm.apply(w, ts.detach(), float(tf), _distortion_coef(lam, ts.shape[0], tn, tf))
 
 
 # --------------------------------------------------------------------------
@@ -503,7 +605,7 @@ def lr_decay_factor(lr_init, lr_final, num_iters):
 
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, background=None, sigma_noise=0.0,
-               noise_seed=0):
+               noise_seed=0, distortion=0.0):
     """zero_grad -> render_nerf -> MSELoss(rgb, gt) -> backward -> [grad all-reduce]
     -> optimizer.step -> lr *= decay.  Returns the (detached) loss.
     Only ``rgb`` feeds the loss, as in the reference (train.py:52).
@@ -513,9 +615,16 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     host synchronisation per step); everything else is the same step.
     background, sigma_noise, noise_seed: ``render_nerf``'s -- the loss is MSELoss(rgb + (1 - acc) background, gt) and the raw
     density carries Gaussian noise of that standard deviation (counter RNG keyed by ``noise_seed``: pass a new one per step).
-    Dense path only: with ``occupancy`` either raises RuntimeError before anything is drawn or launched."""
+    Dense path only: with ``occupancy`` either raises RuntimeError before anything is drawn or launched.
+    distortion: the weight lambda of mip-NeRF 360's distortion loss on the compositor's weights (0 = off, the default): the
+    loss becomes MSE + lambda / (B (tf - tn)) sum_rays D (``distortion_loss``; one fp32 add), on every path that composites
+    through the HIP backward (bf16 fused, precision='fp32', other sizes) and together with background / sigma_noise.  Dense
+    path only (RuntimeError with ``occupancy``); negative or not finite: ValueError.  The returned loss is the total; with
+    lambda > 0 ``.distortion`` on it holds the weighted term."""
     from . import parallel
     from .utils.rendering import render_nerf, _refuse_controls
+    lam = _check_distortion(distortion)
+    _refuse_distortion(lam, occupancy=occupancy)
     _refuse_controls(background, sigma_noise, occupancy=occupancy)
     if occupancy is not None:
         from .utils.occupancy import check_trainable
@@ -528,16 +637,22 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
         kw = {}
         if background is not None or sigma_noise:          # off by default: a call without them is the call it was
             kw = dict(background=background, sigma_noise=sigma_noise, noise_seed=noise_seed)
-        rgb, _, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
+        rgb, _, _, _, w = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
                                       device_rng=device_rng, seed=seed, ray_id0=ray_id0, **kw)
-    loss = mse_loss(rgb, gt)
+    loss, term = mse_loss(rgb, gt), None
+    if lam > 0:
+        term = _distortion_term(w, getattr(w, "ts", None), lam, tn, tf)
+        loss = loss + term
     loss.backward()
     parallel.allreduce_gradients(net.parameters(), group=group)
     optimizer.step()
     if decay != 1.0:
         for pg in optimizer.param_groups:
             pg["lr"] = pg["lr"] * decay
-    return loss.detach()
+    out = loss.detach()
+    if term is not None:
+        out.distortion = term.detach()
+    return out
 
 
 # --------------------------------------------------------------------------
@@ -689,7 +804,7 @@ def _check_guided(net, proposal, precision=None):
 
 
 def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, ts_c=None, u_f=None, decay=1.0,
-                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
+                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, distortion=0.0):
     """One optimisation step of ONE network on grid-guided positions: ts = ``proposal.sample(rays, Nc, Nf, ...)`` (a
     ``ProposalVolume``, utils/proposal.py: no network evaluation, no gradient) -> zero_grad -> render_nerf with gradients on those
     Nc + Nf positions -> MSE(rgb, gt) -> backward -> [grad all-reduce] -> optimizer.step -> lr *= decay.  The loss is that of
@@ -702,8 +817,13 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
     samples weigh nothing; the merged positions come back marked, one host read) -> the stages of ``render_nerf_masked`` on
     those positions under that mark, which is not formed again.  The loss is that of ``render_nerf_masked(rays, net, Nc + Nf,
     occupancy, ts=ts)``, bit for bit; refused as that function refuses (precision='fp32', other network sizes, foreign nets),
-    before anything is drawn."""
+    before anything is drawn.
+
+    distortion: ``train_step``'s -- the loss becomes MSE + lambda / (B (tf - tn)) sum_rays D on the Nc + Nf guided positions.
+    Not with ``occupancy`` (RuntimeError before anything is drawn)."""
     from . import parallel
+    lam = _check_distortion(distortion)
+    _refuse_distortion(lam, occupancy=occupancy)
     _check_guided(net, proposal, precision)
     if occupancy is not None:
         from .utils import occupancy as occ_mod
@@ -723,7 +843,10 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
         optimizer.zero_grad(set_to_none=True)
         outs, _ = _render_train_with_ts(rays, net, int(Nc) + int(Nf), tn, tf, ts, _lib.FLAG_TS_GIVEN,
                                         net.precision if precision is None else precision, seed, ray_id0)
-    loss = mse_loss(outs[0], gt)
+    loss, term = mse_loss(outs[0], gt), None
+    if lam > 0:
+        term = _distortion_term(outs[4], ts, lam, tn, tf)
+        loss = loss + term
     loss.backward()
     parallel.allreduce_gradients(net.parameters(), group=group)
     optimizer.step()
@@ -732,6 +855,8 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
             pg["lr"] = pg["lr"] * decay
     out = loss.detach()
     out.ts = ts
+    if term is not None:
+        out.distortion = term.detach()
     return out
 
 
@@ -936,7 +1061,13 @@ class _DensePass(_Pass):
         alpha, acc, w are not materialised.  ``pdf`` = (u_f, ts_f, Nf): sample_pdf on the weights in the same kernel (they
         never reach HBM), which takes the seed in memory where the counter RNG leaves u_f empty."""
         ptr, s, (rays, jit, _, flags, seed, rid) = _lib.ptr, self.step, self.jitter
-        if pdf is None and s._controls:
+        if pdf is None and s._distortion > 0:
+            # the head with the distortion term beside the MSE (and behind the same controls, if any): still one launch; the
+            # per-ray loss values go to the side branch's sum
+            _launch("nerf_amd_volume_render_mse_backward_dist", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt), ptr(s.background),
+                    s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, s.noise_seed & (2 ** 64 - 1), s._seed_mem, s.ray_id0,
+                    s._t_far, s._dist_coef, ptr(self.rgb), ptr(s._loss_ray), ptr(self.d_raw), s.B, self.N, st)
+        elif pdf is None and s._controls:
             # the same head behind the stepper's background and / or with noise on sigma; the noise key is noise_seed + the
             # step's offset in memory, whatever the jitter source is
             _launch("nerf_amd_volume_render_mse_backward_bg", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt), ptr(s.background),
@@ -1075,11 +1206,20 @@ class GraphedTrainStep:
     ``storage='e4m3'`` and ``buckets=2``: the head sits in front of both.  The dense single step only: the masked,
     hierarchical and guided steppers do not take them.
 
+    ``distortion`` (a weight lambda >= 0, default 0 = off): mip-NeRF 360's distortion loss on the compositor's weights beside
+    the MSE (``distortion_loss``).  With lambda > 0 the head is nerf_amd_volume_render_mse_backward_dist,
+    still one launch (behind the same background / noise, if any), and the side branch sums its per-ray values
+    (nerf_amd_sum_f32): ``stepper.distortion`` is a 0-d device tensor holding the weighted term lambda / (B (tf - tn)) sum_rays D,
+    ``step()`` returns the total MSE + term (one fp32 add) -- the eager ``train_step(..., distortion=lambda)`` bit for bit.
+    lambda is fixed at capture (``stepper.distortion_weight``, read-only): a schedule on it is a recapture.  The dense single
+    step and the guided step only: the masked and hierarchical steppers raise RuntimeError.
+
     ``check_every`` (default 16, 0 = never): every so many steps the forward's range flag is copied back without
     waiting; a later ``step`` raises FloatingPointError once such a copy shows non-finite values inside the network
     (NaN / inf weights or inputs: a diverged run) -- the reference would show a NaN loss there.
     """
 
+    _distortion = 0.0            # the distortion term's weight (the dense single step and the guided step only)
     _controls = False            # a background or sigma noise in the head (the dense single step only)
     background, _bg_stride, _sigma_noise, noise_seed = None, 0, 0.0, 0
     _samples = None              # samples per ray of each pass; None: the one pass of N samples
@@ -1089,9 +1229,13 @@ class GraphedTrainStep:
 
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
                  device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16",
-                 background=None, sigma_noise=0.0, noise_seed=0):
+                 background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0):
         from . import parallel
         from .utils.rendering import _background_arg, _check_sigma_noise
+        self._distortion = _check_distortion(distortion)
+        # the masked and hierarchical steppers inherit this constructor: the term cannot slip through them
+        _refuse_distortion(self._distortion, **{"a coarse / fine pair": self._samples if self._samples and len(self._samples) == 2 else None,
+                                                "an occupancy grid": self._capacities})
         self._check_modules(net, optimizer)
         self._sigma_noise, self.noise_seed = _check_sigma_noise(sigma_noise), int(noise_seed)
         if background is not None:           # this object's own buffer: the captured head reads it at every replay
@@ -1133,6 +1277,12 @@ class GraphedTrainStep:
         self.loss = torch.zeros((), **f32)
         self.hyper = torch.zeros(8, **f32)                 # [lr, b1, b2, eps, 1-b1^t, sqrt(1-b2^t), seed offset (int64)]
         self._alloc_pass_buffers(tn, tf)
+        if self._distortion > 0:
+            # the head writes coef D per ray; the side branch sums it into `distortion` and adds the MSE (now in its own slot)
+            self._t_far, self._dist_coef = float(tf), _distortion_coef(self._distortion, B, tn, tf)
+            self._loss_ray, self.distortion = torch.zeros((B,), **f32), torch.zeros((), **f32)
+            self.mse = torch.zeros((), **f32)
+            self.passes[0].loss = self.mse
         self._ids_next = torch.zeros((B,), dtype=torch.int64, device=dev)      # rays_from: rows of the table (see ray_ids)
         self._ids_cur, self._ids_step, self._primed_for = torch.zeros_like(self._ids_next), -1, -1
         self._select_ws = torch.empty(max(int(lib.nerf_amd_select_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
@@ -1160,6 +1310,11 @@ class GraphedTrainStep:
         if optimizer.net is not net:
             raise RuntimeError("the optimizer belongs to another module")
         _check_fused_trainable(net.precision)
+
+    @property
+    def distortion_weight(self):
+        """The weight lambda of the distortion term captured into the head (read-only: a schedule is a new stepper)."""
+        return self._distortion
 
     @property
     def sigma_noise(self):
@@ -1258,6 +1413,10 @@ class GraphedTrainStep:
         if len(self.passes) == 2:
             with torch.cuda.stream(side):
                 torch.add(self.losses[0], self.losses[1], out=self.loss)       # the total, MSE(rgb_c) + MSE(rgb_f)
+        if self._distortion > 0:
+            _launch("nerf_amd_sum_f32", _lib.ptr(self._loss_ray), _lib.ptr(self.distortion), self.B, ss)
+            with torch.cuda.stream(side):
+                torch.add(self.mse, self.distortion, out=self.loss)            # the total, MSE + the weighted term
         if self.rays_from is not None and self.device_rng:
             # rg.select + the colour gather (train.py:47-49) for the NEXT step, beside the dX chain: this step's rays and
             # colours have been read for the last time (forward or mark + emit, heads on the main branch in front of the
@@ -1336,26 +1495,38 @@ class GraphedTrainStep:
                     self._head_gradients()
             torch.cuda.current_stream(self.dev).wait_stream(side)
             torch.cuda.synchronize(self.dev)
-            self.graph_a = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_a):
-                self._forward_backward(1 if self.bucketed else 0)
-            self.graph_a2 = None
-            if self.bucketed:
-                self.graph_a2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_a2):
-                    self._head_gradients()
-            self.graph_b = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_b):
-                self._update()
-            # Without an exchange nothing has to happen between the two on most steps: one graph for the whole iteration
-            # saves a launch seam (~5-10 us of idle GPU).  Steps that put a status copy / range check between forward and
-            # re-pack (check_every) replay the two separate graphs.
-            self.graph_ab = None
-            if not self.exchange:
-                self.graph_ab = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_ab):
-                    self._forward_backward(0)
+            # A dead reference cycle that holds device objects (an earlier stepper and its passes refer to each other, with
+            # their graphs, streams and pool memory) must not be finalised inside a capture: releasing them calls into the
+            # runtime while a stream captures, an error a destructor cannot report -- the process aborts.  torch collects no
+            # garbage on entering a capture, so: collect now, and keep the collector off until the last capture has ended.
+            import gc
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                self.graph_a = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph_a):
+                    self._forward_backward(1 if self.bucketed else 0)
+                self.graph_a2 = None
+                if self.bucketed:
+                    self.graph_a2 = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.graph_a2):
+                        self._head_gradients()
+                self.graph_b = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph_b):
                     self._update()
+                # Without an exchange nothing has to happen between the two on most steps: one graph for the whole iteration
+                # saves a launch seam (~5-10 us of idle GPU).  Steps that put a status copy / range check between forward and
+                # re-pack (check_every) replay the two separate graphs.
+                self.graph_ab = None
+                if not self.exchange:
+                    self.graph_ab = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.graph_ab):
+                        self._forward_backward(0)
+                        self._update()
+            finally:
+                if gc_was_on:
+                    gc.enable()
             # capture executed nothing, and the warm-up did not touch the parameters
             assert torch.equal(self.opt.flat, params0)
             self._ring.reset()                                   # the warm-up consumed a slot
@@ -1647,7 +1818,8 @@ class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
     N <= 512, the default network."""
 
     def __init__(self, net, optimizer, n_rays, N, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
-                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0):
+        _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
         self._refuse(storage, buckets)
         B, N_ = int(n_rays), int(N)
         if B < 1 or N_ < 1:
@@ -1686,7 +1858,8 @@ class GraphedHierarchicalTrainStep(GraphedTrainStep):
     _one_bucket = True
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc=64, Nf=128, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
-                 ray_id0=0, check_every=16, rays_from=None, select_mode="train"):
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", distortion=0.0):
+        _refuse_distortion(_check_distortion(distortion), **{"a coarse / fine pair": (net_c, net_f)})
         _check_pair(net_c, net_f, Nc, Nf, None)
         self.net_c, self.net_f, self.Nc, self.Nf = net_c, net_f, int(Nc), int(Nf)
         # ``net`` / ``nets`` are the pair, as FusedAdam([net_c, net_f]).net / .nets hold it
@@ -1747,7 +1920,9 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
     [coarse, fine].  bf16 storage, the default network, 3 <= Nc <= 256, Nc + Nf <= 512."""
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc, Nf, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
-                 seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+                 seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
+                 distortion=0.0):
+        _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
         self._refuse(storage, buckets)
         _check_pair(net_c, net_f, Nc, Nf, None)
         B, Nc_, Nf_ = int(n_rays), int(Nc), int(Nf)
@@ -1783,8 +1958,10 @@ class GraphedGuidedTrainStep(GraphedTrainStep):
     _one_bucket = True
 
     def __init__(self, net, optimizer, n_rays, Nc, Nf, proposal, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
-                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0):
         from .utils.proposal import check_sizes
+        lam = _check_distortion(distortion)
+        _refuse_distortion(lam, **{"an occupancy grid": self._capacities})       # the masked guided stepper comes through here
         _MaskedSteps._refuse(self, storage, buckets)
         _check_guided(net, proposal)
         self.Nc, self.Nf = check_sizes(Nc, Nf)
@@ -1796,7 +1973,7 @@ class GraphedGuidedTrainStep(GraphedTrainStep):
         proposal.check(torch.empty((0, 6), dtype=torch.float32, device=proposal.sigma.device), self.Nc, self.Nf)
         self.proposal, self._sigma_ptr = proposal, proposal.sigma.data_ptr()
         super().__init__(net, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
-                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode, distortion=lam)
 
     def _alloc_pass_buffers(self, tn, tf):
         """The dense pass reads given positions: ``ts_f``, which the sampler writes.  ``u`` [B, Nc+Nf] of the reference
@@ -1872,8 +2049,10 @@ class GraphedMaskedGuidedTrainStep(_MaskedSteps, GraphedGuidedTrainStep):
     _masked_pass_type = _MarkedPass
 
     def __init__(self, net, optimizer, n_rays, Nc, Nf, proposal, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
-                 seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16"):
+                 seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
+                 distortion=0.0):
         from .utils.proposal import check_sizes
+        _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
         self._refuse(storage, buckets)
         _check_guided(net, proposal)
         Nc_, Nf_ = check_sizes(Nc, Nf)
