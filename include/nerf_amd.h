@@ -534,6 +534,34 @@ int nerf_amd_gamma_backward(const float* x, int64_t x_stride, const float* d_out
 int nerf_amd_positional_encoder_backward(const float* vec, const float* d_posx, const float* d_posd, float* d_vec,
                                          int64_t P, int Lp, int Ld, void* stream);
 
+/* ---- camera optimiser: per-image pose corrections (not in the reference) -----------------------------------------------
+ * M training images of H x W pixels share the focal length f; image m has the stored pose poses[m] (DEVICE, row-major
+ * 3x4 [R0 | t0]) and the learnable correction xi[m] = (w, tau): an axis-angle and a translation, fp32.  The pose the
+ * rays are formed from is R = exp([w]x) R0, t = t0 + tau.  xi == NULL is xi == 0.
+ *
+ * nerf_amd_camera_rays: rays[i] = [t, R dir_cam(h, w)] of the global ray id ids[i] = m H W + h W + w (the row of the
+ * table nerf_amd_generate_rays builds image by image), dir_cam as nerf_amd_generate_rays forms it, in its operation
+ * order.  With xi[m] == 0 (or xi == NULL) the row equals nerf_amd_generate_rays(poses[m]) bit for bit.  An id outside
+ * [0, M H W) writes a row of NaN and reads no pose.  ids_copy (or NULL) receives ids: a captured step keeps the ids it
+ * ran on without a launch of its own.  rays, ids and ids_copy 8-byte aligned.
+ *
+ * nerf_amd_camera_rays_backward: d_rays [B,6] = d loss / d rays -> g_xi [M,6] = d loss / d xi, WRITTEN (not accumulated):
+ * g_tau[m] = sum of the origin gradients, g_w[m] = J^T sum (y x g_d) over the batch rows of image m, y the row's world
+ * direction and J = I + b K + c K^2 the left Jacobian of the exponential map at w.  Rows in any order, with duplicates;
+ * an image without a row gets zeros (B == 0: all of them), an id outside [0, M H W) contributes nothing.  No atomics and
+ * a fixed summation order: two runs write the same bytes.  workspace: nerf_amd_camera_workspace_bytes(B, M) bytes (0 in
+ * this version: one launch, a block per image; NULL is accepted).  d_rays and g_xi 8-byte aligned.
+ *
+ * nerf_amd_camera_poses: out[m] = [R | t] (row-major 3x4, 16-byte aligned), the bits the rays kernel uses.
+ *
+ * Limits: M, B and H W below 2^31 (NERF_AMD_EUNSUP). */
+int nerf_amd_camera_rays(const float* poses, const float* xi, const int64_t* ids, int64_t* ids_copy, int H, int W, float f,
+                         float* rays, int64_t B, int64_t M, void* stream);
+int64_t nerf_amd_camera_workspace_bytes(int64_t B, int64_t M);
+int nerf_amd_camera_rays_backward(const float* poses, const float* xi, const int64_t* ids, const float* d_rays, int H, int W,
+                                  float f, float* g_xi, void* workspace, int64_t B, int64_t M, void* stream);
+int nerf_amd_camera_poses(const float* poses, const float* xi, float* out, int64_t M, void* stream);
+
 /* ---- density grid and surface extraction (not in the reference) ------------------------------------------------------
  * The reference can only evaluate sigma through the whole Nerf.forward (utils/nets.py:34-43) and has no mesh export.
  *

@@ -124,6 +124,10 @@ _SIGNATURES = {
     "nerf_amd_query_points_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_gamma_backward": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_positional_encoder_backward": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "nerf_amd_camera_rays": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _i64, _i64, _vp]),
+    "nerf_amd_camera_workspace_bytes": (_i64, [_i64, _i64]),
+    "nerf_amd_camera_rays_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i64, _vp]),
+    "nerf_amd_camera_poses": (_i32, [_vp, _vp, _vp, _i64, _vp]),
     "nerf_amd_density_forward": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp]),
     "nerf_amd_density_grid": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
     "nerf_amd_grid_points": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),

@@ -778,6 +778,43 @@ int nerf_amd_adam_step_hyper(float* params, const float* grads, float* exp_avg, 
     return nerf_amd_launch_adam_hyper(params, grads, exp_avg, exp_avg_sq, n, hyper, S(stream));
 }
 
+// ---- camera optimiser: rays from (stored pose, correction, pixel), their backward, the corrected poses ------------------
+int nerf_amd_camera_rays(const float* poses, const float* xi, const int64_t* ids, int64_t* ids_copy, int H, int W, float f,
+                         float* rays, int64_t B, int64_t M, void* stream) {
+    if (bad_camera_sizes(B, M, H, W, f)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (unsupported_camera_sizes(B, M, H, W)) return NERF_AMD_EUNSUP;
+    if (!ids || !rays || (M > 0 && !poses)) return NERF_AMD_EINVAL;
+    if (misaligned(poses, 4) || misaligned(xi, 4) || misaligned(ids, 8) || misaligned(ids_copy, 8) || misaligned(rays, 8))
+        return NERF_AMD_EINVAL;
+    return nerf_amd_launch_camera_rays(poses, xi, reinterpret_cast<const long long*>(ids), reinterpret_cast<long long*>(ids_copy),
+                                       H, W, f, rays, B, M, S(stream));
+}
+
+int64_t nerf_amd_camera_workspace_bytes(int64_t B, int64_t M) { return B < 0 || M < 0 ? NERF_AMD_EINVAL : 0; }
+
+int nerf_amd_camera_rays_backward(const float* poses, const float* xi, const int64_t* ids, const float* d_rays, int H, int W,
+                                  float f, float* g_xi, void* workspace, int64_t B, int64_t M, void* stream) {
+    if (bad_camera_sizes(B, M, H, W, f)) return NERF_AMD_EINVAL;
+    if (M == 0) return 0;                                    // no image: nothing to write (B == 0 still writes M zero rows)
+    if (unsupported_camera_sizes(B, M, H, W)) return NERF_AMD_EUNSUP;
+    if (!poses || !g_xi || (B > 0 && (!ids || !d_rays))) return NERF_AMD_EINVAL;
+    if (misaligned(poses, 4) || misaligned(xi, 4) || misaligned(ids, 8) || misaligned(d_rays, 8) || misaligned(g_xi, 8))
+        return NERF_AMD_EINVAL;
+    (void)workspace;                                         // nerf_amd_camera_workspace_bytes is 0: not looked at
+    return nerf_amd_launch_camera_rays_backward(poses, xi, reinterpret_cast<const long long*>(ids), d_rays, H, W, f, g_xi, B, M,
+                                                S(stream));
+}
+
+int nerf_amd_camera_poses(const float* poses, const float* xi, float* out, int64_t M, void* stream) {
+    if (M < 0) return NERF_AMD_EINVAL;
+    if (M == 0) return 0;
+    if (M > CAMERA_MAX) return NERF_AMD_EUNSUP;
+    if (!poses || !out) return NERF_AMD_EINVAL;
+    if (misaligned(poses, 4) || misaligned(xi, 4) || misaligned(out, 16)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_camera_poses(poses, xi, out, M, S(stream));
+}
+
 // ---- density grid and marching cubes (not in the reference) ----------------------------------------------------------
 int nerf_amd_density_forward(const float* pts, int64_t stride, void* packed, int precision, float* sigma, int64_t P,
                              void* stream) {

@@ -76,3 +76,13 @@ inline int capped_check(const uint64_t* mask, const int64_t* offsets, int64_t C,
     if (!mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8)) return NERF_AMD_EINVAL;
     return 0;
 }
+
+// the camera set every camera entry point takes (M images of H x W pixels, focal length f in pixels): the sizes, then --
+// behind the entry point's own empty problem -- the limits the kernels' 32-bit pixel arithmetic and grids set
+constexpr int64_t CAMERA_MAX = 0x7fffffffll;     // of M, of B and of H W
+inline bool bad_camera_sizes(int64_t B, int64_t M, int H, int W, float f) {
+    return B < 0 || M < 0 || H <= 0 || W <= 0 || !(f > 0.f) || f > 3.402823466e38f;      // f: negative, zero, NaN, inf
+}
+inline bool unsupported_camera_sizes(int64_t B, int64_t M, int H, int W) {
+    return B > CAMERA_MAX || M > CAMERA_MAX || (int64_t)H * W > CAMERA_MAX;
+}

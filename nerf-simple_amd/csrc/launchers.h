@@ -106,4 +106,9 @@ int nerf_amd_launch_sum_f32(const float*, float*, long long, hipStream_t);
 int nerf_amd_launch_composite_mse_backward_dist(const float*, const float*, const float*, const float*, const float*, long long,
                                                 float, unsigned long long, const unsigned long long*, long long, float, float,
                                                 float*, float*, float*, long long, int, hipStream_t);
+int nerf_amd_launch_camera_rays(const float*, const float*, const long long*, long long*, int, int, float, float*, long long,
+                                long long, hipStream_t);
+int nerf_amd_launch_camera_rays_backward(const float*, const float*, const long long*, const float*, int, int, float, float*,
+                                         long long, long long, hipStream_t);
+int nerf_amd_launch_camera_poses(const float*, const float*, float*, long long, hipStream_t);
 }

@@ -1710,6 +1710,146 @@ class GraphedTrainStep:
         return span, exposed
 
 
+class _IdsOnlySelection:
+    """``rays_from`` as GraphedCameraTrainStep hands it to its base: every selection still writes the colours and the ids, and
+    no rays (nerf_amd_select_rays with rays_out = NULL) -- the stepper forms them itself, from the ids and its cameras."""
+
+    def __init__(self, rg):
+        self._rg = rg
+
+    def __getattr__(self, name):
+        return getattr(self._rg, name)
+
+    def launch(self, mode, B, draws, seed, seed_mem, rays, gt, ids, stream=None, workspace=None):
+        self._rg.launch(mode, B, draws, seed, seed_mem, None, gt, ids, stream=stream, workspace=workspace)
+
+
+class _CameraPass(_DensePass):
+    """The dense pass with the pose gradient behind its dX chain, on the main branch: d loss / d rays from the same dY
+    (nerf_amd_input_gradients on the flat fp32 parameters, the step's rays and positions), then its reduction to one
+    6-vector per image (nerf_amd_camera_rays_backward on the ids the rays were formed from)."""
+
+    def dx_chain(self, st):
+        super().dx_chain(st)
+        ptr, s = _lib.ptr, self.step
+        _launch("nerf_amd_input_gradients", ptr(self.dys), ptr(s.opt.flat), None, ptr(s.rays), ptr(self.ts), ptr(s._dv),
+                ptr(s.d_rays), self.P, self.N, st)
+        s.cameras._launch_backward(s.cameras.xi, s._ids_used, s.d_rays, s.camera_grad, stream=st)
+
+
+class GraphedCameraTrainStep(GraphedTrainStep):
+    """GraphedTrainStep with a camera optimiser inside the captured graph: the rays of every step are
+    formed on the device from ``cameras`` (``utils.cameras.CameraRefinement``: stored poses and the learnable corrections
+    ``cameras.xi`` [M,6]) and the ids the selection left, and ``xi`` is trained beside the network by an Adam of its own.
+
+        graph A: hyper fetch -> camera hyper fetch -> camera rays (nerf_amd_camera_rays: writes ``rays`` and keeps a copy of
+                 the ids) -> forward -> head -> dX chain -> input gradients (nerf_amd_input_gradients: ``d_rays``) -> camera
+                 backward (nerf_amd_camera_rays_backward: ``camera_grad`` = d loss / d xi) -> dW products; the side branch
+                 is GraphedTrainStep's, its selection of the next batch writing colours and ids only
+        graph B: Adam -> re-pack -> Adam on (xi, camera_grad) with the camera's own scalars (nerf_amd_adam_step_hyper)
+
+    The rays of step k see the ``xi`` step k - 1 wrote -- which is why they cannot come from the one-step-ahead selection.
+    ``rays_from`` is required (a ``RayGenerator`` with colours whose table has the cameras' M H W rows); ``step()`` takes no
+    rays.  ``camera_lr``, ``camera_betas`` (held rounded to fp32, the kernel's format), ``camera_eps``: the camera Adam's;
+    ``step(camera_decay=)`` multiplies ``camera_lr`` as ``decay`` does the network's rate.  ``camera_grad`` [M,6] is the last
+    step's gradient, ``cameras.xi`` is live, ``ray_ids`` are the rows the last step trained on.  Both jitter sources work.
+    d loss / d rays is what nerf_amd_input_gradients gives, as on the eager fused path (the compositor's |d_hat| factor is 1
+    and carries none).  The addresses of ``cameras.xi`` and of the stored poses are baked into the graph: write them in place
+    (``load_state_dict`` does); ``step`` raises if either tensor was replaced.
+
+    Refused (RuntimeError, before any launch or RNG draw): ``storage='e4m3'`` (nerf_amd_input_gradients reads bf16 dY),
+    ``buckets=2``, a process group that exchanges gradients (``camera_grad`` would need an exchange of its own),
+    ``background`` / ``sigma_noise`` / ``distortion``."""
+
+    _one_bucket = True
+
+    def __init__(self, net, optimizer, n_rays, N, cameras, *, rays_from=None, camera_lr=1e-3, camera_betas=(0.9, 0.999),
+                 camera_eps=1e-8, select_mode="train", group=None, buckets=1, storage="bf16", background=None, sigma_noise=0.0,
+                 distortion=0.0, **kw):
+        from . import parallel
+        from .utils.cameras import CameraRefinement
+        if storage != "bf16":
+            raise RuntimeError("GraphedCameraTrainStep: storage='e4m3' is not served (nerf_amd_input_gradients reads bf16 dY)")
+        if buckets != 1:
+            raise RuntimeError("GraphedCameraTrainStep: one exchange bucket only (buckets=1)")
+        if background is not None or sigma_noise or distortion:
+            raise RuntimeError("GraphedCameraTrainStep does not take background / sigma_noise / distortion yet")
+        if parallel.collectives_active(group):
+            raise RuntimeError("GraphedCameraTrainStep trains on one replica: the camera gradient has no exchange yet")
+        if not isinstance(cameras, CameraRefinement):
+            raise RuntimeError("cameras must be a utils.cameras.CameraRefinement")
+        if rays_from is None:
+            raise RuntimeError("GraphedCameraTrainStep forms its rays from the ids of a selection: rays_from=<RayGenerator> is required")
+        if select_mode not in rays_from.colours:
+            raise RuntimeError(f"rays_from has no colour table for mode {select_mode!r}")
+        if int(rays_from.rays_dataset[select_mode].shape[0]) != cameras.n_rays:
+            raise RuntimeError(f"the table of rays_from holds {int(rays_from.rays_dataset[select_mode].shape[0])} rays, the cameras "
+                               f"span {cameras.M} x {cameras.H} x {cameras.W} = {cameras.n_rays}")
+        if cameras.xi.device != optimizer.flat.device:
+            raise RuntimeError(f"the cameras live on {cameras.xi.device}, the module on {optimizer.flat.device}")
+        self.cameras, self._camera_ptrs = cameras, (cameras.xi.data_ptr(), cameras.poses0.data_ptr())
+        # the kernel reads its betas as fp32 and forms 1 - beta from them: the bias corrections are formed from the same
+        # rounded values (_set_hyper), so the update is Adam's for exactly the betas held here
+        self.camera_lr, self.camera_eps = float(camera_lr), float(camera_eps)
+        self.camera_betas = tuple(float(torch.tensor(float(b), dtype=torch.float32)) for b in camera_betas)
+        self.camera_steps = 0
+        dev = cameras.xi.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.camera_grad = torch.zeros_like(cameras.xi, requires_grad=False)
+        self._cam_m, self._cam_v = torch.zeros_like(self.camera_grad), torch.zeros_like(self.camera_grad)
+        self._cam_hyper, self._cam_ring = torch.zeros(8, **f32), _HyperRing(dev)
+        self.d_rays = torch.zeros((int(n_rays), 6), **f32)
+        self._dv = torch.empty((int(n_rays) * int(N), 6), **f32)
+        self._ids_used = torch.zeros((int(n_rays),), dtype=torch.int64, device=dev)
+        super().__init__(net, optimizer, n_rays, N, rays_from=_IdsOnlySelection(rays_from), select_mode=select_mode, group=group, **kw)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        super()._alloc_pass_buffers(tn, tf)
+        self.passes[0].__class__ = _CameraPass       # the base's dense pass and its buffers, the pose gradient behind its dX chain
+
+    def _before_forward(self, st):
+        self._cam_ring.fetch(self._cam_hyper, self.dev)
+        self.cameras._launch_rays(self.cameras.xi, self._ids_next, self._ids_used, self.rays, stream=st)
+
+    @property
+    def ray_ids(self):
+        """Rows of the table the LAST step trained on: the copy the camera rays kernel kept."""
+        return self._ids_used
+
+    def _set_hyper(self, step):
+        super()._set_hyper(step)
+        t, (b1, b2) = self.camera_steps + 1, self.camera_betas
+        self._cam_ring.push((self.camera_lr, b1, b2, self.camera_eps, 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5))
+
+    def _update(self):
+        super()._update()
+        ptr, xi = _lib.ptr, self.cameras.xi
+        _launch("nerf_amd_adam_step_hyper", ptr(xi), ptr(self.camera_grad), ptr(self._cam_m), ptr(self._cam_v), xi.numel(),
+                ptr(self._cam_hyper), _lib.stream_ptr(self.dev))
+
+    def _capture(self):
+        super()._capture()
+        self._cam_ring.reset()                       # the warm-up consumed a slot
+
+    def _enqueue_step(self, decay):
+        loss = super()._enqueue_step(decay)
+        self._cam_ring.launched(self.dev)
+        self.camera_steps += 1
+        return loss
+
+    def step(self, rays=None, gt=None, u=None, decay=1.0, camera_decay=1.0):
+        if rays is not None or gt is not None:
+            raise RuntimeError("GraphedCameraTrainStep forms its rays from its cameras and the selected ids: step() takes no rays")
+        if (self.cameras.xi.data_ptr(), self.cameras.poses0.data_ptr()) != self._camera_ptrs:
+            raise RuntimeError("cameras.xi or the stored poses were replaced: their addresses are baked into the captured graph "
+                               "(write them in place, or build a new GraphedCameraTrainStep)")
+        loss = super().step(None, None, u=u, decay=decay)
+        self.camera_lr *= float(camera_decay)
+        return loss
+
+    __call__ = step
+
+
 class _MaskedSteps:
     """What the two masked steppers share (listed in front of their stepper base): the refusals, the grid and the capacities,
     and the overflow report -- ``counts`` on the device is int64 {live, kept} per pass, copied back every ``check_every``
