@@ -562,6 +562,41 @@ int nerf_amd_camera_rays_backward(const float* poses, const float* xi, const int
                                   float f, float* g_xi, void* workspace, int64_t B, int64_t M, void* stream);
 int nerf_amd_camera_poses(const float* poses, const float* xi, float* out, int64_t M, void* stream);
 
+/* ---- image metrics: squared error, the reference's PSNR and SSIM on the device (SSIM is not in the reference) -----------
+ * pred and gt hold M images of H x W pixels as rows of floats: image m starts at row m H W, a row is `pred_stride`
+ * (`gt_stride`) floats apart and its first three floats are r, g, b -- whatever lies behind them (the disparity column of
+ * the [H W, 4] pixels a view render returns) is never read.  fp32, data range 1.
+ *
+ *   sums [M,4] (double):  sse_c = sum over all H W pixels of (pred - gt)^2 per channel -- the difference and its square
+ *                         formed in fp32, accumulated in double -- and max_gt = max(gt) over the three channels.
+ *                         mse = (sse_r + sse_g + sse_b) / (3 H W);  psnr = -10 log10(mse);  the reference's img_psnr
+ *                         (train.py:21-26, peak max(gt)) = 20 log10(max_gt) - 10 log10(mse): left to the caller, in double.
+ *   ssim [M,3] (double, or NULL):  per channel the mean over the (H-10)(W-10) window positions of
+ *   ssim_map [M, H-10, W-10, 3] (float, or NULL):
+ *       (2 mu_a mu_b + C1)(2 s_ab + C2) / ((mu_a^2 + mu_b^2 + C1)(s_aa + s_bb + C2)),  C1 = 0.01^2, C2 = 0.03^2,
+ *       mu = sum G x,  s_xy = sum G (x - mu_x)(y - mu_y) over the 11 x 11 window at the position ("valid": no padding),
+ *       G_ij = g_i g_j,  g_k = exp(-(k-5)^2 / (2 1.5^2)) normalised to sum 1 in double and rounded once to fp32.
+ *       This is tf.image.ssim(max_val = 1) per channel (the image's SSIM is the mean of the three) and skimage's
+ *       structural_similarity(gaussian_weights=True, use_sample_covariance=False, data_range=1).  The second moments are
+ *       evaluated CENTRED, in a second pass behind the means, every operation rounded on its own: each map value lies
+ *       within a few units of 2^-24 of the float64 value where E[x^2] - mu^2 loses 5e-4 on a white background
+ *       (DESIGN.md section 27), and pred == gt gives exactly 1.
+ *   ssim == NULL and ssim_map == NULL: squared error and max_gt only, for any H, W >= 1.
+ *
+ * A NaN pixel makes sse and -- through every window that contains it -- the SSIM of its own channel of its own image
+ * NaN and touches nothing else; a NaN in gt makes max_gt NaN.  Two launches (tiles, then one block per image adds the
+ * tiles' partial sums in a fixed order), no atomics: two runs write the same bytes, and M images in one call give what M
+ * calls give.  workspace: nerf_amd_image_metrics_workspace_bytes(M, H, W) bytes, 8-byte aligned.
+ *
+ * Rules, in this order: NERF_AMD_EINVAL for M < 0, H <= 0, W <= 0 or a stride below 3;  M == 0 launches nothing and
+ * returns 0 (the size query: 0);  NERF_AMD_EUNSUP for H W >= 2^31 (or a workspace size that leaves an int64);
+ * NERF_AMD_EUNSUP for H < 11 or W < 11 when ssim or ssim_map is given;  NERF_AMD_EINVAL for a missing pred, gt, sums or
+ * workspace;  NERF_AMD_EINVAL for alignment: sums, ssim and workspace 8 bytes, pred, gt and ssim_map 4.  The size query
+ * applies the first three. */
+int64_t nerf_amd_image_metrics_workspace_bytes(int64_t M, int H, int W);
+int nerf_amd_image_metrics(const float* pred, int64_t pred_stride, const float* gt, int64_t gt_stride, double* sums, double* ssim,
+                           float* ssim_map, void* workspace, int64_t M, int H, int W, void* stream);
+
 /* ---- density grid and surface extraction (not in the reference) ------------------------------------------------------
  * The reference can only evaluate sigma through the whole Nerf.forward (utils/nets.py:34-43) and has no mesh export.
  *

@@ -128,6 +128,8 @@ _SIGNATURES = {
     "nerf_amd_camera_workspace_bytes": (_i64, [_i64, _i64]),
     "nerf_amd_camera_rays_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _i64, _i64, _vp]),
     "nerf_amd_camera_poses": (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    "nerf_amd_image_metrics_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "nerf_amd_image_metrics": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "nerf_amd_density_forward": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp]),
     "nerf_amd_density_grid": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp]),
     "nerf_amd_grid_points": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),

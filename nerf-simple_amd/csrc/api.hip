@@ -815,6 +815,27 @@ int nerf_amd_camera_poses(const float* poses, const float* xi, float* out, int64
     return nerf_amd_launch_camera_poses(poses, xi, out, M, S(stream));
 }
 
+// ---- image metrics: squared error, max(gt) and SSIM of M image pairs (csrc/image_metrics.hip) ---------------------------
+int64_t nerf_amd_image_metrics_workspace_bytes(int64_t M, int H, int W) {
+    if (bad_metrics_sizes(M, H, W, 3, 3)) return NERF_AMD_EINVAL;
+    if (M == 0) return 0;
+    if (unsupported_metrics_sizes(H, W)) return NERF_AMD_EUNSUP;
+    return nerf_amd_image_metrics_ws_bytes(M, H, W);              // NERF_AMD_EUNSUP where the size leaves an int64
+}
+
+int nerf_amd_image_metrics(const float* pred, int64_t pred_stride, const float* gt, int64_t gt_stride, double* sums, double* ssim,
+                           float* ssim_map, void* workspace, int64_t M, int H, int W, void* stream) {
+    if (bad_metrics_sizes(M, H, W, pred_stride, gt_stride)) return NERF_AMD_EINVAL;
+    if (M == 0) return 0;
+    if (unsupported_metrics_sizes(H, W) || nerf_amd_image_metrics_ws_bytes(M, H, W) < 0) return NERF_AMD_EUNSUP;
+    if ((ssim || ssim_map) && unsupported_ssim_sizes(H, W)) return NERF_AMD_EUNSUP;
+    if (!pred || !gt || !sums || !workspace) return NERF_AMD_EINVAL;
+    if (misaligned(pred, 4) || misaligned(gt, 4) || misaligned(ssim_map, 4) || misaligned(sums, 8) || misaligned(ssim, 8) ||
+        misaligned(workspace, 8))
+        return NERF_AMD_EINVAL;
+    return nerf_amd_launch_image_metrics(pred, pred_stride, gt, gt_stride, sums, ssim, ssim_map, workspace, M, H, W, S(stream));
+}
+
 // ---- density grid and marching cubes (not in the reference) ----------------------------------------------------------
 int nerf_amd_density_forward(const float* pts, int64_t stride, void* packed, int precision, float* sigma, int64_t P,
                              void* stream) {

@@ -86,3 +86,12 @@ inline bool bad_camera_sizes(int64_t B, int64_t M, int H, int W, float f) {
 inline bool unsupported_camera_sizes(int64_t B, int64_t M, int H, int W) {
     return B > CAMERA_MAX || M > CAMERA_MAX || (int64_t)H * W > CAMERA_MAX;
 }
+
+// the image metrics (M image pairs of H x W pixels, rows of at least 3 floats): the sizes, then -- behind the empty problem --
+// the limit of the kernels' 32-bit pixel arithmetic, and the smallest image that holds one 11 x 11 SSIM window
+constexpr int SSIM_WINDOW = 11;
+inline bool bad_metrics_sizes(int64_t M, int H, int W, int64_t pred_stride, int64_t gt_stride) {
+    return M < 0 || H <= 0 || W <= 0 || pred_stride < 3 || gt_stride < 3;
+}
+inline bool unsupported_metrics_sizes(int H, int W) { return (int64_t)H * W > CAMERA_MAX; }
+inline bool unsupported_ssim_sizes(int H, int W) { return H < SSIM_WINDOW || W < SSIM_WINDOW; }

@@ -111,4 +111,7 @@ int nerf_amd_launch_camera_rays(const float*, const float*, const long long*, lo
 int nerf_amd_launch_camera_rays_backward(const float*, const float*, const long long*, const float*, int, int, float, float*,
                                          long long, long long, hipStream_t);
 int nerf_amd_launch_camera_poses(const float*, const float*, float*, long long, hipStream_t);
+long long nerf_amd_image_metrics_ws_bytes(long long, int, int);
+int nerf_amd_launch_image_metrics(const float*, long long, const float*, long long, double*, double*, float*, void*, long long, int,
+                                  int, hipStream_t);
 }
