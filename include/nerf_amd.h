@@ -562,6 +562,53 @@ int nerf_amd_camera_rays_backward(const float* poses, const float* xi, const int
                                   float f, float* g_xi, void* workspace, int64_t B, int64_t M, void* stream);
 int nerf_amd_camera_poses(const float* poses, const float* xi, float* out, int64_t M, void* stream);
 
+/* ---- appearance: a per-image colour correction (gain and bias) trained beside the network (not in the reference) --------
+ * M training images of HW pixels each; image m holds theta[m] = (a[3], b[3]) in fp32 (DEVICE, [M,6], zeros = the identity).
+ * A ray of image m is compared with its pixel behind
+ *     c'_k = (1 + a_k) c_k + b_k,   k = r, g, b,   c = the compositor's rgb (before any clip),
+ * evaluated as fl(fl(fl(1 + a) c) + b): three separately rounded fp32 operations per channel, no fma -- torch's eager fp32
+ * expression (1 + a) * c + b has the same bits.  The image of a ray is m = id / HW of its global ray id (the row of the table
+ * nerf_amd_generate_rays builds image by image, as nerf_amd_camera_rays reads it).
+ *
+ * nerf_amd_appearance_gather: theta_ray[i] = theta[ids[i] / HW], one row per ray; an id outside [0, M HW) writes a row of NaN
+ * and reads no theta -- that ray's colour, loss and d_raw are NaN, no image receives anything from it, and every other ray is
+ * what it is alone.  ids_copy (or NULL) receives ids: a captured step keeps the ids it ran on without a launch of its own.
+ *
+ * nerf_amd_appearance_apply: out[i] = c' of rgb[i] under the row theta_ray + i theta_stride: theta_stride = 6 for one row per
+ * ray, 0 for one row for all rays.  out may be rgb.
+ *
+ * nerf_amd_appearance_apply_backward: g_out [B,3] = d loss / d c' -> g_rgb = g_out fl(1 + a) (may be g_out) and the ray's own
+ * row g_theta_ray[i] = (g_out rgb, g_out), each one rounded product.  rgb is the UNCORRECTED colour.
+ *
+ * nerf_amd_appearance_reduce: g_theta[m] = sum of the rows g_theta_ray[i] with ids[i] / HW == m, WRITTEN (not accumulated), then
+ * the gauge: g_theta[m] += reg theta[m] for EVERY image, with or without a row in the batch (the gradient of the ridge
+ * (reg / 2) sum ||theta||^2; reg finite and >= 0; an image without a row gets reg theta[m]), or, where frozen (int32 [M], or
+ * NULL) is non-zero, exactly zero and no ridge.  An id outside [0, M HW) contributes nothing.  One launch, a block per image,
+ * no atomics, no workspace, a fixed summation order: two runs write the same bytes.
+ *
+ * nerf_amd_volume_render_mse_backward_affine: the training head in one launch -- BY DEFINITION, and bit for bit, the chain
+ * nerf_amd_volume_render_rays (rgb) -> nerf_amd_appearance_apply -> g' = 2 (c' - target) / (3 B) as
+ * nerf_amd_volume_render_mse_backward forms it -> nerf_amd_appearance_apply_backward -> nerf_amd_volume_render_rays_backward
+ * (g_rgb only).  rgb (or NULL) receives c': nerf_amd_mse_loss(rgb, target) is the loss.  g_theta_ray [B,6] and d_raw [B,N,4]
+ * are written.  N == 1 is the reference's empty sample axis: rgb = 0, c' = fl(fl(fl(1 + a) 0) + b), d_raw = 0, g_theta_ray =
+ * (g' 0, g').  theta == 0 gives nerf_amd_volume_render_mse_backward's d_raw bit for bit.
+ *
+ * Rules, in this order: NERF_AMD_EINVAL for B < 0, M <= 0, HW <= 0, N <= 0, a theta_stride other than 0 or 6, a reg that is
+ * negative or not finite;  B == 0 launches nothing, looks at nothing else and returns 0;  NERF_AMD_EUNSUP for B, M or HW >= 2^31
+ * and, for the head, N > 512;  NERF_AMD_EINVAL for a missing pointer (ids_copy, frozen and the head's rgb may be NULL);
+ * NERF_AMD_EINVAL for alignment: theta, theta_ray, g_theta_ray, g_theta, ids and ids_copy 8 bytes, raw and d_raw 16, the
+ * rest 4. */
+int nerf_amd_appearance_gather(const float* theta, const int64_t* ids, int64_t* ids_copy, int64_t HW, float* theta_ray, int64_t B,
+                               int64_t M, void* stream);
+int nerf_amd_appearance_apply(const float* rgb, const float* theta_ray, int64_t theta_stride, float* out, int64_t B, void* stream);
+int nerf_amd_appearance_apply_backward(const float* g_out, const float* rgb, const float* theta_ray, int64_t theta_stride,
+                                       float* g_rgb, float* g_theta_ray, int64_t B, void* stream);
+int nerf_amd_appearance_reduce(const float* g_theta_ray, const int64_t* ids, int64_t HW, const float* theta, float reg,
+                               const int32_t* frozen, float* g_theta, int64_t B, int64_t M, void* stream);
+int nerf_amd_volume_render_mse_backward_affine(const float* raw, const float* ts, const float* rays, const float* target,
+                                               const float* theta_ray, int64_t theta_stride, float* rgb, float* g_theta_ray,
+                                               float* d_raw, int64_t B, int N, void* stream);
+
 /* ---- image metrics: squared error, the reference's PSNR and SSIM on the device (SSIM is not in the reference) -----------
  * pred and gt hold M images of H x W pixels as rows of floats: image m starts at row m H W, a row is `pred_stride`
  * (`gt_stride`) floats apart and its first three floats are r, g, b -- whatever lies behind them (the disparity column of

@@ -815,6 +815,65 @@ int nerf_amd_camera_poses(const float* poses, const float* xi, float* out, int64
     return nerf_amd_launch_camera_poses(poses, xi, out, M, S(stream));
 }
 
+// ---- per-image colour correction (csrc/appearance.hip).  Order of the rules: sizes and the stride; the empty problem (B == 0:
+// nothing is launched or looked at); the limits (NERF_AMD_EUNSUP); the pointers; their alignment (rows of six floats: 8 bytes).
+int nerf_amd_appearance_gather(const float* theta, const int64_t* ids, int64_t* ids_copy, int64_t HW, float* theta_ray, int64_t B,
+                               int64_t M, void* stream) {
+    if (bad_appearance_sizes(B, M, HW)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (unsupported_appearance_sizes(B, M, HW)) return NERF_AMD_EUNSUP;
+    if (!theta || !ids || !theta_ray) return NERF_AMD_EINVAL;
+    if (misaligned(theta, 8) || misaligned(ids, 8) || misaligned(ids_copy, 8) || misaligned(theta_ray, 8)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_appearance_gather(theta, reinterpret_cast<const long long*>(ids), reinterpret_cast<long long*>(ids_copy),
+                                             HW, theta_ray, B, M, S(stream));
+}
+
+int nerf_amd_appearance_apply(const float* rgb, const float* theta_ray, int64_t theta_stride, float* out, int64_t B, void* stream) {
+    if (B < 0 || bad_theta_stride(theta_stride)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (B > CAMERA_MAX) return NERF_AMD_EUNSUP;
+    if (!rgb || !theta_ray || !out) return NERF_AMD_EINVAL;
+    if (misaligned(rgb, 4) || misaligned(theta_ray, 8) || misaligned(out, 4)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_appearance_apply(rgb, theta_ray, theta_stride, out, B, S(stream));
+}
+
+int nerf_amd_appearance_apply_backward(const float* g_out, const float* rgb, const float* theta_ray, int64_t theta_stride,
+                                       float* g_rgb, float* g_theta_ray, int64_t B, void* stream) {
+    if (B < 0 || bad_theta_stride(theta_stride)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (B > CAMERA_MAX) return NERF_AMD_EUNSUP;
+    if (!g_out || !rgb || !theta_ray || !g_rgb || !g_theta_ray) return NERF_AMD_EINVAL;
+    if (misaligned(g_out, 4) || misaligned(rgb, 4) || misaligned(theta_ray, 8) || misaligned(g_rgb, 4) || misaligned(g_theta_ray, 8))
+        return NERF_AMD_EINVAL;
+    return nerf_amd_launch_appearance_apply_backward(g_out, rgb, theta_ray, theta_stride, g_rgb, g_theta_ray, B, S(stream));
+}
+
+int nerf_amd_appearance_reduce(const float* g_theta_ray, const int64_t* ids, int64_t HW, const float* theta, float reg,
+                               const int32_t* frozen, float* g_theta, int64_t B, int64_t M, void* stream) {
+    if (bad_appearance_sizes(B, M, HW)) return NERF_AMD_EINVAL;
+    if (!(reg >= 0.f) || reg > 3.402823466e38f) return NERF_AMD_EINVAL;        // negative, NaN, inf
+    if (B == 0) return 0;
+    if (unsupported_appearance_sizes(B, M, HW)) return NERF_AMD_EUNSUP;
+    if (!g_theta_ray || !ids || !theta || !g_theta) return NERF_AMD_EINVAL;
+    if (misaligned(g_theta_ray, 8) || misaligned(ids, 8) || misaligned(theta, 8) || misaligned(frozen, 4) || misaligned(g_theta, 8))
+        return NERF_AMD_EINVAL;
+    return nerf_amd_launch_appearance_reduce(g_theta_ray, reinterpret_cast<const long long*>(ids), HW, theta, reg, frozen, g_theta,
+                                             B, M, S(stream));
+}
+
+int nerf_amd_volume_render_mse_backward_affine(const float* raw, const float* ts, const float* rays, const float* target,
+                                               const float* theta_ray, int64_t theta_stride, float* rgb, float* g_theta_ray,
+                                               float* d_raw, int64_t B, int N, void* stream) {
+    if (B < 0 || N <= 0) return NERF_AMD_EINVAL;
+    if (bad_theta_stride(theta_stride)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
+    if (!raw || !ts || !rays || !target || !theta_ray || !g_theta_ray || !d_raw) return NERF_AMD_EINVAL;
+    if (misaligned(raw, 16) || misaligned(d_raw, 16) || misaligned(theta_ray, 8) || misaligned(g_theta_ray, 8)) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_composite_mse_backward_affine(raw, ts, rays, target, theta_ray, theta_stride, rgb, g_theta_ray, d_raw, B,
+                                                         N, S(stream));
+}
+
 // ---- image metrics: squared error, max(gt) and SSIM of M image pairs (csrc/image_metrics.hip) ---------------------------
 int64_t nerf_amd_image_metrics_workspace_bytes(int64_t M, int H, int W) {
     if (bad_metrics_sizes(M, H, W, 3, 3)) return NERF_AMD_EINVAL;

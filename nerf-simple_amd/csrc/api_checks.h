@@ -87,6 +87,14 @@ inline bool unsupported_camera_sizes(int64_t B, int64_t M, int H, int W) {
     return B > CAMERA_MAX || M > CAMERA_MAX || (int64_t)H * W > CAMERA_MAX;
 }
 
+// the per-image colour correction (M images of HW pixels each, rows of six floats): the sizes, then -- behind the entry point's
+// own empty problem -- the limits of the grids and of the product M HW; a row per ray (stride 6) or one row for all rays (0)
+inline bool bad_appearance_sizes(int64_t B, int64_t M, int64_t HW) { return B < 0 || M <= 0 || HW <= 0; }
+inline bool unsupported_appearance_sizes(int64_t B, int64_t M, int64_t HW) {
+    return B > CAMERA_MAX || M > CAMERA_MAX || HW > CAMERA_MAX;
+}
+inline bool bad_theta_stride(int64_t theta_stride) { return theta_stride != 0 && theta_stride != 6; }
+
 // the image metrics (M image pairs of H x W pixels, rows of at least 3 floats): the sizes, then -- behind the empty problem --
 // the limit of the kernels' 32-bit pixel arithmetic, and the smallest image that holds one 11 x 11 SSIM window
 constexpr int SSIM_WINDOW = 11;

@@ -1,0 +1,196 @@
+// appearance.hip -- the per-image colour correction trained beside the network: image m of M holds theta[m] = (a[3], b[3]),
+// and a ray of it is compared with its pixel behind  c' = (1 + a) rgb + b  (appearance_device.h: the three-op map and its
+// backward; the contract is include/nerf_amd.h).  Four small stages and the training head:
+//
+//   gather            theta_ray[i] = theta[ids[i] / HW] (a row of NaN for an id outside [0, M HW)); keeps a copy of the ids
+//   apply             c' = (1 + a) rgb + b per ray
+//   apply_backward    g_rgb = g fl(1 + a),  the ray's row of d loss / d theta = (g rgb, g)
+//   reduce            g_theta[m] = sum of the rows of image m, + reg theta[m] (the ridge), or zeros for a frozen image
+//   head              compositor -> apply -> MSE gradient -> apply_backward -> compositor backward: BY DEFINITION that
+//                     composition, in one launch on composite_backward_ray (AffineMseHead)
+//
+// The reduction is ONE launch without atomics or a workspace, as camera.hip's: a block per image walks the B ids, every
+// thread sums its own rows in row order, the block's 256 partial sums are folded by a fixed shuffle tree and a fixed LDS
+// order -- two runs write the same bytes.  An id outside [0, M HW) matches no image.
+#include "composite_backward_device.h"
+#include "launchers.h"
+
+namespace {
+
+using namespace nerf_appearance;
+constexpr int THREADS = 256;
+constexpr int RAYS_PER_BLOCK = 4;
+constexpr int MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;          // N <= 512
+
+// ---- the stages ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(THREADS) void appearance_gather_kernel(const float* __restrict__ theta, const long long* __restrict__ ids,
+                                                                    long long* __restrict__ ids_copy, long long HW,
+                                                                    float* __restrict__ theta_ray, long long B, long long M) {
+    const long long i = blockIdx.x * (long long)THREADS + threadIdx.x;
+    if (i >= B) return;
+    const long long id = ids[i];
+    if (ids_copy) ids_copy[i] = id;
+    const Row r = (id < 0 || id >= M * HW) ? nan_row() : load_row(theta + (id / HW) * 6);
+    store_row(theta_ray + i * 6, r.a, r.b);
+}
+
+// out may be rgb: every thread reads its own ray before it writes it
+__global__ __launch_bounds__(THREADS) void appearance_apply_kernel(const float* rgb, const float* __restrict__ theta_ray,
+                                                                   long long theta_stride, float* out, long long B) {
+    const long long i = blockIdx.x * (long long)THREADS + threadIdx.x;
+    if (i >= B) return;
+    const Row r = load_row(theta_ray + i * theta_stride);
+    float gain[3];
+    gains(r, gain);
+    const float c0 = rgb[i * 3 + 0], c1 = rgb[i * 3 + 1], c2 = rgb[i * 3 + 2];
+    out[i * 3 + 0] = apply(gain[0], c0, r.b[0]);
+    out[i * 3 + 1] = apply(gain[1], c1, r.b[1]);
+    out[i * 3 + 2] = apply(gain[2], c2, r.b[2]);
+}
+
+// g_rgb may be g_out (the same reason)
+__global__ __launch_bounds__(THREADS) void appearance_apply_backward_kernel(const float* g_out, const float* __restrict__ rgb,
+                                                                            const float* __restrict__ theta_ray,
+                                                                            long long theta_stride, float* g_rgb,
+                                                                            float* __restrict__ g_theta_ray, long long B) {
+    const long long i = blockIdx.x * (long long)THREADS + threadIdx.x;
+    if (i >= B) return;
+    const Row r = load_row(theta_ray + i * theta_stride);
+    float gain[3], g_c[3], g_a[3];
+    gains(r, gain);
+    const float g[3] = {g_out[i * 3 + 0], g_out[i * 3 + 1], g_out[i * 3 + 2]};
+    const float c[3] = {rgb[i * 3 + 0], rgb[i * 3 + 1], rgb[i * 3 + 2]};
+    apply_backward(g, c, gain, g_c, g_a);
+    g_rgb[i * 3 + 0] = g_c[0]; g_rgb[i * 3 + 1] = g_c[1]; g_rgb[i * 3 + 2] = g_c[2];
+    store_row(g_theta_ray + i * 6, g_a, g);
+}
+
+__global__ __launch_bounds__(THREADS) void appearance_reduce_kernel(const float* __restrict__ g_theta_ray,
+                                                                    const long long* __restrict__ ids, long long HW_,
+                                                                    const float* __restrict__ theta, float reg,
+                                                                    const int* __restrict__ frozen, float* __restrict__ g_theta,
+                                                                    long long B) {
+    const long long m = blockIdx.x;
+    const unsigned long long HW = (unsigned long long)HW_, lo = (unsigned long long)m * HW;
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long long i = threadIdx.x; i < B; i += THREADS) {
+        const unsigned long long pix = (unsigned long long)ids[i] - lo;        // a bad id wraps far past HW
+        if (pix >= HW) continue;
+        const Row r = load_row(g_theta_ray + i * 6);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[k] = add_rn(acc[k], r.a[k]);
+            acc[3 + k] = add_rn(acc[3 + k], r.b[k]);
+        }
+    }
+    __shared__ float part[THREADS / 64][6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) acc[k] = add_rn(acc[k], __shfl_down(acc[k], d, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) part[threadIdx.x >> 6][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float t[6];
+    const bool hold = frozen && frozen[m] != 0;    // a frozen image: exactly zero, no ridge
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        t[k] = part[0][k];
+#pragma unroll
+        for (int v = 1; v < THREADS / 64; ++v) t[k] = add_rn(t[k], part[v][k]);
+        // the ridge (reg / 2) ||theta||^2 reaches every row, with or without a ray in the batch
+        t[k] = hold ? 0.f : add_rn(t[k], mul_rn(reg, theta[m * 6 + k]));
+    }
+    store_row(g_theta + m * 6, t, t + 3);
+}
+
+// ---- the training head: one wavefront per ray, as composite_bg_head_kernel ------------------------------------------------
+__global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_affine_head_kernel(
+    const float* __restrict__ raw, const float* __restrict__ ts, const float* __restrict__ rays,
+    const float* __restrict__ target, const float* __restrict__ theta_ray, long long theta_stride, float* __restrict__ rgb_out,
+    float* __restrict__ g_theta_ray, float* __restrict__ d_raw, long long B, int N, float scale) {
+    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
+    if (ray >= B) return;                      // whole wave leaves together; no barriers below
+    const int lane = threadIdx.x & 63;
+    f32x4* rout = reinterpret_cast<f32x4*>(d_raw) + ray * N;
+    if (N == 1) {
+        // the reference composites an EMPTY sample axis at N == 1 (composite_device.h): rgb = 0, so c' = fl(fl(1 + a) 0) + b,
+        // no sample receives anything and the ray's row of g_theta is (g 0, g)
+        if (lane == 0) {
+            rout[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const Row row = load_row(theta_ray + ray * theta_stride);
+            float gain[3], g[3], g_c[3], g_a[3];
+            const float zero[3] = {0.f, 0.f, 0.f};
+            gains(row, gain);
+            for (int c = 0; c < 3; ++c) {
+                const float v = apply(gain[c], 0.f, row.b[c]);
+                g[c] = mul_rn(mul_rn(2.0f, sub_rn(v, target[ray * 3 + c])), scale);
+                if (rgb_out) rgb_out[ray * 3 + c] = v;
+            }
+            apply_backward(g, zero, gain, g_c, g_a);
+            store_row(g_theta_ray + ray * 6, g_a, g);
+        }
+        return;
+    }
+    const float* d = rays + ray * 6 + 3;
+    const float dnorm = nerf_composite::unit_dir_norm(d[0], d[1], d[2], true);
+    const nerf_composite::DenseSamples dense{ts + ray * N, reinterpret_cast<const f32x4*>(raw) + ray * N};
+    nerf_composite::composite_backward_ray<MAX_CHUNKS>(
+        dense, nerf_composite::AffineMseHead{target, rgb_out, scale, theta_ray, theta_stride, g_theta_ray},
+        nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
+}
+
+inline dim3 per_element(long long n) { return dim3((unsigned)((n + THREADS - 1) / THREADS)); }
+
+}  // namespace
+
+// B, M >= 1 and below 2^31 (api.hip refuses the rest): the grids fit
+extern "C" int nerf_amd_launch_appearance_gather(const float* theta, const long long* ids, long long* ids_copy, long long HW,
+                                                 float* theta_ray, long long B, long long M, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(appearance_gather_kernel, per_element(B), dim3(THREADS), 0, stream, theta, ids, ids_copy, HW, theta_ray, B, M);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nerf_amd_launch_appearance_apply(const float* rgb, const float* theta_ray, long long theta_stride, float* out,
+                                                long long B, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(appearance_apply_kernel, per_element(B), dim3(THREADS), 0, stream, rgb, theta_ray, theta_stride, out, B);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nerf_amd_launch_appearance_apply_backward(const float* g_out, const float* rgb, const float* theta_ray,
+                                                         long long theta_stride, float* g_rgb, float* g_theta_ray, long long B,
+                                                         hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(appearance_apply_backward_kernel, per_element(B), dim3(THREADS), 0, stream, g_out, rgb, theta_ray,
+                       theta_stride, g_rgb, g_theta_ray, B);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nerf_amd_launch_appearance_reduce(const float* g_theta_ray, const long long* ids, long long HW, const float* theta,
+                                                 float reg, const int* frozen, float* g_theta, long long B, long long M,
+                                                 hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(appearance_reduce_kernel, dim3((unsigned)M), dim3(THREADS), 0, stream, g_theta_ray, ids, HW, theta, reg,
+                       frozen, g_theta, B);
+    return (int)hipGetLastError();
+}
+
+extern "C" int nerf_amd_launch_composite_mse_backward_affine(const float* raw, const float* ts, const float* rays,
+                                                             const float* target, const float* theta_ray, long long theta_stride,
+                                                             float* rgb, float* g_theta_ray, float* d_raw, long long B, int N,
+                                                             hipStream_t stream) {
+    (void)hipGetLastError();
+    if (B == 0) return 0;
+    if (N > nerf_layout::COMPOSITE_BWD_MAX_N) return -2;
+    const dim3 grid((unsigned)((B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
+    const float scale = 1.0f / (3.0f * (float)B);
+    hipLaunchKernelGGL(composite_affine_head_kernel, grid, block, 0, stream, raw, ts, rays, target, theta_ray, theta_stride, rgb,
+                       g_theta_ray, d_raw, B, N, scale);
+    return (int)hipGetLastError();
+}

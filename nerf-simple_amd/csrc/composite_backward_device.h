@@ -18,9 +18,11 @@
 //   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd)
 //   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; MseHead: the loss gradient formed here;
 //           BgMseHead: the same behind a background colour, whose gradient to acc reaches every w_i; DistMseHead: the same
-//           with the distortion loss of the ray's weights beside the MSE, whose gradient joins G_i where FiveGrads adds g_w)
+//           with the distortion loss of the ray's weights beside the MSE, whose gradient joins G_i where FiveGrads adds g_w;
+//           AffineMseHead: the MSE behind a per-image colour map of rgb, whose backward scales the gradient to rgb)
 //   Sink -- where the forward sweep's weights go (NoSink; PdfSink: the sampler's LDS slice, sample_pdf_device.h)
 #pragma once
+#include "appearance_device.h"          // AffineMseHead: the per-image colour map and its backward
 #include "composite_device.h"
 
 namespace nerf_composite {
@@ -136,6 +138,22 @@ template <> inline constexpr bool behind_background<DistMseHead<true>> = true;
 template <class Up> inline constexpr bool with_distortion = false;
 template <bool BG> inline constexpr bool with_distortion<DistMseHead<BG>> = true;
 
+// The MSE head behind a per-image colour correction (appearance_device.h): c' = (1 + a) rgb + b with the ray's row of
+// theta = (a, b), loss = MSELoss(c', target).  By definition the chain  compositor (rgb) -> nerf_amd_appearance_apply -> 2 (c' -
+// target) scale -> nerf_amd_appearance_apply_backward (g_rgb = g fl(1 + a); the ray's row of d loss / d theta = (g rgb, g)) ->
+// compositor backward (g_rgb), bit for bit.
+struct AffineMseHead {
+    static constexpr bool MSE = true;
+    const float* target;               // [B,3]
+    float* rgb_out;                    // [B,3]: c', or NULL
+    float scale;                       // 1 / (3 B)
+    const float* theta;                // one row per ray [B,6] (theta_stride 6) or one for all rays (theta_stride 0)
+    long long theta_stride;
+    float* g_theta;                    // [B,6]: every ray's own row of d loss / d theta (its image sums them)
+};
+template <class Up> inline constexpr bool behind_affine = false;
+template <> inline constexpr bool behind_affine<AffineMseHead> = true;
+
 // ---- weight sinks ----------------------------------------------------------------------------------------------------------
 struct NoSink {
     __device__ __forceinline__ void put(int, float, float) const {}
@@ -217,9 +235,24 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
             const float through = sub_rn(1.0f, wave_total(sa));
             sr = add_rn(sr, mul_rn(through, b0)); sg = add_rn(sg, mul_rn(through, b1)); sb = add_rn(sb, mul_rn(through, b2));
         }
+        [[maybe_unused]] float plain[3], gain[3];
+        if constexpr (behind_affine<Up>) {         // sr, sg, sb become c': the loss's prediction and the rgb output
+            const nerf_appearance::Row row = nerf_appearance::load_row(up.theta + ray * up.theta_stride);
+            nerf_appearance::gains(row, gain);
+            plain[0] = sr; plain[1] = sg; plain[2] = sb;
+            sr = nerf_appearance::apply(gain[0], sr, row.b[0]); sg = nerf_appearance::apply(gain[1], sg, row.b[1]);
+            sb = nerf_appearance::apply(gain[2], sb, row.b[2]);
+        }
         gr = mul_rn(mul_rn(2.0f, sub_rn(sr, up.target[ray * 3 + 0])), up.scale);
         gg = mul_rn(mul_rn(2.0f, sub_rn(sg, up.target[ray * 3 + 1])), up.scale);
         gb = mul_rn(mul_rn(2.0f, sub_rn(sb, up.target[ray * 3 + 2])), up.scale);
+        if constexpr (behind_affine<Up>) {         // the map's backward: the ray's row of g_theta, then g_rgb = g fl(1 + a)
+            const float g[3] = {gr, gg, gb};
+            float g_c[3], g_a[3];
+            nerf_appearance::apply_backward(g, plain, gain, g_c, g_a);
+            if (lane == 0) nerf_appearance::store_row(up.g_theta + ray * 6, g_a, g);
+            gr = g_c[0]; gg = g_c[1]; gb = g_c[2];
+        }
         if constexpr (behind_background<Up>) gac = -add_rn(add_rn(mul_rn(gr, b0), mul_rn(gg, b1)), mul_rn(gb, b2));
         if (up.rgb_out && lane == 0) { up.rgb_out[ray * 3 + 0] = sr; up.rgb_out[ray * 3 + 1] = sg; up.rgb_out[ray * 3 + 2] = sb; }
     } else {

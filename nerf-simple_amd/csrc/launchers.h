@@ -114,4 +114,13 @@ int nerf_amd_launch_camera_poses(const float*, const float*, float*, long long, 
 long long nerf_amd_image_metrics_ws_bytes(long long, int, int);
 int nerf_amd_launch_image_metrics(const float*, long long, const float*, long long, double*, double*, float*, void*, long long, int,
                                   int, hipStream_t);
+int nerf_amd_launch_appearance_gather(const float*, const long long*, long long*, long long, float*, long long, long long,
+                                      hipStream_t);
+int nerf_amd_launch_appearance_apply(const float*, const float*, long long, float*, long long, hipStream_t);
+int nerf_amd_launch_appearance_apply_backward(const float*, const float*, const float*, long long, float*, float*, long long,
+                                              hipStream_t);
+int nerf_amd_launch_appearance_reduce(const float*, const long long*, long long, const float*, float, const int*, float*,
+                                      long long, long long, hipStream_t);
+int nerf_amd_launch_composite_mse_backward_affine(const float*, const float*, const float*, const float*, const float*, long long,
+                                                  float*, float*, float*, long long, int, hipStream_t);
 }

@@ -1850,6 +1850,141 @@ class GraphedCameraTrainStep(GraphedTrainStep):
     __call__ = step
 
 
+class _AppearancePass(_DensePass):
+    """The dense pass with the loss behind the per-image colour correction: the affine head (compositor + the map + MSE
+    gradient + the map's backward + compositor backward, ONE kernel: nerf_amd_volume_render_mse_backward_affine; ``rgb`` is
+    c', so the side branch's loss is the MSE behind the correction), and the reduction of the rays' rows of d loss / d theta
+    to one per image (nerf_amd_appearance_reduce on the ids the rows were gathered by) on the main branch."""
+
+    def _reduce(self, st):
+        s = self.step
+        a = s.appearance
+        a._launch("nerf_amd_appearance_reduce", s._g_theta_ray, s._ids_used, a.HW, a.theta, a.reg, a._frozen_arg,
+                  s.appearance_grad, s.B, a.M, stream=st)
+
+    def head(self, st, pdf=None):
+        ptr, s, (rays, *_) = _lib.ptr, self.step, self.jitter
+        _launch("nerf_amd_volume_render_mse_backward_affine", ptr(self.raw), ptr(self.ts), rays, ptr(s.gt), ptr(s._theta_ray), 6,
+                ptr(self.rgb), ptr(s._g_theta_ray), ptr(self.d_raw), s.B, self.N, st)
+        if s._reduce_behind == "head":
+            self._reduce(st)
+
+    def dx_chain(self, st):
+        super().dx_chain(st)
+        if self.step._reduce_behind == "dx":
+            self._reduce(st)
+
+
+class GraphedAppearanceTrainStep(GraphedTrainStep):
+    """GraphedTrainStep with a per-image colour correction inside the captured graph: the loss of every
+    step is ``MSELoss((1 + a) rgb + b, gt)`` with the row (a, b) of each ray's image (``appearance``: a
+    ``utils.appearance.AppearanceCorrection``, ``appearance.theta`` [M,6]), and ``theta`` is trained beside the network by an
+    Adam of its own.
+
+        graph A: hyper fetch -> appearance hyper fetch -> gather (nerf_amd_appearance_gather: one row of theta per ray, and a
+                 copy of the ids) -> forward -> affine head (nerf_amd_volume_render_mse_backward_affine) -> dX chain -> reduce
+                 (nerf_amd_appearance_reduce: ``appearance_grad`` = d loss / d theta, with the ridge and the frozen rows) -> dW
+                 products; the side branch is GraphedTrainStep's, its selection of the next batch writing the shared id buffer
+                 while this step reduces by its own copy
+        graph B: Adam -> re-pack -> Adam on (theta, appearance_grad) with scalars of its own (nerf_amd_adam_step_hyper)
+
+    ``rays_from`` is required (a ``RayGenerator`` with colours whose table has the correction's M HW rows): the image of a ray
+    is its row // HW, so ``step()`` takes no rays.  ``appearance_lr``, ``appearance_betas`` (held rounded to fp32, the kernel's
+    format), ``appearance_eps``: the second Adam's; ``step(appearance_decay=)`` multiplies ``appearance_lr`` as ``decay`` does
+    the network's rate.  ``step`` returns the MSE behind the correction.  ``appearance_grad`` [M,6] is the last step's gradient,
+    ``appearance.theta`` is live, ``ray_ids`` are the rows the last step trained on.  Both jitter sources work, and so does
+    ``storage='e4m3'`` (the head does not touch the storage form).  The address of ``appearance.theta`` is baked into the graph:
+    write it in place (``load_state_dict`` does); ``step`` raises if the tensor was replaced.
+
+    Refused (RuntimeError, before any launch or RNG draw): a process group that exchanges gradients (``appearance_grad`` has no
+    exchange yet), ``background`` / ``sigma_noise`` / ``distortion``, an ``appearance`` whose M HW is not the table's length or
+    that lives on another device.  The masked, hierarchical, guided and camera steppers do not take a correction."""
+
+    _reduce_behind = "dx"        # where the reduction sits on the main branch: behind the "dx" chain or behind the "head"
+
+    def __init__(self, net, optimizer, n_rays, N, appearance, *, rays_from, appearance_lr=1e-3, appearance_betas=(0.9, 0.999),
+                 appearance_eps=1e-8, select_mode="train", group=None, **kw):
+        from . import parallel
+        from .utils.appearance import AppearanceCorrection
+        if kw.get("background") is not None or kw.get("sigma_noise") or kw.get("distortion"):
+            raise RuntimeError("GraphedAppearanceTrainStep does not take background / sigma_noise / distortion yet")
+        if parallel.collectives_active(group):
+            raise RuntimeError("GraphedAppearanceTrainStep trains on one replica: the appearance gradient has no exchange yet")
+        if not isinstance(appearance, AppearanceCorrection):
+            raise RuntimeError("appearance must be a utils.appearance.AppearanceCorrection")
+        if rays_from is None:
+            raise RuntimeError("GraphedAppearanceTrainStep finds a ray's image from the ids of a selection: "
+                               "rays_from=<RayGenerator> is required")
+        if select_mode not in rays_from.colours:
+            raise RuntimeError(f"rays_from has no colour table for mode {select_mode!r}")
+        if int(rays_from.rays_dataset[select_mode].shape[0]) != appearance.n_rays:
+            raise RuntimeError(f"the table of rays_from holds {int(rays_from.rays_dataset[select_mode].shape[0])} rays, the "
+                               f"correction spans {appearance.M} x {appearance.HW} = {appearance.n_rays}")
+        if appearance.theta.device != optimizer.flat.device:
+            raise RuntimeError(f"the correction lives on {appearance.theta.device}, the module on {optimizer.flat.device}")
+        self.appearance, self._theta_ptr = appearance, appearance.theta.data_ptr()
+        # the kernel reads its betas as fp32 and forms 1 - beta from them: the bias corrections are formed from the same
+        # rounded values (_set_hyper), so the update is Adam's for exactly the betas held here
+        self.appearance_lr, self.appearance_eps = float(appearance_lr), float(appearance_eps)
+        self.appearance_betas = tuple(float(torch.tensor(float(b), dtype=torch.float32)) for b in appearance_betas)
+        self.appearance_steps = 0
+        dev = appearance.theta.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.appearance_grad = torch.zeros_like(appearance.theta, requires_grad=False)
+        self._app_m, self._app_v = torch.zeros_like(self.appearance_grad), torch.zeros_like(self.appearance_grad)
+        self._app_hyper, self._app_ring = torch.zeros(8, **f32), _HyperRing(dev)
+        self._theta_ray, self._g_theta_ray = torch.zeros((int(n_rays), 6), **f32), torch.zeros((int(n_rays), 6), **f32)
+        self._ids_used = torch.zeros((int(n_rays),), dtype=torch.int64, device=dev)
+        super().__init__(net, optimizer, n_rays, N, rays_from=rays_from, select_mode=select_mode, group=group, **kw)
+
+    def _alloc_pass_buffers(self, tn, tf):
+        super()._alloc_pass_buffers(tn, tf)
+        self.passes[0].__class__ = _AppearancePass   # the base's dense pass and its buffers, the loss behind the correction
+
+    def _before_forward(self, st):
+        a = self.appearance
+        self._app_ring.fetch(self._app_hyper, self.dev)
+        a._launch("nerf_amd_appearance_gather", a.theta, self._ids_next, self._ids_used, a.HW, self._theta_ray, self.B, a.M, stream=st)
+
+    @property
+    def ray_ids(self):
+        """Rows of the table the LAST step trained on: the copy the gather kept."""
+        return self._ids_used
+
+    def _set_hyper(self, step):
+        super()._set_hyper(step)
+        t, (b1, b2) = self.appearance_steps + 1, self.appearance_betas
+        self._app_ring.push((self.appearance_lr, b1, b2, self.appearance_eps, 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5))
+
+    def _update(self):
+        super()._update()
+        ptr, theta = _lib.ptr, self.appearance.theta
+        _launch("nerf_amd_adam_step_hyper", ptr(theta), ptr(self.appearance_grad), ptr(self._app_m), ptr(self._app_v),
+                theta.numel(), ptr(self._app_hyper), _lib.stream_ptr(self.dev))
+
+    def _capture(self):
+        super()._capture()
+        self._app_ring.reset()                       # the warm-up consumed a slot
+
+    def _enqueue_step(self, decay):
+        loss = super()._enqueue_step(decay)
+        self._app_ring.launched(self.dev)
+        self.appearance_steps += 1
+        return loss
+
+    def step(self, rays=None, gt=None, u=None, decay=1.0, appearance_decay=1.0):
+        if rays is not None or gt is not None:
+            raise RuntimeError("GraphedAppearanceTrainStep finds a ray's image from the selected ids: step() takes no rays")
+        if self.appearance.theta.data_ptr() != self._theta_ptr:
+            raise RuntimeError("appearance.theta was replaced: its address is baked into the captured graph "
+                               "(write it in place, or build a new GraphedAppearanceTrainStep)")
+        loss = super().step(None, None, u=u, decay=decay)
+        self.appearance_lr *= float(appearance_decay)
+        return loss
+
+    __call__ = step
+
+
 class _MaskedSteps:
     """What the two masked steppers share (listed in front of their stepper base): the refusals, the grid and the capacities,
     and the overflow report -- ``counts`` on the device is int64 {live, kept} per pass, copied back every ``check_every``
