@@ -376,9 +376,11 @@ int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, co
     if (B == 0) return 0;
     if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
-    return nerf_amd_launch_composite_mse_backward_bg(raw, ts, rays, target, bg, bg_stride, std, seed,
-                                                     (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                                                     ray_id0, rgb, d_raw, B, N, S(stream));
+    const DenseHeadArgs a{.raw = raw, .ts = ts, .rays = rays, .target = target, .rgb = rgb, .d_raw = d_raw, .B = B, .N = N,
+                          .bg = bg, .bg_stride = bg_stride, .std = std, .seed = seed,
+                          .seed_mem = (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
+                          .ray_id0 = ray_id0};
+    return nerf_amd_launch_dense_head(&a, S(stream));          // bg == NULL and std == 0: the plain head's launch
 }
 
 // The distortion term (composite_dist.hip).  Order of the rules: sizes; [the noise arguments; the background's stride;] the
@@ -409,9 +411,11 @@ int nerf_amd_volume_render_mse_backward_dist(const float* raw, const float* ts, 
     if (B == 0) return 0;
     if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
-    return nerf_amd_launch_composite_mse_backward_dist(raw, ts, rays, target, bg, bg_stride, std, seed,
-                                                       (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                                                       ray_id0, t_far, coef, rgb, loss_ray, d_raw, B, N, S(stream));
+    const DenseHeadArgs a{.raw = raw, .ts = ts, .rays = rays, .target = target, .rgb = rgb, .d_raw = d_raw, .B = B, .N = N,
+                          .bg = bg, .bg_stride = bg_stride, .std = std, .seed = seed,
+                          .seed_mem = (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
+                          .ray_id0 = ray_id0, .dist = true, .t_far = t_far, .coef = coef, .loss_ray = loss_ray};
+    return nerf_amd_launch_dense_head(&a, S(stream));
 }
 
 int nerf_amd_mse_loss(const float* pred, const float* target, float* loss, float* g_pred, int64_t n, void* stream) {
@@ -870,8 +874,9 @@ int nerf_amd_volume_render_mse_backward_affine(const float* raw, const float* ts
     if (N > COMPOSITE_BWD_MAX_N) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !theta_ray || !g_theta_ray || !d_raw) return NERF_AMD_EINVAL;
     if (misaligned(raw, 16) || misaligned(d_raw, 16) || misaligned(theta_ray, 8) || misaligned(g_theta_ray, 8)) return NERF_AMD_EINVAL;
-    return nerf_amd_launch_composite_mse_backward_affine(raw, ts, rays, target, theta_ray, theta_stride, rgb, g_theta_ray, d_raw, B,
-                                                         N, S(stream));
+    const DenseHeadArgs a{.raw = raw, .ts = ts, .rays = rays, .target = target, .rgb = rgb, .d_raw = d_raw, .B = B, .N = N,
+                          .theta = theta_ray, .theta_stride = theta_stride, .g_theta = g_theta_ray};
+    return nerf_amd_launch_dense_head(&a, S(stream));
 }
 
 // ---- image metrics: squared error, max(gt) and SSIM of M image pairs (csrc/image_metrics.hip) ---------------------------

@@ -1,26 +1,24 @@
 // appearance.hip -- the per-image colour correction trained beside the network: image m of M holds theta[m] = (a[3], b[3]),
 // and a ray of it is compared with its pixel behind  c' = (1 + a) rgb + b  (appearance_device.h: the three-op map and its
-// backward; the contract is include/nerf_amd.h).  Four small stages and the training head:
+// backward; the contract is include/nerf_amd.h).  Four small stages; the training head is their composition:
 //
 //   gather            theta_ray[i] = theta[ids[i] / HW] (a row of NaN for an id outside [0, M HW)); keeps a copy of the ids
 //   apply             c' = (1 + a) rgb + b per ray
 //   apply_backward    g_rgb = g fl(1 + a),  the ray's row of d loss / d theta = (g rgb, g)
 //   reduce            g_theta[m] = sum of the rows of image m, + reg theta[m] (the ridge), or zeros for a frozen image
 //   head              compositor -> apply -> MSE gradient -> apply_backward -> compositor backward: BY DEFINITION that
-//                     composition, in one launch on composite_backward_ray (AffineMseHead)
+//                     composition, in one launch: dense_head_kernel<.., AFFINE> (composite_head.hip)
 //
 // The reduction is ONE launch without atomics or a workspace, as camera.hip's: a block per image walks the B ids, every
 // thread sums its own rows in row order, the block's 256 partial sums are folded by a fixed shuffle tree and a fixed LDS
 // order -- two runs write the same bytes.  An id outside [0, M HW) matches no image.
-#include "composite_backward_device.h"
+#include "appearance_device.h"
 #include "launchers.h"
 
 namespace {
 
 using namespace nerf_appearance;
 constexpr int THREADS = 256;
-constexpr int RAYS_PER_BLOCK = 4;
-constexpr int MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;          // N <= 512
 
 // ---- the stages ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void appearance_gather_kernel(const float* __restrict__ theta, const long long* __restrict__ ids,
@@ -108,42 +106,6 @@ __global__ __launch_bounds__(THREADS) void appearance_reduce_kernel(const float*
     store_row(g_theta + m * 6, t, t + 3);
 }
 
-// ---- the training head: one wavefront per ray, as composite_bg_head_kernel ------------------------------------------------
-__global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_affine_head_kernel(
-    const float* __restrict__ raw, const float* __restrict__ ts, const float* __restrict__ rays,
-    const float* __restrict__ target, const float* __restrict__ theta_ray, long long theta_stride, float* __restrict__ rgb_out,
-    float* __restrict__ g_theta_ray, float* __restrict__ d_raw, long long B, int N, float scale) {
-    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
-    if (ray >= B) return;                      // whole wave leaves together; no barriers below
-    const int lane = threadIdx.x & 63;
-    f32x4* rout = reinterpret_cast<f32x4*>(d_raw) + ray * N;
-    if (N == 1) {
-        // the reference composites an EMPTY sample axis at N == 1 (composite_device.h): rgb = 0, so c' = fl(fl(1 + a) 0) + b,
-        // no sample receives anything and the ray's row of g_theta is (g 0, g)
-        if (lane == 0) {
-            rout[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const Row row = load_row(theta_ray + ray * theta_stride);
-            float gain[3], g[3], g_c[3], g_a[3];
-            const float zero[3] = {0.f, 0.f, 0.f};
-            gains(row, gain);
-            for (int c = 0; c < 3; ++c) {
-                const float v = apply(gain[c], 0.f, row.b[c]);
-                g[c] = mul_rn(mul_rn(2.0f, sub_rn(v, target[ray * 3 + c])), scale);
-                if (rgb_out) rgb_out[ray * 3 + c] = v;
-            }
-            apply_backward(g, zero, gain, g_c, g_a);
-            store_row(g_theta_ray + ray * 6, g_a, g);
-        }
-        return;
-    }
-    const float* d = rays + ray * 6 + 3;
-    const float dnorm = nerf_composite::unit_dir_norm(d[0], d[1], d[2], true);
-    const nerf_composite::DenseSamples dense{ts + ray * N, reinterpret_cast<const f32x4*>(raw) + ray * N};
-    nerf_composite::composite_backward_ray<MAX_CHUNKS>(
-        dense, nerf_composite::AffineMseHead{target, rgb_out, scale, theta_ray, theta_stride, g_theta_ray},
-        nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
-}
-
 inline dim3 per_element(long long n) { return dim3((unsigned)((n + THREADS - 1) / THREADS)); }
 
 }  // namespace
@@ -178,19 +140,5 @@ extern "C" int nerf_amd_launch_appearance_reduce(const float* g_theta_ray, const
     (void)hipGetLastError();
     hipLaunchKernelGGL(appearance_reduce_kernel, dim3((unsigned)M), dim3(THREADS), 0, stream, g_theta_ray, ids, HW, theta, reg,
                        frozen, g_theta, B);
-    return (int)hipGetLastError();
-}
-
-extern "C" int nerf_amd_launch_composite_mse_backward_affine(const float* raw, const float* ts, const float* rays,
-                                                             const float* target, const float* theta_ray, long long theta_stride,
-                                                             float* rgb, float* g_theta_ray, float* d_raw, long long B, int N,
-                                                             hipStream_t stream) {
-    (void)hipGetLastError();
-    if (B == 0) return 0;
-    if (N > nerf_layout::COMPOSITE_BWD_MAX_N) return -2;
-    const dim3 grid((unsigned)((B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
-    const float scale = 1.0f / (3.0f * (float)B);
-    hipLaunchKernelGGL(composite_affine_head_kernel, grid, block, 0, stream, raw, ts, rays, target, theta_ray, theta_stride, rgb,
-                       g_theta_ray, d_raw, B, N, scale);
     return (int)hipGetLastError();
 }

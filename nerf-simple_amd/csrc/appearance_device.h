@@ -1,5 +1,5 @@
-// appearance_device.h -- the per-image colour correction (appearance.hip, and the AffineMseHead of
-// composite_backward_device.h): image m holds theta[m] = (a[3], b[3]) in fp32, and a ray of it sees
+// appearance_device.h -- the per-image colour correction (appearance.hip, and the AFFINE term of
+// composite_backward_device.h's LossHead): image m holds theta[m] = (a[3], b[3]) in fp32, and a ray of it sees
 //
 //     c'_k = (1 + a_k) c_k + b_k          k = r, g, b          (c: the compositor's rgb, before any clip)
 //

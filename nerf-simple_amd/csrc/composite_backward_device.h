@@ -16,33 +16,16 @@
 //
 // The three axes on which the callers differ are compile-time choices; a term a caller does not have is not computed.
 //   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd)
-//   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; MseHead: the loss gradient formed here;
-//           BgMseHead: the same behind a background colour, whose gradient to acc reaches every w_i; DistMseHead: the same
-//           with the distortion loss of the ray's weights beside the MSE, whose gradient joins G_i where FiveGrads adds g_w;
-//           AffineMseHead: the MSE behind a per-image colour map of rgb, whose backward scales the gradient to rgb)
+//   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; LossHead<BG, DIST, AFFINE>: the MSE loss
+//           gradient formed here -- BG: behind a background colour, whose gradient to acc reaches every w_i; DIST: with the
+//           distortion loss of the ray's weights beside the MSE, whose gradient joins G_i where FiveGrads adds g_w; AFFINE:
+//           behind a per-image colour map of rgb, whose backward scales the gradient to rgb.  MseHead is the plain one)
 //   Sink -- where the forward sweep's weights go (NoSink; PdfSink: the sampler's LDS slice, sample_pdf_device.h)
 #pragma once
-#include "appearance_device.h"          // AffineMseHead: the per-image colour map and its backward
+#include "appearance_device.h"          // LossHead<.., AFFINE>: the per-image colour map and its backward
 #include "composite_device.h"
+#include "composite_dist_device.h"      // LossHead<.., DIST, ..>: the distortion loss of a ray's weights
 
-namespace nerf_composite {
-
-// exclusive suffix sum over the 64 lanes (inclusive suffix sum, then shift down by one lane) and the wave's total
-__device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& total) {
-    float incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float dn = __shfl_down(incl, off);
-        if (lane + off < 64) incl = add_rn(incl, dn);
-    }
-    total = __shfl(incl, 0);
-    float ex = __shfl_down(incl, 1);
-    if (lane == 63) ex = 0.f;
-    return ex;
-}
-
-}  // namespace nerf_composite
-#include "composite_dist_device.h"      // distortion_ray: the distortion loss of a ray's weights (uses wave_suffix_excl)
 namespace nerf_composite {
 
 // ---- sample sources --------------------------------------------------------------------------------------------------------
@@ -95,64 +78,71 @@ struct MaskedSamplesBwd {
 
 // ---- upstream gradients ----------------------------------------------------------------------------------------------------
 struct FiveGrads {                     // of rgb[B,3], disp[B], alpha[B,N], acc[B], w[B,N]; NULL = zero
-    static constexpr bool MSE = false;
+    static constexpr bool MSE = false, BG = false, DIST = false, AFFINE = false;
     const float *g_rgb, *g_disp, *g_alpha, *g_acc, *g_w;
 };
-struct MseHead {                       // loss = MSELoss(rgb, target) (train.py:52): d loss / d rgb = 2 (rgb - target) scale
-    static constexpr bool MSE = true;
-    const float* target;               // [B,3]
-    float* rgb_out;                    // [B,3]: the forward compositor's rgb, or NULL
-    float scale;                       // 1 / (3 B)
-};
 
-// The MSE head behind a background colour: rgb_bg = rgb + (1 - acc) bg (two rounded ops per channel, no fma), loss =
-// MSELoss(rgb_bg, target).  By definition the chain  compositor (rgb, acc) -> blend -> 2 (rgb_bg - target) scale -> the
-// blend's backward (g_rgb passes through, g_acc = -((g0 bg0 + g1 bg1) + g2 bg2)) -> compositor backward (g_rgb, g_acc),
-// bit for bit: acc is summed with the forward compositor's ops, g_acc joins G_i where FiveGrads adds gac.
-struct BgMseHead {
-    static constexpr bool MSE = true;
+// loss = MSELoss(rgb, target) (train.py:52): d loss / d rgb = 2 (rgb - target) scale, formed from the forward sweep's rgb.
+// Three optional terms, each BY DEFINITION -- and bit for bit -- a chain of the stages around the compositor:
+//   BG      the MSE behind a background colour: rgb_bg = rgb + (1 - acc) bg (two rounded ops per channel, no fma).  The chain
+//           compositor (rgb, acc) -> blend -> 2 (rgb_bg - target) scale -> the blend's backward (g_rgb passes through, g_acc =
+//           -((g0 bg0 + g1 bg1) + g2 bg2)) -> compositor backward (g_rgb, g_acc): acc is summed with the forward compositor's
+//           ops, g_acc joins G_i where FiveGrads adds gac.
+//   DIST    loss = MSE + sum_rays coef D(w, t) (composite_dist_device.h).  The chain  compositor (rgb, acc, w) ->
+//           nerf_amd_distortion_loss on that w (loss_ray, g_w) -> [blend] -> the MSE gradient -> [the blend's backward] ->
+//           compositor backward (g_rgb, g_acc, g_w): G_i = (rgb terms + g_acc) + g_w_i.
+//   AFFINE  the MSE behind a per-image colour correction (appearance_device.h): c' = (1 + a) rgb + b with the ray's row of
+//           theta = (a, b).  The chain  compositor (rgb) -> nerf_amd_appearance_apply -> 2 (c' - target) scale ->
+//           nerf_amd_appearance_apply_backward (g_rgb = g fl(1 + a); the ray's row of d loss / d theta = (g rgb, g)) ->
+//           compositor backward (g_rgb).
+// A term's fields are looked at only where the term is on; MseHead{target, rgb_out, scale} leaves them zero.
+template <bool BG_, bool DIST_, bool AFFINE_>
+struct LossHead {
+    static_assert(!(BG_ && AFFINE_), "the order of the blend and the colour map in one chain is not defined");
+    static constexpr bool MSE = true, BG = BG_, DIST = DIST_, AFFINE = AFFINE_;
     const float* target;               // [B,3]
-    float* rgb_out;                    // [B,3]: rgb_bg, or NULL
+    float* rgb_out;                    // [B,3]: the loss's prediction (rgb, rgb_bg or c'), or NULL
     float scale;                       // 1 / (3 B)
-    const float* bg;                   // one colour [3] (bg_stride 0) or one per ray [B,3] (bg_stride 3); no gradient
+    const float* bg;                   // BG: one colour [3] (bg_stride 0) or one per ray [B,3] (bg_stride 3); no gradient
     long long bg_stride;
-};
-template <class Up> inline constexpr bool behind_background = false;
-template <> inline constexpr bool behind_background<BgMseHead> = true;
-
-// The MSE head with the distortion term beside it: loss = MSELoss(rgb_bg, target) + sum_rays coef D(w, t) (composite_dist_device.h).
-// By definition the chain  compositor (rgb, acc, w) -> nerf_amd_distortion_loss on that w (loss_ray, g_w) -> [blend] -> the MSE
-// gradient -> [the blend's backward] -> compositor backward (g_rgb, g_acc, g_w), bit for bit: G_i = (rgb terms + g_acc) + g_w_i.
-template <bool BG>
-struct DistMseHead {
-    static constexpr bool MSE = true;
-    const float* target;               // [B,3]
-    float* rgb_out;                    // [B,3]: rgb_bg (rgb without a background), or NULL
-    float scale;                       // 1 / (3 B)
-    const float* bg;                   // as BgMseHead's; not looked at without BG
-    long long bg_stride;
-    float t_far, coef;                 // the last sample's interval ends at t_far; coef = lambda / (B (tf - tn))
-    float* loss_ray;                   // [B]: coef D of each ray, or NULL
-};
-template <> inline constexpr bool behind_background<DistMseHead<true>> = true;
-template <class Up> inline constexpr bool with_distortion = false;
-template <bool BG> inline constexpr bool with_distortion<DistMseHead<BG>> = true;
-
-// The MSE head behind a per-image colour correction (appearance_device.h): c' = (1 + a) rgb + b with the ray's row of
-// theta = (a, b), loss = MSELoss(c', target).  By definition the chain  compositor (rgb) -> nerf_amd_appearance_apply -> 2 (c' -
-// target) scale -> nerf_amd_appearance_apply_backward (g_rgb = g fl(1 + a); the ray's row of d loss / d theta = (g rgb, g)) ->
-// compositor backward (g_rgb), bit for bit.
-struct AffineMseHead {
-    static constexpr bool MSE = true;
-    const float* target;               // [B,3]
-    float* rgb_out;                    // [B,3]: c', or NULL
-    float scale;                       // 1 / (3 B)
-    const float* theta;                // one row per ray [B,6] (theta_stride 6) or one for all rays (theta_stride 0)
+    float t_far, coef;                 // DIST: the last sample's interval ends at t_far; coef = lambda / (B (tf - tn))
+    float* loss_ray;                   // DIST: [B]: coef D of each ray, or NULL
+    const float* theta;                // AFFINE: one row per ray [B,6] (theta_stride 6) or one for all rays (theta_stride 0)
     long long theta_stride;
-    float* g_theta;                    // [B,6]: every ray's own row of d loss / d theta (its image sums them)
+    float* g_theta;                    // AFFINE: [B,6]: every ray's own row of d loss / d theta (its image sums them)
 };
-template <class Up> inline constexpr bool behind_affine = false;
-template <> inline constexpr bool behind_affine<AffineMseHead> = true;
+using MseHead = LossHead<false, false, false>;
+
+// The reference composites an EMPTY sample axis at N == 1 (composite_device.h): rgb = acc = 0 and no sample receives anything.
+// So d_raw's one row is 0, the ray has no weight (D = 0), rgb_bg = bg exactly (through the blend's own three rounded ops),
+// and c' = fl(fl(1 + a) 0) + b with the ray's row of g_theta = (g 0, g).  rout: the ray's row of d_raw.
+template <class Up>
+__device__ __forceinline__ void loss_head_empty_ray(const Up& up, int lane, long long ray, f32x4* rout) {
+    if (lane != 0) return;
+    rout[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (Up::DIST) {
+        if (up.loss_ray) up.loss_ray[ray] = 0.f;
+    }
+    float c[3] = {0.f, 0.f, 0.f};
+    if constexpr (Up::BG) {
+        for (int k = 0; k < 3; ++k) c[k] = add_rn(0.f, mul_rn(sub_rn(1.0f, 0.f), up.bg[ray * up.bg_stride + k]));
+    }
+    if constexpr (Up::AFFINE) {
+        const nerf_appearance::Row row = nerf_appearance::load_row(up.theta + ray * up.theta_stride);
+        float gain[3], g[3], g_c[3], g_a[3];
+        const float zero[3] = {0.f, 0.f, 0.f};
+        nerf_appearance::gains(row, gain);
+        for (int k = 0; k < 3; ++k) {
+            c[k] = nerf_appearance::apply(gain[k], 0.f, row.b[k]);
+            g[k] = mul_rn(mul_rn(2.0f, sub_rn(c[k], up.target[ray * 3 + k])), up.scale);
+        }
+        nerf_appearance::apply_backward(g, zero, gain, g_c, g_a);
+        nerf_appearance::store_row(up.g_theta + ray * 6, g_a, g);
+    }
+    if (up.rgb_out) {
+        for (int k = 0; k < 3; ++k) up.rgb_out[ray * 3 + k] = c[k];
+    }
+}
 
 // ---- weight sinks ----------------------------------------------------------------------------------------------------------
 struct NoSink {
@@ -215,7 +205,7 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
                 if constexpr (Up::MSE) {
                     // the same ops as the forward compositor (composite_device.h), so rgb_out equals its rgb
                     sr = __fmaf_rn(wt, cc[ch][0], sr); sg = __fmaf_rn(wt, cc[ch][1], sg); sb = __fmaf_rn(wt, cc[ch][2], sb);
-                    if constexpr (behind_background<Up>) sa = add_rn(sa, wt);
+                    if constexpr (Up::BG) sa = add_rn(sa, wt);
                 } else {
                     depth = add_rn(depth, mul_rn(wt, tt[ch])); accw = add_rn(accw, wt);
                 }
@@ -229,14 +219,14 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
     if constexpr (Up::MSE) {
         sr = wave_total(sr); sg = wave_total(sg); sb = wave_total(sb);
         float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-        if constexpr (behind_background<Up>) {     // sr, sg, sb become rgb_bg: the loss's prediction and the rgb output
+        if constexpr (Up::BG) {     // sr, sg, sb become rgb_bg: the loss's prediction and the rgb output
             const float* bg = up.bg + ray * up.bg_stride;
             b0 = bg[0]; b1 = bg[1]; b2 = bg[2];
             const float through = sub_rn(1.0f, wave_total(sa));
             sr = add_rn(sr, mul_rn(through, b0)); sg = add_rn(sg, mul_rn(through, b1)); sb = add_rn(sb, mul_rn(through, b2));
         }
         [[maybe_unused]] float plain[3], gain[3];
-        if constexpr (behind_affine<Up>) {         // sr, sg, sb become c': the loss's prediction and the rgb output
+        if constexpr (Up::AFFINE) {         // sr, sg, sb become c': the loss's prediction and the rgb output
             const nerf_appearance::Row row = nerf_appearance::load_row(up.theta + ray * up.theta_stride);
             nerf_appearance::gains(row, gain);
             plain[0] = sr; plain[1] = sg; plain[2] = sb;
@@ -246,14 +236,14 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
         gr = mul_rn(mul_rn(2.0f, sub_rn(sr, up.target[ray * 3 + 0])), up.scale);
         gg = mul_rn(mul_rn(2.0f, sub_rn(sg, up.target[ray * 3 + 1])), up.scale);
         gb = mul_rn(mul_rn(2.0f, sub_rn(sb, up.target[ray * 3 + 2])), up.scale);
-        if constexpr (behind_affine<Up>) {         // the map's backward: the ray's row of g_theta, then g_rgb = g fl(1 + a)
+        if constexpr (Up::AFFINE) {         // the map's backward: the ray's row of g_theta, then g_rgb = g fl(1 + a)
             const float g[3] = {gr, gg, gb};
             float g_c[3], g_a[3];
             nerf_appearance::apply_backward(g, plain, gain, g_c, g_a);
             if (lane == 0) nerf_appearance::store_row(up.g_theta + ray * 6, g_a, g);
             gr = g_c[0]; gg = g_c[1]; gb = g_c[2];
         }
-        if constexpr (behind_background<Up>) gac = -add_rn(add_rn(mul_rn(gr, b0), mul_rn(gg, b1)), mul_rn(gb, b2));
+        if constexpr (Up::BG) gac = -add_rn(add_rn(mul_rn(gr, b0), mul_rn(gg, b1)), mul_rn(gb, b2));
         if (up.rgb_out && lane == 0) { up.rgb_out[ray * 3 + 0] = sr; up.rgb_out[ray * 3 + 1] = sg; up.rgb_out[ray * 3 + 2] = sb; }
     } else {
         depth = wave_sum(depth); accw = wave_sum(accw);
@@ -270,8 +260,8 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
         }
     }
     // the distortion term on the forward sweep's weights: its gradient to every w_i, and the ray's loss value
-    [[maybe_unused]] float gw[with_distortion<Up> ? CHUNKS : 1];
-    if constexpr (with_distortion<Up>) {
+    [[maybe_unused]] float gw[Up::DIST ? CHUNKS : 1];
+    if constexpr (Up::DIST) {
         float wv[CHUNKS];
 #pragma unroll
         for (int ch = 0; ch < CHUNKS; ++ch) wv[ch] = (ch * 64 + lane < N) ? mul_rn(al[ch], Tt[ch]) : 0.f;
@@ -290,8 +280,8 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
             float G = 0.f;
             if (valid) {
                 G = add_rn(add_rn(mul_rn(gr, cc[ch][0]), mul_rn(gg, cc[ch][1])), mul_rn(gb, cc[ch][2]));
-                if constexpr (behind_background<Up>) G = add_rn(G, gac);
-                if constexpr (with_distortion<Up>) G = add_rn(G, gw[ch]);
+                if constexpr (Up::BG) G = add_rn(G, gac);
+                if constexpr (Up::DIST) G = add_rn(G, gw[ch]);
                 if constexpr (!Up::MSE) {
                     G = add_rn(add_rn(G, mul_rn(gdep, tt[ch])), gac);
                     if (up.g_w) G = add_rn(G, up.g_w[ray * N + i]);

@@ -3,16 +3,13 @@
 // and a background colour behind the volume (white_bkgd elsewhere):
 //   sigma'  = sigma + std z                 in front of the softplus (sigma_noise_device.h)
 //   rgb_bg  = rgb + (1 - acc) bg            two rounded ops per channel, no fma: torch's fp32 expression gives the same bits
-// Three small stages (noise, blend, the blend's backward) and the training head, which is BY DEFINITION their composition
-// with the compositor, the MSE gradient and the compositor's backward, in one launch on composite_backward_ray.
-#include "composite_backward_device.h"
+// Three small stages (noise, blend, the blend's backward).  The training head is BY DEFINITION their composition with the
+// compositor, the MSE gradient and the compositor's backward, in one launch: dense_head_kernel<NOISE, BG, ..> (composite_head.hip).
+#include "composite_device.h"
 #include "launchers.h"
 #include "sigma_noise_device.h"
 
 namespace {
-
-constexpr int RAYS_PER_BLOCK = 4;
-constexpr int MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;          // N <= 512
 
 // ---- the stages ----------------------------------------------------------------------------------------------------------
 // raw[B,N,4] -> out[B,N,4] (out may be raw: every thread reads its own sample before it writes it): colours copied,
@@ -63,48 +60,6 @@ __global__ __launch_bounds__(256) void background_blend_backward_kernel(const fl
     g_acc[ray] = -add_rn(add_rn(mul_rn(g[ray * 3 + 0], b[0]), mul_rn(g[ray * 3 + 1], b[1])), mul_rn(g[ray * 3 + 2], b[2]));
 }
 
-// ---- the training head (its noisy sample source: sigma_noise_device.h NoisySamples) ---------------------------------------
-// NOISE: sigma' in front of the softplus; BG: the loss sits behind the blend.  (false, false) is composite_backward_kernel<0>
-// with the MSE head (composite.hip) and is not instantiated here.
-template <bool NOISE, bool BG>
-__global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_bg_head_kernel(
-    const float* __restrict__ raw, const float* __restrict__ ts, const float* __restrict__ rays,
-    const float* __restrict__ target, const float* __restrict__ bg, long long bg_stride, float std, unsigned long long seed,
-    const unsigned long long* __restrict__ seed_mem, long long ray_id0, float* __restrict__ rgb_out,
-    float* __restrict__ d_raw, long long B, int N, float scale) {
-    const long long ray = (long long)blockIdx.x * RAYS_PER_BLOCK + (threadIdx.x >> 6);
-    if (ray >= B) return;                      // whole wave leaves together; no barriers below
-    const int lane = threadIdx.x & 63;
-    f32x4* rout = reinterpret_cast<f32x4*>(d_raw) + ray * N;
-    if (N == 1) {
-        // the reference composites an EMPTY sample axis at N == 1 (composite_device.h): rgb = acc = 0, so rgb_bg = bg exactly
-        if (lane == 0) {
-            rout[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (rgb_out) {
-                for (int c = 0; c < 3; ++c) rgb_out[ray * 3 + c] = BG ? add_rn(0.f, mul_rn(sub_rn(1.0f, 0.f), bg[ray * bg_stride + c])) : 0.f;
-            }
-        }
-        return;
-    }
-    const float* d = rays + ray * 6 + 3;
-    const float dnorm = nerf_composite::unit_dir_norm(d[0], d[1], d[2], true);
-    const nerf_composite::DenseSamples dense{ts + ray * N, reinterpret_cast<const f32x4*>(raw) + ray * N};
-    auto run = [&](auto src) {
-        if constexpr (BG) {
-            nerf_composite::composite_backward_ray<MAX_CHUNKS>(src, nerf_composite::BgMseHead{target, rgb_out, scale, bg, bg_stride},
-                                                               nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
-        } else {
-            nerf_composite::composite_backward_ray<MAX_CHUNKS>(src, nerf_composite::MseHead{target, rgb_out, scale},
-                                                               nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
-        }
-    };
-    if constexpr (NOISE) {
-        run(nerf_noise::NoisySamples{dense, std, nerf_noise::noise_key(seed, seed_mem), (unsigned long long)((ray_id0 + ray) * N)});
-    } else {
-        run(dense);
-    }
-}
-
 inline dim3 per_element(long long n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
@@ -141,27 +96,5 @@ extern "C" int nerf_amd_launch_background_blend_backward(const float* g_rgb_bg, 
     (void)hipGetLastError();
     if (B == 0) return 0;
     hipLaunchKernelGGL(background_blend_backward_kernel, per_element(B), dim3(256), 0, stream, g_rgb_bg, bg, bg_stride, g_acc, B);
-    return (int)hipGetLastError();
-}
-
-// bg == NULL and std == 0: the plain head's launch itself (composite.hip)
-extern "C" int nerf_amd_launch_composite_mse_backward_bg(const float* raw, const float* ts, const float* rays,
-                                                         const float* target, const float* bg, long long bg_stride, float std,
-                                                         unsigned long long seed, const unsigned long long* seed_mem,
-                                                         long long ray_id0, float* rgb, float* d_raw, long long B, int N,
-                                                         hipStream_t stream) {
-    if (!bg && std == 0.f) return nerf_amd_launch_composite_mse_backward(raw, ts, rays, target, rgb, d_raw, B, N, stream);
-    (void)hipGetLastError();
-    if (B == 0) return 0;
-    if (N > nerf_layout::COMPOSITE_BWD_MAX_N) return -2;
-    const dim3 grid((unsigned)((B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
-    const float scale = 1.0f / (3.0f * (float)B);
-#define NERF_BG_HEAD(NOISE_, BG_)                                                                                          \
-    hipLaunchKernelGGL((composite_bg_head_kernel<NOISE_, BG_>), grid, block, 0, stream, raw, ts, rays, target, bg, bg_stride, \
-                       std, seed, seed_mem, ray_id0, rgb, d_raw, B, N, scale)
-    if (std == 0.f) NERF_BG_HEAD(false, true);
-    else if (!bg) NERF_BG_HEAD(true, false);
-    else NERF_BG_HEAD(true, true);
-#undef NERF_BG_HEAD
     return (int)hipGetLastError();
 }

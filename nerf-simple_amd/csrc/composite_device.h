@@ -15,6 +15,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// exclusive suffix sum over the 64 lanes (inclusive suffix sum, then shift down by one lane) and the wave's total
+__device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& total) {
+    float incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float dn = __shfl_down(incl, off);
+        if (lane + off < 64) incl = add_rn(incl, dn);
+    }
+    total = __shfl(incl, 0);
+    float ex = __shfl_down(incl, 1);
+    if (lane == 63) ex = 0.f;
+    return ex;
+}
+
 // Cross-lane moves as DPP modifiers (VALU speed) instead of ds_bpermute round trips through the LDS
 // crossbar: row_shr:n inside each row of 16 lanes, row_bcast:15 / row_bcast:31 between rows.  A lane
 // with no source (or in a row ROW_MASK leaves out) receives `idle`, the identity of the caller's op.

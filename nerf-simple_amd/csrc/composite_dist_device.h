@@ -1,6 +1,6 @@
 // composite_dist_device.h -- mip-NeRF 360's distortion loss of ONE ray's weights and its gradient to them, shared by
 // nerf_amd_distortion_loss (composite_dist.hip: t and w read from HBM) and the training head behind it
-// (composite_backward_ray with a DistMseHead: w straight from the forward sweep's registers).  With
+// (composite_backward_ray with a LossHead<.., DIST, ..>: w straight from the forward sweep's registers).  With
 //   delta_i = t_{i+1} - t_i (i < N - 1), delta_{N-1} = max(t_far - t_{N-1}, 0), m_i = t_i + delta_i / 2
 //   D        = 2 sum_i w_i sum_{j<i} w_j (m_i - m_j) + (1/3) sum_i w_i^2 delta_i
 //   dD/dw_i  = 2 [ sum_{j<i} w_j (m_i - m_j) + sum_{j>i} w_j (m_j - m_i) ] + (2/3) w_i delta_i
@@ -12,8 +12,6 @@
 // ONE wavefront per ray, one sample per lane, chunks of 64 walked forward once (prefix sums, carries between chunks) and
 // backward once (suffix sums); no atomics, no LDS, nothing crosses a wave.  Every floating-point operation is one explicitly
 // rounded op, as in composite_backward_device.h, so both callers write the same bits from the same t and w.
-//
-// Included by composite_backward_device.h behind wave_suffix_excl, which the backward sweep here uses; include that header.
 #pragma once
 #include "composite_device.h"
 

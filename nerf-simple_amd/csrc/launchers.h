@@ -10,6 +10,28 @@
 struct MlpArgs;          // nerf_device.h
 struct DensityArgs;
 
+// What the dense training head reads (composite_head.hip), filled by api.hip's three entry points.  A term's fields are
+// looked at only where the term is on: std != 0 (noise), bg != NULL, dist, theta != NULL (the affine map; with no other term).
+struct DenseHeadArgs {
+    const float *raw, *ts, *rays, *target;
+    float *rgb, *d_raw;                                // rgb [B,3] = the loss's prediction, or NULL
+    long long B;
+    int N;
+    float scale;                                       // 1 / (3 B): the launcher's
+    const float* bg;                                   // one colour (bg_stride 0) or one per ray (bg_stride 3)
+    long long bg_stride;
+    float std;                                         // noise on sigma: keyed by seed (+ *seed_mem), ray ids from ray_id0
+    unsigned long long seed;
+    const unsigned long long* seed_mem;
+    long long ray_id0;
+    bool dist;                                         // the distortion term (coef may be 0): t_far, coef, loss_ray [B] or NULL
+    float t_far, coef;
+    float* loss_ray;
+    const float* theta;                                // the affine map: rows [B,6] (theta_stride 6) or one row (theta_stride 0),
+    long long theta_stride;
+    float* g_theta;                                    // and every ray's row of d loss / d theta [B,6]
+};
+
 extern "C" {
 int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
 int nerf_amd_launch_pack_train(const float*, void*, void*, hipStream_t);
@@ -98,14 +120,9 @@ int nerf_amd_launch_sigma_noise(const float*, float*, float, unsigned long long,
 int nerf_amd_launch_background_blend(const float*, const float*, const float*, const float*, long long, float*, float*,
                                      long long, hipStream_t);
 int nerf_amd_launch_background_blend_backward(const float*, const float*, long long, float*, long long, hipStream_t);
-int nerf_amd_launch_composite_mse_backward_bg(const float*, const float*, const float*, const float*, const float*, long long,
-                                              float, unsigned long long, const unsigned long long*, long long, float*, float*,
-                                              long long, int, hipStream_t);
+int nerf_amd_launch_dense_head(const DenseHeadArgs*, hipStream_t);
 int nerf_amd_launch_distortion_loss(const float*, const float*, float, float, float*, float*, long long, int, hipStream_t);
 int nerf_amd_launch_sum_f32(const float*, float*, long long, hipStream_t);
-int nerf_amd_launch_composite_mse_backward_dist(const float*, const float*, const float*, const float*, const float*, long long,
-                                                float, unsigned long long, const unsigned long long*, long long, float, float,
-                                                float*, float*, float*, long long, int, hipStream_t);
 int nerf_amd_launch_camera_rays(const float*, const float*, const long long*, long long*, int, int, float, float*, long long,
                                 long long, hipStream_t);
 int nerf_amd_launch_camera_rays_backward(const float*, const float*, const long long*, const float*, int, int, float, float*,
@@ -121,6 +138,4 @@ int nerf_amd_launch_appearance_apply_backward(const float*, const float*, const 
                                               hipStream_t);
 int nerf_amd_launch_appearance_reduce(const float*, const long long*, long long, const float*, float, const int*, float*,
                                       long long, long long, hipStream_t);
-int nerf_amd_launch_composite_mse_backward_affine(const float*, const float*, const float*, const float*, const float*, long long,
-                                                  float*, float*, float*, long long, int, hipStream_t);
 }

@@ -1,6 +1,6 @@
 // sigma_noise_device.h -- the sigma-noise regulariser (the NeRF paper's raw_noise_std; the reference leaves it as
 // `## TODO add gaussian noise regularizer`, utils/rendering.py:63): sigma' = sigma + std z in front of the softplus, z a
-// standard normal from the counter RNG.  Written ONCE: nerf_amd_sigma_noise and the training head (composite_bg.hip) call
+// standard normal from the counter RNG.  Written ONCE: nerf_amd_sigma_noise and the training head (composite_head.hip) call
 // the routine below, so both write the same bits for the same (key, sample).
 //
 // Key: (noise_seed + the step's offset in memory) ^ NOISE_KEY -- the offset goes in front of the xor, as in the sampler's
@@ -45,9 +45,9 @@ __device__ __forceinline__ float noisy_sigma(float sigma, float std, unsigned lo
     return add_rn(sigma, mul_rn(std, standard_normal(key, sample)));
 }
 
-// DenseSamples with the routine above applied to sigma as a chunk is loaded, for the training heads (composite_bg.hip,
-// composite_dist.hip): the forward sweep keeps sigma'-derived values per chunk and the backward sweep reuses them, so each
-// sample's noise is generated once.
+// DenseSamples with the routine above applied to sigma as a chunk is loaded, for the training head (composite_head.hip):
+// the forward sweep keeps sigma'-derived values per chunk and the backward sweep reuses them, so each sample's noise is
+// generated once.
 struct NoisySamples {
     nerf_composite::DenseSamples dense;
     float std;

@@ -84,6 +84,16 @@ def mse_loss(pred, target):
 # --------------------------------------------------------------------------
 # compositor with a HIP backward
 # --------------------------------------------------------------------------
+def _five_outputs(B, N, dev):
+    """rgb [B,3], disp [B], alpha [B,N], acc [B], w [B,N]: the compositor's outputs, in its order"""
+    return tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((B, 3), (B,), (B, N), (B,), (B, N)))
+
+
+def _grad_arg(g):
+    """An upstream gradient as the backward kernels take it: fp32 contiguous, or None for a missing or empty one"""
+    return None if (g is None or g.numel() == 0) else g.contiguous().float()
+
+
 class _VolumeRender(torch.autograd.Function):
     """volume_render with the HIP backward.  ``from_rays``: ``dirs`` is the [B,6] ray table and the
     kernels normalise rays[:,3:] themselves (render_nerf, utils/rendering.py:37,43)."""
@@ -93,11 +103,7 @@ class _VolumeRender(torch.autograd.Function):
         B, N = raw.shape[0], raw.shape[1]
         dev = raw.device
         raw, ts, dirs = raw.contiguous(), ts.contiguous(), dirs.contiguous()
-        rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        disp = torch.empty((B,), dtype=torch.float32, device=dev)
-        acc = torch.empty((B,), dtype=torch.float32, device=dev)
-        alpha = torch.empty((B, N), dtype=torch.float32, device=dev)
-        w = torch.empty((B, N), dtype=torch.float32, device=dev)
+        rgb, disp, alpha, acc, w = _five_outputs(B, N, dev)
         lib = _lib.lib()
         with torch.cuda.device(dev):
             if from_rays:
@@ -122,10 +128,7 @@ class _VolumeRender(torch.autograd.Function):
         B, N = raw.shape[0], raw.shape[1]
         dev = raw.device
         d_raw = torch.empty_like(raw)
-
-        def c(g):
-            return None if (g is None or g.numel() == 0) else g.contiguous().float()
-        g_rgb, g_disp, g_alpha, g_acc, g_w = map(c, (g_rgb, g_disp, g_alpha, g_acc, g_w))
+        g_rgb, g_disp, g_alpha, g_acc, g_w = map(_grad_arg, (g_rgb, g_disp, g_alpha, g_acc, g_w))
         lib = _lib.lib()
         with torch.cuda.device(dev):
             if ctx.from_rays:
@@ -347,11 +350,7 @@ class _FusedDense(torch.autograd.Function):
         if watch is None:
             watch = net.__dict__["_watch"] = _StatusWatch()
             net.__dict__["_watch_calls"] = 0
-        bad = watch.poll()
-        if bad is not None:
-            what = " and ".join(w for w, on in (("activations", bad[1]), ("weights", bad[2])) if on)
-            raise FloatingPointError(f"non-finite values inside the network in training forward {bad[0]} ({what}): "
-                                     "NaN / inf weights or inputs, the run has diverged")
+        watch.raise_if_diverged("forward")
         packed = net.packed_weights(_lib.BF16)
         need_w = any(ctx.needs_input_grad[9:])
         need_in = ctx.needs_input_grad[1] or ctx.needs_input_grad[8]
@@ -483,11 +482,7 @@ class _MaskedVolumeRender(torch.autograd.Function):
         rays, jit, tbins, flags, seed, ray_id0, mask, offsets = head
         dev = rays.device
         raw_live = raw_live.contiguous()
-        rgb = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        disp = torch.empty((B,), dtype=torch.float32, device=dev)
-        acc = torch.empty((B,), dtype=torch.float32, device=dev)
-        alpha = torch.empty((B, N), dtype=torch.float32, device=dev)
-        w = torch.empty((B, N), dtype=torch.float32, device=dev)
+        rgb, disp, alpha, acc, w = _five_outputs(B, N, dev)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().nerf_amd_volume_render_masked(
                 _lib.ptr(raw_live) if raw_live.numel() else None, _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags,
@@ -505,10 +500,7 @@ class _MaskedVolumeRender(torch.autograd.Function):
         flags, seed, ray_id0, B, N = ctx.args
         dev = rays.device
         d_raw = torch.empty_like(raw_live)
-
-        def c(g):
-            return None if (g is None or g.numel() == 0) else g.contiguous().float()
-        g_rgb, g_disp, g_alpha, g_acc, g_w = map(c, (g_rgb, g_disp, g_alpha, g_acc, g_w))
+        g_rgb, g_disp, g_alpha, g_acc, g_w = map(_grad_arg, (g_rgb, g_disp, g_alpha, g_acc, g_w))
         live = raw_live.numel() > 0
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().nerf_amd_volume_render_masked_backward(
@@ -603,6 +595,19 @@ def lr_decay_factor(lr_init, lr_final, num_iters):
     return math.exp(math.log(lr_final / lr_init) / num_iters)
 
 
+def _optimise(loss, params, optimizer, decay, group):
+    """The tail of an eager optimisation step (train.py:53-57): backward, the gradients averaged over ``group``, the
+    optimizer's step, the learning-rate decay.  Returns the detached loss."""
+    from . import parallel
+    loss.backward()
+    parallel.allreduce_gradients(params, group=group)
+    optimizer.step()
+    if decay != 1.0:
+        for pg in optimizer.param_groups:
+            pg["lr"] = pg["lr"] * decay
+    return loss.detach()
+
+
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, background=None, sigma_noise=0.0,
                noise_seed=0, distortion=0.0):
@@ -621,7 +626,6 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     through the HIP backward (bf16 fused, precision='fp32', other sizes) and together with background / sigma_noise.  Dense
     path only (RuntimeError with ``occupancy``); negative or not finite: ValueError.  The returned loss is the total; with
     lambda > 0 ``.distortion`` on it holds the weighted term."""
-    from . import parallel
     from .utils.rendering import render_nerf, _refuse_controls
     lam = _check_distortion(distortion)
     _refuse_distortion(lam, occupancy=occupancy)
@@ -643,13 +647,7 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     if lam > 0:
         term = _distortion_term(w, getattr(w, "ts", None), lam, tn, tf)
         loss = loss + term
-    loss.backward()
-    parallel.allreduce_gradients(net.parameters(), group=group)
-    optimizer.step()
-    if decay != 1.0:
-        for pg in optimizer.param_groups:
-            pg["lr"] = pg["lr"] * decay
-    out = loss.detach()
+    out = _optimise(loss, net.parameters(), optimizer, decay, group)
     if term is not None:
         out.distortion = term.detach()
     return out
@@ -720,7 +718,6 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     synchronisations per step (one live count per pass); ``occupancy.last_stats`` holds the sums and the two passes'
     own reports under 'coarse' / 'fine'.  The default network and the bf16 training kernels only, rays without
     requires_grad; refused before any jitter is drawn."""
-    from . import parallel
     from .optim import FusedAdam
     from .utils.host_rng import reference_rand
     from .utils.rendering import render_nerf, sample_pdf
@@ -777,13 +774,7 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     loss_c = mse_loss(coarse[0], gt)
     loss_f = mse_loss(fine[0], gt)
     loss = loss_c + loss_f
-    loss.backward()
-    parallel.allreduce_gradients(params, group=group)
-    optimizer.step()
-    if decay != 1.0:
-        for pg in optimizer.param_groups:
-            pg["lr"] = pg["lr"] * decay
-    out = loss.detach()
+    out = _optimise(loss, params, optimizer, decay, group)
     out.losses, out.ts_f = [loss_c.detach(), loss_f.detach()], ts_f
     return out
 
@@ -821,7 +812,6 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
 
     distortion: ``train_step``'s -- the loss becomes MSE + lambda / (B (tf - tn)) sum_rays D on the Nc + Nf guided positions.
     Not with ``occupancy`` (RuntimeError before anything is drawn)."""
-    from . import parallel
     lam = _check_distortion(distortion)
     _refuse_distortion(lam, occupancy=occupancy)
     _check_guided(net, proposal, precision)
@@ -847,13 +837,7 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
     if lam > 0:
         term = _distortion_term(outs[4], ts, lam, tn, tf)
         loss = loss + term
-    loss.backward()
-    parallel.allreduce_gradients(net.parameters(), group=group)
-    optimizer.step()
-    if decay != 1.0:
-        for pg in optimizer.param_groups:
-            pg["lr"] = pg["lr"] * decay
-    out = loss.detach()
+    out = _optimise(loss, net.parameters(), optimizer, decay, group)
     out.ts = ts
     if term is not None:
         out.distortion = term.detach()
@@ -941,6 +925,14 @@ class _StatusWatch:
             if hit is None and (words[0] != 0 or words[1] != 0):
                 hit = (step, words[0] != 0, words[1] != 0)
         return hit
+
+    def raise_if_diverged(self, unit):
+        """FloatingPointError once a completed sample shows a flag; ``unit`` names what the sample's number counts."""
+        bad = self.poll()
+        if bad is not None:
+            what = " and ".join(w for w, on in (("activations", bad[1]), ("weights", bad[2])) if on)
+            raise FloatingPointError(f"non-finite values inside the network in training {unit} {bad[0]} ({what}): "
+                                     "NaN / inf weights or inputs, the run has diverged")
 
 
 class _CountsWatch:
@@ -1225,6 +1217,7 @@ class GraphedTrainStep:
     _samples = None              # samples per ray of each pass; None: the one pass of N samples
     _capacities = None           # point capacity of each pass (masked passes through ``occupancy``); None: dense passes
     _one_bucket = False          # the two-bucket exchange exists for the dense single step only
+    _dense_pass_type = _DensePass        # what a dense pass is: the plain one, or one with more behind its head / dX chain
     _masked_pass_type = _MaskedPass      # what a masked pass is: with its own mark, or behind a launch that marks (_MarkedPass)
 
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
@@ -1348,7 +1341,7 @@ class GraphedTrainStep:
             self.passes = [self._masked_pass_type(self, N_, C, self._counts[2 * k:2 * k + 2])
                            for k, (N_, C) in enumerate(zip(samples, self._capacities))]
         else:
-            self.passes = [_DensePass(self, N_, self._e4m3) for N_ in samples]
+            self.passes = [self._dense_pass_type(self, N_, self._e4m3) for N_ in samples]
         # the stratified pass: the buffer, or the counter RNG with this step's seed offset read from device memory
         if self.device_rng:
             jitter = (ptr(self.rays), self._seed_mem, ptr(self.tbins), _lib.FLAG_DEVICE_RNG | _lib.FLAG_SEED_IN_MEMORY,
@@ -1358,8 +1351,7 @@ class GraphedTrainStep:
         self.passes[0].jitter = jitter
         if pair:
             Nc, Nf = samples[0], samples[1] - samples[0]
-            flat_u = self.u.view(-1)
-            self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, Nf)
+            self._split_u(Nc, Nf)                   # a pair is a _PairJitter stepper
             self.losses = torch.zeros(2, dtype=torch.float32, device=dev)
             self.ts_f = torch.empty((B, samples[1]), dtype=torch.float32, device=dev)     # the coarse head's output:
             self.passes[1].jitter = (ptr(self.rays), ptr(self.ts_f), None, _lib.FLAG_TS_GIVEN, 0, 0)   # the fine positions
@@ -1581,11 +1573,7 @@ class GraphedTrainStep:
             raise RuntimeError("step() without rays needs GraphedTrainStep(..., rays_from=<utils.dataload.RayGenerator>)")
         if rays is not None and (rays.shape != self.rays.shape or gt.shape != self.gt.shape):
             raise RuntimeError(f"GraphedTrainStep was captured for rays {tuple(self.rays.shape)}, gt {tuple(self.gt.shape)}")
-        bad = self._watch.poll()
-        if bad is not None:
-            what = " and ".join(w for w, on in (("activations", bad[1]), ("weights", bad[2])) if on)
-            raise FloatingPointError(f"non-finite values inside the network in training step {bad[0]} ({what}): "
-                                     "NaN / inf weights or inputs, the run has diverged")
+        self._watch.raise_if_diverged("step")
         self._own_images()
         if rays is None and self.device_rng and self._primed_for != self.opt.step_count + 1:
             # the first step (or one after the step counter was moved by hand): the graph prefetches batch k + 1 while
@@ -1710,6 +1698,100 @@ class GraphedTrainStep:
         return span, exposed
 
 
+class _TableAdam:
+    """The optimiser of a per-image table (``table`` [M,6]) trained beside the network inside the captured graph: an Adam of
+    its own -- nerf_amd_adam_step_hyper on (table, ``grad``) -- with scalars of its own, fed through a ring of its own.
+    The kernel reads its betas as fp32 and forms 1 - beta from them: ``betas`` are held rounded to fp32 and the bias
+    corrections are formed from the same rounded values, so the update is Adam's for exactly the betas held here."""
+
+    def __init__(self, table, lr, betas, eps):
+        self.table, self.lr, self.eps, self.steps = table, float(lr), float(eps), 0
+        self.betas = tuple(float(torch.tensor(float(b), dtype=torch.float32)) for b in betas)
+        self.grad = torch.zeros_like(table, requires_grad=False)
+        self.m, self.v = torch.zeros_like(self.grad), torch.zeros_like(self.grad)
+        self.hyper, self.ring = torch.zeros(8, dtype=torch.float32, device=table.device), _HyperRing(table.device)
+
+    def push(self):
+        t, (b1, b2) = self.steps + 1, self.betas
+        self.ring.push((self.lr, b1, b2, self.eps, 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5))
+
+    def update(self):
+        ptr = _lib.ptr
+        _launch("nerf_amd_adam_step_hyper", ptr(self.table), ptr(self.grad), ptr(self.m), ptr(self.v), self.table.numel(),
+                ptr(self.hyper), _lib.stream_ptr(self.table.device))
+
+
+def _table_adam_attr(name):
+    """A stepper's public name for a field of its table's optimiser (``camera_lr`` = ``_adam2.lr``, assignable)."""
+    return property(lambda self: getattr(self._adam2, name), lambda self, value: setattr(self._adam2, name, value))
+
+
+class _TableTrainStep(GraphedTrainStep):
+    """What the steppers with a per-image table share.  The table (``_table``: its attribute of the object the stepper is
+    given) is trained by ``_adam2`` (a _TableAdam) inside the captured graph, its images are the images of ``rays_from``'s
+    table, and the stepper's first launch keeps the ids a step ran on in ``_ids_used``.  ``_words``: what differs between
+    the steppers' messages (``spans`` is formatted with the object); ``_baked_now()``: the addresses the graph holds."""
+
+    def _bind_table(self, obj, kind, optimizer, n_rays, rays_from, select_mode, group, controls, lr, betas, eps):
+        """The refusals the table steppers share, in their order, before any launch or RNG draw; then the table's optimiser."""
+        from . import parallel
+        name, w = type(self).__name__, self._words
+        if controls[0] is not None or controls[1] or controls[2]:
+            raise RuntimeError(f"{name} does not take background / sigma_noise / distortion yet")
+        if parallel.collectives_active(group):
+            raise RuntimeError(f"{name} trains on one replica: the {w['gradient']} gradient has no exchange yet")
+        if not isinstance(obj, kind):
+            raise RuntimeError(w["type"])
+        if rays_from is None:
+            raise RuntimeError(f"{name} {w['why']} the ids of a selection: rays_from=<RayGenerator> is required")
+        if select_mode not in rays_from.colours:
+            raise RuntimeError(f"rays_from has no colour table for mode {select_mode!r}")
+        rows, table = int(rays_from.rays_dataset[select_mode].shape[0]), getattr(obj, self._table)
+        if rows != obj.n_rays:
+            raise RuntimeError(f"the table of rays_from holds {rows} rays, {w['spans'].format(obj)} = {obj.n_rays}")
+        if table.device != optimizer.flat.device:
+            raise RuntimeError(f"{w['lives']} on {table.device}, the module on {optimizer.flat.device}")
+        self._adam2 = _TableAdam(table, lr, betas, eps)
+        self._ids_used = torch.zeros((int(n_rays),), dtype=torch.int64, device=table.device)
+
+    @property
+    def ray_ids(self):
+        """Rows of the table the LAST step trained on: the copy the stepper's first launch kept."""
+        return self._ids_used
+
+    def _before_forward(self, st):
+        """The table's scalars behind the step's own; the subclass's first launch follows."""
+        self._adam2.ring.fetch(self._adam2.hyper, self.dev)
+
+    def _set_hyper(self, step):
+        super()._set_hyper(step)
+        self._adam2.push()
+
+    def _update(self):
+        super()._update()
+        self._adam2.update()
+
+    def _capture(self):
+        super()._capture()
+        self._adam2.ring.reset()                     # the warm-up consumed a slot
+
+    def _enqueue_step(self, decay):
+        loss = super()._enqueue_step(decay)
+        self._adam2.ring.launched(self.dev)
+        self._adam2.steps += 1
+        return loss
+
+    def _table_step(self, rays, gt, u, decay, table_decay):
+        name, w = type(self).__name__, self._words
+        if rays is not None or gt is not None:
+            raise RuntimeError(f"{name} {w['why']} the selected ids: step() takes no rays")
+        if self._baked_now() != self._baked:
+            raise RuntimeError(f"{w['baked']} replaced: baked into the captured graph (write in place, or build a new {name})")
+        loss = super().step(None, None, u=u, decay=decay)
+        self._adam2.lr *= float(table_decay)
+        return loss
+
+
 class _IdsOnlySelection:
     """``rays_from`` as GraphedCameraTrainStep hands it to its base: every selection still writes the colours and the ids, and
     no rays (nerf_amd_select_rays with rays_out = NULL) -- the stepper forms them itself, from the ids and its cameras."""
@@ -1737,7 +1819,7 @@ class _CameraPass(_DensePass):
         s.cameras._launch_backward(s.cameras.xi, s._ids_used, s.d_rays, s.camera_grad, stream=st)
 
 
-class GraphedCameraTrainStep(GraphedTrainStep):
+class GraphedCameraTrainStep(_TableTrainStep):
     """GraphedTrainStep with a camera optimiser inside the captured graph: the rays of every step are
     formed on the device from ``cameras`` (``utils.cameras.CameraRefinement``: stored poses and the learnable corrections
     ``cameras.xi`` [M,6]) and the ids the selection left, and ``xi`` is trained beside the network by an Adam of its own.
@@ -1762,90 +1844,39 @@ class GraphedCameraTrainStep(GraphedTrainStep):
     ``background`` / ``sigma_noise`` / ``distortion``."""
 
     _one_bucket = True
+    _dense_pass_type = _CameraPass               # the dense pass and its buffers, the pose gradient behind its dX chain
+    _table = "xi"
+    _words = dict(gradient="camera", type="cameras must be a utils.cameras.CameraRefinement", why="forms its rays from",
+                  spans="the cameras span {0.M} x {0.H} x {0.W}", lives="the cameras live",
+                  baked="cameras.xi or the stored poses were")
+    camera_lr, camera_betas, camera_eps, camera_steps, camera_grad = map(_table_adam_attr, ("lr", "betas", "eps", "steps", "grad"))
 
     def __init__(self, net, optimizer, n_rays, N, cameras, *, rays_from=None, camera_lr=1e-3, camera_betas=(0.9, 0.999),
                  camera_eps=1e-8, select_mode="train", group=None, buckets=1, storage="bf16", background=None, sigma_noise=0.0,
                  distortion=0.0, **kw):
-        from . import parallel
         from .utils.cameras import CameraRefinement
         if storage != "bf16":
             raise RuntimeError("GraphedCameraTrainStep: storage='e4m3' is not served (nerf_amd_input_gradients reads bf16 dY)")
         if buckets != 1:
             raise RuntimeError("GraphedCameraTrainStep: one exchange bucket only (buckets=1)")
-        if background is not None or sigma_noise or distortion:
-            raise RuntimeError("GraphedCameraTrainStep does not take background / sigma_noise / distortion yet")
-        if parallel.collectives_active(group):
-            raise RuntimeError("GraphedCameraTrainStep trains on one replica: the camera gradient has no exchange yet")
-        if not isinstance(cameras, CameraRefinement):
-            raise RuntimeError("cameras must be a utils.cameras.CameraRefinement")
-        if rays_from is None:
-            raise RuntimeError("GraphedCameraTrainStep forms its rays from the ids of a selection: rays_from=<RayGenerator> is required")
-        if select_mode not in rays_from.colours:
-            raise RuntimeError(f"rays_from has no colour table for mode {select_mode!r}")
-        if int(rays_from.rays_dataset[select_mode].shape[0]) != cameras.n_rays:
-            raise RuntimeError(f"the table of rays_from holds {int(rays_from.rays_dataset[select_mode].shape[0])} rays, the cameras "
-                               f"span {cameras.M} x {cameras.H} x {cameras.W} = {cameras.n_rays}")
-        if cameras.xi.device != optimizer.flat.device:
-            raise RuntimeError(f"the cameras live on {cameras.xi.device}, the module on {optimizer.flat.device}")
-        self.cameras, self._camera_ptrs = cameras, (cameras.xi.data_ptr(), cameras.poses0.data_ptr())
-        # the kernel reads its betas as fp32 and forms 1 - beta from them: the bias corrections are formed from the same
-        # rounded values (_set_hyper), so the update is Adam's for exactly the betas held here
-        self.camera_lr, self.camera_eps = float(camera_lr), float(camera_eps)
-        self.camera_betas = tuple(float(torch.tensor(float(b), dtype=torch.float32)) for b in camera_betas)
-        self.camera_steps = 0
-        dev = cameras.xi.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.camera_grad = torch.zeros_like(cameras.xi, requires_grad=False)
-        self._cam_m, self._cam_v = torch.zeros_like(self.camera_grad), torch.zeros_like(self.camera_grad)
-        self._cam_hyper, self._cam_ring = torch.zeros(8, **f32), _HyperRing(dev)
+        self._bind_table(cameras, CameraRefinement, optimizer, n_rays, rays_from, select_mode, group,
+                         (background, sigma_noise, distortion), camera_lr, camera_betas, camera_eps)
+        self.cameras = cameras
+        self._baked = self._baked_now()
+        f32 = dict(dtype=torch.float32, device=cameras.xi.device)
         self.d_rays = torch.zeros((int(n_rays), 6), **f32)
         self._dv = torch.empty((int(n_rays) * int(N), 6), **f32)
-        self._ids_used = torch.zeros((int(n_rays),), dtype=torch.int64, device=dev)
         super().__init__(net, optimizer, n_rays, N, rays_from=_IdsOnlySelection(rays_from), select_mode=select_mode, group=group, **kw)
 
-    def _alloc_pass_buffers(self, tn, tf):
-        super()._alloc_pass_buffers(tn, tf)
-        self.passes[0].__class__ = _CameraPass       # the base's dense pass and its buffers, the pose gradient behind its dX chain
+    def _baked_now(self):
+        return self.cameras.xi.data_ptr(), self.cameras.poses0.data_ptr()
 
     def _before_forward(self, st):
-        self._cam_ring.fetch(self._cam_hyper, self.dev)
+        super()._before_forward(st)
         self.cameras._launch_rays(self.cameras.xi, self._ids_next, self._ids_used, self.rays, stream=st)
 
-    @property
-    def ray_ids(self):
-        """Rows of the table the LAST step trained on: the copy the camera rays kernel kept."""
-        return self._ids_used
-
-    def _set_hyper(self, step):
-        super()._set_hyper(step)
-        t, (b1, b2) = self.camera_steps + 1, self.camera_betas
-        self._cam_ring.push((self.camera_lr, b1, b2, self.camera_eps, 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5))
-
-    def _update(self):
-        super()._update()
-        ptr, xi = _lib.ptr, self.cameras.xi
-        _launch("nerf_amd_adam_step_hyper", ptr(xi), ptr(self.camera_grad), ptr(self._cam_m), ptr(self._cam_v), xi.numel(),
-                ptr(self._cam_hyper), _lib.stream_ptr(self.dev))
-
-    def _capture(self):
-        super()._capture()
-        self._cam_ring.reset()                       # the warm-up consumed a slot
-
-    def _enqueue_step(self, decay):
-        loss = super()._enqueue_step(decay)
-        self._cam_ring.launched(self.dev)
-        self.camera_steps += 1
-        return loss
-
     def step(self, rays=None, gt=None, u=None, decay=1.0, camera_decay=1.0):
-        if rays is not None or gt is not None:
-            raise RuntimeError("GraphedCameraTrainStep forms its rays from its cameras and the selected ids: step() takes no rays")
-        if (self.cameras.xi.data_ptr(), self.cameras.poses0.data_ptr()) != self._camera_ptrs:
-            raise RuntimeError("cameras.xi or the stored poses were replaced: their addresses are baked into the captured graph "
-                               "(write them in place, or build a new GraphedCameraTrainStep)")
-        loss = super().step(None, None, u=u, decay=decay)
-        self.camera_lr *= float(camera_decay)
-        return loss
+        return self._table_step(rays, gt, u, decay, camera_decay)
 
     __call__ = step
 
@@ -1875,7 +1906,7 @@ class _AppearancePass(_DensePass):
             self._reduce(st)
 
 
-class GraphedAppearanceTrainStep(GraphedTrainStep):
+class GraphedAppearanceTrainStep(_TableTrainStep):
     """GraphedTrainStep with a per-image colour correction inside the captured graph: the loss of every
     step is ``MSELoss((1 + a) rgb + b, gt)`` with the row (a, b) of each ray's image (``appearance``: a
     ``utils.appearance.AppearanceCorrection``, ``appearance.theta`` [M,6]), and ``theta`` is trained beside the network by an
@@ -1901,86 +1932,36 @@ class GraphedAppearanceTrainStep(GraphedTrainStep):
     that lives on another device.  The masked, hierarchical, guided and camera steppers do not take a correction."""
 
     _reduce_behind = "dx"        # where the reduction sits on the main branch: behind the "dx" chain or behind the "head"
+    _dense_pass_type = _AppearancePass           # the dense pass and its buffers, the loss behind the correction
+    _table = "theta"
+    _words = dict(gradient="appearance", type="appearance must be a utils.appearance.AppearanceCorrection",
+                  why="finds a ray's image from", spans="the correction spans {0.M} x {0.HW}", lives="the correction lives",
+                  baked="appearance.theta was")
+    appearance_lr, appearance_betas, appearance_eps, appearance_steps, appearance_grad = map(
+        _table_adam_attr, ("lr", "betas", "eps", "steps", "grad"))
 
     def __init__(self, net, optimizer, n_rays, N, appearance, *, rays_from, appearance_lr=1e-3, appearance_betas=(0.9, 0.999),
                  appearance_eps=1e-8, select_mode="train", group=None, **kw):
-        from . import parallel
         from .utils.appearance import AppearanceCorrection
-        if kw.get("background") is not None or kw.get("sigma_noise") or kw.get("distortion"):
-            raise RuntimeError("GraphedAppearanceTrainStep does not take background / sigma_noise / distortion yet")
-        if parallel.collectives_active(group):
-            raise RuntimeError("GraphedAppearanceTrainStep trains on one replica: the appearance gradient has no exchange yet")
-        if not isinstance(appearance, AppearanceCorrection):
-            raise RuntimeError("appearance must be a utils.appearance.AppearanceCorrection")
-        if rays_from is None:
-            raise RuntimeError("GraphedAppearanceTrainStep finds a ray's image from the ids of a selection: "
-                               "rays_from=<RayGenerator> is required")
-        if select_mode not in rays_from.colours:
-            raise RuntimeError(f"rays_from has no colour table for mode {select_mode!r}")
-        if int(rays_from.rays_dataset[select_mode].shape[0]) != appearance.n_rays:
-            raise RuntimeError(f"the table of rays_from holds {int(rays_from.rays_dataset[select_mode].shape[0])} rays, the "
-                               f"correction spans {appearance.M} x {appearance.HW} = {appearance.n_rays}")
-        if appearance.theta.device != optimizer.flat.device:
-            raise RuntimeError(f"the correction lives on {appearance.theta.device}, the module on {optimizer.flat.device}")
-        self.appearance, self._theta_ptr = appearance, appearance.theta.data_ptr()
-        # the kernel reads its betas as fp32 and forms 1 - beta from them: the bias corrections are formed from the same
-        # rounded values (_set_hyper), so the update is Adam's for exactly the betas held here
-        self.appearance_lr, self.appearance_eps = float(appearance_lr), float(appearance_eps)
-        self.appearance_betas = tuple(float(torch.tensor(float(b), dtype=torch.float32)) for b in appearance_betas)
-        self.appearance_steps = 0
-        dev = appearance.theta.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.appearance_grad = torch.zeros_like(appearance.theta, requires_grad=False)
-        self._app_m, self._app_v = torch.zeros_like(self.appearance_grad), torch.zeros_like(self.appearance_grad)
-        self._app_hyper, self._app_ring = torch.zeros(8, **f32), _HyperRing(dev)
+        self._bind_table(appearance, AppearanceCorrection, optimizer, n_rays, rays_from, select_mode, group,
+                         (kw.get("background"), kw.get("sigma_noise"), kw.get("distortion")), appearance_lr, appearance_betas,
+                         appearance_eps)
+        self.appearance = appearance
+        self._baked = self._baked_now()
+        f32 = dict(dtype=torch.float32, device=appearance.theta.device)
         self._theta_ray, self._g_theta_ray = torch.zeros((int(n_rays), 6), **f32), torch.zeros((int(n_rays), 6), **f32)
-        self._ids_used = torch.zeros((int(n_rays),), dtype=torch.int64, device=dev)
         super().__init__(net, optimizer, n_rays, N, rays_from=rays_from, select_mode=select_mode, group=group, **kw)
 
-    def _alloc_pass_buffers(self, tn, tf):
-        super()._alloc_pass_buffers(tn, tf)
-        self.passes[0].__class__ = _AppearancePass   # the base's dense pass and its buffers, the loss behind the correction
+    def _baked_now(self):
+        return self.appearance.theta.data_ptr()
 
     def _before_forward(self, st):
         a = self.appearance
-        self._app_ring.fetch(self._app_hyper, self.dev)
+        super()._before_forward(st)
         a._launch("nerf_amd_appearance_gather", a.theta, self._ids_next, self._ids_used, a.HW, self._theta_ray, self.B, a.M, stream=st)
 
-    @property
-    def ray_ids(self):
-        """Rows of the table the LAST step trained on: the copy the gather kept."""
-        return self._ids_used
-
-    def _set_hyper(self, step):
-        super()._set_hyper(step)
-        t, (b1, b2) = self.appearance_steps + 1, self.appearance_betas
-        self._app_ring.push((self.appearance_lr, b1, b2, self.appearance_eps, 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5))
-
-    def _update(self):
-        super()._update()
-        ptr, theta = _lib.ptr, self.appearance.theta
-        _launch("nerf_amd_adam_step_hyper", ptr(theta), ptr(self.appearance_grad), ptr(self._app_m), ptr(self._app_v),
-                theta.numel(), ptr(self._app_hyper), _lib.stream_ptr(self.dev))
-
-    def _capture(self):
-        super()._capture()
-        self._app_ring.reset()                       # the warm-up consumed a slot
-
-    def _enqueue_step(self, decay):
-        loss = super()._enqueue_step(decay)
-        self._app_ring.launched(self.dev)
-        self.appearance_steps += 1
-        return loss
-
     def step(self, rays=None, gt=None, u=None, decay=1.0, appearance_decay=1.0):
-        if rays is not None or gt is not None:
-            raise RuntimeError("GraphedAppearanceTrainStep finds a ray's image from the selected ids: step() takes no rays")
-        if self.appearance.theta.data_ptr() != self._theta_ptr:
-            raise RuntimeError("appearance.theta was replaced: its address is baked into the captured graph "
-                               "(write it in place, or build a new GraphedAppearanceTrainStep)")
-        loss = super().step(None, None, u=u, decay=decay)
-        self.appearance_lr *= float(appearance_decay)
-        return loss
+        return self._table_step(rays, gt, u, decay, appearance_decay)
 
     __call__ = step
 
@@ -2111,7 +2092,34 @@ class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
     __call__ = step
 
 
-class GraphedHierarchicalTrainStep(GraphedTrainStep):
+class _PairJitter:
+    """The jitter of a stepper that draws coarse and fine positions (listed in front of its stepper base): ``u`` [B, Nc+Nf] of
+    the reference stream as two views -- its first B*Nc values are torch.rand(B,Nc) = ``u_c``, the rest torch.rand(B,Nf) =
+    ``u_f``, the same numbers as the two draws in a row -- and ``step(..., u_c=, u_f=)``."""
+
+    def _split_u(self, Nc, Nf):
+        flat_u, B = self.u.view(-1), self.B
+        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, Nf)
+
+    def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
+        if (u_c is None) != (u_f is None):
+            raise RuntimeError("step(): u_c and u_f come together (or neither)")
+        u = None
+        if u_c is not None:
+            if tuple(u_c.shape) != tuple(self.u_c.shape) or tuple(u_f.shape) != tuple(self.u_f.shape):
+                raise RuntimeError(f"u_c / u_f must be {tuple(self.u_c.shape)} / {tuple(self.u_f.shape)}")
+            if self.device_rng:
+                raise RuntimeError(f"this {type(self).__name__} draws its jitter on the device (device_rng=True): "
+                                   "u_c / u_f must be None")
+            self.u_c.copy_(u_c, non_blocking=True)
+            self.u_f.copy_(u_f, non_blocking=True)
+            u = self.u
+        return super().step(rays, gt, u=u, decay=decay)
+
+    __call__ = step
+
+
+class GraphedHierarchicalTrainStep(_PairJitter, GraphedTrainStep):
     """``train_step_hierarchical`` for the fused bf16 path as captured hipGraphs: GraphedTrainStep with two dense passes,
     coarse and fine (hyper ring, status watch, ``rays_from`` selection in both jitter modes, exchange, capture: inherited):
 
@@ -2150,24 +2158,6 @@ class GraphedHierarchicalTrainStep(GraphedTrainStep):
         if optimizer.nets is None or len(optimizer.nets) != 2 or optimizer.nets[0] is not net[0] or optimizer.nets[1] is not net[1]:
             raise RuntimeError("the optimizer is not FusedAdam([net_c, net_f]) of this pair")
         _check_fused_trainable(net[0].precision)
-
-    def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
-        if (u_c is None) != (u_f is None):
-            raise RuntimeError("step(): u_c and u_f come together (or neither)")
-        u = None
-        if u_c is not None:
-            if tuple(u_c.shape) != tuple(self.u_c.shape) or tuple(u_f.shape) != tuple(self.u_f.shape):
-                raise RuntimeError(f"u_c / u_f must be {tuple(self.u_c.shape)} / {tuple(self.u_f.shape)}")
-            if self.device_rng:
-                raise RuntimeError("this GraphedHierarchicalTrainStep draws its jitter on the device (device_rng=True): "
-                                   "u_c / u_f must be None")
-            self.u_c.copy_(u_c, non_blocking=True)
-            self.u_f.copy_(u_f, non_blocking=True)
-            u = self.u
-        return super().step(rays, gt, u=u, decay=decay)
-
-    __call__ = step
-
 
 class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainStep):
     """``train_step_hierarchical(..., occupancy=)`` as captured hipGraphs: GraphedHierarchicalTrainStep's
@@ -2215,7 +2205,7 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
     __call__ = step
 
 
-class GraphedGuidedTrainStep(GraphedTrainStep):
+class GraphedGuidedTrainStep(_PairJitter, GraphedTrainStep):
     """``train_step_guided`` as captured hipGraphs: GraphedTrainStep with its one dense pass at
     N = Nc + Nf under NERF_AMD_TS_GIVEN, and ONE more node in graph A:
 
@@ -2251,14 +2241,12 @@ class GraphedGuidedTrainStep(GraphedTrainStep):
                          ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode, distortion=lam)
 
     def _alloc_pass_buffers(self, tn, tf):
-        """The dense pass reads given positions: ``ts_f``, which the sampler writes.  ``u`` [B, Nc+Nf] of the reference
-        stream is the pair's: its first B*Nc values are torch.rand(B,Nc) = ``u_c``, the rest torch.rand(B,Nf) = ``u_f``."""
+        """The dense pass reads given positions: ``ts_f``, which the sampler writes.  ``u`` is split as a pair's."""
         from .utils.rendering import _tbins
         super()._alloc_pass_buffers(tn, tf)
         ptr, B, Nc, Nf, dev = _lib.ptr, self.B, self.Nc, self.Nf, self.dev
         self.tbins = _tbins(tn, tf, Nc, dev)                        # of the COARSE positions, the only ones drawn from bins
-        flat_u = self.u.view(-1)
-        self.u_c, self.u_f = flat_u[:B * Nc].view(B, Nc), flat_u[B * Nc:].view(B, Nf)
+        self._split_u(Nc, Nf)
         self.ts_f = torch.empty((B, Nc + Nf), dtype=torch.float32, device=dev)
         if self.device_rng:
             self._coarse_jitter = (ptr(self.rays), self._seed_mem, ptr(self.tbins),
@@ -2284,19 +2272,7 @@ class GraphedGuidedTrainStep(GraphedTrainStep):
         if self.proposal.sigma.data_ptr() != self._sigma_ptr:
             raise RuntimeError("the proposal's sigma tensor was replaced: its address is baked into the captured graph "
                                "(ProposalVolume.update writes in place); build a new GraphedGuidedTrainStep")
-        if (u_c is None) != (u_f is None):
-            raise RuntimeError("step(): u_c and u_f come together (or neither)")
-        u = None
-        if u_c is not None:
-            if tuple(u_c.shape) != tuple(self.u_c.shape) or tuple(u_f.shape) != tuple(self.u_f.shape):
-                raise RuntimeError(f"u_c / u_f must be {tuple(self.u_c.shape)} / {tuple(self.u_f.shape)}")
-            if self.device_rng:
-                raise RuntimeError("this GraphedGuidedTrainStep draws its jitter on the device (device_rng=True): "
-                                   "u_c / u_f must be None")
-            self.u_c.copy_(u_c, non_blocking=True)
-            self.u_f.copy_(u_f, non_blocking=True)
-            u = self.u
-        return super().step(rays, gt, u=u, decay=decay)
+        return super().step(rays, gt, u_c=u_c, u_f=u_f, decay=decay)
 
     __call__ = step
 

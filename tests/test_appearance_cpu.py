@@ -111,10 +111,11 @@ def test_exports_header_and_ctypes_agree(lib):
     csrc = os.path.join(ROOT, "nerf-simple_amd", "csrc")
     assert "apply_backward" in open(os.path.join(csrc, "appearance_device.h")).read()
     assert '#include "appearance_device.h"' in open(os.path.join(csrc, "composite_backward_device.h")).read()
-    text = open(os.path.join(csrc, "appearance.hip")).read()
-    assert "AffineMseHead" in text and "atomicAdd" not in text and "fmaf" not in text
+    for name, uses in (("appearance.hip", '#include "appearance_device.h"'), ("composite_head.hip", "LossHead<BG, DIST, AFFINE>")):
+        text = open(os.path.join(csrc, name)).read()
+        assert uses in text and "atomicAdd" not in text and "fmaf" not in text, name
     mk = open(os.path.join(csrc, "Makefile")).read()
-    assert "appearance.hip" in mk and "appearance_device.h" in mk
+    assert "appearance.hip" in mk and "composite_head.hip" in mk and "appearance_device.h" in mk
 
 
 # (entry point, arguments, expected code, the rule)
@@ -268,17 +269,36 @@ def test_a_process_group_is_refused(monkeypatch):
 
 
 # ---- the compiled kernels --------------------------------------------------------------------------------------------------------
-def test_appearance_kernels_use_no_scratch():
-    """csrc/appearance.hip for gfx950: five kernels, none with a byte of scratch (the head keeps its 8 chunks of per-sample state
-    and the six floats of the ray's row in registers)."""
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("hipcc not available")
+def _scratch_of(source):
+    """{demangled kernel name: scratch bytes per lane} of one csrc file compiled for gfx950"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "nerf-simple_amd", "csrc", "appearance.hip")
+    src = os.path.join(ROOT, "nerf-simple_amd", "csrc", source)
     out = subprocess.run([hipcc, "-O3", "-std=c++20", "--offload-arch=gfx950", "--cuda-device-only", "-c", src, "-o", os.devnull,
                           "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     names = re.findall(r"Function Name: (\S+)", out.stderr)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    assert len(names) == len(scratch) == 5 and any("composite_affine_head_kernel" in n for n in names), names
-    assert scratch == [0] * 5, dict(zip(names, scratch))
+    assert len(names) == len(scratch) == len(set(names)), names
+    plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")
+    return dict(zip(plain, scratch))
+
+
+def test_appearance_kernels_use_no_scratch():
+    """For gfx950: csrc/appearance.hip is the four stages, and csrc/composite_head.hip exactly the eight instantiations
+    (NOISE, BG, DIST, AFFINE) of the dense head the entry points reach, the affine one among them; none with a byte of
+    scratch (the head keeps its 8 chunks of per-sample state and the six floats of the ray's row in registers)."""
+    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("hipcc not available")
+    stages = _scratch_of("appearance.hip")
+    assert len(stages) == 4 and all("appearance_" in n for n in stages), stages
+    assert set(stages.values()) == {0}, stages
+    heads = _scratch_of("composite_head.hip")
+    flags = lambda *on: ", ".join("true" if b else "false" for b in on)      # noqa: E731
+    want = {flags(0, 1, 0, 0), flags(1, 0, 0, 0), flags(1, 1, 0, 0),         # background and noise
+            flags(0, 0, 1, 0), flags(0, 1, 1, 0), flags(1, 0, 1, 0), flags(1, 1, 1, 0),      # with the distortion term
+            flags(0, 0, 0, 1)}                                               # the affine head
+    got = {re.search(r"dense_head_kernel<([^>]*)>", n).group(1) for n in heads}
+    assert len(heads) == 8 and got == want, heads
+    assert set(heads.values()) == {0}, heads
+    affine = [n for n in heads if f"<{flags(0, 0, 0, 1)}>" in n]
+    assert len(affine) == 1 and heads[affine[0]] == 0, heads

@@ -1,5 +1,5 @@
-"""The launch sequence of the four graphed training steps (training.GraphedTrainStep and its three subclasses; DESIGN.md
-section 19): what each stepper enqueues, in which order, on which of its two streams and over how many points.
+"""The launch sequence of the graphed training steps (training.GraphedTrainStep and its subclasses):
+what each stepper enqueues, in which order, on which of its two streams and over how many points.
 
 A recording proxy stands in for the object ``_lib.lib()`` returns.  It forwards every call and notes, for each launching
 entry point of the step, (name, stream, point count); the stream is the entry point's last argument.  Constructing a
@@ -10,7 +10,9 @@ the dX chain, the next batch's selection last on it).  ``step()`` replays graphs
 the selection that primes the first batch.
 
 The lists are literal on purpose: they were written against the four separate implementations this sequence had, and hold
-the one that replaced them to the same launches."""
+the one that replaced them to the same launches.  The lists of the dense step's controls, the two guided steppers and the
+two steppers with a per-image table (cameras, appearance) were written the same way, against the steppers as each of them
+carried its own copy of the second Adam and of the u_c / u_f handling, in front of the change that folded those copies."""
 import math
 
 import numpy as np
@@ -44,6 +46,17 @@ COUNT = {
     "nerf_amd_mlp_forward_train": _rows(-3),                              # ..., B, N, stream
     "nerf_amd_volume_render_mse_backward": _rows(-3),                     # ..., B, N, stream
     "nerf_amd_volume_render_mse_backward_pdf": _rows(-4),                 # ..., B, Nc, Nf, stream
+    "nerf_amd_volume_render_mse_backward_bg": _rows(-3),                  # ..., B, N, stream
+    "nerf_amd_volume_render_mse_backward_dist": _rows(-3),
+    "nerf_amd_volume_render_mse_backward_affine": _rows(-3),
+    "nerf_amd_sum_f32": _at(-2),                                          # x, out, n, stream
+    "nerf_amd_sample_pdf_volume": _rows(-4),                              # ..., B, Nc, Nf, stream: the coarse positions
+    "nerf_amd_sample_pdf_volume_masked": _rows(-4),
+    "nerf_amd_camera_rays": _at(-3),                                      # ..., B, M, stream
+    "nerf_amd_camera_rays_backward": _at(-3),
+    "nerf_amd_input_gradients": _at(-3),                                  # ..., P, N, stream
+    "nerf_amd_appearance_gather": _at(-3),                                # ..., B, M, stream
+    "nerf_amd_appearance_reduce": _at(-3),
     "nerf_amd_sample_encode_bf16": _rows(-3),                             # ..., B, N, stream
     "nerf_amd_mlp_backward": _at(-2),                                     # ..., P, stream
     "nerf_amd_mlp_backward_e4m3": _at(-2),
@@ -181,6 +194,89 @@ def masked_pair(Pc, Pf, Cc, Cf, select):
                ("nerf_amd_param_gradients_finish_bucket", "main", Cf)])
 
 
+def dense_controls(P, select):
+    return ([(FETCH, "main", None),
+             ("nerf_amd_mlp_forward_train", "main", P),
+             ("nerf_amd_volume_render_mse_backward_bg", "main", P),          # the head behind the background, noise on sigma
+             ("nerf_amd_mlp_backward", "main", P),
+             ("nerf_amd_sample_encode_bf16", "side", P),
+             ("nerf_amd_mse_loss", "side", 3 * B),
+             ("nerf_amd_param_gradients_begin", "side", P)]
+            + ([(SELECT, "side", B)] if select else [])
+            + [("nerf_amd_param_gradients_finish_bucket", "main", P)])
+
+
+def dense_distortion(P, select):
+    return ([(FETCH, "main", None),
+             ("nerf_amd_mlp_forward_train", "main", P),
+             ("nerf_amd_volume_render_mse_backward_dist", "main", P),        # the head with the term beside the MSE
+             ("nerf_amd_mlp_backward", "main", P),
+             ("nerf_amd_sample_encode_bf16", "side", P),
+             ("nerf_amd_mse_loss", "side", 3 * B),
+             ("nerf_amd_param_gradients_begin", "side", P),
+             ("nerf_amd_sum_f32", "side", B)]                                # the per-ray values of the term, summed
+            + ([(SELECT, "side", B)] if select else [])
+            + [("nerf_amd_param_gradients_finish_bucket", "main", P)])
+
+
+def guided(Pc, P, select):
+    return ([(FETCH, "main", None),
+             ("nerf_amd_sample_pdf_volume", "main", Pc),                     # the placement, between the fetch and the forward
+             ("nerf_amd_mlp_forward_train", "main", P),
+             ("nerf_amd_volume_render_mse_backward", "main", P),
+             ("nerf_amd_mlp_backward", "main", P),
+             ("nerf_amd_sample_encode_bf16", "side", P),
+             ("nerf_amd_mse_loss", "side", 3 * B),
+             ("nerf_amd_param_gradients_begin", "side", P)]
+            + ([(SELECT, "side", B)] if select else [])
+            + [("nerf_amd_param_gradients_finish_bucket", "main", P)])
+
+
+def masked_guided(Pc, C, select):
+    return ([(FETCH, "main", None),
+             ("nerf_amd_sample_pdf_volume_masked", "main", Pc),              # places and marks: no nerf_amd_occupancy_mark
+             ("nerf_amd_occupancy_points_capped", "main", C),
+             ("nerf_amd_mlp_forward_train_points", "main", C),
+             ("nerf_amd_volume_render_masked_mse_backward", "main", C),
+             ("nerf_amd_mlp_backward", "main", C),
+             ("nerf_amd_encode_points_bf16", "side", C),
+             ("nerf_amd_mse_loss", "side", 3 * B),
+             ("nerf_amd_param_gradients_begin", "side", C)]
+            + ([(SELECT, "side", B)] if select else [])
+            + [("nerf_amd_param_gradients_finish_bucket", "main", C)])
+
+
+# The two steppers with a per-image table fetch a second set of scalars: the cut in front of every fetch leaves the step's
+# own fetch as a piece of its own, and the rest starts at the table's.
+def camera(P):
+    return [(FETCH, "main", None),                                          # the camera Adam's scalars
+            ("nerf_amd_camera_rays", "main", B),                            # the step's rays from the ids and the poses
+            ("nerf_amd_mlp_forward_train", "main", P),
+            ("nerf_amd_volume_render_mse_backward", "main", P),
+            ("nerf_amd_mlp_backward", "main", P),
+            ("nerf_amd_input_gradients", "main", P),                        # behind the dX chain, on the main branch
+            ("nerf_amd_camera_rays_backward", "main", B),
+            ("nerf_amd_sample_encode_bf16", "side", P),
+            ("nerf_amd_mse_loss", "side", 3 * B),
+            ("nerf_amd_param_gradients_begin", "side", P),
+            (SELECT, "side", B),
+            ("nerf_amd_param_gradients_finish_bucket", "main", P)]
+
+
+def appearance(P):
+    return [(FETCH, "main", None),                                          # the appearance Adam's scalars
+            ("nerf_amd_appearance_gather", "main", B),                      # one row of theta per ray
+            ("nerf_amd_mlp_forward_train", "main", P),
+            ("nerf_amd_volume_render_mse_backward_affine", "main", P),
+            ("nerf_amd_mlp_backward", "main", P),
+            ("nerf_amd_appearance_reduce", "main", B),                      # behind the dX chain, on the main branch
+            ("nerf_amd_sample_encode_bf16", "side", P),
+            ("nerf_amd_mse_loss", "side", 3 * B),
+            ("nerf_amd_param_gradients_begin", "side", P),
+            (SELECT, "side", B),
+            ("nerf_amd_param_gradients_finish_bucket", "main", P)]
+
+
 def update(n_params, n_nets):
     return [(ADAM, "main", n_params)] + [("nerf_amd_pack_weights_train", "main", None)] * n_nets
 
@@ -219,10 +315,12 @@ def make_nets(dev, synthetic, n):
     return nets
 
 
-def run_case(monkeypatch, dev, synthetic, n_nets, build, step, want, warmup_tail, select):
+def run_case(monkeypatch, dev, synthetic, n_nets, build, step, want, warmup_tail, select, table_adam=None):
     """build(nets, opt) -> stepper under the recorder; step(stepper) runs one iteration.  ``want`` is the forward / backward
     sequence, ``warmup_tail`` what the warm-up enqueues behind its copy of it (the dense stepper warms the head-gradient
-    launch of its two-bucket form up too)."""
+    launch of its two-bucket form up too).  ``table_adam`` = the element count of a per-image table with an Adam of its own:
+    the step's own fetch is then a piece in front of ``want`` (which starts at the table's fetch), and the table's Adam a
+    piece behind the update."""
     from nerf_simple_amd import _lib
     from nerf_simple_amd.optim import FusedAdam
     rec = Recorder(_lib.lib())
@@ -232,15 +330,19 @@ def run_case(monkeypatch, dev, synthetic, n_nets, build, step, want, warmup_tail
     rec.take()
     stepper = build(nets, opt)
     got = sequences(rec.take())
-    upd = update(opt.flat.numel(), n_nets)
+    lead = [[(FETCH, "main", None)]] if table_adam else []
+    upd = [update(opt.flat.numel(), n_nets)] + ([[(ADAM, "main", table_adam)]] if table_adam else [])
     # one process, no exchange: the warm-up, graph A, graph B, then the whole iteration as one graph
     assert stepper.graph_ab is not None and stepper.graph_a2 is None
-    names = ["warm-up", "graph A", "graph B", "graph AB: forward / backward", "graph AB: update"]
-    wanted = [want + warmup_tail, want, upd, want, upd]
+    parts = (("warm-up", lead + [want + warmup_tail]), ("graph A", lead + [want]), ("graph B", upd),
+             ("graph AB: forward / backward", lead + [want]), ("graph AB: update", upd))
+    names = [name for name, pieces in parts for _ in pieces]
+    wanted = [piece for _, pieces in parts for piece in pieces]
     assert len(got) == len(wanted), [p[0][0] for p in got]
     for name, g, w in zip(names, got, wanted):
         assert g == w, (name, [x for x in zip(g, w) if x[0] != x[1]][:3], len(g), len(w))
-    assert got[1] == got[3] and got[0][:len(want)] == got[1]               # the warm-up and the captures are one sequence
+    n, a, ab = len(lead), len(lead) + 1, 2 * (len(lead) + 1) + len(upd)
+    assert got[a:2 * a] == got[ab:ab + a] and got[n][:len(want)] == got[a + n]     # the warm-up and the captures are one sequence
     loss = step(stepper)
     eager = rec.take()
     # step() replays: by hand it launches the selection that primes the first batch, on the current stream, and nothing else
@@ -302,3 +404,88 @@ def test_masked_pair_step(monkeypatch, dev, synthetic, inputs, variant):
                  lambda s: s.step() if select else s.step(inputs["rays"], inputs["gt"], u_c=inputs["u_c"], u_f=inputs["u_f"]),
                  masked_pair(Pc, Pf, Cc, Cf, select), [], select)
     assert s.capacity == (Cc, Cf)
+
+
+@pytest.mark.parametrize("variant", JITTER)
+def test_dense_step_background_and_noise(monkeypatch, dev, synthetic, inputs, variant):
+    from nerf_simple_amd.training import GraphedTrainStep
+    P, select = B * N, variant == JITTER[1]
+    kw = dict(background=torch.tensor([1.0, 0.5, 0.25]), sigma_noise=0.5, noise_seed=5, **jitter_kw(variant, inputs))
+    want = dense_controls(P, select)
+    run_case(monkeypatch, dev, synthetic, 1, lambda nets, opt: GraphedTrainStep(nets[0], opt, B, N, **kw),
+             lambda s: s.step() if select else s.step(inputs["rays"], inputs["gt"], u=inputs["u"]), want,
+             [(want[-1][0], "main", P)], select)
+
+
+@pytest.mark.parametrize("variant", JITTER)
+def test_dense_step_distortion(monkeypatch, dev, synthetic, inputs, variant):
+    from nerf_simple_amd.training import GraphedTrainStep
+    P, select = B * N, variant == JITTER[1]
+    want = dense_distortion(P, select)
+    run_case(monkeypatch, dev, synthetic, 1,
+             lambda nets, opt: GraphedTrainStep(nets[0], opt, B, N, distortion=0.01, **jitter_kw(variant, inputs)),
+             lambda s: s.step() if select else s.step(inputs["rays"], inputs["gt"], u=inputs["u"]), want,
+             [(want[-1][0], "main", P)], select)
+
+
+@pytest.mark.parametrize("variant", JITTER)
+def test_guided_step(monkeypatch, dev, synthetic, inputs, variant):
+    from nerf_simple_amd.training import GraphedGuidedTrainStep
+    from nerf_simple_amd.utils.proposal import ProposalVolume
+    select = variant == JITTER[1]
+    prop = ProposalVolume(17, BOUNDS, device=dev)
+    run_case(monkeypatch, dev, synthetic, 1,
+             lambda nets, opt: GraphedGuidedTrainStep(nets[0], opt, B, NC, NF, prop, **jitter_kw(variant, inputs)),
+             lambda s: s.step() if select else s.step(inputs["rays"], inputs["gt"], u_c=inputs["u_c"], u_f=inputs["u_f"]),
+             guided(B * NC, B * (NC + NF), select), [], select)
+
+
+@pytest.mark.parametrize("variant", JITTER)
+def test_masked_guided_step(monkeypatch, dev, synthetic, inputs, variant):
+    from nerf_simple_amd.training import GraphedMaskedGuidedTrainStep
+    from nerf_simple_amd.utils.proposal import ProposalVolume
+    select = variant == JITTER[1]
+    C = math.ceil(0.5 * B * (NC + NF))
+    prop = ProposalVolume(17, BOUNDS, device=dev)
+    s = run_case(monkeypatch, dev, synthetic, 1,
+                 lambda nets, opt: GraphedMaskedGuidedTrainStep(nets[0], opt, B, NC, NF, prop, inputs["occ"], 0.5,
+                                                                **jitter_kw(variant, inputs)),
+                 lambda s: s.step() if select else s.step(inputs["rays"], inputs["gt"], u_c=inputs["u_c"], u_f=inputs["u_f"]),
+                 masked_guided(B * NC, C, select), [], select)
+    assert s.capacity == C
+
+
+TABLE_M, TABLE_SIDE = 3, 5          # the smallest table that holds a batch: 3 images of 5 x 5 = 75 rows for B = 37
+
+
+@pytest.fixture(scope="module")
+def image_table(dev, oracle, synthetic):
+    """A ray generator over TABLE_M images of TABLE_SIDE x TABLE_SIDE pixels, built image by image from their poses"""
+    from nerf_simple_amd.utils.dataload import RayGenerator
+    cam = [TABLE_SIDE, TABLE_SIDE, synthetic.focal_from_fov(TABLE_SIDE)]
+    colours = torch.rand(TABLE_M, TABLE_SIDE, TABLE_SIDE, 3, generator=torch.Generator().manual_seed(5)).numpy()
+    poses = [np.asarray(oracle.spherical_to_pose(4, -30 - 5 * m, 90 * m), dtype=np.float32) for m in range(TABLE_M)]
+    return RayGenerator.from_samples({"train": [{"img": im, "transform": p} for im, p in zip(colours, poses)]}, cam, dev)
+
+
+def test_camera_step(monkeypatch, dev, synthetic, image_table):
+    from nerf_simple_amd.training import GraphedCameraTrainStep
+    from nerf_simple_amd.utils.cameras import CameraRefinement
+    cams = CameraRefinement.from_ray_generator(image_table)
+    assert cams.n_rays == TABLE_M * TABLE_SIDE * TABLE_SIDE
+    s = run_case(monkeypatch, dev, synthetic, 1,
+                 lambda nets, opt: GraphedCameraTrainStep(nets[0], opt, B, N, cams, rays_from=image_table, device_rng=True, seed=11),
+                 lambda s: s.step(), camera(B * N), [], True, table_adam=TABLE_M * 6)
+    assert s.camera_steps == 1
+
+
+def test_appearance_step(monkeypatch, dev, synthetic, image_table):
+    from nerf_simple_amd.training import GraphedAppearanceTrainStep
+    from nerf_simple_amd.utils.appearance import AppearanceCorrection
+    app = AppearanceCorrection.from_ray_generator(image_table)
+    assert (app.M, app.HW) == (TABLE_M, TABLE_SIDE * TABLE_SIDE)
+    want = appearance(B * N)
+    s = run_case(monkeypatch, dev, synthetic, 1,
+                 lambda nets, opt: GraphedAppearanceTrainStep(nets[0], opt, B, N, app, rays_from=image_table, device_rng=True, seed=11),
+                 lambda s: s.step(), want, [(want[-1][0], "main", B * N)], True, table_adam=TABLE_M * 6)
+    assert s.appearance_steps == 1
