@@ -371,6 +371,10 @@ int nerf_amd_param_gradients_finish_bucket(const void* acts, const void* dys, co
  * [feature/16 (16)][point in tile (256)][16 x e4m3]; behind the 10 layers, per layer and 32-point block 8 exponent
  * bytes (byte Q: features 32Q .. 32Q+31; value = e4m3 * 2^(byte - 127); the producers choose one exponent per 128
  * features, so bytes 4k .. 4k+3 are equal -- a consumer need not rely on it); `acts` then carries the ReLU masks.
+ * What no point or feature owns -- the data of points >= P in the last tile and of features past a layer's width, the
+ * exponent bytes of 32-point blocks with no point and of fragments past the width -- is written by no producer and looked
+ * at by no consumer: the buffers may be allocated uninitialised (the exponent byte 0xFF is e8m0's NaN, and the scaled MFMA
+ * returns NaN for it even over zero data, so the products mask the exponents of a slab's absent second block).
  *   nerf_amd_mlp_forward_train(..., flags | NERF_AMD_STORE_E4M3, ...)  with acts of nerf_amd_train_activation_bytes_e4m3(P)
  *   nerf_amd_mlp_backward_e4m3: dys of nerf_amd_train_gradient_bytes_e4m3(P)
  *   nerf_amd_param_gradients_begin (unchanged: packs d_raw into `scratch`);

@@ -97,6 +97,8 @@ __global__ __launch_bounds__(512, 2) void dw_gemm_e4m3_kernel(GemmTableF8 tab) {
     const int slice = blockIdx.x - d.wg0;
     const long long nslab = (tab.P + SLAB - 1) / SLAB;
     const long long s_begin = nslab * slice / d.wgs, s_end = nslab * (slice + 1) / d.wgs;
+    // the iteration of this slice, if any, whose slab has one 32-point block only: the last slab of an odd number of blocks
+    const int it_one_block = (s_end == nslab && tab.P % SLAB >= 1 && tab.P % SLAB <= 32) ? (int)(s_end - s_begin) - 1 : -1;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -206,9 +208,13 @@ __global__ __launch_bounds__(512, 2) void dw_gemm_e4m3_kernel(GemmTableF8 tab) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();              // slab s published; everyone is done with slab s-1
         if (s + RING - 1 < s_end) issue_slab(it + RING - 1, (it + RING - 1) & (RING - 1));     // into the slot of slab s-1
-        // the scale registers of this slab: lanes 0..31 carry block 0's exponent, lanes 32..63 block 1's
-        const unsigned a_dw = (h ? (wm ? ea[3] : ea[2]) : (wm ? ea[1] : ea[0])) & amask;
-        const unsigned b_dw = ((h ? ((wn >> 1) ? eb[3] : eb[2]) : ((wn >> 1) ? eb[1] : eb[0])) >> (16 * (wn & 1))) & bmask;
+        // the scale registers of this slab: lanes 0..31 carry block 0's exponent, lanes 32..63 block 1's.  A second block
+        // with no point (the last slab of an odd number of blocks) has zero data (the DMA mask) and exponent bytes nobody
+        // wrote: they are not looked at either -- the byte 0xFF, e8m0's NaN, makes the instruction's result NaN even over
+        // zero data (profiles/f8_probe_accumulator.txt).  Wave-uniform: scalar selects beside the MFMAs.
+        const bool one_block = it == it_one_block;
+        const unsigned a_dw = (h ? (one_block ? 0u : wm ? ea[3] : ea[2]) : (wm ? ea[1] : ea[0])) & amask;
+        const unsigned b_dw = ((h ? (one_block ? 0u : (wn >> 1) ? eb[3] : eb[2]) : ((wn >> 1) ? eb[1] : eb[0])) >> (16 * (wn & 1))) & bmask;
         const u32x4 ea_now = ea;
         if (left >= 2) load_scales(s + 1, ea, eb);
 #if defined(F8_TIMING) && F8_TIMING == 4       // timing-only build: the LDS-DMA stream, its waits and barriers alone

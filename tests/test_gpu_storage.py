@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from storage_model import E4M3, decode_e4m3_layers, decode_scratch  # the 8-bit form's layout lives with its model
 from train_chain_model import bf16_to_f32, decode_bf16_layers     # the bf16 form's layout lives with its model
 
 pytestmark = pytest.mark.gpu
@@ -35,34 +36,12 @@ def dev():
     return torch.device("cuda:0")
 
 
-E4M3 = np.array([np.nan if (v & 0x7f) == 0x7f else
-                 (-1.0 if v & 0x80 else 1.0) * ((v & 7) / 8.0 * 2.0 ** -6 if (v >> 3) & 15 == 0 else (1 + (v & 7) / 8.0) * 2.0 ** (((v >> 3) & 15) - 7))
-                 for v in range(256)])
-
-
-def decode_e4m3_layers(host, P):
-    """([10][P, 256] float64 values, [10][P, 256] bytes, [10][blocks, 8] exponent bytes) from the 8-bit buffer
-    (nerf_layout.h f8_elem_offset / f8_scale_offset_bytes)."""
-    nt = (P + 255) // 256
-    vals, raws, exps = [], [], []
-    scale0 = 10 * nt * 65536
-    for L in range(10):
-        blk = host[L * nt * 65536:(L + 1) * nt * 65536].reshape(nt, 16, 256, 16)
-        b = blk.transpose(0, 2, 1, 3).reshape(nt * 256, 256)[:P]
-        e = host[scale0 + L * nt * 64: scale0 + (L + 1) * nt * 64].reshape(nt * 8, 8)
-        sc = 2.0 ** (e.astype(np.float64) - 127.0)                                    # [block, Q]
-        per_elem = np.repeat(np.repeat(sc, 32, axis=0)[:P], 32, axis=1)               # [P, 256]
-        vals.append(E4M3[b] * per_elem)
-        raws.append(b)
-        exps.append(e)
-    return vals, raws, exps
-
-
-def run_chain(dev, synthetic, B, N, e4m3, kind="default", seed=4, buckets=False, sd=None, d_raw_in=None):
+def run_chain(dev, synthetic, B, N, e4m3, kind="default", seed=4, buckets=False, sd=None, d_raw_in=None, fill=0):
     """Forward (saving), compositor backward, dX chain, dW through the C ABI in either storage form; returns the host
     copies of everything.  ``sd``: a state dict to run instead of the synthetic one of ``kind``; ``d_raw_in`` [P, 4]: an
     upstream gradient that replaces the compositor's behind its launch (at N = 1 the reference composites an empty sample
-    axis, so the compositor's own d_raw is identically zero there)."""
+    axis, so the compositor's own d_raw is identically zero there).  ``fill``: the byte that acts, dys, scratch and scratch8
+    hold before the first kernel writes them (a training step allocates them uninitialised)."""
     from nerf_simple_amd import _lib
     from nerf_simple_amd.utils.nets import Nerf
     from nerf_simple_amd.utils.xyz import camera_rays, spherical_to_pose
@@ -83,14 +62,17 @@ def run_chain(dev, synthetic, B, N, e4m3, kind="default", seed=4, buckets=False,
     posd = torch.empty(P, 32, dtype=torch.bfloat16, device=dev)
     grads = torch.zeros(int(lib.nerf_amd_param_count()), device=dev)
     scratch = torch.empty(max(int(lib.nerf_amd_param_gradients_scratch_bytes(P)), 16), dtype=torch.uint8, device=dev)
+    if fill:
+        scratch.fill_(fill)
     st, ptr, ck = _lib.stream_ptr(dev), _lib.ptr, _lib.check
+    filled = lambda n: torch.full((int(n),), fill, dtype=torch.uint8, device=dev)
     if e4m3:
-        acts = torch.zeros(int(lib.nerf_amd_train_activation_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
-        dys = torch.zeros(int(lib.nerf_amd_train_gradient_bytes_e4m3(P)), dtype=torch.uint8, device=dev)
-        scratch8 = torch.zeros(int(lib.nerf_amd_param_gradients_scratch_e4m3_bytes(P)), dtype=torch.uint8, device=dev)
+        acts = filled(lib.nerf_amd_train_activation_bytes_e4m3(P))
+        dys = filled(lib.nerf_amd_train_gradient_bytes_e4m3(P))
+        scratch8 = filled(lib.nerf_amd_param_gradients_scratch_e4m3_bytes(P))
     else:
-        acts = torch.zeros(int(lib.nerf_amd_train_activation_bytes(P)), dtype=torch.uint8, device=dev)
-        dys = torch.zeros_like(acts)
+        acts = filled(lib.nerf_amd_train_activation_bytes(P))
+        dys = filled(lib.nerf_amd_train_activation_bytes(P))
     packed, image = net.packed_weights(_lib.BF16), net.packed_weights(_lib.BF16_BWD)
     ck(lib.nerf_amd_sample_encode_bf16(ptr(rays), ptr(u), ptr(tbins), 0, 0, 0, ptr(posx), ptr(posd), None, B, N, st), "encode")
     ck(lib.nerf_amd_mlp_forward_train(ptr(rays), ptr(u), ptr(tbins), ptr(packed), _lib.FLAG_STORE_E4M3 if e4m3 else 0, 0, 0,
@@ -177,21 +159,10 @@ def test_e4m3_buffers_are_the_bf16_ones_rounded(dev, synthetic, B, N):
     # the encoder rows and the packed d_raw (nerf_amd_param_gradients_convert_e4m3)
     from_rows = {64: a16["posx"], 32: a16["posd"],
                  16: bf16_to_f32(a16["scratch"][:P * 64].view(np.uint16).reshape(P, 32))[:, :16]}
-    off = 0
-    for W in (64, 32, 16):
-        data_bytes = nt * (W // 16) * 4096
-        total = data_bytes + nt * 64
-        buf = a8["scratch8"][off:off + total]
-        blk = buf[:data_bytes].reshape(nt, W // 16, 256, 16).transpose(0, 2, 1, 3).reshape(nt * 256, W)[:P]
-        e = buf[data_bytes:].reshape(nt * 8, 8)
-        nq = (W + 31) // 32
-        sc = 2.0 ** (e[:, :nq].astype(np.float64) - 127.0)
-        per = np.repeat(np.repeat(sc, 32, axis=0)[:P], 32, axis=1)[:, :W]
-        v8 = E4M3[blk] * per
+    for W, (v8, _, _, per) in decode_scratch(a8["scratch8"], P).items():
         want = from_rows[W].astype(np.float64)
         tol = np.maximum(np.abs(want) / per * 2.0 ** -4, 2.0 ** -10) * per
         assert (np.abs(v8 - want) <= tol * (1 + 1e-12)).all(), W
-        off += (total + 255) // 256 * 256
 
 
 def expected_grads(a8, layout):
@@ -200,18 +171,7 @@ def expected_grads(a8, layout):
     nt = (P + 255) // 256
     X, _, _ = decode_e4m3_layers(a8["acts"], P)
     dY, _, _ = decode_e4m3_layers(a8["dys"], P)
-    off = 0
-    narrow = {}
-    for W in (64, 32, 16):
-        data_bytes = nt * (W // 16) * 4096
-        total = data_bytes + nt * 64
-        buf = a8["scratch8"][off:off + total]
-        blk = buf[:data_bytes].reshape(nt, W // 16, 256, 16).transpose(0, 2, 1, 3).reshape(nt * 256, W)[:P]
-        e = buf[data_bytes:].reshape(nt * 8, 8)
-        nq = (W + 31) // 32
-        per = np.repeat(np.repeat(2.0 ** (e[:, :nq].astype(np.float64) - 127.0), 32, axis=0)[:P], 32, axis=1)[:, :W]
-        narrow[W] = E4M3[blk] * per
-        off += (total + 255) // 256 * 256
+    narrow = {W: vals for W, (vals, _, _, _) in decode_scratch(a8["scratch8"], P).items()}
     posx, posd, dsr = narrow[64][:, :63], narrow[32][:, :27], narrow[16]
     d_raw = a8["d_raw"].astype(np.float64)
     g = {}

@@ -9,7 +9,9 @@
 //      scale register of lane r; K block 1 = bytes 16..31 of both lanes, scale from lane r + 32 -- NOT "a lane's 32 bytes
 //      are one block", which is the model the first check prints as failing.)
 //   4. how exact is the sum inside one instruction (products 2^-14 below the largest of their group of eight are dropped;
-//      on random signed data the mean error is 5e-9 of the sum of |products|: nothing beside 8-bit operands).
+//      on random signed data the mean error is 5e-9 of the sum of |products|: nothing beside 8-bit operands), and how
+//      the instruction's sum is added into the accumulator C = 2^k (profiles/f8_probe_accumulator.txt);
+//   5. what the exponent byte 0xFF (e8m0's NaN) does to a K block whose data bytes are zero, and to one whose are not.
 //   hipcc --offload-arch=gfx950 -O2 -o f8_probe f8_probe.hip && ./f8_probe
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -46,6 +48,14 @@ __global__ void mfma_kernel(const v8i* a, const v8i* b, const int* sa, const int
     const int l = threadIdx.x;
     v16f c;
     for (int r = 0; r < 16; ++r) c[r] = 0.f;
+    d[l] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[l], b[l], c, 0, 0, OA, sa[l], OB, sb[l]);
+}
+
+template <int OA, int OB>
+__global__ void mfma_c_kernel(const v8i* a, const v8i* b, const int* sa, const int* sb, float c0, v16f* d) {
+    const int l = threadIdx.x;
+    v16f c;
+    for (int r = 0; r < 16; ++r) c[r] = c0;
     d[l] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[l], b[l], c, 0, 0, OA, sa[l], OB, sb[l]);
 }
 
@@ -280,6 +290,55 @@ int main() {
         }
         printf("random blocks (A > 0, B signed, magnitudes 2^-3..2^8): mean error %.4g, rms error %.4g, mean sum of |products| %.4g\n",
                se / cnt, sqrt(sa2 / cnt), sabs / cnt);
+        // the accumulator: C = 2^k, row = one product of 1.0 (63 zeros beside it), then 64 products of 1.0.  A true fp32
+        // add gives D - C = 1 up to k = 23 and 0 (a tie, to even) at k = 24; 64 is exact at every k here.
+        printf("sum into the accumulator: C = 2^k; D - C for a row of one product of 1.0 | of 64 products of 1.0\n");
+        memset(hb, 0x38, sizeof(hb));
+        CK(hipMemcpy(db, hb, 2048, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dsa, one, 256, hipMemcpyHostToDevice)); CK(hipMemcpy(dsb, one, 256, hipMemcpyHostToDevice));
+        for (int k = 8; k <= 24; ++k) {
+            const float c0 = ldexpf(1.f, k);
+            double diff[2][2];
+            for (int many = 0; many < 2; ++many) {
+                memset(ha, many ? 0x38 : 0x00, sizeof(ha));
+                for (int m = 0; m < 32; ++m) ha[m][0] = 0x38;
+                CK(hipMemcpy(da, ha, 2048, hipMemcpyHostToDevice));
+                hipLaunchKernelGGL((mfma_c_kernel<1, 2>), dim3(1), dim3(64), 0, 0, da, db, dsa, dsb, c0, dd);
+                float hd[64][16];
+                CK(hipMemcpy(hd, dd, 4096, hipMemcpyDeviceToHost));
+                diff[many][0] = (double)hd[0][0] - (double)c0;                  // D[0][0]
+                diff[many][1] = (double)hd[63][15] - (double)c0;                // D[31][31]
+            }
+            printf("  k = %2d: D - C = %.9g (D[31][31]: %.9g) | %.9g (D[31][31]: %.9g)\n", k, diff[0][0], diff[0][1], diff[1][0], diff[1][1]);
+        }
+    }
+    // ---- 5. the exponent byte 0xFF (the NaN of e8m0) on a K block: lanes 32..63 of A (K block 1) carry it, block 0 is a
+    // row of 32 products of 1.0.  Does the block turn the output into NaN when its data bytes are all zero?  When they are not?
+    {
+        v8i *da, *db; int *dsa, *dsb; v16f* dd;
+        CK(hipMalloc(&da, 2048)); CK(hipMalloc(&db, 2048)); CK(hipMalloc(&dsa, 256)); CK(hipMalloc(&dsb, 256)); CK(hipMalloc(&dd, 4096));
+        unsigned char ha[64][32], hb[64][32];
+        int one[64], sa[64];
+        for (int l = 0; l < 64; ++l) { one[l] = 0x7f7f7f7f; sa[l] = l < 32 ? 0x7f7f7f7f : 0x7f7fff7f; }
+        memset(hb, 0x38, sizeof(hb));
+        CK(hipMemcpy(db, hb, 2048, hipMemcpyHostToDevice)); CK(hipMemcpy(dsb, one, 256, hipMemcpyHostToDevice));
+        printf("exponent byte 0xFF on K block 1 of A (block 0: 32 products of 1.0, exponent 127):\n");
+        for (int kind = 0; kind < 3; ++kind) {
+            // 0: block 1 zero data under 0xFF; 1: block 1 ones under 0xFF; 2: block 1 zero data under byte 0 (2^-127)
+            memset(ha, 0x38, sizeof(ha));
+            for (int l = 0; l < 64; ++l)
+                for (int j = 16; j < 32; ++j) ha[l][j] = kind == 1 ? 0x38 : 0x00;
+            if (kind == 2) for (int l = 32; l < 64; ++l) sa[l] = 0x7f7f007f;
+            CK(hipMemcpy(da, ha, 2048, hipMemcpyHostToDevice)); CK(hipMemcpy(dsa, sa, 256, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL((mfma_c_kernel<1, 2>), dim3(1), dim3(64), 0, 0, da, db, dsa, dsb, 0.f, dd);
+            float hd[64][16];
+            CK(hipMemcpy(hd, dd, 4096, hipMemcpyDeviceToHost));
+            int nans = 0;
+            for (int l = 0; l < 64; ++l)
+                for (int r = 0; r < 16; ++r) nans += std::isnan(hd[l][r]) ? 1 : 0;
+            printf("  block 1 %s: D[0][0] = %.9g, %d of 1024 outputs NaN\n",
+                   kind == 0 ? "zero data, exponent 0xFF" : kind == 1 ? "ones, exponent 0xFF     " : "zero data, exponent 0x00", (double)hd[0][0], nans);
+        }
     }
     return 0;
 }
