@@ -823,7 +823,7 @@ int nerf_amd_volume_render_masked_mse_backward(const float* raw_live, const floa
                                                const int64_t* offsets, const float* gt, float* rgb, float* d_raw_live,
                                                int64_t capacity, int64_t B, int N, void* stream);
 
-/* ---- masked hierarchical pair: one occupancy grid for the coarse and the fine pass (csrc/occupancy_hier.hip) -----------
+/* ---- masked hierarchical pair: one occupancy grid for the coarse and the fine pass (csrc/occupancy_graph.hip) ----------
  * Not in the reference.  tests/occupancy_hierarchical_model.py restates the semantics in numpy; DESIGN.md section 15.
  *
  * ONE grid masks both passes (while training it follows the FINE network).  The masked hierarchical render is BY DEFINITION

@@ -1052,9 +1052,13 @@ int nerf_amd_volume_render_masked_backward(const float* raw_live, const float* r
         misaligned(d_raw_live, 16) || (!raw_live != !d_raw_live))
         return NERF_AMD_EINVAL;
     const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
-    return nerf_amd_launch_occ_composite_backward(&a, reinterpret_cast<const unsigned long long*>(mask),
-                                                  reinterpret_cast<const long long*>(offsets), raw_live, g_rgb, g_disp, g_alpha,
-                                                  g_acc, g_w, d_raw_live, B, S(stream));
+    MaskedBackwardArgs b{};                    // the five gradients, no MSE head, no sampler, no capacity clamp
+    b.mask = reinterpret_cast<const unsigned long long*>(mask);
+    b.offsets = reinterpret_cast<const long long*>(offsets);
+    b.raw_live = raw_live; b.d_raw_live = d_raw_live;
+    b.B = B; b.capacity = MASKED_NO_CLAMP;
+    b.g_rgb = g_rgb; b.g_disp = g_disp; b.g_alpha = g_alpha; b.g_acc = g_acc; b.g_w = g_w;
+    return nerf_amd_launch_masked_backward(&a, &b, S(stream));
 }
 
 int nerf_amd_occupancy_decay_max(float* state, const float* sigma_now, float decay, int64_t n, void* stream) {

@@ -1,5 +1,5 @@
 // api_checks.h -- host-side argument rules shared by the sources that implement the C ABI (include/nerf_amd.h): api.hip and
-// the self-contained entry points in occupancy_graph.hip, occupancy_hier.hip and occupancy_terminate.hip.  Host code only.
+// the self-contained entry points in occupancy_graph.hip and occupancy_terminate.hip.  Host code only.
 // Each limit and each rule that more than one entry point applies is stated here once (the limits a kernel's static sizes
 // depend on: nerf_layout.h, sample_pdf_device.h); an entry point chooses the ORDER in which it applies them, and that order
 // is part of the ABI (tests/test_abi_refusals_cpu.py).

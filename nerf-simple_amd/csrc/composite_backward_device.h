@@ -1,7 +1,7 @@
-// composite_backward_device.h -- the per-ray backward walk of the compositor, shared by its four kernels:
-// composite_backward_kernel<E> (composite.hip, dense raw[B, N, 4]), occ_composite_backward_kernel (occupancy_train.hip,
-// masked), occ_head_capped_kernel (occupancy_graph.hip, masked under the capacity clamp, MSE head) and
-// occ_head_capped_pdf_kernel<E> (occupancy_hier.hip, the same with the fine pass's sampler behind it).
+// composite_backward_device.h -- the per-ray backward walk of the compositor, shared by its kernels:
+// composite_backward_kernel<E> (composite.hip, dense raw[B, N, 4]), dense_head_kernel (composite_head.hip, the dense head
+// with its optional terms) and masked_backward_kernel<Up, E> (occupancy_train.hip, the masked samples: the five gradients,
+// or the MSE head under the capacity clamp, alone or with the fine pass's sampler behind it).
 //
 // d loss / d raw given the upstream gradients of the five outputs.  With G_i = dL/dw_i gathered from every consumer of w,
 //   dL/dc_i     = w_i * g_rgb
@@ -180,19 +180,14 @@ __device__ __forceinline__ void composite_backward_ray(Src src, const Up& up, co
             const BwdSample s = src.chunk(ch, i, lane, valid, N);
             float a = 0.f, fac = 1.0f;
             if (valid) {
-                float delta = (i == N - 1) ? 1e10f : sub_rn(s.t_next, s.t);
-                delta = mul_rn(delta, dnorm);
                 const float sigma = s.c[3];
-                const float z = expf(sigma);
-                const float sp = sigma > 20.f ? sigma : log1pf(z);
+                const AlphaFactor f = alpha_factor((i == N - 1) ? 1e10f : sub_rn(s.t_next, s.t), dnorm, sigma);
+                a = f.alpha; fac = f.fac;
                 // softplus' as torch's backward forms it: z / (z + 1) keeps exp(sigma) down to the subnormals, where
                 // 1 / (1 + exp(-sigma)) is 0 from sigma = -88.7 on (a last sample's delta = 1e10 brings that back up)
-                const float spd = sigma > 20.f ? 1.0f : __fdiv_rn(z, add_rn(z, 1.0f));
-                const float e = expf(mul_rn(-sp, delta));
-                a = sub_rn(1.0f, e);
-                fac = add_rn(sub_rn(1.0f, a), 1e-10f);
+                const float spd = sigma > 20.f ? 1.0f : __fdiv_rn(f.z, add_rn(f.z, 1.0f));
                 // e itself, not 1 - alpha: that recovers e to an absolute 2^-24, a relative 2^-24 / e on a nearly opaque sample
-                ds[ch] = mul_rn(mul_rn(e, delta), spd);
+                ds[ch] = mul_rn(mul_rn(f.e, f.delta), spd);
                 tt[ch] = s.t; cc[ch] = s.c; rk[ch] = s.row;
             }
             // the forward compositor's scan (composite_device.h): same tree, same rounded products

@@ -67,6 +67,26 @@ __device__ __forceinline__ float unit_dir_norm(float d0, float d1, float d2, boo
     return norm3(d0, d1, d2);
 }
 
+// softplus(beta = 1, threshold = 20) of sigma, given z = exp(sigma)
+__device__ __forceinline__ float softplus(float sigma, float z) { return sigma > 20.f ? sigma : log1pf(z); }
+
+// The alpha of one sample and its transmittance factor (rendering.py:62-68), the ONE place they are formed: the forward
+// compositor, the backward sweep (composite_backward_device.h) and the ray termination (occupancy_terminate.hip) hold the
+// same bits because they call this.  dt = t(i + 1) - t(i), 1e10 at the ray's last sample (the caller's: it owns the loads).
+struct AlphaFactor {
+    float alpha, fac;      // 1 - e and (1 - alpha) + 1e-10
+    float e, delta, z;     // for the backward: exp(-softplus(sigma) delta), the interval scaled by dnorm, exp(sigma)
+};
+__device__ __forceinline__ AlphaFactor alpha_factor(float dt, float dnorm, float sigma) {
+    AlphaFactor f;
+    f.delta = mul_rn(dt, dnorm);
+    f.z = expf(sigma);
+    f.e = expf(mul_rn(-softplus(sigma, f.z), f.delta));
+    f.alpha = sub_rn(1.0f, f.e);
+    f.fac = add_rn(sub_rn(1.0f, f.alpha), 1e-10f);
+    return f;
+}
+
 struct RayOut {            // any pointer may be NULL
     float* rgb;            // [B,3]
     float* disp;           // [B]
@@ -94,12 +114,8 @@ __device__ __forceinline__ void composite_ray(const Src& src, int N, int lane, f
         if (valid) {
             t = src.t(i);
             c = src.c(i);
-            float delta = (i == N - 1) ? 1e10f : sub_rn(src.t(i + 1), t);
-            delta = mul_rn(delta, dnorm);
-            const float sigma = c[3];
-            const float sp = sigma > 20.f ? sigma : log1pf(expf(sigma));      // softplus(beta=1, threshold=20)
-            a = sub_rn(1.0f, expf(mul_rn(-sp, delta)));
-            fac = add_rn(sub_rn(1.0f, a), 1e-10f);
+            const AlphaFactor f = alpha_factor((i == N - 1) ? 1e10f : sub_rn(src.t(i + 1), t), dnorm, c[3]);
+            a = f.alpha; fac = f.fac;
         }
         // inclusive product scan across the wave, shifted by one lane = exclusive cumprod (rendering.py:68)
         const float incl = wave_scan_mul(fac);

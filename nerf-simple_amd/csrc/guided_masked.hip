@@ -9,33 +9,33 @@
 //              weights that are exactly 0 at a dead sample";
 //   weights:   composite_ray (composite_device.h) over raw = (0, 0, 0, value) into the wave's own LDS slice, as guided_sample.hip;
 //   sampler:   nerf_pdf::sample_ray (sample_pdf_device.h), which leaves the merged positions in WaveLds::all;
-//   mark:      the merged positions once more: the point as fetch_point_rays forms it from a given position
-//              (add_rn(o, mul_rn(d, t)) per axis), sample_live, one ballot per 64 samples -> mask[B, ceil((Nc + Nf) / 64)] and the
-//              ray's live count at the head of the scan workspace (occ_ws_counts).
+//   mark:      the merged positions once more, through the mark kernel's own body (mark_ray, occ_grid_device.h): the point as
+//              fetch_point_rays forms it from a given position (add_rn(o, mul_rn(d, t)) per axis), sample_live, one ballot per 64
+//              samples -> mask[B, ceil((Nc + Nf) / 64)] and the ray's live count at the head of the scan workspace (occ_ws_counts).
 // The exclusive scan of the counts is occupancy.hip's (nerf_amd_launch_occ_scan).  No atomics, no cross-wave traffic: two runs
 // write the same bytes.  The host wrapper below is the C ABI itself (argument rules: api_checks.h).
 #include "composite_device.h"
 #include "sample_pdf_device.h"
 #include "sigma_volume_device.h"
 #include "occ_grid_device.h"
+#include "occ_scan_device.h"
 #include "api_checks.h"
 #include "launchers.h"
 
 namespace {
 
-constexpr int GUIDED_RAYS_PER_BLOCK = 4;
 using nerf_pdf::MAXC;
 
 template <int E>
-__global__ __launch_bounds__(64 * GUIDED_RAYS_PER_BLOCK) void guided_masked_kernel(
+__global__ __launch_bounds__(MASKED_THREADS) void guided_masked_kernel(
     MlpArgs a, SigmaVolume g, const float* __restrict__ vol, OccGrid og, const float* __restrict__ u_f, float* __restrict__ ts_out,
     float* __restrict__ sigma_c, float* __restrict__ w_c, unsigned long long* __restrict__ mask, int* __restrict__ counts,
     long long B, int Nf) {
-    __shared__ nerf_pdf::WaveLds<E> s_pdf[GUIDED_RAYS_PER_BLOCK];
-    __shared__ float s_sigma[GUIDED_RAYS_PER_BLOCK][MAXC];
-    __shared__ float s_w[GUIDED_RAYS_PER_BLOCK][MAXC];
+    __shared__ nerf_pdf::WaveLds<E> s_pdf[MASKED_RAYS_PER_BLOCK];
+    __shared__ float s_sigma[MASKED_RAYS_PER_BLOCK][MAXC];
+    __shared__ float s_w[MASKED_RAYS_PER_BLOCK][MAXC];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long ray = (long long)blockIdx.x * GUIDED_RAYS_PER_BLOCK + wv;
+    const long long ray = (long long)blockIdx.x * MASKED_RAYS_PER_BLOCK + wv;
     if (ray >= B) return;                      // whole wave leaves together; only wave-local LDS below, no workgroup barrier
     const int Nc = a.N;
     nerf_pdf::WaveLds<E>& s = s_pdf[wv];
@@ -48,11 +48,9 @@ __global__ __launch_bounds__(64 * GUIDED_RAYS_PER_BLOCK) void guided_masked_kern
         if (sigma_c) sigma_c[ray * Nc + i] = v;
     }
     wave_lds_fence();
-    const float* r6 = a.rays + ray * 6;
-    const float dnorm = nerf_composite::unit_dir_norm(r6[3], r6[4], r6[5], true);
     // the compositor's forward sweep; its w goes to this wave's LDS slice (ray index 0 of a [1, Nc] output)
     const nerf_composite::RayOut o{nullptr, nullptr, nullptr, nullptr, s_w[wv], nullptr};
-    nerf_composite::composite_ray(VolumeSamples{s.ts, s_sigma[wv]}, Nc, lane, dnorm, 0, o);
+    nerf_composite::composite_ray(VolumeSamples{s.ts, s_sigma[wv]}, Nc, lane, ray_dnorm(a, ray), 0, o);
     // the sweep's stores went through a generic pointer: wait on both counters before the wave's hand-over
     __builtin_amdgcn_s_waitcnt(0);
     wave_lds_fence();
@@ -63,21 +61,14 @@ __global__ __launch_bounds__(64 * GUIDED_RAYS_PER_BLOCK) void guided_masked_kern
     nerf_pdf::sample_ray<E>(s, s_w[wv], Nc, Nf, lane, u_f, (a.flags & NERF_FLAG_DEVICE_RNG) != 0, seed, a.ray_id0, ray,
                             ts_out + ray * M);
     // the mark of the merged positions (sample_ray fenced WaveLds::all behind its last write): the values ts_out holds
+    const float* r6 = a.rays + ray * 6;
     const float ox = r6[0], oy = r6[1], oz = r6[2], dx = r6[3], dy = r6[4], dz = r6[5];
-    const int words = (M + 63) >> 6;
-    int cnt = 0;
-    for (int q = 0; q < words; ++q) {
-        const int i = q * 64 + lane;
-        bool live = false;
-        if (i < M) {
-            const float t = s.all[i];
-            live = sample_live(og, add_rn(ox, mul_rn(dx, t)), add_rn(oy, mul_rn(dy, t)), add_rn(oz, mul_rn(dz, t)));
-        }
-        const unsigned long long m = __ballot(live);
-        if (lane == 0) mask[ray * words + q] = m;
-        cnt += __popcll(m);
-    }
-    if (lane == 0) counts[ray] = cnt;
+    mark_ray(og, M, lane,
+             [&](int i) {
+                 const float t = s.all[i];
+                 return make_float3(add_rn(ox, mul_rn(dx, t)), add_rn(oy, mul_rn(dy, t)), add_rn(oz, mul_rn(dz, t)));
+             },
+             mask + ray * ((M + 63) >> 6), counts + ray);
 }
 
 }  // namespace
@@ -97,7 +88,7 @@ extern "C" int nerf_amd_launch_sample_pdf_volume_masked(const MlpArgs* args, con
         const SigmaVolume g = sigma_volume_args(vx, vy, vz, v_lo, v_inv_step);
         const OccGrid og = occ_grid_args(bits, gx, gy, gz, g_lo, g_inv_step, outside_live);
         int* counts = occ_ws_counts(ws);
-        const dim3 grid((unsigned)((B + GUIDED_RAYS_PER_BLOCK - 1) / GUIDED_RAYS_PER_BLOCK)), block(64 * GUIDED_RAYS_PER_BLOCK);
+        const dim3 grid((unsigned)((B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
         // keys per lane of the register sort: ceil_pow2(Nf) / 64 (nerf_pdf::keys_per_lane)
 #define GUIDED_MASKED_LAUNCH(E)                                                                                                  \
     hipLaunchKernelGGL(guided_masked_kernel<E>, grid, block, 0, stream, *args, g, volume, og, u_f, ts_out, sigma_c, w_c, mask,   \

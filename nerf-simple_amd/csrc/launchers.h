@@ -32,6 +32,28 @@ struct DenseHeadArgs {
     float* g_theta;                                    // and every ray's row of d loss / d theta [B,6]
 };
 
+// What the masked compositor backward reads beside the rays (occupancy_train.hip), filled by the three entry points that
+// reach it (api.hip: the eager backward; occupancy_graph.hip: the two capped heads).  The upstream gradients are the MSE
+// head's where target != NULL and the five pointers otherwise; the fine pass's sampler runs behind the sweep where
+// ts_out != NULL.
+struct MaskedBackwardArgs {
+    const unsigned long long* mask;                    // [B, ceil(N / 64)]
+    const long long* offsets;                          // [B + 1]
+    const float* raw_live;
+    float* d_raw_live;
+    long long B;
+    long long capacity;                                // rows of raw_live / d_raw_live, the clamp of every row index and
+                                                       // the end of the zero fill; MASKED_NO_CLAMP: the rows are offsets[B]
+    const float *g_rgb, *g_disp, *g_alpha, *g_acc, *g_w;   // each may be NULL
+    const float* target;                               // the MSE head: [B,3]
+    float* rgb;                                        // [B,3]
+    float scale;                                       // 1 / (3 B): the launcher's
+    const float* u_f;                                  // the sampler: u_f[B, Nf] (unused with the counter RNG)
+    float* ts_out;                                     // [B, N + Nf]
+    int Nf;
+};
+constexpr long long MASKED_NO_CLAMP = 0x7fffffffffffffffll;
+
 extern "C" {
 int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
 int nerf_amd_launch_pack_train(const float*, void*, void*, hipStream_t);
@@ -112,8 +134,7 @@ int nerf_amd_launch_occ_scan(void*, long long*, long long*, long long, hipStream
 int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const long long*, float*, long long, long long, hipStream_t);
 int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
 int nerf_amd_occ_train_max_n(void);
-int nerf_amd_launch_occ_composite_backward(const MlpArgs*, const unsigned long long*, const long long*, const float*, const float*,
-                                           const float*, const float*, const float*, const float*, float*, long long, hipStream_t);
+int nerf_amd_launch_masked_backward(const MlpArgs*, const MaskedBackwardArgs*, hipStream_t);
 int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
 int nerf_amd_launch_sigma_noise(const float*, float*, float, unsigned long long, const unsigned long long*, long long, long long,
                                 int, hipStream_t);

@@ -45,7 +45,10 @@ constexpr int FUSED_RENDER_MAX_N = 768;
 // samples per ray of the masked render and of ray termination (occupancy.hip: the masked compositor's LDS row; the mask
 // layout) -- the fused render's own limit, so a masked render serves whatever the dense one does in one launch
 constexpr int MASKED_MAX_N = FUSED_RENDER_MAX_N;
-// samples per ray of every compositor backward (composite.hip, occupancy_train.hip, occupancy_graph.hip): the sweep
+// one wavefront per ray, this many rays per block: the launch shape of every per-ray kernel of the masked sources
+// (occupancy.hip, occupancy_train.hip, occupancy_graph.hip, occupancy_terminate.hip, guided_masked.hip)
+constexpr int MASKED_RAYS_PER_BLOCK = 4;
+// samples per ray of every compositor backward (composite.hip, occupancy_train.hip): the sweep
 // holds a ray in COMPOSITE_BWD_MAX_CHUNKS registers per lane (composite_backward_device.h)
 constexpr int COMPOSITE_BWD_MAX_CHUNKS = 8;
 constexpr int COMPOSITE_BWD_MAX_N = 64 * COMPOSITE_BWD_MAX_CHUNKS;

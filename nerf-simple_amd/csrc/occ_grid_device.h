@@ -1,6 +1,7 @@
-// occ_grid_device.h -- the occupancy grid as a kernel sees it and the test of one point against it, shared by the mark kernel
-// (occupancy.hip) and the masked guided sampler (guided_masked.hip); and where a ray's live count goes for the scan that
-// follows a mark (nerf_amd_launch_occ_scan, occupancy.hip).  Layout of the bits: include/nerf_amd.h.
+// occ_grid_device.h -- the occupancy grid as a kernel sees it, the test of one point against it and the mark of one ray
+// (mark_ray), shared by the mark kernel (occupancy.hip) and the masked guided sampler (guided_masked.hip); and where a ray's
+// live count goes for the scan that follows a mark (nerf_amd_launch_occ_scan, occupancy.hip).  Layout of the bits:
+// include/nerf_amd.h.
 #pragma once
 #include "nerf_device.h"
 
@@ -38,4 +39,25 @@ __device__ __forceinline__ bool sample_live(const OccGrid& g, float x, float y, 
     }
     const unsigned word = g.bits[(c[0] * g.cells[1] + c[1]) * g.wz + (c[2] >> 5)];
     return (word >> (c[2] & 31)) & 1u;
+}
+
+// One wavefront, one ray: the mark of its M samples.  point_of(i) is sample i's point (anything with x, y, z); its cell's
+// bit, one ballot per 64 samples -> mask_row[ceil(M / 64)], and the ray's live count -> *count_out.
+template <class PointOf>
+__device__ __forceinline__ void mark_ray(const OccGrid& g, int M, int lane, PointOf point_of, unsigned long long* mask_row,
+                                         int* count_out) {
+    const int words = (M + 63) >> 6;
+    int cnt = 0;
+    for (int q = 0; q < words; ++q) {
+        const int i = q * 64 + lane;
+        bool live = false;
+        if (i < M) {
+            const auto pt = point_of(i);
+            live = sample_live(g, pt.x, pt.y, pt.z);
+        }
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) mask_row[q] = m;
+        cnt += __popcll(m);
+    }
+    if (lane == 0) *count_out = cnt;
 }

@@ -1,8 +1,27 @@
-// occ_scan_device.h -- two device pieces the occupancy sources share: the workgroup exclusive scan behind every offsets[]
-// array (occupancy.hip, occupancy_terminate.hip) and the per-ray body of the emit kernels (occupancy.hip,
-// occupancy_graph.hip).  Fixed order, no atomics: every run writes the same bytes.
+// occ_scan_device.h -- the device pieces the occupancy sources share: the workgroup exclusive scan behind every offsets[]
+// array (occupancy.hip, occupancy_terminate.hip), the per-ray body of the emit kernels (occupancy.hip, occupancy_graph.hip)
+// and the per-ray prologue of the masked kernels (one wavefront per ray, nerf_layout::MASKED_RAYS_PER_BLOCK rays per block):
+// the ray's positions into an LDS slice, its dnorm, and the min the clamps are formed with.  Fixed order, no atomics: every
+// run writes the same bytes.
 #pragma once
-#include "nerf_device.h"
+#include "composite_device.h"
+
+using nerf_layout::MASKED_RAYS_PER_BLOCK;
+constexpr int MASKED_THREADS = 64 * MASKED_RAYS_PER_BLOCK;
+
+__device__ __forceinline__ long long min_ll(long long a, long long b) { return a < b ? a : b; }
+
+// the ray's N positions, as every render forms them, into ts[] (the wave's own LDS slice), fenced for the wave's reads
+__device__ __forceinline__ void fill_ray_positions(const MlpArgs& a, long long ray, int lane, float* ts) {
+    for (int i = lane; i < a.N; i += 64) ts[i] = fetch_point_rays<false>(a, ray * a.N + i, RaySample{ray, i}).t;
+    wave_lds_fence();
+}
+
+// the norm of the ray's unit direction, the compositor's scale of every interval
+__device__ __forceinline__ float ray_dnorm(const MlpArgs& a, long long ray) {
+    const float* d = a.rays + ray * 6 + 3;
+    return nerf_composite::unit_dir_norm(d[0], d[1], d[2], true);
+}
 
 // exclusive scan of one value per thread over a workgroup of THREADS threads, in thread order, and the block total.  The
 // leading barrier makes a second call on the same lds_waves[THREADS / 64] safe: the slots may still be read from the first.

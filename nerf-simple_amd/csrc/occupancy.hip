@@ -26,7 +26,6 @@
 
 namespace {
 
-constexpr int OCC_RAYS_PER_BLOCK = 4;
 constexpr int OCC_MAX_N = nerf_layout::MASKED_MAX_N;      // samples per ray (the fused render's own limit, nerf_layout.h)
 constexpr int OCC_MAX_DILATE = 15;             // 33 + 2 d grid points along z feed one word: one per lane
 constexpr int OCC_SCAN_THREADS = 256;
@@ -73,26 +72,12 @@ __global__ __launch_bounds__(256) void occ_pack_kernel(const unsigned char* __re
 }
 
 // ---- mark ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * OCC_RAYS_PER_BLOCK) void occ_mark_kernel(MlpArgs a, OccGrid g,
-                                                                           unsigned long long* __restrict__ mask,
-                                                                           int* __restrict__ counts, long long B) {
-    const long long ray = (long long)blockIdx.x * OCC_RAYS_PER_BLOCK + (threadIdx.x >> 6);
+__global__ __launch_bounds__(MASKED_THREADS) void occ_mark_kernel(MlpArgs a, OccGrid g, unsigned long long* __restrict__ mask,
+                                                                  int* __restrict__ counts, long long B) {
+    const long long ray = (long long)blockIdx.x * MASKED_RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= B) return;                      // whole wave leaves together
-    const int lane = threadIdx.x & 63;
-    const int words = (a.N + 63) >> 6;
-    int cnt = 0;
-    for (int q = 0; q < words; ++q) {
-        const int i = q * 64 + lane;
-        bool live = false;
-        if (i < a.N) {
-            const PointIn pt = fetch_point_rays<false>(a, ray * a.N + i, RaySample{ray, i});
-            live = sample_live(g, pt.x, pt.y, pt.z);
-        }
-        const unsigned long long m = __ballot(live);
-        if (lane == 0) mask[ray * words + q] = m;
-        cnt += __popcll(m);
-    }
-    if (lane == 0) counts[ray] = cnt;
+    mark_ray(g, a.N, threadIdx.x & 63, [&](int i) { return fetch_point_rays<false>(a, ray * a.N + i, RaySample{ray, i}); },
+             mask + ray * ((a.N + 63) >> 6), counts + ray);
 }
 
 // ---- scan ----------------------------------------------------------------------------------------------------------------
@@ -158,11 +143,11 @@ __global__ __launch_bounds__(OCC_SCAN_THREADS) void occ_offsets_kernel(const int
 }
 
 // ---- emit ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * OCC_RAYS_PER_BLOCK) void occ_emit_kernel(MlpArgs a, const unsigned long long* __restrict__ mask,
+__global__ __launch_bounds__(MASKED_THREADS) void occ_emit_kernel(MlpArgs a, const unsigned long long* __restrict__ mask,
                                                                            const long long* __restrict__ offsets,
                                                                            float* __restrict__ pts, long long max_points,
                                                                            long long B) {
-    const long long ray = (long long)blockIdx.x * OCC_RAYS_PER_BLOCK + (threadIdx.x >> 6);
+    const long long ray = (long long)blockIdx.x * MASKED_RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= B) return;
     const int lane = threadIdx.x & 63;
     const long long first = offsets[ray];
@@ -189,20 +174,18 @@ struct MaskedSamples {
     }
 };
 
-__global__ __launch_bounds__(64 * OCC_RAYS_PER_BLOCK) void occ_composite_kernel(MlpArgs a, const unsigned long long* __restrict__ mask,
+__global__ __launch_bounds__(MASKED_THREADS) void occ_composite_kernel(MlpArgs a, const unsigned long long* __restrict__ mask,
                                                                                 const long long* __restrict__ offsets,
                                                                                 const float* __restrict__ raw,
                                                                                 nerf_composite::RayOut o, long long B) {
-    __shared__ float s_t[OCC_RAYS_PER_BLOCK][OCC_MAX_N];
+    __shared__ float s_t[MASKED_RAYS_PER_BLOCK][OCC_MAX_N];
     const int wv = threadIdx.x >> 6;
-    const long long ray = (long long)blockIdx.x * OCC_RAYS_PER_BLOCK + wv;
+    const long long ray = (long long)blockIdx.x * MASKED_RAYS_PER_BLOCK + wv;
     if (ray >= B) return;                      // whole wave leaves together; no workgroup barrier below
     const int lane = threadIdx.x & 63;
     const int N = a.N;
-    for (int i = lane; i < N; i += 64) s_t[wv][i] = fetch_point_rays<false>(a, ray * N + i, RaySample{ray, i}).t;
-    wave_lds_fence();
-    const float* d = a.rays + ray * 6 + 3;
-    const float dnorm = nerf_composite::unit_dir_norm(d[0], d[1], d[2], true);
+    fill_ray_positions(a, ray, lane, s_t[wv]);
+    const float dnorm = ray_dnorm(a, ray);
     const long long first = offsets[ray];
     const MaskedSamples src{s_t[wv], mask + ray * ((N + 63) >> 6), reinterpret_cast<const f32x4*>(raw) + first,
                             offsets[ray + 1] - first};
@@ -275,8 +258,8 @@ extern "C" int nerf_amd_launch_occ_mark(const MlpArgs* args, const unsigned* bit
     (void)hipGetLastError();
     const OccGrid g = occ_grid_args(bits, nx, ny, nz, h_lo, h_inv_step, outside_live);
     if (B > 0) {
-        const long long blocks = (B + OCC_RAYS_PER_BLOCK - 1) / OCC_RAYS_PER_BLOCK;
-        hipLaunchKernelGGL(occ_mark_kernel, dim3((unsigned)blocks), dim3(64 * OCC_RAYS_PER_BLOCK), 0, stream, *args, g, mask,
+        const long long blocks = (B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK;
+        hipLaunchKernelGGL(occ_mark_kernel, dim3((unsigned)blocks), dim3(MASKED_THREADS), 0, stream, *args, g, mask,
                            occ_ws_counts(ws), B);
     }
     return nerf_amd_launch_occ_scan(ws, offsets, live, B, stream);
@@ -286,8 +269,8 @@ extern "C" int nerf_amd_launch_occ_emit(const MlpArgs* args, const unsigned long
                                         long long max_points, long long B, hipStream_t stream) {
     (void)hipGetLastError();
     if (B == 0) return 0;
-    const long long blocks = (B + OCC_RAYS_PER_BLOCK - 1) / OCC_RAYS_PER_BLOCK;
-    hipLaunchKernelGGL(occ_emit_kernel, dim3((unsigned)blocks), dim3(64 * OCC_RAYS_PER_BLOCK), 0, stream, *args, mask, offsets, pts,
+    const long long blocks = (B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK;
+    hipLaunchKernelGGL(occ_emit_kernel, dim3((unsigned)blocks), dim3(MASKED_THREADS), 0, stream, *args, mask, offsets, pts,
                        max_points, B);
     return (int)hipGetLastError();
 }
@@ -296,9 +279,9 @@ extern "C" int nerf_amd_launch_occ_composite(const MlpArgs* args, const unsigned
                                              const float* raw, long long B, hipStream_t stream) {
     (void)hipGetLastError();
     if (B == 0) return 0;
-    const long long blocks = (B + OCC_RAYS_PER_BLOCK - 1) / OCC_RAYS_PER_BLOCK;
+    const long long blocks = (B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK;
     const nerf_composite::RayOut o{args->rgb, args->disp, args->alpha, args->acc, args->w, args->pixels};
-    hipLaunchKernelGGL(occ_composite_kernel, dim3((unsigned)blocks), dim3(64 * OCC_RAYS_PER_BLOCK), 0, stream, *args, mask, offsets,
+    hipLaunchKernelGGL(occ_composite_kernel, dim3((unsigned)blocks), dim3(MASKED_THREADS), 0, stream, *args, mask, offsets,
                        raw, o, B);
     return (int)hipGetLastError();
 }

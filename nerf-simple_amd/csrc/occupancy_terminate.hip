@@ -25,7 +25,6 @@
 
 namespace {
 
-constexpr int TERM_RAYS_PER_BLOCK = 4;
 constexpr int TERM_SCAN_THREADS = 256;
 constexpr int TERM_SCAN_PER_THREAD = 8;
 constexpr long long TERM_SCAN_ITEMS = (long long)TERM_SCAN_THREADS * TERM_SCAN_PER_THREAD;      // rays per scan block
@@ -48,10 +47,8 @@ struct TermArgs {
     int* rem;                                  // [B]: M0 bits at or beyond s1 of a ray still alive
 };
 
-__device__ __forceinline__ long long term_min(long long a, long long b) { return a < b ? a : b; }
-
-__global__ __launch_bounds__(64 * TERM_RAYS_PER_BLOCK) void term_advance_kernel(MlpArgs a, TermArgs t, long long B) {
-    const long long ray = (long long)blockIdx.x * TERM_RAYS_PER_BLOCK + (threadIdx.x >> 6);
+__global__ __launch_bounds__(MASKED_THREADS) void term_advance_kernel(MlpArgs a, TermArgs t, long long B) {
+    const long long ray = (long long)blockIdx.x * MASKED_RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= B) return;                      // whole wave leaves together; no workgroup barrier below
     const int lane = threadIdx.x & 63;
     const int N = a.N, W = (N + 63) >> 6, K = (N + t.S - 1) / t.S;
@@ -67,12 +64,12 @@ __global__ __launch_bounds__(64 * TERM_RAYS_PER_BLOCK) void term_advance_kernel(
         const unsigned long long mw = m0[q], below = (1ull << lane) - 1ull;
         const long long row0 = t.offsets0[ray] + before + __popcll(mw & below);
         f32x4 c = {0.f, 0.f, 0.f, -__builtin_inff()};
-        if (((mw >> lane) & 1ull) && i < t.s1 && row0 >= 0 && row0 < term_min(t.offsets0[ray + 1], t.rows0)) {
+        if (((mw >> lane) & 1ull) && i < t.s1 && row0 >= 0 && row0 < min_ll(t.offsets0[ray + 1], t.rows0)) {
             bool retired = false;
             if (t.raw_slab && i >= t.s0) {
                 const unsigned long long ms = t.mask_slab[ray * W + q];
                 const long long src = t.offsets_slab[ray] + __popcll(ms & below);
-                if (((ms >> lane) & 1ull) && src >= 0 && src < term_min(t.offsets_slab[ray + 1], t.rows_slab)) {
+                if (((ms >> lane) & 1ull) && src >= 0 && src < min_ll(t.offsets_slab[ray + 1], t.rows_slab)) {
                     c = t.raw_slab[src];
                     t.raw0[row0] = c;
                     retired = true;
@@ -85,18 +82,9 @@ __global__ __launch_bounds__(64 * TERM_RAYS_PER_BLOCK) void term_advance_kernel(
         if (i < N && i <= t.s1) tc = fetch_point_rays<false>(a, ray * N + i, RaySample{ray, i}).t;
         float tn = __shfl_down(tc, 1);
         if (lane == 63 && i + 1 < N && i < t.s1) tn = fetch_point_rays<false>(a, ray * N + i + 1, RaySample{ray, i + 1}).t;
-        const float* d = a.rays + ray * 6 + 3;
-        const float dnorm = nerf_composite::unit_dir_norm(d[0], d[1], d[2], true);
-        float fac = 1.0f;
-        if (i < t.s1) {
-            // composite_ray's factor of sample i, op for op (composite_device.h)
-            float delta = (i == N - 1) ? 1e10f : sub_rn(tn, tc);
-            delta = mul_rn(delta, dnorm);
-            const float sigma = c[3];
-            const float sp = sigma > 20.f ? sigma : log1pf(expf(sigma));
-            const float al = sub_rn(1.0f, expf(mul_rn(-sp, delta)));
-            fac = add_rn(sub_rn(1.0f, al), 1e-10f);
-        }
+        const float dnorm = ray_dnorm(a, ray);
+        float fac = 1.0f;      // composite_ray's factor of sample i: the routine it calls (composite_device.h)
+        if (i < t.s1) fac = nerf_composite::alpha_factor((i == N - 1) ? 1e10f : sub_rn(tn, tc), dnorm, c[3]).fac;
         const float incl = nerf_composite::wave_scan_mul(fac);
         const float upto = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), t.s1 - cb - 1));
         T = mul_rn(t.carry[ray], upto);
@@ -255,8 +243,8 @@ extern "C" int nerf_amd_termination_advance(const float* raw_slab, const uint64_
     t.rem = reinterpret_cast<int*>(b + w.off_rem);
     long long* blk = reinterpret_cast<long long*>(b + w.off_blk);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const long long blocks = (B + TERM_RAYS_PER_BLOCK - 1) / TERM_RAYS_PER_BLOCK;
-    hipLaunchKernelGGL(term_advance_kernel, dim3((unsigned)blocks), dim3(64 * TERM_RAYS_PER_BLOCK), 0, s, a, t, (long long)B);
+    const long long blocks = (B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK;
+    hipLaunchKernelGGL(term_advance_kernel, dim3((unsigned)blocks), dim3(MASKED_THREADS), 0, s, a, t, (long long)B);
     hipLaunchKernelGGL(term_block_sum_kernel, dim3((unsigned)w.nblk), dim3(TERM_SCAN_THREADS), 0, s, (const int*)t.cnt,
                        (const int*)t.rem, (long long)B, blk);
     hipLaunchKernelGGL(term_offsets_kernel, dim3((unsigned)w.nblk), dim3(TERM_SCAN_THREADS), 0, s, (const int*)t.cnt, (long long)B,

@@ -1,5 +1,5 @@
 """torch / numpy restatement of the masked hierarchical pair (include/nerf_amd.h, "masked hierarchical pair";
-csrc/occupancy_hier.hip; training.train_step_hierarchical(occupancy=) / GraphedMaskedHierarchicalTrainStep; DESIGN.md
+csrc/occupancy_graph.hip; training.train_step_hierarchical(occupancy=) / GraphedMaskedHierarchicalTrainStep; DESIGN.md
 section 15), built from tests/occupancy_model.py, tests/occupancy_train_model.py, tests/occupancy_graphed_model.py and the
 oracle's sample_pdf.  Test infrastructure; nothing here is fitted to what the GPU showed.
 

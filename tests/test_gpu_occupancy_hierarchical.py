@@ -1,4 +1,4 @@
-"""The masked hierarchical pair on the GPU (csrc/occupancy_hier.hip, training.train_step_hierarchical(occupancy=),
+"""The masked hierarchical pair on the GPU (csrc/occupancy_graph.hip, csrc/occupancy_train.hip, training.train_step_hierarchical(occupancy=),
 training.GraphedMaskedHierarchicalTrainStep, rendering.render_hierarchical[_view](occupancy=)).
 Yardsticks: tests/occupancy_hierarchical_model.py on the occupancy / graphed models.
 

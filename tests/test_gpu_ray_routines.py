@@ -238,7 +238,8 @@ def test_four_backward_kernels_write_the_same_bytes(dev, N):
     """The compositor's backward walk is one routine (csrc/composite_backward_device.h): from the same raw and gt, under an
     all-live mask, the dense MSE backward, the masked backward fed the g_rgb nerf_amd_mse_loss forms, the capped head at
     C = B N and the capped pdf head at C = B N (Nf = 8) write the same d_raw bytes.  N: one partial chunk, one full chunk, a
-    chunk seam, and the pdf head's four-chunk limit."""
+    chunk seam, and the pdf head's four-chunk limit.  Then, under a sparse mask, the three masked launches among themselves:
+    the same d_raw and rgb bytes at C = P', and the two capped heads the same bytes at C = P' - 3."""
     from nerf_simple_amd import _lib
     lib, ptr = _lib.lib(), _lib.ptr
     st = _lib.stream_ptr(dev)
@@ -276,6 +277,55 @@ def test_four_backward_kernels_write_the_same_bytes(dev, N):
     assert torch.equal(rgb_head, rgb) and torch.equal(rgb_pdf, rgb)
     for name, d in (("masked backward", d_masked), ("capped head", d_head), ("capped pdf head", d_pdf)):
         assert torch.equal(d.view(torch.int32), want), name
+
+    # A second, sparse mask, compared among the three masked launches (one kernel, csrc/occupancy_train.hip, under its three
+    # heads): ray 0 dead -- the nothing-kept early out in both LDS layouts --, ray 1 live at its last sample only, rays 2 .. 4
+    # live at i with (7 i + 3 ray) % 5 < 2, across the mask word boundary from N = 65 on.
+    s = np.arange(N)
+    live = np.zeros((B, N), bool)
+    live[1, N - 1] = True
+    for r in range(2, B):
+        live[r] = (7 * s + 3 * r) % 5 < 2
+    counts = live.sum(1)
+    P = int(counts.sum())
+    assert P >= 4 and (N != 3 or counts.tolist() == [0, 1, 2, 1, 1])
+    assert N < 65 or any(live[r, :64].any() and live[r, 64:].any() for r in range(B))
+    words2 = np.zeros((B, (N + 63) // 64), np.uint64)
+    for r, k in zip(*np.nonzero(live)):
+        words2[r, k // 64] |= np.uint64(1) << np.uint64(k % 64)
+    mask2 = torch.from_numpy(words2.view(np.int64)).to(dev)
+    offsets2 = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)).to(dev)
+    raw_live = raw.view(B * N, 4)[torch.from_numpy(live.reshape(-1)).to(dev)].contiguous()
+    jit2 = (ptr(rays), ptr(ts), None, TS_GIVEN, 0, 0, ptr(mask2), ptr(offsets2))
+    rgb_fwd, disp, acc = nan(B, 3), nan(B), nan(B)
+    _lib.check(lib.nerf_amd_volume_render_masked(ptr(raw_live), *jit2, ptr(rgb_fwd), ptr(disp), None, ptr(acc), None, B, N, st),
+               "nerf_amd_volume_render_masked")
+    g_rgb2, d_eager = nan(B, 3), nan(P, 4)
+    _lib.check(lib.nerf_amd_mse_loss(ptr(rgb_fwd), ptr(gt), ptr(loss), ptr(g_rgb2), B * 3, st), "nerf_amd_mse_loss")
+    _lib.check(lib.nerf_amd_volume_render_masked_backward(ptr(raw_live), *jit2, ptr(g_rgb2), None, None, None, None, ptr(d_eager), B, N,
+                                                          st), "nerf_amd_volume_render_masked_backward")
+
+    def heads(C):
+        """(rgb, d_raw[C]) of the capped head and of the capped pdf head at capacity C"""
+        rgb_a, d_a, rgb_b, d_b, ts_b = nan(B, 3), nan(C, 4), nan(B, 3), nan(C, 4), nan(B, N + Nf)
+        _lib.check(lib.nerf_amd_volume_render_masked_mse_backward(ptr(raw_live), *jit2, ptr(gt), ptr(rgb_a), ptr(d_a), C, B, N, st),
+                   "nerf_amd_volume_render_masked_mse_backward")
+        _lib.check(lib.nerf_amd_volume_render_masked_mse_backward_pdf(ptr(raw_live), *jit2, ptr(gt), ptr(u_f), ptr(rgb_b), ptr(d_b),
+                                                                      ptr(ts_b), C, B, N, Nf, st),
+                   "nerf_amd_volume_render_masked_mse_backward_pdf")
+        torch.cuda.synchronize(dev)
+        assert torch.isfinite(ts_b).all()
+        return rgb_a.view(torch.int32), d_a.view(torch.int32), rgb_b.view(torch.int32), d_b.view(torch.int32)
+
+    rgb_a, d_a, rgb_b, d_b = heads(P)                                # C = P': nothing is cut
+    assert torch.isfinite(d_eager).all() and (d_eager != 0).any() and (rgb_fwd[0] == 0).all()
+    assert torch.equal(rgb_a, rgb_fwd.view(torch.int32)) and torch.equal(rgb_b, rgb_a)
+    assert torch.equal(d_a, d_eager.view(torch.int32)) and torch.equal(d_b, d_a)
+    rgb_a, d_a, rgb_b, d_b = heads(P - 3)                            # the clamp cuts inside a ray
+    first = np.cumsum(counts) - counts
+    assert ((first < P - 3) & (P - 3 < first + counts)).any()
+    assert torch.equal(rgb_b, rgb_a) and torch.equal(d_b, d_a)
+    assert torch.isfinite(d_a.view(torch.float32)).all() and torch.isfinite(rgb_a.view(torch.float32)).all()
 
 
 @pytest.mark.parametrize("case", M.pdf_cases(), ids=lambda c: c.id)

@@ -183,22 +183,12 @@ def test_capacity_rule_is_capacity_points(monkeypatch):
 
 
 def test_new_kernels_pass_the_static_isa_checks():
-    """tools/check_vmcnt.py on csrc/occupancy_graph.hip: no counted vmcnt wait is short, no wide store has its data
-    registers overwritten by the next instruction, and no kernel uses an atomic (every row is written by exactly one lane)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import check_vmcnt
-    finally:
-        sys.path.pop(0)
-    asm = check_vmcnt.assemble(os.path.join(ROOT, "nerf-simple_amd", "csrc", "occupancy_graph.hip"))
-    kernels = check_vmcnt.kernels_of(asm)
-    assert len(kernels) == 2 and any("occ_emit_capped_kernel" in k for k in kernels) \
-        and any("occ_head_capped_kernel" in k for k in kernels), list(kernels)
-    for name, lines in kernels.items():
-        checked, bad = check_vmcnt.check_kernel(lines)
-        assert not bad, (name, bad[:5])
-        n, offenders = check_vmcnt.check_store_data_hazard(lines)
-        assert not offenders, (name, offenders[:3])
-        text = "\n".join(lines) if not isinstance(lines, str) else lines
-        assert "atomic" not in text, name
+    """tools/check_vmcnt.py (tests/static_isa.py) on the two kernels of the step: no counted vmcnt wait is short, no wide store
+    has its data registers overwritten by the next instruction, and no kernel uses an atomic (every row is written by exactly
+    one lane).  occ_emit_capped_kernel is csrc/occupancy_graph.hip's only kernel; the fused head is the (MseHead, 0)
+    instantiation of the masked compositor backward in csrc/occupancy_train.hip."""
+    import static_isa
+    kernels = static_isa.checked_kernels("occupancy_graph.hip")
+    assert len(kernels) == 1 and all("occ_emit_capped_kernel" in k for k in kernels), list(kernels)
+    heads = static_isa.masked_backward_instantiations(static_isa.checked_kernels("occupancy_train.hip"))
+    assert heads.count(("MseHead", 0)) == 1, heads

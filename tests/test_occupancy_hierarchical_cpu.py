@@ -2,7 +2,7 @@
 of nerf_amd_volume_render_masked_mse_backward_pdf -- nothing touches a device), the composition model
 (tests/occupancy_hierarchical_model.py) against its parts, the coarse live counts of the GPU tests' inputs
 (tests/test_gpu_occupancy_hierarchical.py) from the existing CPU model, the Python surface and its refusals, and the
-static ISA checks of csrc/occupancy_hier.hip."""
+static ISA checks of the masked coarse head (csrc/occupancy_train.hip)."""
 import ctypes
 import inspect
 import os
@@ -210,21 +210,9 @@ def test_refusals_that_need_no_gpu_leave_the_generator_untouched():
 
 
 def test_new_kernel_passes_the_static_isa_checks():
-    """tools/check_vmcnt.py on csrc/occupancy_hier.hip: the four keys-per-lane instantiations, no counted vmcnt wait is short,
-    no wide store has its data registers overwritten by the next instruction, and no kernel uses an atomic."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import check_vmcnt
-    finally:
-        sys.path.pop(0)
-    asm = check_vmcnt.assemble(os.path.join(ROOT, "nerf-simple_amd", "csrc", "occupancy_hier.hip"))
-    kernels = check_vmcnt.kernels_of(asm)
-    assert len(kernels) == 4 and all("occ_head_capped_pdf_kernel" in k for k in kernels), list(kernels)
-    for name, lines in kernels.items():
-        checked, bad = check_vmcnt.check_kernel(lines)
-        assert not bad, (name, bad[:5])
-        n, offenders = check_vmcnt.check_store_data_hazard(lines)
-        assert not offenders, (name, offenders[:3])
-        text = "\n".join(lines) if not isinstance(lines, str) else lines
-        assert "atomic" not in text, name
+    """tools/check_vmcnt.py (tests/static_isa.py) on the masked coarse head, the sampler instantiations of the masked compositor
+    backward in csrc/occupancy_train.hip: exactly the four keys-per-lane ones, no counted vmcnt wait is short, no wide store
+    has its data registers overwritten by the next instruction, and no kernel uses an atomic."""
+    import static_isa
+    heads = static_isa.masked_backward_instantiations(static_isa.checked_kernels("occupancy_train.hip"))
+    assert [h for h in heads if h[1] > 0] == [("MseHead", 1), ("MseHead", 2), ("MseHead", 4), ("MseHead", 8)], heads

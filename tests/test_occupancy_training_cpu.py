@@ -240,21 +240,11 @@ def test_steps_until_dead():
 
 
 def test_new_kernels_pass_the_static_isa_checks():
-    """tools/check_vmcnt.py on csrc/occupancy_train.hip: no counted vmcnt wait is short, and no wide store has its data
-    registers overwritten by the next instruction (the store-data hazard of csrc/nerf_device.h store_granule)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import check_vmcnt
-    finally:
-        sys.path.pop(0)
-    asm = check_vmcnt.assemble(os.path.join(ROOT, "nerf-simple_amd", "csrc", "occupancy_train.hip"))
-    kernels = check_vmcnt.kernels_of(asm)
-    assert len(kernels) == 2 and any("occ_composite_backward_kernel" in k for k in kernels), list(kernels)
-    for name, lines in kernels.items():
-        checked, bad = check_vmcnt.check_kernel(lines)
-        assert not bad, (name, bad[:5])
-        n, offenders = check_vmcnt.check_store_data_hazard(lines)
-        assert not offenders, (name, offenders[:3])
-        text = "\n".join(lines) if not isinstance(lines, str) else lines
-        assert "atomic" not in text, name                       # every output row is written by exactly one lane
+    """tools/check_vmcnt.py on csrc/occupancy_train.hip (tests/static_isa.py): no counted vmcnt wait is short, no wide store
+    has its data registers overwritten by the next instruction, no atomic.  The source holds the six instantiations of the
+    masked compositor backward -- the eager backward's is (FiveGrads, 0) -- and occ_decay_max_kernel, and nothing else."""
+    import static_isa
+    kernels = static_isa.checked_kernels("occupancy_train.hip")
+    assert static_isa.masked_backward_instantiations(kernels) == \
+        [("FiveGrads", 0), ("MseHead", 0), ("MseHead", 1), ("MseHead", 2), ("MseHead", 4), ("MseHead", 8)], list(kernels)
+    assert len(kernels) == 7 and sum("occ_decay_max_kernel" in k for k in kernels) == 1, list(kernels)
