@@ -27,6 +27,7 @@
 // point in all); 128 FLOP per byte.
 #include "nerf_device.h"
 #include "launchers.h"
+#include "dw_products.h"
 
 using namespace nerf_layout;
 
@@ -93,9 +94,9 @@ __device__ __forceinline__ bf16x8 whole(const Frag& f) {
 
 __global__ __launch_bounds__(512, 2) void dw_gemm_kernel(GemmTable tab) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // which product, which K slice
-    int di = 0;
-    while (di + 1 < tab.n && (int)blockIdx.x >= tab.d[di + 1].wg0) ++di;
+    // which product, which K slice (dw_products.h)
+    int di;
+    dw_product_of_workgroup(tab, di);
     const GemmDesc d = tab.d[di];
     const int slice = blockIdx.x - d.wg0;
     const long long nslab = (tab.P + SLAB - 1) / SLAB;
@@ -362,10 +363,10 @@ extern "C" int nerf_amd_launch_param_gradients_begin(const float* d_raw, void* s
     return (int)hipGetLastError();
 }
 
-// bucket 0: all 14 products in one launch.  Buckets 1 and 2 split them at the boundary of the flat gradient
-// vector that data-parallel training reduces in two pieces (nerf_layout.h GRAD_BUCKET_SPLIT): bucket 1 = the LATE
-// layers (skip_conn_layer ... color_fc.2, the tail of the vector), bucket 2 = layers_0.* (its head), so the
-// all-reduce of bucket 1 runs while bucket 2 is still being computed.  Either launch fills the chip.
+// bucket 0: all 14 products in one launch.  Buckets 1 and 2 (dw_products.h dw_plan) split them at the boundary of the flat
+// gradient vector that data-parallel training reduces in two pieces: bucket 1 = the LATE layers (skip_conn_layer ...
+// color_fc.2, the tail of the vector), bucket 2 = layers_0.* (its head), so the all-reduce of bucket 1 runs while bucket 2
+// is still being computed.  Either launch fills the chip.
 extern "C" int nerf_amd_launch_param_gradients_finish(const void* acts_v, const void* dys_v, const void* posx64_v,
                                                       const void* posd32_v, const void* scratch, float* grads,
                                                       long long P, int bucket, hipStream_t stream) {
@@ -377,87 +378,32 @@ extern "C" int nerf_amd_launch_param_gradients_finish(const void* acts_v, const 
     const __bf16* posx = reinterpret_cast<const __bf16*>(posx64_v);
     const __bf16* posd = reinterpret_cast<const __bf16*>(posd32_v);
     const __bf16* dsr = reinterpret_cast<const __bf16*>(scratch);
-    // point-blocked activation layers (nerf_layout.h): layer L at L * act_layer_stride(P) bytes; leading dimension 0
-    auto act = [&](int L) { return acts + act_offset_bytes(L, P) / 2; };
-    auto dy = [&](int L) { return dys + act_offset_bytes(L, P) / 2; };
-    constexpr int BLK = 0;
-
+    // a DwOperand as this kernel reads it: point-blocked layers (nerf_layout.h: layer L at L * act_layer_stride(P) bytes) have
+    // leading dimension 0, the row-major operands are as wide as their rows
+    struct Operand { const __bf16* p; int ld, width; };
+    auto operand = [&](DwOperand o) -> Operand {
+        const int w = dw_operand_width(o, DW_BF16);
+        if (o.kind == DwKind::DY || o.kind == DwKind::ACT)
+            return {(o.kind == DwKind::DY ? dys : acts) + act_offset_bytes(o.layer, P) / 2, 0, w};
+        return {o.kind == DwKind::POSX ? posx : o.kind == DwKind::POSD ? posd : dsr, w, w};
+    };
+    // which products, on which workgroups: dw_products.h
+    const DwPlan plan = dw_plan(DW_BF16, P, bucket, device_cus());
     GemmTable t{};
     t.P = P;
-    int n = 0;
-    auto add = [&](const __bf16* A, int lda, int M, const __bf16* B, int ldb, int N, int coff, int ldc, int r0,
-                   int Mv, int Nv, int boff = -1) {
-        GemmDesc& g = t.d[n++];
-        g.A = A; g.lda = lda; g.M = M; g.B = B; g.ldb = ldb; g.N = N;
-        g.C = grads + coff; g.ldc = ldc; g.r0 = r0; g.Mv = Mv; g.Nv = Nv;
-        g.bias = boff >= 0 ? grads + boff : nullptr;      // db of the layer whose dY is this product's A (point-blocked A only)
-    };
-    const int LW = 256 * 256 + 256;
-    add(dy(0), BLK, 256, posx, 64, 64, OFF_L0_W, 63, 0, 256, 63, OFF_L0_B);               // layers_0.0
-    for (int l = 1; l <= 4; ++l)                                                          // layers_0.{2,4,6,8}
-        add(dy(l), BLK, 256, act(l - 1), BLK, 256, OFF_L1_W + (l - 1) * LW, 256, 0, 256, 256,
-            OFF_L1_W + (l - 1) * LW + 65536);
-    add(dy(5), BLK, 256, act(4), BLK, 256, OFF_SKIP_W, 319, 0, 256, 256, OFF_SKIP_B);     // skip [h ; x]: h part
-    add(dy(5), BLK, 256, posx, 64, 64, OFF_SKIP_W + 256, 319, 0, 256, 63);                //               x part
-    add(dy(6), BLK, 256, act(5), BLK, 256, OFF_L6_W, 256, 0, 256, 256, OFF_L6_W + 65536); // layers_1.0
-    add(dy(7), BLK, 256, act(6), BLK, 256, OFF_L6_W + LW, 256, 0, 256, 256, OFF_L6_W + LW + 65536);  // layers_1.2
-    add(dsr, 32, 32, act(7), BLK, 256, OFF_SIG_W, 256, 3, 1, 256);                        // sigma_fc.0 (row 3 of dsr)
-    add(dy(8), BLK, 256, act(7), BLK, 256, OFF_L2_W, 256, 0, 256, 256, OFF_L2_B);         // layers_2
-    add(dy(9), BLK, 128, act(8), BLK, 256, OFF_C0_W, 283, 0, 128, 256, OFF_C0_B);         // color_fc.0 [h ; d]: h part
-    add(dy(9), BLK, 128, posd, 32, 32, OFF_C0_W + 256, 283, 0, 128, 27);                  //                      d part
-    add(dsr, 32, 32, act(9), BLK, 128, OFF_C1_W, 128, 0, 3, 128);                         // color_fc.2 (rows 0..2)
-    if (bucket != 0) {
-        // keep the products whose destination lies in this bucket's part of the flat vector
-        int m = 0;
-        for (int i = 0; i < n; ++i) {
-            const bool head = t.d[i].C - grads < GRAD_BUCKET_SPLIT;
-            if (head == (bucket == 2)) t.d[m++] = t.d[i];
-        }
-        n = m;
-    }
-    t.n = n;
-    // workgroups per product, one per CU in total.  A slab costs a workgroup the bytes it streams,
-    // (M + N) * 2 per point, plus a fixed part (barrier, DMA issue, fragment reads) that measures
-    // larger than the byte part: profiles/r01e_dw_sweep.jsonl -- weights (M + N) + c with c = 0 /
-    // 256 / 1024 / 8192 give 0.79 / 0.63 / 0.62 / 0.61 ms at 262144 points.  (Sizing by flops
-    // left the thin products -- 32 x 256 reads as much of X as 256 x 256 -- as a 2 ms tail.)
-    constexpr double slab_cost = 1024.0;
-    const int cus = device_cus();
-    double total = 0;
-    for (int i = 0; i < n; ++i) total += (double)(t.d[i].M + t.d[i].N) + slab_cost;
-    const long long nslab = (P + SLAB - 1) / SLAB;
-    // exactly `cus` workgroups in total when the slices allow it (the 128 KiB ring leaves one
-    // workgroup per CU, so a 257th would run as a second wave and double the kernel's time):
-    // floor of each share, then the largest remainders get the leftover workgroups
-    const long long need = (P * 512 >> 30) + 1;           // a slice's operand stays below 1 GiB (32-bit buffer range)
-    long long w[16];
-    double rem[16];
-    long long used = 0;
-    for (int i = 0; i < n; ++i) {
-        const double share = ((double)(t.d[i].M + t.d[i].N) + slab_cost) / total * cus;
-        w[i] = (long long)share;
-        rem[i] = share - (double)w[i];
-        if (w[i] < need) { w[i] = need; rem[i] = 0; }
-        if (w[i] >= nslab) { w[i] = nslab; rem[i] = -1; }
-        used += w[i];
-    }
-    while (used < cus) {
-        int best = -1;
-        for (int i = 0; i < n; ++i)
-            if (rem[i] >= 0 && w[i] < nslab && (best < 0 || rem[i] > rem[best])) best = i;
-        if (best < 0) break;
-        ++w[best]; rem[best] = 0; ++used;      // a second round goes by product order
-    }
-    int wg = 0;
-    for (int i = 0; i < n; ++i) {
-        t.d[i].wg0 = wg;
-        t.d[i].wgs = (int)w[i];
-        wg += (int)w[i];
+    t.n = plan.n;
+    for (int i = 0; i < plan.n; ++i) {
+        const DwProduct& p = DW_PRODUCTS[plan.product[i]];
+        const Operand A = operand(p.a), B = operand(p.b);
+        GemmDesc& g = t.d[i];
+        g.A = A.p; g.lda = A.ld; g.M = A.width; g.B = B.p; g.ldb = B.ld; g.N = B.width;
+        g.C = grads + p.coff; g.ldc = p.ldc; g.r0 = p.r0; g.Mv = p.Mv; g.Nv = p.Nv;
+        g.bias = p.boff >= 0 ? grads + p.boff : nullptr;      // db of the layer whose dY is this product's A (point-blocked A only)
+        g.wg0 = plan.wg0[i]; g.wgs = plan.wgs[i];
     }
     e = allow_dynamic_lds(reinterpret_cast<const void*>(dw_gemm_kernel), LDS_BYTES);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(dw_gemm_kernel, dim3(wg), dim3(512), LDS_BYTES, stream, t);
-
+    hipLaunchKernelGGL(dw_gemm_kernel, dim3(plan.workgroups), dim3(512), LDS_BYTES, stream, t);
     return (int)hipGetLastError();
 }
 

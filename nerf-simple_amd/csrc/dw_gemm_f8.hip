@@ -21,6 +21,7 @@
 // HBM-bound by design at half the bytes of the bf16 form: (M + N) bytes per point and product.
 #include "nerf_device.h"
 #include "launchers.h"
+#include "dw_products.h"
 
 using namespace nerf_layout;
 
@@ -91,8 +92,9 @@ __device__ __forceinline__ void mfma(const Frag& a, const Frag& b, f32x16& c, in
 
 __global__ __launch_bounds__(512, 2) void dw_gemm_e4m3_kernel(GemmTableF8 tab) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int di = 0;
-    while (di + 1 < tab.n && (int)blockIdx.x >= tab.d[di + 1].wg0) ++di;
+    // which product, which K slice (dw_products.h)
+    int di;
+    dw_product_of_workgroup(tab, di);
     const GemmDescF8 d = tab.d[di];
     const int slice = blockIdx.x - d.wg0;
     const long long nslab = (tab.P + SLAB - 1) / SLAB;
@@ -326,9 +328,9 @@ __global__ __launch_bounds__(256) void rows_to_e4m3_kernel(const __bf16* __restr
 
 }  // namespace
 
-// scratch_f8: the narrow operands in the 8-bit form, nerf_amd_f8_scratch_bytes(P): posx (64) | posd (32) | dsr (16)
+// scratch_f8: the narrow operands in the 8-bit form, posx (64) | posd (32) | dsr (16) at the offsets of dw_products.h f8_scratch
 extern "C" long long nerf_amd_f8_scratch_bytes(long long P) {
-    return align256(f8_narrow_bytes(64, P)) + align256(f8_narrow_bytes(32, P)) + align256(f8_narrow_bytes(16, P));
+    return f8_scratch(P).total;
 }
 
 // The narrow operands of the products -- the row-major bf16 encoder rows (which & 1) and the packed d_raw that
@@ -339,9 +341,8 @@ extern "C" int nerf_amd_launch_param_gradients_convert_e4m3(const void* posx64_v
                                                             void* scratch_f8, long long P, int which, hipStream_t stream) {
     (void)hipGetLastError();
     if (P <= 0) return 0;
-    char* px = reinterpret_cast<char*>(scratch_f8);
-    char* pd = px + align256(f8_narrow_bytes(64, P));
-    char* ds = pd + align256(f8_narrow_bytes(32, P));
+    char* base = reinterpret_cast<char*>(scratch_f8);
+    const F8Scratch at = f8_scratch(P);
     const long long nblk = (P + 31) / 32;
     auto convert = [&](const void* src, int ld, int W, char* dst) {
         const long long waves = nblk * ((W + 31) / 32);
@@ -350,10 +351,10 @@ extern "C" int nerf_amd_launch_param_gradients_convert_e4m3(const void* posx64_v
                            reinterpret_cast<unsigned char*>(dst + f8_narrow_scale_offset(W, P)));
     };
     if (which & 1) {
-        convert(posx64_v, 64, 64, px);
-        convert(posd32_v, 32, 32, pd);
+        convert(posx64_v, 64, 64, base + at.px);
+        convert(posd32_v, 32, 32, base + at.pd);
     }
-    if (which & 2) convert(scratch, 32, 16, ds);
+    if (which & 2) convert(scratch, 32, 16, base + at.ds);
     return (int)hipGetLastError();
 }
 
@@ -366,80 +367,34 @@ extern "C" int nerf_amd_launch_param_gradients_finish_e4m3(const void* acts_v, c
     hipError_t e = hipSuccess;
     const char* acts = reinterpret_cast<const char*>(acts_v);
     const char* dys = reinterpret_cast<const char*>(dys_v);
-    const char* px = reinterpret_cast<const char*>(scratch_f8);
-    const char* pd = px + align256(f8_narrow_bytes(64, P));
-    const char* ds = pd + align256(f8_narrow_bytes(32, P));
-
-    auto blocked = [&](const char* buf, int L) {
-        return F8Operand{buf + f8_offset_bytes(L, P), reinterpret_cast<const unsigned char*>(buf + f8_scale_offset_bytes(L, P)),
-                         (int)F8_BLOCK_BYTES, act_width(L)};
+    const char* narrow = reinterpret_cast<const char*>(scratch_f8);
+    const F8Scratch at = f8_scratch(P);
+    // a DwOperand as this kernel reads it: data, exponents, bytes per tile, features
+    auto operand = [&](DwOperand o) -> F8Operand {
+        const int w = dw_operand_width(o, DW_E4M3);
+        if (o.kind == DwKind::DY || o.kind == DwKind::ACT) {
+            const char* buf = o.kind == DwKind::DY ? dys : acts;
+            return {buf + f8_offset_bytes(o.layer, P), reinterpret_cast<const unsigned char*>(buf + f8_scale_offset_bytes(o.layer, P)),
+                    (int)F8_BLOCK_BYTES, w};
+        }
+        const char* buf = narrow + (o.kind == DwKind::POSX ? at.px : o.kind == DwKind::POSD ? at.pd : at.ds);
+        return {buf, reinterpret_cast<const unsigned char*>(buf + f8_narrow_scale_offset(w, P)), (int)f8_narrow_block_bytes(w), w};
     };
-    auto narrow = [&](const char* buf, int W) {
-        return F8Operand{buf, reinterpret_cast<const unsigned char*>(buf + f8_narrow_scale_offset(W, P)), (int)f8_narrow_block_bytes(W), W};
-    };
+    // which products, on which workgroups: dw_products.h
+    const DwPlan plan = dw_plan(DW_E4M3, P, bucket, device_cus());
     GemmTableF8 t{};
     t.P = P;
-    int n = 0;
-    auto add = [&](F8Operand A, F8Operand B, int coff, int ldc, int r0, int Mv, int Nv, int boff = -1) {
-        GemmDescF8& g = t.d[n++];
-        g.A = A; g.B = B; g.C = grads + coff; g.ldc = ldc; g.r0 = r0; g.Mv = Mv; g.Nv = Nv;
-        g.bias = boff >= 0 ? grads + boff : nullptr;
-    };
-    const int LW = 256 * 256 + 256;
-    add(blocked(dys, 0), narrow(px, 64), OFF_L0_W, 63, 0, 256, 63, OFF_L0_B);                               // layers_0.0
-    for (int l = 1; l <= 4; ++l)                                                                             // layers_0.{2,4,6,8}
-        add(blocked(dys, l), blocked(acts, l - 1), OFF_L1_W + (l - 1) * LW, 256, 0, 256, 256, OFF_L1_W + (l - 1) * LW + 65536);
-    add(blocked(dys, 5), blocked(acts, 4), OFF_SKIP_W, 319, 0, 256, 256, OFF_SKIP_B);                        // skip [h ; x]: h part
-    add(blocked(dys, 5), narrow(px, 64), OFF_SKIP_W + 256, 319, 0, 256, 63);                                //               x part
-    add(blocked(dys, 6), blocked(acts, 5), OFF_L6_W, 256, 0, 256, 256, OFF_L6_W + 65536);                    // layers_1.0
-    add(blocked(dys, 7), blocked(acts, 6), OFF_L6_W + LW, 256, 0, 256, 256, OFF_L6_W + LW + 65536);          // layers_1.2
-    add(narrow(ds, 16), blocked(acts, 7), OFF_SIG_W, 256, 3, 1, 256);                                        // sigma_fc.0 (row 3 of dsr)
-    add(blocked(dys, 8), blocked(acts, 7), OFF_L2_W, 256, 0, 256, 256, OFF_L2_B);                            // layers_2
-    add(blocked(dys, 9), blocked(acts, 8), OFF_C0_W, 283, 0, 128, 256, OFF_C0_B);                            // color_fc.0 [h ; d]: h part
-    add(blocked(dys, 9), narrow(pd, 32), OFF_C0_W + 256, 283, 0, 128, 27);                                   //                      d part
-    add(narrow(ds, 16), blocked(acts, 9), OFF_C1_W, 128, 0, 3, 128);                                         // color_fc.2 (rows 0..2)
-    if (bucket != 0) {
-        int m = 0;
-        for (int i = 0; i < n; ++i) {
-            const bool head = t.d[i].C - grads < GRAD_BUCKET_SPLIT;
-            if (head == (bucket == 2)) t.d[m++] = t.d[i];
-        }
-        n = m;
-    }
-    t.n = n;
-    // workgroup shares as in dw_gemm.hip: bytes streamed per point (M + N) plus a fixed cost per slab
-    constexpr double slab_cost = 1024.0;
-    const int cus = device_cus();
-    double total = 0;
-    for (int i = 0; i < n; ++i) total += (double)(t.d[i].A.width + t.d[i].B.width) + slab_cost;
-    const long long nslab = (P + SLAB - 1) / SLAB;
-    const long long need = (P * 256 >> 30) + 1;            // a slice's operand stays below 1 GiB (32-bit buffer range)
-    long long w[16];
-    double rem[16];
-    long long used = 0;
-    for (int i = 0; i < n; ++i) {
-        const double share = ((double)(t.d[i].A.width + t.d[i].B.width) + slab_cost) / total * cus;
-        w[i] = (long long)share;
-        rem[i] = share - (double)w[i];
-        if (w[i] < need) { w[i] = need; rem[i] = 0; }
-        if (w[i] >= nslab) { w[i] = nslab; rem[i] = -1; }
-        used += w[i];
-    }
-    while (used < cus) {
-        int best = -1;
-        for (int i = 0; i < n; ++i)
-            if (rem[i] >= 0 && w[i] < nslab && (best < 0 || rem[i] > rem[best])) best = i;
-        if (best < 0) break;
-        ++w[best]; rem[best] = 0; ++used;
-    }
-    int wg = 0;
-    for (int i = 0; i < n; ++i) {
-        t.d[i].wg0 = wg;
-        t.d[i].wgs = (int)w[i];
-        wg += (int)w[i];
+    t.n = plan.n;
+    for (int i = 0; i < plan.n; ++i) {
+        const DwProduct& p = DW_PRODUCTS[plan.product[i]];
+        GemmDescF8& g = t.d[i];
+        g.A = operand(p.a); g.B = operand(p.b);
+        g.C = grads + p.coff; g.ldc = p.ldc; g.r0 = p.r0; g.Mv = p.Mv; g.Nv = p.Nv;
+        g.bias = p.boff >= 0 ? grads + p.boff : nullptr;
+        g.wg0 = plan.wg0[i]; g.wgs = plan.wgs[i];
     }
     e = allow_dynamic_lds(reinterpret_cast<const void*>(dw_gemm_e4m3_kernel), LDS_BYTES);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(dw_gemm_e4m3_kernel, dim3(wg), dim3(512), LDS_BYTES, stream, t);
+    hipLaunchKernelGGL(dw_gemm_e4m3_kernel, dim3(plan.workgroups), dim3(512), LDS_BYTES, stream, t);
     return (int)hipGetLastError();
 }

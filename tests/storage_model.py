@@ -4,7 +4,7 @@ in numpy, in both directions, and crafted operands on which the products of csrc
 
   decode_e4m3_layers / decode_e4m3_narrow    device image -> values, bytes, exponent bytes
   encode_e4m3_layers / encode_e4m3_narrow    integer values + exponent bytes -> device image, everything else poisoned
-  workgroup_shares                           the launcher's split of the workgroups over the products (the test sizes' source)
+  workgroup_shares                           the launchers' split of the workgroups over the products (the test sizes' source)
   crafted                                    integer operands under independently drawn power-of-two exponents, their images
                                              and the float64 gradient they must give
 
@@ -166,27 +166,36 @@ def scratch_image(narrow_ints, narrow_exps, P, fill=EXP_POISON):
     return out
 
 
-# ---- the launcher's arithmetic (csrc/dw_gemm_f8.hip nerf_amd_launch_param_gradients_finish_e4m3) -------------------------------
-# (features of A + features of B, head of the flat vector?) of the 14 products in table order
+# ---- the launchers' arithmetic (csrc/dw_products.h dw_plan; checked against it by tests/test_dw_products_cpu.py) --------------
+# (features of A + features of B, head of the flat vector?) of the 14 products in table order, in the e4m3 form
 PRODUCT_WIDTHS = ((256 + 64, True), (512, True), (512, True), (512, True), (512, True), (512, False), (256 + 64, False),
                   (512, False), (512, False), (16 + 256, False), (512, False), (128 + 256, False), (128 + 32, False),
                   (16 + 128, False))
+DRAW_PRODUCTS = (9, 13)                      # the products whose A operand is the packed d_raw: the 16 above, 32 in the bf16 form
 SLAB_COST = 1024.0
+# what a storage form brings to the arithmetic: points per slab, operand bytes per feature, features of the packed d_raw
+E4M3_FORM = dict(slab=SLAB, bytes_per_feature=1, draw=16)        # the defaults below
+BF16_FORM = dict(slab=32, bytes_per_feature=2, draw=32)
 
 
-def ideal_shares(bucket, cus=256):
+def product_widths(draw=16):
+    """PRODUCT_WIDTHS with the packed d_raw ``draw`` features wide."""
+    return tuple((w + (draw - 16 if i in DRAW_PRODUCTS else 0), head) for i, (w, head) in enumerate(PRODUCT_WIDTHS))
+
+
+def ideal_shares(bucket, cus=256, draw=16):
     """The workgroups each product of the launch would get with slabs to spare: cus * (M + N + 1024) / sum of the same."""
-    w = [float(a + SLAB_COST) for a, head in PRODUCT_WIDTHS if bucket == 0 or head == (bucket == 2)]
+    w = [float(a + SLAB_COST) for a, head in product_widths(draw) if bucket == 0 or head == (bucket == 2)]
     return [x / sum(w) * cus for x in w]
 
 
-def workgroup_shares(P, bucket, cus=256):
+def workgroup_shares(P, bucket, cus=256, slab=SLAB, bytes_per_feature=1, draw=16):
     """[wgs of each product of the launch] for P points: the integer parts of the ideal shares, at least ``need`` (a slice's
     operand stays below 1 GiB), at most one workgroup per slab, the workgroups left over by largest remainder."""
-    nslab = (P + SLAB - 1) // SLAB
-    need = (P * 256 >> 30) + 1
+    nslab = (P + slab - 1) // slab
+    need = (P * 256 * bytes_per_feature >> 30) + 1
     w, rem = [], []
-    for share in ideal_shares(bucket, cus):
+    for share in ideal_shares(bucket, cus, draw):
         wi, ri = int(share), share - int(share)
         if wi < need:
             wi, ri = need, 0.0
@@ -208,15 +217,23 @@ def workgroup_shares(P, bucket, cus=256):
     return w
 
 
-def share_edge_sizes(cus=256):
+def clamp_binds(P, bucket, cus=256, slab=SLAB, bytes_per_feature=1, draw=16):
+    """Does ``need`` raise a share, or the slab count stop one (before or after its leftover workgroup)?  Where neither
+    happens the shares add up to ``cus``."""
+    nslab = (P + slab - 1) // slab
+    need = (P * 256 * bytes_per_feature >> 30) + 1
+    return any(int(s) < need or int(s) + 1 >= nslab for s in ideal_shares(bucket, cus, draw))
+
+
+def share_edge_sizes(cus=256, slab=SLAB, bytes_per_feature=1, draw=16):
     """For each of the three launches (bucket 0, 1, 2) and for its smallest and its largest per-product share w: the sizes with
     w - 1, w and w + 1 slabs, each one point short of, at and one point past the slab boundary."""
     out = set()
     for bucket in (0, 1, 2):
-        sh = workgroup_shares(1 << 20, bucket, cus)    # slabs to spare: the shares no clamp has touched
+        sh = workgroup_shares(1 << 20, bucket, cus, slab, bytes_per_feature, draw)    # slabs to spare: the shares no clamp has touched
         for w in (min(sh), max(sh)):
             for s in (w - 1, w, w + 1):
-                out.update((SLAB * s - 1, SLAB * s, SLAB * s + 1))
+                out.update((slab * s - 1, slab * s, slab * s + 1))
     return sorted(out)
 
 
@@ -228,7 +245,8 @@ def share_edge_sizes(cus=256):
 #   s_begin / s_end, the vmcnt ladder and ``left`` take their edge values (a workgroup with one slab, with two, a product
 #   clamped to one workgroup per slab);
 # 2405: ragged, several slabs per workgroup; 36,928 = 577 slabs: the ring in steady state, 145 tiles (about 100 MB per buffer).
-# (the ``need`` clamp -- more than 2^22 points, 1 GiB per operand -- is out of reach of a test that stays quick.)
+# (the ``need`` clamp -- more than 2^22 points, 1 GiB per operand -- is out of reach of a GPU test that stays quick; the
+# arithmetic itself is run there on the host: tests/test_dw_products_cpu.py.)
 SMALL_SIZES = (1, 31, 32, 33, 63, 64, 65, 95, 96, 97, 255, 256, 257)
 INT_SIZES = tuple(sorted(set(SMALL_SIZES) | set(share_edge_sizes()) | {2405, 36928}))
 

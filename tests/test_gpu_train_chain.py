@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import storage_model as S
 import train_chain_model as M
 from test_gpu_storage import run_chain
 
@@ -93,6 +94,10 @@ INT_SIZES = [1, 31, 32, 33,                                        # fewer slabs
              255, 256, 257,                                        # tile edges
              2405, 4096, 36928,
              131072 + 37]                                          # one large ragged case
+# ... and every size of the model at which a product has one slab fewer than, as many as, one more than its workgroups on 256
+# CUs (smallest and largest share of each of the three launches; the launcher's plan is the model's:
+# tests/test_dw_products_cpu.py)
+INT_SIZES += [P for P in S.share_edge_sizes(256, **S.BF16_FORM) if P not in INT_SIZES]
 
 
 def _crafted(P, seed):

@@ -230,9 +230,9 @@ def dx_stage(L, W, dY, dsr):
 
 def expected_param_grads(X, dY, posx, posd, dsr, d_raw, with_mass=True):
     """(y, mass): the flat 595,844-entry gradient vector in float64 and the mass of every entry -- the 14 products and the
-    bias sums of nerf_amd_launch_param_gradients_finish (the table in csrc/dw_gemm.hip), head biases from the fp32 d_raw.
-    posx [P, >= 63], posd [P, >= 27]: only the true columns enter.  ``with_mass=False`` leaves the mass at zero (the
-    exact-integer test needs none)."""
+    bias sums of nerf_amd_launch_param_gradients_finish (the table DW_PRODUCTS in csrc/dw_products.h), head biases from the
+    fp32 d_raw.  posx [P, >= 63], posd [P, >= 27]: only the true columns enter.  ``with_mass=False`` leaves the mass at zero
+    (the exact-integer test needs none)."""
     y, mass = np.zeros(PARAM_COUNT), np.zeros(PARAM_COUNT)
 
     def put(name, A, B=None):
