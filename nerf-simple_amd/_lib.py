@@ -222,3 +222,43 @@ def require_cuda_f32(t, name):
     if t.dtype != torch.float32:
         raise RuntimeError(f"{name} must be float32, got {t.dtype}")
     return t
+
+
+# ---- the entry points' argument rules, each stated once ---------------------------------------------
+def require_rays(rays):
+    """rays [B, 6], float32 on the GPU -> B."""
+    require_cuda_f32(rays, "rays")
+    if rays.dim() != 2 or rays.shape[1] != 6:
+        raise RuntimeError("rays must be [B, 6]")
+    return rays.size(0)
+
+
+def require_shape(t, name, shape):
+    """An optional per-ray argument (None passes): float32 on the GPU and exactly ``shape`` = (B, n)."""
+    if t is not None and tuple(require_cuda_f32(t, name).shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be [B, {shape[1]}]")
+    return t
+
+
+def require_same_device(what, tensor, dev):
+    """``tensor`` (of the occupancy grid, the proposal volume) sits where the rays do."""
+    if tensor.device != dev:
+        raise RuntimeError(f"the {what} lives on {tensor.device}, the rays on {dev}")
+
+
+def require_pair_sizes(Nc, Nf):
+    """nerf_amd_sample_pdf's sample counts for a coarse / fine pair."""
+    if Nc < 3 or Nc > 256 or Nf < 0 or Nc + Nf > 512:
+        raise ValueError(f"hierarchical sampling needs 3 <= Nc <= 256 and Nc + Nf <= 512 (got Nc={Nc}, Nf={Nf})")
+
+
+def precision_of(net, precision):
+    """The precision code of a call: the module's own unless the call names one."""
+    return precision_code(net.precision if precision is None else precision)
+
+
+def workspace(nbytes, dev, floor=256):
+    """A scratch buffer of ``nbytes`` (at least ``floor``) on ``dev``; ``floor=0``: None for an entry point that needs none
+    (nerf_amd_render_workspace_bytes is 0 for the one-launch render, which takes NULL)."""
+    n = max(int(nbytes), floor) if floor else int(nbytes)
+    return torch.empty(n, dtype=torch.uint8, device=dev) if n else None

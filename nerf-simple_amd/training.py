@@ -29,6 +29,7 @@ the reference's autograd to 1e-5; long dW / db reductions are summed with float 
 import torch
 
 from . import _lib
+from .utils.rendering import _check_guided
 
 
 def img_mse(gt, pred):
@@ -560,23 +561,18 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     drawn, for rays that require grad, precision='fp32' modules, other network sizes, foreign nets and N > 512.
     ``return_ts=True``: returns (5-tuple, ts [B,N]) -- the sample positions of this jitter as nerf_amd_query_points forms
     them (the coarse pass of the masked pair hands them to the sampler)."""
-    from .utils import occupancy as occ_mod
-    from .utils.rendering import _tbins
-    _lib.require_cuda_f32(rays, "rays")
-    if rays.dim() != 2 or rays.shape[1] != 6:
-        raise RuntimeError("rays must be [B, 6]")
-    B, N = rays.size(0), int(N)
+    from .utils import jitter, occupancy as occ_mod
+    B, N = _lib.require_rays(rays), int(N)
     dev = rays.device
     occ_mod.check_trainable(occupancy, net, rays, N)
     if N < 1:
         raise RuntimeError(f"masked training serves 1 <= N <= {occ_mod.MAX_N_TRAIN} samples per ray, got N = {N}")
-    if occupancy.words.device != dev:
-        raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {dev}")
+    _lib.require_same_device("occupancy grid", occupancy.words, dev)
     net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
-    jit, flags, pending = occ_mod._jitter(B, N, dev, u, ts, device_rng)
+    jit, flags, pending = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
     try:
         rays = rays.detach().contiguous()
-        tbins = None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, N, dev)
+        tbins = jitter.tbins(tn, tf, N, dev, flags)
         out = _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0)
         if return_ts:
             return out, occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
@@ -663,10 +659,8 @@ def _check_pair(net_c, net_f, Nc, Nf, precision):
         raise ValueError("the coarse and the fine network must be two distinct modules")
     if net_c.precision != net_f.precision:
         raise ValueError(f"the coarse and the fine network differ in precision ({net_c.precision!r} vs {net_f.precision!r})")
-    Nc, Nf = int(Nc), int(Nf)
-    if Nc < 3 or Nc > 256 or Nf < 0 or Nc + Nf > 512:
-        raise ValueError(f"hierarchical sampling needs 3 <= Nc <= 256 and Nc + Nf <= 512 (got Nc={Nc}, Nf={Nf})")
-    return _lib.precision_code(net_c.precision if precision is None else precision)
+    _lib.require_pair_sizes(int(Nc), int(Nf))
+    return _lib.precision_of(net_c, precision)
 
 
 def _pair_stats(coarse, fine):
@@ -719,7 +713,7 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     own reports under 'coarse' / 'fine'.  The default network and the bf16 training kernels only, rays without
     requires_grad; refused before any jitter is drawn."""
     from .optim import FusedAdam
-    from .utils.host_rng import reference_rand
+    from .utils import jitter
     from .utils.rendering import render_nerf, sample_pdf
     _check_pair(net_c, net_f, Nc, Nf, precision)
     Nc, Nf = int(Nc), int(Nf)
@@ -731,30 +725,16 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
         opt_ids = {id(p) for pg in optimizer.param_groups for p in pg["params"]}
         if opt_ids != {id(p) for p in params}:
             raise RuntimeError("the optimizer does not hold exactly the parameters of the coarse and the fine network")
-    _lib.require_cuda_f32(rays, "rays")
-    if rays.dim() != 2 or rays.shape[1] != 6:
-        raise RuntimeError("rays must be [B, 6]")
-    B, dev = rays.size(0), rays.device
-    for name, t_, n in (("u_c", u_c, Nc), ("u_f", u_f, Nf)):
-        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
-            raise RuntimeError(f"{name} must be [B, {n}]")
+    B, dev = _lib.require_rays(rays), rays.device
+    _lib.require_shape(u_c, "u_c", (B, Nc))
+    _lib.require_shape(u_f, "u_f", (B, Nf))
     if occupancy is not None:
         from .utils.occupancy import check_trainable
         check_trainable(occupancy, net_c, rays, Nc, precision)       # before any draw: a refused call changes nothing
         check_trainable(occupancy, net_f, rays, Nc + Nf, precision)
-        if occupancy.words.device != dev:
-            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {dev}")
+        _lib.require_same_device("occupancy grid", occupancy.words, dev)
     rays = rays.detach().contiguous()
-    flags = 0
-    if device_rng and u_c is None:
-        flags = _lib.FLAG_DEVICE_RNG
-    elif u_c is None:
-        u_c, pend = reference_rand(B, Nc, dev)
-        pend.finish()
-    if u_f is None and not device_rng:
-        u_f, pend = reference_rand(B, Nf, dev)
-        pend.finish()
-    jit_c = None if u_c is None else u_c.contiguous()
+    jit_c, flags, u_f = jitter.pair(B, Nc, Nf, dev, u_c=u_c, u_f=u_f, device_rng=device_rng)
 
     optimizer.zero_grad(set_to_none=True)
     if occupancy is not None:
@@ -782,18 +762,6 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
 # --------------------------------------------------------------------------
 # grid-guided fine sampling: ONE network, its Nf new samples placed from a sigma volume
 # --------------------------------------------------------------------------
-def _check_guided(net, proposal, precision=None):
-    """The guided steps' limits, checked before anything is drawn or launched."""
-    from .utils.nets import Nerf
-    from .utils.proposal import ProposalVolume
-    if not isinstance(proposal, ProposalVolume):
-        raise TypeError("proposal must be a ProposalVolume (utils/proposal.py)")
-    if not (isinstance(net, Nerf) and net._fused_ok()):
-        raise RuntimeError("guided sampling serves the default Nerf(10, 4, 256) only: other network sizes and foreign nets "
-                           "are not supported; nothing falls back")
-    return _lib.precision_code(net.precision if precision is None else precision)
-
-
 def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, ts_c=None, u_f=None, decay=1.0,
                       group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, distortion=0.0):
     """One optimisation step of ONE network on grid-guided positions: ts = ``proposal.sample(rays, Nc, Nf, ...)`` (a
@@ -814,7 +782,8 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
     Not with ``occupancy`` (RuntimeError before anything is drawn)."""
     lam = _check_distortion(distortion)
     _refuse_distortion(lam, occupancy=occupancy)
-    _check_guided(net, proposal, precision)
+    _check_guided(net, proposal)
+    _lib.precision_of(net, precision)             # a precision the kernels do not know: ValueError before anything else
     if occupancy is not None:
         from .utils import occupancy as occ_mod
         occ_mod.check_trainable(occupancy, net, rays, int(Nc) + int(Nf), precision)

@@ -101,7 +101,7 @@ def density_grid(net, resolution, bounds=DEFAULT_BOUNDS, *, precision=None):
                                                      _lib.ptr(sigma), _lib.stream_ptr(dev)), "nerf_amd_density_grid")
             return sigma
 
-        code = _lib.precision_code(net.precision if precision is None else precision)
+        code = _lib.precision_of(net, precision)
         return guarded_launch([net], code, launch)
 
 

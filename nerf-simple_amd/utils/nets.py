@@ -191,7 +191,7 @@ class Nerf(nn.Module):
         return self._packed_entry(precision).buf
 
     def _packed_entry(self, precision=None):
-        code = _lib.precision_code(self.precision if precision is None else precision)
+        code = _lib.precision_of(self, precision)
         if not self._fused_ok():
             raise RuntimeError(f"Nerf(Lp={self.Lp}, Ld={self.Ld}, H={self.H}) has no packed weight image (NERF_AMD_EUNSUP): "
                                "the fused kernels implement (10, 4, 256); other sizes run through utils/generic_mlp.py")
@@ -289,7 +289,7 @@ class Nerf(nn.Module):
         if not self._fused_ok():
             with torch.no_grad():
                 return self.forward(v)
-        code = _lib.precision_code(self.precision if precision is None else precision)
+        code = _lib.precision_of(self, precision)
         v = v.detach().contiguous()
         P = v.shape[0]
 
@@ -313,7 +313,7 @@ class Nerf(nn.Module):
         if x.dim() != 2 or x.shape[1] not in (3, 6):
             raise RuntimeError("Nerf.density expects a [P, 3] or [P, 6] tensor")
         wants_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        code = _lib.precision_code(self.precision if precision is None else precision)
+        code = _lib.precision_of(self, precision)
         if not self._fused_ok() or wants_grad or code == _lib.F32:
             v = x if x.shape[1] == 6 else torch.cat([x, torch.zeros_like(x[:, :2]), torch.ones_like(x[:, :1])], 1)
             return self.forward(v, precision=precision)[:, 3]

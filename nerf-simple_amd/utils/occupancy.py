@@ -43,6 +43,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import jitter
 from .mesh import DEFAULT_BOUNDS, _host_f32x3, _resolution, density_grid, grid_axes
 
 _POLICIES = ("live", "empty")
@@ -136,13 +137,10 @@ class OccupancyGrid:
         """Which samples a render of ``rays`` with these arguments evaluates: a ``MarkResult`` (with ``points=True``
         also the compacted query points).  Jitter sources as ``render_nerf`` (u / ts explicit, the counter RNG, default
         one reference ``torch.rand(B, N)``).  One host synchronisation."""
-        _lib.require_cuda_f32(rays, "rays")
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise RuntimeError("rays must be [B, 6]")
-        B, N = rays.size(0), int(N)
-        jit, flags, pending = _jitter(B, N, rays.device, u, ts, device_rng)
+        B, N = _lib.require_rays(rays), int(N)
+        jit, flags, pending = jitter.single(B, N, rays.device, u=u, ts=ts, device_rng=device_rng)
         try:
-            rays, tbins = rays.detach().contiguous(), _tb(tn, tf, N, rays.device, flags)
+            rays, tbins = rays.detach().contiguous(), jitter.tbins(tn, tf, N, rays.device, flags)
             m = _mark(self, rays, jit, tbins, flags, seed, ray_id0, N)
             if points:
                 m.points = _points(m, rays, jit, tbins, flags, seed, ray_id0)
@@ -211,7 +209,7 @@ def check_trainable(occupancy, net, rays, N, precision=None):
     if not (isinstance(net, Nerf) and net._fused_ok()):
         raise RuntimeError("masked training (occupancy=) serves the default Nerf(10, 4, 256) only: other network sizes and "
                            "foreign nets are not supported; train without occupancy")
-    if _lib.precision_code(net.precision if precision is None else precision) == _lib.F32:
+    if _lib.precision_of(net, precision) == _lib.F32:
         raise RuntimeError("masked training (occupancy=) runs the fused bf16 training kernels: precision='fp32' modules are "
                            "not supported; build the module with precision='bf16' or 'fp16', or train without occupancy")
     if rays.requires_grad:
@@ -221,32 +219,11 @@ def check_trainable(occupancy, net, rays, N, precision=None):
         raise RuntimeError(f"masked training serves 1 <= N <= {MAX_N_TRAIN} samples per ray, got N = {N}")
 
 
-def _jitter(B, N, dev, u, ts, device_rng):
-    """(jitter tensor or None, flags, pending generator session or None) of the render entry points' jitter arguments."""
-    from .host_rng import reference_rand
-    for name, t_ in (("ts", ts), ("u", u)):
-        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, N):
-            raise RuntimeError("u / ts must be [B, N]")
-    if ts is not None:
-        return ts.contiguous(), _lib.FLAG_TS_GIVEN, None
-    if u is not None:
-        return u.contiguous(), 0, None
-    if device_rng:
-        return None, _lib.FLAG_DEVICE_RNG, None
-    jit, pending = reference_rand(B, N, dev)
-    return jit, 0, pending
-
-
 def _grid_words(lib, R):
     n = int(lib.nerf_amd_occupancy_grid_words(*R))
     if n < 0:
         raise RuntimeError(f"occupancy grid: unsupported resolution {R}")
     return n
-
-
-def _tb(tn, tf, N, dev, flags):
-    from .rendering import _tbins
-    return None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, N, dev)
 
 
 def occupancy_grid(net, resolution=128, level=None, bounds=DEFAULT_BOUNDS, *, dilate=1, outside="live", precision=None):
@@ -275,15 +252,14 @@ def check_renderable(occupancy, net, rays_require_grad):
 
 def _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N):
     B, dev = rays.size(0), rays.device
-    if occ.words.device != dev:
-        raise RuntimeError(f"the occupancy grid lives on {occ.words.device}, the rays on {dev}")
+    _lib.require_same_device("occupancy grid", occ.words, dev)
     lib = _lib.lib()
     nwords = int(lib.nerf_amd_occupancy_mask_words(B, N))
     if nwords < 0:
         raise RuntimeError(f"the masked render serves 1 <= N <= {MAX_N} samples per ray, got N = {N}")
     mask = torch.empty((B, (N + 63) // 64), dtype=torch.int64, device=dev)
     offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(lib.nerf_amd_occupancy_workspace_bytes(B), dev)
     mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
     with torch.cuda.device(dev):
         _lib.check(lib.nerf_amd_occupancy_mark(
@@ -458,7 +434,7 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
     masks = [torch.empty((B, W), dtype=torch.int64, device=dev) for _ in range(2)]
     offs = [torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(2)]
     totals = torch.zeros(2, dtype=torch.int64, device=dev)
-    ws = torch.empty(max(int(lib.nerf_amd_termination_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(lib.nerf_amd_termination_workspace_bytes(B), dev)
     dead_row = torch.tensor([0.0, 0.0, 0.0, -np.inf], dtype=torch.float32, device=dev) if B else None
     head = (_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0))
 

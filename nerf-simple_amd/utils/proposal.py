@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import jitter
 from .mesh import DEFAULT_BOUNDS, _host_f32x3, _resolution, _warn_if_out_of_range, density_grid, grid_axes
 
 MIN_NC, MAX_NC, MAX_TOTAL = 3, 256, 512           # the sampler's sizes (csrc/sample_pdf_device.h)
@@ -78,7 +79,7 @@ class ProposalVolume:
         dev = self.sigma.device
         if next(net.parameters()).device != dev:
             raise RuntimeError(f"the proposal volume lives on {dev}, the network on {next(net.parameters()).device}")
-        code = _lib.precision_code(net.precision if precision is None else precision)
+        code = _lib.precision_of(net, precision)
         R = self.resolution
         _warn_if_out_of_range(R, self.lo, self.step)
         lib, h_lo, h_step = _lib.lib(), _host_f32x3(self.lo), _host_f32x3(self.step)
@@ -127,17 +128,13 @@ class ProposalVolume:
             if not isinstance(occupancy, OccupancyGrid):
                 raise TypeError("occupancy must be an OccupancyGrid (utils/occupancy.py)")
         Nc, Nf = check_sizes(Nc, Nf)
-        _lib.require_cuda_f32(rays, "rays")
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise RuntimeError("rays must be [B, 6]")
-        B = rays.size(0)
+        B = _lib.require_rays(rays)
         if torch.is_grad_enabled() and rays.requires_grad:
             raise RuntimeError("guided sampling gives no gradients to the rays; detach them")
         if not (torch.is_tensor(self.sigma) and self.sigma.is_cuda and self.sigma.dtype == torch.float32
                 and self.sigma.is_contiguous() and tuple(self.sigma.shape) == self.resolution):
             raise RuntimeError("ProposalVolume.sigma must stay the contiguous float32 device volume it was built with")
-        if self.sigma.device != rays.device:
-            raise RuntimeError(f"the proposal volume lives on {self.sigma.device}, the rays on {rays.device}")
+        _lib.require_same_device("proposal volume", self.sigma, rays.device)
         if u_c is not None and ts_c is not None:
             raise ValueError("give u_c or ts_c, not both")
         if device_rng and u_c is not None:
@@ -145,10 +142,9 @@ class ProposalVolume:
         if device_rng and u_f is not None:
             raise ValueError("device_rng=True draws the fine jitter on the device: it cannot be combined with u_f")
         for name, t_, n in (("u_c", u_c, Nc), ("ts_c", ts_c, Nc), ("u_f", u_f, Nf)):
-            if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
-                raise RuntimeError(f"{name} must be [B, {n}]")
-        if occupancy is not None and occupancy.words.device != rays.device:
-            raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {rays.device}")
+            _lib.require_shape(t_, name, (B, n))
+        if occupancy is not None:
+            _lib.require_same_device("occupancy grid", occupancy.words, rays.device)
         return B, Nc, Nf
 
     def sample(self, rays, Nc, Nf, tn=2, tf=6, *, u_c=None, ts_c=None, u_f=None, device_rng=False, seed=0, ray_id0=0,
@@ -167,28 +163,24 @@ class ProposalVolume:
         after that masking (-inf at a dead coarse sample).  return_mark (needs ``occupancy``): the ``MarkResult`` of the
         merged positions (utils/occupancy.py) comes back as the last element; reading its live count is the call's one host
         synchronisation."""
-        from .host_rng import reference_rand
-        from .rendering import _tbins
         if return_mark and occupancy is None:
             raise ValueError("return_mark=True needs an occupancy grid")
         B, Nc, Nf = self.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)
         dev = rays.device
         rays = rays.detach().contiguous()
-        flags, jit = 0, None
-        if ts_c is not None:
-            jit, flags = ts_c.detach().contiguous(), _lib.FLAG_TS_GIVEN
-        elif u_c is not None:
-            jit = u_c.detach().contiguous()
-        elif not device_rng:
-            jit, pending = reference_rand(B, Nc, dev)
+        # ``check`` has refused what this sampler refuses (u_c / u_f with device_rng, u_c with ts_c) and looked at every shape
+        jit, flags, pending = jitter.single(B, Nc, dev, u=u_c, ts=ts_c, device_rng=device_rng, names=("u_c", "ts_c"),
+                                            shape_error=None)
+        if pending is not None:
             pending.finish()
         if device_rng:
-            flags |= _lib.FLAG_DEVICE_RNG
-        elif u_f is None and Nf > 0:
-            u_f, pending = reference_rand(B, Nf, dev)
+            flags |= _lib.FLAG_DEVICE_RNG             # with ts_c given too: the fine samples still come from the counter RNG
+        # this entry point's own rule (section 31): nothing is drawn for Nf == 0 and u_f stays None
+        u_f, _, pending = jitter.single(B, Nf, dev, u=u_f, device_rng=device_rng or Nf == 0, names=("u_f", None),
+                                        shape_error=None)
+        if pending is not None:
             pending.finish()
-        u_f = None if u_f is None else u_f.detach().contiguous()
-        tbins = None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, Nc, dev)
+        tbins = jitter.tbins(tn, tf, Nc, dev, flags)
         ts = torch.empty((B, Nc + Nf), dtype=torch.float32, device=dev)
         sigma_c = w_c = None
         if return_weights:
@@ -201,7 +193,7 @@ class ProposalVolume:
         N = Nc + Nf
         mask = torch.empty((B, (N + 63) // 64), dtype=torch.int64, device=dev)
         offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
-        ws = torch.empty(max(int(_lib.lib().nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib().nerf_amd_occupancy_workspace_bytes(B), dev)
         self._launch_masked(occupancy, rays, jit, tbins, flags, seed, ray_id0, u_f, ts, sigma_c, w_c, mask, offsets, None, ws,
                             B, Nc, Nf)
         out = (ts, sigma_c, w_c) if return_weights else (ts,)

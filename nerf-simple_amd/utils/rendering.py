@@ -25,7 +25,8 @@ import torch
 from tqdm import tqdm
 
 from .. import _lib
-from .host_rng import ReferenceJitter, reference_rand
+from . import jitter
+from .host_rng import ReferenceJitter
 from .nets import Nerf, guarded_launch
 
 ALL_OUTPUTS = ("rgb", "disp", "alpha", "acc", "w")
@@ -170,10 +171,7 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     """
     _refuse_controls(background, sigma_noise, occupancy=occupancy, terminate=terminate)
     std = _check_sigma_noise(sigma_noise) if sigma_noise else 0.0
-    _lib.require_cuda_f32(rays, "rays")
-    if rays.dim() != 2 or rays.shape[1] != 6:
-        raise RuntimeError("rays must be [B, 6]")
-    B, N = rays.size(0), int(N)
+    B, N = _lib.require_rays(rays), int(N)
     dev = rays.device
     controls = None
     if background is not None or sigma_noise:
@@ -200,37 +198,24 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
         check_renderable(occupancy, net, rays_grad)
     # everything that can raise cheaply is checked BEFORE the jitter is drawn, so a failed call
     # leaves torch's CPU generator untouched
-    for name, t_ in (("ts", ts), ("u", u)):
-        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, N):
-            raise RuntimeError("u / ts must be [B, N]")
+    jitter.check(B, N, u=u, ts=ts)
     code = None
     if fused and not training:
-        code = _lib.precision_code(net.precision if precision is None else precision)
+        code = _lib.precision_of(net, precision)
         net.packed_weights(code)              # packs now if it has to: errors surface before the jitter is drawn
-
-    flags, jit, pending_rng = 0, None, None
-    if ts is not None:
-        jit, flags = ts.contiguous(), _lib.FLAG_TS_GIVEN
-    elif u is not None:
-        jit = u.contiguous()
-    elif device_rng:
-        flags = _lib.FLAG_DEVICE_RNG
-    else:
-        # the reference's single CPU draw per call (:28-30): same numbers, same advance of torch's
-        # CPU generator, produced on the device (host_rng.py)
-        jit, pending_rng = reference_rand(B, N, dev)
+    jit, flags, pending_rng = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
     # the reference's |x| > 1 warning (utils/xyz.py:8-9, raised inside net.forward's positional_encoder): verdict formed on
     # the device from the first / last sample of every ray, raised lazily (xyz.range_check_rays); a foreign net encodes
     # its own inputs and warns (or not) by itself
     if fused:
         from .xyz import range_check_rays
-        range_check_rays(rays, jit, None if ts is not None else _tbins(tn, tf, N, dev), flags, seed, ray_id0, N)
+        tb = jitter.tbins(tn, tf, N, dev, flags)
+        range_check_rays(rays, jit, tb, flags, seed, ray_id0, N)
     if pending_rng is not None and not fused:
         pending_rng.finish()                  # the net's own forward follows: the generator must be current
         pending_rng = None
     if terminate is not None or occupancy is not None:
         from .occupancy import render_masked, render_terminated
-        tb = None if ts is not None else _tbins(tn, tf, N, dev)
         try:
             if terminate is not None:
                 return render_terminated(terminate, occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
@@ -251,15 +236,8 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
         return _render_generic(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, controls)
 
     def launch(code, packed):
-        lib = _lib.lib()
-        rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
-        nws = int(lib.nerf_amd_render_workspace_bytes(code, B, N))        # 0: the fused one-launch render
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_render_forward(
-                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)), _lib.ptr(packed[0]), code,
-                flags, int(seed), int(ray_id0), _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha),
-                _lib.ptr(acc), _lib.ptr(w), _lib.ptr(ws), B, N, _lib.stream_ptr(dev)), "nerf_amd_render_forward")
+        rgb, disp, alpha, acc, w = _render_forward(rays, jit, _tbins(tn, tf, N, dev), packed[0], code, flags, seed, ray_id0, N,
+                                                   outputs)
         if controls is not None:              # the same one-launch render, then the blend (acc is always among the outputs)
             rgb = _blend(rgb, acc, None, controls[0], controls[1])
         return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
@@ -272,6 +250,19 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
 
 
 render_rays = render_nerf      # the name BASELINE.json uses for the same function
+
+
+def _render_forward(rays, jit, tbins, image, code, flags, seed, ray_id0, N, outputs):
+    """nerf_amd_render_forward with its outputs and its workspace: the five buffers of ``_five_outputs``, as the kernel left
+    them (``render_nerf`` and ``render_view(background=)`` differ in the outputs they ask for and in the blend behind)."""
+    B, dev, lib = rays.size(0), rays.device, _lib.lib()
+    out = _five_outputs(B, N, outputs, dev)
+    ws = _lib.workspace(lib.nerf_amd_render_workspace_bytes(code, B, N), dev, floor=0)     # 0 bytes: the one-launch render
+    with torch.cuda.device(dev):
+        _lib.check(lib.nerf_amd_render_forward(
+            _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), _lib.ptr(image), code, flags, int(seed), int(ray_id0),
+            *[_lib.ptr(t_) for t_ in out], _lib.ptr(ws), B, N, _lib.stream_ptr(dev)), "nerf_amd_render_forward")
+    return out
 
 
 def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, controls=None):
@@ -455,21 +446,26 @@ def render_rays_sharded(net, rays, batch_size, *, N=128, tn=2, tf=6, u=None, gro
     return parallel.render_image_sharded(rays, render_fn, group=group, u=u)
 
 
+def _host_pose(pose):
+    """pose [4,4] or [3,4] (host tensor / array) as the entry points take it: a contiguous float32 [3,4] numpy copy."""
+    import numpy as np
+    h_pose = np.zeros((3, 4), dtype=np.float32)
+    h_pose[:] = np.asarray(pose, dtype=np.float32)[:3, :4]
+    return h_pose
+
+
 def generate_rays(pose, cam_params, device, ray0=0, n_rays=None):
     """Pinhole rays of an HxW view on the GPU (reference utils/xyz.py:38-52 +
     utils/rendering.py:129-134 run on the CPU): pose [4,4] or [3,4] (host tensor /
     array), cam_params [H,W,f] -> rays [n_rays,6] for pixels ray0.. in row-major
     order."""
-    import numpy as np
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
     n = H * W - ray0 if n_rays is None else int(n_rays)
-    h_pose = np.ascontiguousarray(np.asarray(pose, dtype=np.float32)[:3, :4])
-    h_pose4 = np.zeros((3, 4), dtype=np.float32)
-    h_pose4[:] = h_pose
+    h_pose = _host_pose(pose)
     rays = torch.empty((n, 6), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
         _lib.check(_lib.lib().nerf_amd_generate_rays(
-            h_pose4.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(rays), _lib.stream_ptr(device)),
+            h_pose.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(rays), _lib.stream_ptr(device)),
             "nerf_amd_generate_rays")
     return rays
 
@@ -491,7 +487,6 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     background: a colour [3] (or one per pixel of the range, [n,3]) behind the volume: pixels = [clip(rgb + (1 - acc)
     background, 0, 1), disparity], the clip behind the blend.  Device ray generation, nerf_amd_render_forward for rgb, disp
     and acc, then one small blend launch (without a background: the one call it was).  Not with occupancy / terminate."""
-    import numpy as np
     _refuse_controls(background, 0.0, occupancy=occupancy, terminate=terminate)
     dev = next(net.parameters()).device
     if terminate is not None:
@@ -512,15 +507,11 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
                                              **({} if background is None else {"background": background}))
         return torch.cat([rgb.clamp(0., 1.), disp[:, None]], dim=1)
     bg = None if background is None else _background_arg(background, n, dev)
-    code = _lib.precision_code(net.precision if precision is None else precision)
+    code = _lib.precision_of(net, precision)
     net.packed_weights(code)
-    flags, jit = 0, None
-    if u is not None:
-        jit = _lib.require_cuda_f32(u, "u").contiguous()
-    elif device_rng:
-        flags = _lib.FLAG_DEVICE_RNG
-    else:
-        jit, pending_rng = reference_rand(n, N, dev)
+    # the shape of ``u`` is looked at below, on the masked and background branches only (section 31)
+    jit, flags, pending_rng = jitter.single(n, N, dev, u=u, device_rng=device_rng, shape_error=None)
+    if pending_rng is not None:
         pending_rng.finish()
     lib = _lib.lib()
     if terminate is not None or occupancy is not None:
@@ -533,18 +524,9 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
                                      code, (), pixels=True)
         return render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0, code, (),
                              pixels=True)
-    h_pose = np.zeros((3, 4), dtype=np.float32)
-    h_pose[:] = np.asarray(pose, dtype=np.float32)[:3, :4]
 
     def launch_bg(code, packed):
-        rgb, disp, _, acc, _ = _five_outputs(n, int(N), (), dev)
-        nws = int(lib.nerf_amd_render_workspace_bytes(code, n, int(N)))
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_render_forward(
-                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)), _lib.ptr(packed[0]), code, flags, int(seed),
-                int(ray0), _lib.ptr(rgb), _lib.ptr(disp), None, _lib.ptr(acc), None, _lib.ptr(ws), n, int(N),
-                _lib.stream_ptr(dev)), "nerf_amd_render_forward")
+        rgb, disp, _, acc, _ = _render_forward(rays, jit, _tbins(tn, tf, N, dev), packed[0], code, flags, seed, ray0, int(N), ())
         return _blend(rgb, acc, disp, *bg, pixels=True)
 
     if bg is not None:
@@ -552,10 +534,11 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
             raise RuntimeError("u must be [n_rays, N]")
         rays = generate_rays(pose, cam_params, dev, ray0, n)
         return guarded_launch([net], code, launch_bg)
+    h_pose = _host_pose(pose)
 
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        ws = torch.empty(max(int(lib.nerf_amd_render_image_workspace_bytes(code, n, N)), 256), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(lib.nerf_amd_render_image_workspace_bytes(code, n, N), dev)
         with torch.cuda.device(dev):
             _lib.check(lib.nerf_amd_render_image_forward(
                 h_pose.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)),
@@ -592,13 +575,8 @@ def sample_pdf(ts, w, Nf, *, u=None, device_rng=False, seed=0, ray_id0=0):
     _lib.require_cuda_f32(w, "w")
     B, Nc = ts.shape
     dev = ts.device
-    flags, jit = 0, None
-    if u is not None:
-        jit = _lib.require_cuda_f32(u, "u").contiguous()
-    elif device_rng:
-        flags = _lib.FLAG_DEVICE_RNG
-    else:
-        jit, pending_rng = reference_rand(B, Nf, dev)
+    jit, flags, pending_rng = jitter.single(B, Nf, dev, u=u, device_rng=device_rng, shape_error=None)    # u's shape: the caller's
+    if pending_rng is not None:
         pending_rng.finish()
     out = torch.empty((B, Nc + Nf), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -615,26 +593,14 @@ def _masked_pair_args(occupancy, net_coarse, net_fine, B, Nc, Nf, u_c, u_f, prec
     from .occupancy import check_renderable
     check_renderable(occupancy, net_coarse, False)
     check_renderable(occupancy, net_fine, False)
-    if Nc < 3 or Nc > 256 or Nf < 0 or Nc + Nf > 512:
-        raise ValueError(f"hierarchical sampling needs 3 <= Nc <= 256 and Nc + Nf <= 512 (got Nc={Nc}, Nf={Nf})")
-    if occupancy.words.device != dev:
-        raise RuntimeError(f"the occupancy grid lives on {occupancy.words.device}, the rays on {dev}")
-    for name, t_, n in (("u_c", u_c, Nc), ("u_f", u_f, Nf)):
-        if t_ is not None and tuple(_lib.require_cuda_f32(t_, name).shape) != (B, n):
-            raise RuntimeError(f"{name} must be [B, {n}]")
-    code = _lib.precision_code(net_coarse.precision if precision is None else precision)
+    _lib.require_pair_sizes(Nc, Nf)
+    _lib.require_same_device("occupancy grid", occupancy.words, dev)
+    _lib.require_shape(u_c, "u_c", (B, Nc))
+    _lib.require_shape(u_f, "u_f", (B, Nf))
+    code = _lib.precision_of(net_coarse, precision)
     net_coarse.packed_weights(code)
     net_fine.packed_weights(code)
-    flags = 0
-    if u_c is None and device_rng:
-        flags = _lib.FLAG_DEVICE_RNG
-    elif u_c is None:
-        u_c, pending_rng = reference_rand(B, Nc, dev)
-        pending_rng.finish()
-    if u_f is None and not device_rng:
-        u_f, pending_rng = reference_rand(B, Nf, dev)
-        pending_rng.finish()
-    return (code, None if u_c is None else u_c.contiguous(), flags, None if u_f is None else u_f.contiguous())
+    return (code,) + jitter.pair(B, Nc, Nf, dev, u_c=u_c, u_f=u_f, device_rng=device_rng)
 
 
 def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *, u_c=None, u_f=None,
@@ -656,8 +622,7 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
     dev, B = rays.device, rays.size(0)
     if occupancy is not None:
         from .occupancy import render_masked_pair
-        if rays.dim() != 2 or rays.shape[1] != 6:
-            raise RuntimeError("rays must be [B, 6]")
+        _lib.require_rays(rays)
         Nc, Nf = int(Nc), int(Nf)
         if torch.is_grad_enabled() and rays.requires_grad:
             raise RuntimeError("the masked render (occupancy=) is inference only: call it under torch.no_grad()")
@@ -670,14 +635,12 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
             return render_masked_pair(occupancy, rays, net_coarse, net_fine, Nc, Nf, tb, jit, flags, u_f, device_rng, seed,
                                       ray_id0, code)
     rays = rays.detach().contiguous()
-    code = _lib.precision_code(net_coarse.precision if precision is None else precision)
+    code = _lib.precision_of(net_coarse, precision)
     net_coarse.packed_weights(code)
-    flags, jit = _lib.FLAG_DEVICE_RNG, None
-    if u_c is None and not device_rng:
-        u_c, pending_rng = reference_rand(B, Nc, dev)
+    # the coarse half of the pair rule; ``sample_pdf`` below settles u_f behind the coarse pass (the same draw order)
+    jit, flags, pending_rng = jitter.single(B, Nc, dev, u=u_c, device_rng=device_rng, names=("u_c", None), shape_error=None)
+    if pending_rng is not None:
         pending_rng.finish()
-    if u_c is not None:
-        flags, jit = 0, _lib.require_cuda_f32(u_c, "u_c").contiguous()
     # the coarse pass through the stage-1 entry point: the sampler needs the positions the kernel drew
     lib = _lib.lib()
 
@@ -711,41 +674,26 @@ def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=1
     Parity unpinned (no reference counterpart).
     occupancy: an ``OccupancyGrid`` for both passes -- device ray generation, then the composition of
     ``render_hierarchical(..., occupancy=)``, then the clip (not one library call: two host reads, one per pass)."""
-    import numpy as np
     dev = next(net_coarse.parameters()).device
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
     n = H * W - ray0 if n_rays is None else int(n_rays)
+    if device_rng:
+        u_c = u_f = None                 # this entry point's own rule (section 31): device_rng drops given uniforms
     if occupancy is not None:
         from .occupancy import render_masked_pair
         Nc, Nf = int(Nc), int(Nf)
-        if device_rng:
-            u_c = u_f = None
         code, jit, flags, u_f = _masked_pair_args(occupancy, net_coarse, net_fine, n, Nc, Nf, u_c, u_f, precision, device_rng, dev)
         rays = generate_rays(pose, cam_params, dev, ray0, n)
         with torch.no_grad():
             return render_masked_pair(occupancy, rays, net_coarse, net_fine, Nc, Nf, _tbins(tn, tf, Nc, dev), jit, flags, u_f,
                                       device_rng, seed, ray0, code, pixels=True)[0]
-    code = _lib.precision_code(net_coarse.precision if precision is None else precision)
-    flags = 0
-    if device_rng:
-        flags, u_c, u_f = _lib.FLAG_DEVICE_RNG, None, None
-    else:
-        if u_c is None:
-            u_c, pend = reference_rand(n, Nc, dev)
-            pend.finish()
-        if u_f is None:
-            u_f, pend = reference_rand(n, Nf, dev)
-            pend.finish()
-        u_c = _lib.require_cuda_f32(u_c, "u_c").contiguous()
-        u_f = _lib.require_cuda_f32(u_f, "u_f").contiguous()
-    lib = _lib.lib()
-    h_pose = np.zeros((3, 4), dtype=np.float32)
-    h_pose[:] = np.asarray(pose, dtype=np.float32)[:3, :4]
+    code = _lib.precision_of(net_coarse, precision)
+    u_c, flags, u_f = jitter.pair(n, Nc, Nf, dev, u_c=u_c, u_f=u_f, device_rng=device_rng)
+    lib, h_pose = _lib.lib(), _host_pose(pose)
 
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        ws = torch.empty(max(int(lib.nerf_amd_render_hierarchical_workspace_bytes(n, Nc, Nf)), 256), dtype=torch.uint8,
-                         device=dev)
+        ws = _lib.workspace(lib.nerf_amd_render_hierarchical_workspace_bytes(n, Nc, Nf), dev)
         with torch.cuda.device(dev):
             _lib.check(lib.nerf_amd_render_hierarchical_forward(
                 h_pose.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(u_c), _lib.ptr(u_f), _lib.ptr(_tbins(tn, tf, Nc, dev)),
@@ -773,6 +721,7 @@ def render_hierarchical_sharded(net_coarse, net_fine, pose, cam_params, Nc=64, N
 
 
 def _check_guided(net, proposal):
+    """The guided renders' and steps' limits, checked before anything is drawn or launched."""
     from .proposal import ProposalVolume
     if not isinstance(proposal, ProposalVolume):
         raise TypeError("proposal must be a ProposalVolume (utils/proposal.py)")
@@ -800,7 +749,7 @@ def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=Non
                                      ray_id0, occupancy)
     B, Nc, Nf = proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng)
     if not (torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters())):
-        net.packed_weights(_lib.precision_code(net.precision if precision is None else precision))     # errors before the draws
+        net.packed_weights(_lib.precision_of(net, precision))     # errors before the draws
     ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
     return render_nerf(rays, net, Nc + Nf, tn, tf, ts=ts, outputs=outputs, precision=precision) + (ts,)
 
@@ -812,7 +761,7 @@ def _render_guided_masked(rays, net, Nc, Nf, proposal, tn, tf, u_c, ts_c, u_f, o
     from .xyz import range_check_rays
     check_renderable(occupancy, net, torch.is_tensor(rays) and rays.requires_grad)
     proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)
-    code = _lib.precision_code(net.precision if precision is None else precision)
+    code = _lib.precision_of(net, precision)
     net.packed_weights(code)                      # errors before the draws
     with torch.no_grad():
         rays = rays.detach().contiguous()
@@ -838,7 +787,7 @@ def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u
         check_renderable(occupancy, net, False)
     dev = next(net.parameters()).device
     n = int(cam_params[0]) * int(cam_params[1]) - ray0 if n_rays is None else int(n_rays)
-    code = _lib.precision_code(net.precision if precision is None else precision)
+    code = _lib.precision_of(net, precision)
     net.packed_weights(code)
     rays = generate_rays(pose, cam_params, dev, ray0, n)
     if occupancy is not None:
@@ -853,8 +802,7 @@ def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u
 
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        nws = int(lib.nerf_amd_render_workspace_bytes(code, n, N))
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+        ws = _lib.workspace(lib.nerf_amd_render_workspace_bytes(code, n, N), dev, floor=0)
         with torch.cuda.device(dev):
             _lib.check(lib.nerf_amd_render_pixels_forward(
                 _lib.ptr(rays), _lib.ptr(ts), None, _lib.ptr(packed[0]), code, _lib.FLAG_TS_GIVEN, int(seed), int(ray0),
