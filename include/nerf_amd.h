@@ -1079,6 +1079,53 @@ int nerf_amd_volume_render_mse_backward_dist(const float* raw, const float* ts, 
                                              const uint64_t* seed_mem, int64_t ray_id0, float t_far, float coef, float* rgb,
                                              float* loss_ray, float* d_raw, int64_t B, int N, void* stream);
 
+/* ---- masked training controls: background, sigma noise and distortion loss for the masked steps (csrc/masked_controls.hip) --
+ * The three terms of the dense training path for the masked single-network steps (one network behind an occupancy grid,
+ * plain or on guided positions; not the masked coarse + fine pair).  Definitions of mask, offsets, the live rows raw_live[P',4]
+ * and the capacity clamp: "training with the occupancy grid" and "graphed masked training step" above.
+ *
+ * nerf_amd_sigma_noise_masked: the noise stage on live rows, raw_live[P',4] -> out[P',4] (out may be raw_live).  Row
+ *   offsets[b] + rank of the live sample i of ray b (rank = live samples of the ray in front of it) gets its colours copied
+ *   and sigma' = sigma + std z, z the standard normal nerf_amd_sigma_noise draws for sample (ray_id0 + b) N + i: the counter is
+ *   the ORIGINAL sample index, so an all-live grid reproduces nerf_amd_sigma_noise bit for bit.  std == 0: out = raw_live, no
+ *   noise code runs.  flags / seed / seed_mem as in nerf_amd_sigma_noise.  N <= 512.  P' = offsets[B] is known to the device
+ *   only: raw_live == out == NULL says P' == 0, launches nothing and returns 0.
+ *   Rules in order: NERF_AMD_EINVAL for B < 0 or N <= 0; the noise arguments as in nerf_amd_sigma_noise; B == 0 launches
+ *   nothing; NERF_AMD_EUNSUP for N > 512 (or B > 2^32); NERF_AMD_EINVAL for a missing or misaligned mask / offsets (8 bytes), for
+ *   exactly one of raw_live / out missing, or either off 16 bytes. */
+int nerf_amd_sigma_noise_masked(const float* raw_live, float* out, float std, uint32_t flags, uint64_t seed,
+                                const uint64_t* seed_mem, int64_t ray_id0, const uint64_t* mask, const int64_t* offsets, int64_t B,
+                                int N, void* stream);
+
+/* nerf_amd_volume_render_masked_mse_backward_dist: the masked training head with the three terms, ONE launch under the capacity
+ *   clamp.  By definition, bit for bit (tests/test_gpu_masked_controls.py), it is the composition under mask_C / offsets_C --
+ *   the stricter mask nerf_amd_volume_render_masked_mse_backward defines: kept iff live and global rank < capacity --
+ *     nerf_amd_sigma_noise_masked (std, noise_flags, noise_seed, seed_mem, ray_id0)
+ *     -> nerf_amd_volume_render_masked (rgb, acc, w) -> nerf_amd_distortion_loss (ts, w, t_far, coef): loss_ray, g_w
+ *     -> nerf_amd_background_blend -> g = 2 (rgb_bg - gt) / (3 B) -> nerf_amd_background_blend_backward
+ *     -> nerf_amd_volume_render_masked_backward (g_rgb = g, g_acc, g_w)
+ *   so the kept rows of d_raw_live[capacity,4] are the gradient of MSELoss(rgb_bg, gt) + sum_rays coef D, and the surplus rows
+ *   [min(P', capacity), capacity) are zero-filled on every launch: every row is written by exactly one lane, no atomics, two
+ *   runs write the same bytes.  rgb[B,3] = rgb_bg.  ray_id0 is shared by the jitter and the noise; the noise has flags, seed
+ *   and seed_mem of its own.  A dead or over-capacity sample is dead whatever the noise: it is (0, 0, 0, -inf), never noised,
+ *   alpha = w = 0 exactly.  A ray with nothing kept, or N == 1: rgb = bg through the blend's own rounded ops (0 without a
+ *   background), loss_ray = 0, a kept row gets zeros.
+ *   bg == NULL: no background (bg_stride is still checked); std == 0: no noise; coef == 0: no distortion term -- rgb and
+ *   d_raw_live are the chain without it and loss_ray (may be NULL) is all zeros.  With none of the three it IS
+ *   nerf_amd_volume_render_masked_mse_backward (the same launch; a loss_ray that is given is cleared by a memset in front of
+ *   it).  N <= 512.
+ *   Rules in order: NERF_AMD_EINVAL for capacity < 1, B < 0, N <= 0 or the jitter arguments, as the plain masked head; the noise
+ *   arguments as in nerf_amd_sigma_noise; bg_stride; t_far and coef as in nerf_amd_distortion_loss; B == 0 (NERF_AMD_EINVAL:
+ *   1 <= capacity <= B N leaves B >= 1); NERF_AMD_EUNSUP for N > 512 (or B > 2^32); NERF_AMD_EINVAL for missing rays,
+ *   capacity > B N, a missing or misaligned mask / offsets, a missing raw_live / gt / rgb / d_raw_live, raw_live or d_raw_live
+ *   off 16 bytes. */
+int nerf_amd_volume_render_masked_mse_backward_dist(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                                    uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                                    const int64_t* offsets, const float* gt, const float* bg, int64_t bg_stride,
+                                                    float std, uint32_t noise_flags, uint64_t noise_seed, const uint64_t* seed_mem,
+                                                    float t_far, float coef, float* rgb, float* loss_ray, float* d_raw_live,
+                                                    int64_t capacity, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

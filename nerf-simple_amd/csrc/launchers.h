@@ -54,6 +54,28 @@ struct MaskedBackwardArgs {
 };
 constexpr long long MASKED_NO_CLAMP = 0x7fffffffffffffffll;
 
+// What the masked training head with its optional terms reads beside the rays (masked_controls.hip): the MSE head under the
+// capacity clamp, as MaskedBackwardArgs describes it, and the terms' fields as DenseHeadArgs has them.  A term's fields are
+// looked at only where the term is on: std != 0 (noise; the ray ids are the jitter's, MlpArgs::ray_id0), bg != NULL, coef != 0.
+struct MaskedHeadArgs {
+    const unsigned long long* mask;                    // [B, ceil(N / 64)]
+    const long long* offsets;                          // [B + 1]
+    const float* raw_live;
+    float* d_raw_live;
+    long long B;
+    long long capacity;                                // rows of raw_live / d_raw_live: the clamp and the end of the zero fill
+    const float* target;                               // [B,3]
+    float* rgb;                                        // [B,3] = the loss's prediction
+    float scale;                                       // 1 / (3 B): the launcher's
+    const float* bg;                                   // one colour (bg_stride 0) or one per ray (bg_stride 3)
+    long long bg_stride;
+    float std;                                         // noise on sigma: keyed by noise_seed (+ *seed_mem)
+    unsigned long long noise_seed;
+    const unsigned long long* seed_mem;
+    float t_far, coef;                                 // the distortion term; coef == 0: off, loss_ray gets zeros
+    float* loss_ray;                                   // [B] or NULL
+};
+
 extern "C" {
 int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
 int nerf_amd_launch_pack_train(const float*, void*, void*, hipStream_t);
@@ -144,6 +166,9 @@ int nerf_amd_launch_background_blend_backward(const float*, const float*, long l
 int nerf_amd_launch_dense_head(const DenseHeadArgs*, hipStream_t);
 int nerf_amd_launch_distortion_loss(const float*, const float*, float, float, float*, float*, long long, int, hipStream_t);
 int nerf_amd_launch_sum_f32(const float*, float*, long long, hipStream_t);
+int nerf_amd_launch_sigma_noise_masked(const float*, float*, float, unsigned long long, const unsigned long long*, long long,
+                                       const unsigned long long*, const long long*, long long, int, hipStream_t);
+int nerf_amd_launch_masked_head(const MlpArgs*, const MaskedHeadArgs*, hipStream_t);
 int nerf_amd_launch_camera_rays(const float*, const float*, const long long*, long long*, int, int, float, float*, long long,
                                 long long, hipStream_t);
 int nerf_amd_launch_camera_rays_backward(const float*, const float*, const long long*, const float*, int, int, float, float*,

@@ -314,6 +314,62 @@ def _distortion_term(w, ts, lam, tn, tf):
 
 
 # --------------------------------------------------------------------------
+# the three terms as ONE argument: what the masked steps take, and the dense ones beside their flat keywords
+# --------------------------------------------------------------------------
+class Controls:
+    """``Controls(background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0)``: the training controls as one frozen value --
+    a background colour ([3], or one per ray [B,3]) behind the volume, the standard deviation of Gaussian noise on the raw
+    density with the counter RNG's ``noise_seed``, and the weight of the distortion loss (``train_step`` describes each).
+    Validated here as the flat keywords are (ValueError for a negative or non-finite ``sigma_noise`` / ``distortion``); the
+    background's shape is checked where the number of rays is known.  ``controls=`` is the one keyword the masked steps take
+    them through; on the dense steps it is the equivalent of the flat keywords, so a grid can be toggled without respelling
+    the call."""
+
+    __slots__ = ("background", "sigma_noise", "noise_seed", "distortion")
+
+    def __init__(self, background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0):
+        from .utils.rendering import _check_sigma_noise
+        set_ = object.__setattr__
+        set_(self, "background", background)
+        set_(self, "sigma_noise", _check_sigma_noise(sigma_noise))
+        set_(self, "noise_seed", int(noise_seed))
+        set_(self, "distortion", _check_distortion(distortion))
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError(f"Controls is frozen: build a new one to change {name!r}")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self):
+        return (f"Controls(background={self.background!r}, sigma_noise={self.sigma_noise!r}, noise_seed={self.noise_seed!r}, "
+                f"distortion={self.distortion!r})")
+
+    def replace(self, **changes):
+        """A new Controls with some fields changed."""
+        return Controls(**{**{n: getattr(self, n) for n in self.__slots__}, **changes})
+
+
+def _controls_arg(controls, *, background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0):
+    """``controls=`` of an entry point: None, or a Controls -- TypeError for anything else, ValueError where the flat keywords of
+    the same call (passed on here by those entry points that have them) say something too."""
+    if controls is None:
+        return None
+    if not isinstance(controls, Controls):
+        raise TypeError(f"controls must be a training.Controls (or None), got {type(controls).__name__}")
+    if background is not None or sigma_noise or noise_seed or distortion:
+        raise ValueError("controls= and the flat keywords background / sigma_noise / noise_seed / distortion say the same thing: "
+                         "give one of the two")
+    return controls
+
+
+def _refuse_bundle(controls, what):
+    """The paths ``controls=`` does not reach yet: refused before any launch and any RNG draw."""
+    if controls is not None:
+        _controls_arg(controls)
+        raise RuntimeError(f"controls= serves the dense and the masked single-network steps: not {what}")
+
+
+# --------------------------------------------------------------------------
 # fused dense layers: HIP forward (saving activations) + HIP dX chain + HIP dW
 # --------------------------------------------------------------------------
 def ctypes_stream(stream):
@@ -512,6 +568,30 @@ class _MaskedVolumeRender(torch.autograd.Function):
         return d_raw, None, None, None
 
 
+class _MaskedSigmaNoise(torch.autograd.Function):
+    """raw_live [P',4] -> the same with sigma' = sigma + std z in column 3 (nerf_amd_sigma_noise_masked: the noise each live
+    sample would get in the dense raw [B,N,4], keyed by its ORIGINAL index).  d sigma' / d sigma = 1: the backward is the
+    identity.  ``head`` = (mask, offsets, B, N)."""
+
+    @staticmethod
+    def forward(ctx, raw_live, std, noise_seed, ray_id0, head):
+        mask, offsets, B, N = head
+        dev = raw_live.device
+        raw_live = raw_live.contiguous()
+        out = torch.empty_like(raw_live)
+        live = raw_live.numel() > 0
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().nerf_amd_sigma_noise_masked(
+                _lib.ptr(raw_live) if live else None, _lib.ptr(out) if live else None, float(std), 0,
+                int(noise_seed) & (2 ** 64 - 1), None, int(ray_id0), _lib.ptr(mask), _lib.ptr(offsets), B, N,
+                _lib.stream_ptr(dev)), "nerf_amd_sigma_noise_masked")
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None, None, None
+
+
 class _ZeroParamGrads(torch.autograd.Function):
     """An empty raw_live [0,4] that still hangs on the parameters: a batch with no live sample launches no network kernel
     and its backward hands every parameter a zero tensor, not None."""
@@ -526,10 +606,12 @@ class _ZeroParamGrads(torch.autograd.Function):
         return tuple(torch.zeros_like(p) for p in ctx.like)
 
 
-def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, mark=None):
+def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, mark=None, controls=None):
     """The stages of ``render_nerf_masked`` once rays and jitter are settled: mark (or ``mark``, the ready MarkResult of these
     positions: the masked guided placement produces it with them) -> emit -> training forward on the live points -> masked
-    compositor, with gradients.  Sets ``occupancy.last_stats``."""
+    compositor, with gradients.  Sets ``occupancy.last_stats``.
+    ``controls`` = (bg, stride, sigma_noise, noise_seed, ray id of the first ray) or None: the noise stage on the live rows in
+    front of the compositor, the blend behind it, and the sample positions attached to the weights as ``w.ts``."""
     from .utils import occupancy as occ_mod
     B = rays.size(0)
     m = occ_mod._mark(occupancy, rays, jit, tbins, flags, seed, ray_id0, N) if mark is None else mark
@@ -546,11 +628,29 @@ def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, m
         stats["network_launches"] = 1
     else:
         raw_live = _ZeroParamGrads.apply(*params)
-    return _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+    if controls is None:
+        return _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+    bg, stride, std, noise_seed, noise_ray_id0 = controls
+    if std:
+        raw_live = _MaskedSigmaNoise.apply(raw_live, std, noise_seed, noise_ray_id0, (m.mask, m.offsets, B, N))
+    out = _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
+    out[4].ts = occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
+    if bg is not None:
+        out = (_Background.apply(out[0], out[3], bg, stride),) + tuple(out[1:])
+    return out
+
+
+def _masked_controls(controls, B, dev, ray_id0):
+    """A Controls as ``_masked_outputs`` takes it (None passes); the distortion term is the step's, not the render's."""
+    if controls is None:
+        return None
+    from .utils.rendering import _background_arg
+    bg = (None, 0) if controls.background is None else _background_arg(controls.background, B, dev)
+    return (*bg, controls.sigma_noise, controls.noise_seed, int(ray_id0))
 
 
 def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0,
-                       return_ts=False):
+                       return_ts=False, controls=None):
     """``render_nerf`` through an occupancy grid WITH gradients to the parameters of ``net``: the network is evaluated
     (fused bf16 training kernels, points mode) at the live samples only, a dead sample is (0, 0, 0, -inf) -- it contributes
     exactly nothing and receives no gradient.  Returns the same 5-tuple; alpha / w are dense [B,N], zero at dead samples.
@@ -560,20 +660,29 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     launched and every parameter gradient is a zero tensor.  Sets ``occupancy.last_stats``.  Raises, before any jitter is
     drawn, for rays that require grad, precision='fp32' modules, other network sizes, foreign nets and N > 512.
     ``return_ts=True``: returns (5-tuple, ts [B,N]) -- the sample positions of this jitter as nerf_amd_query_points forms
-    them (the coarse pass of the masked pair hands them to the sampler)."""
+    them (the coarse pass of the masked pair hands them to the sampler).
+    ``controls``: a ``Controls`` -- Gaussian noise on the live rows of the raw density (nerf_amd_sigma_noise_masked: a live
+    sample draws what the dense render gives that sample; a dead one stays dead) and rgb + (1 - acc) background behind the
+    masked compositor; ``w.ts`` then holds the sample positions.  The distortion term belongs to the step: a non-zero
+    ``controls.distortion`` raises ValueError."""
     from .utils import jitter, occupancy as occ_mod
+    controls = _controls_arg(controls)
+    if controls is not None and controls.distortion:
+        raise ValueError("render_nerf_masked renders: the distortion term belongs to the step (train_step(..., occupancy=, "
+                         "controls=), or distortion_loss on the weights it returns)")
     B, N = _lib.require_rays(rays), int(N)
     dev = rays.device
     occ_mod.check_trainable(occupancy, net, rays, N)
     if N < 1:
         raise RuntimeError(f"masked training serves 1 <= N <= {occ_mod.MAX_N_TRAIN} samples per ray, got N = {N}")
     _lib.require_same_device("occupancy grid", occupancy.words, dev)
+    controls = _masked_controls(controls, B, dev, ray_id0)     # the background's shape: before the jitter is drawn
     net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
     jit, flags, pending = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
     try:
         rays = rays.detach().contiguous()
         tbins = jitter.tbins(tn, tf, N, dev, flags)
-        out = _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0)
+        out = _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, controls=controls)
         if return_ts:
             return out, occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
         return out
@@ -606,7 +715,7 @@ def _optimise(loss, params, optimizer, decay, group):
 
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, background=None, sigma_noise=0.0,
-               noise_seed=0, distortion=0.0):
+               noise_seed=0, distortion=0.0, controls=None):
     """zero_grad -> render_nerf -> MSELoss(rgb, gt) -> backward -> [grad all-reduce]
     -> optimizer.step -> lr *= decay.  Returns the (detached) loss.
     Only ``rgb`` feeds the loss, as in the reference (train.py:52).
@@ -621,18 +730,29 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     loss becomes MSE + lambda / (B (tf - tn)) sum_rays D (``distortion_loss``; one fp32 add), on every path that composites
     through the HIP backward (bf16 fused, precision='fp32', other sizes) and together with background / sigma_noise.  Dense
     path only (RuntimeError with ``occupancy``); negative or not finite: ValueError.  The returned loss is the total; with
-    lambda > 0 ``.distortion`` on it holds the weighted term."""
+    lambda > 0 ``.distortion`` on it holds the weighted term.
+    controls: a ``Controls`` -- the same four as ONE argument, on the dense path (bit for bit the flat keywords; giving both
+    raises ValueError) AND with ``occupancy``: the masked step with the noise on its live rows, the loss behind the background
+    and the distortion term on the masked compositor's weights, assembled as the dense step assembles them."""
     from .utils.rendering import render_nerf, _refuse_controls
+    controls = _controls_arg(controls, background=background, sigma_noise=sigma_noise, noise_seed=noise_seed,
+                             distortion=distortion)
+    if controls is not None and occupancy is None:       # the dense step: the flat keywords' meaning
+        background, sigma_noise, noise_seed, distortion = (controls.background, controls.sigma_noise, controls.noise_seed,
+                                                           controls.distortion)
     lam = _check_distortion(distortion)
     _refuse_distortion(lam, occupancy=occupancy)
     _refuse_controls(background, sigma_noise, occupancy=occupancy)
     if occupancy is not None:
         from .utils.occupancy import check_trainable
         check_trainable(occupancy, net, rays, N, precision)      # before zero_grad: a refused call changes nothing
+        if controls is not None:
+            lam = controls.distortion
+            _masked_controls(controls, _lib.require_rays(rays), rays.device, ray_id0)      # the background's shape, likewise
     optimizer.zero_grad(set_to_none=True)
     if occupancy is not None:
-        rgb, _, _, _, _ = render_nerf_masked(rays, net, N, occupancy, tn, tf, u=u, device_rng=device_rng, seed=seed,
-                                             ray_id0=ray_id0)
+        rgb, _, _, _, w = render_nerf_masked(rays, net, N, occupancy, tn, tf, u=u, device_rng=device_rng, seed=seed,
+                                             ray_id0=ray_id0, controls=None if controls is None else controls.replace(distortion=0.0))
     else:
         kw = {}
         if background is not None or sigma_noise:          # off by default: a call without them is the call it was
@@ -693,7 +813,8 @@ def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray
 
 
 def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
-                            decay=1.0, group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
+                            decay=1.0, group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None,
+                            controls=None):
     """One optimisation step of the coarse / fine pair (the NeRF paper's objective; the reference has no hierarchical
     path, its CoarseNet / FineNet are empty): zero_grad -> coarse render_nerf with gradients (Nc stratified samples) ->
     sample_pdf on the DETACHED coarse weights (the coarse net learns from its own loss only) -> fine render_nerf of
@@ -715,6 +836,7 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     from .optim import FusedAdam
     from .utils import jitter
     from .utils.rendering import render_nerf, sample_pdf
+    _refuse_bundle(controls, "the coarse + fine pair (train_step_hierarchical)")
     _check_pair(net_c, net_f, Nc, Nf, precision)
     Nc, Nf = int(Nc), int(Nf)
     params = list(net_c.parameters()) + list(net_f.parameters())
@@ -763,7 +885,8 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
 # grid-guided fine sampling: ONE network, its Nf new samples placed from a sigma volume
 # --------------------------------------------------------------------------
 def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, ts_c=None, u_f=None, decay=1.0,
-                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, distortion=0.0):
+                      group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, distortion=0.0,
+                      controls=None):
     """One optimisation step of ONE network on grid-guided positions: ts = ``proposal.sample(rays, Nc, Nf, ...)`` (a
     ``ProposalVolume``, utils/proposal.py: no network evaluation, no gradient) -> zero_grad -> render_nerf with gradients on those
     Nc + Nf positions -> MSE(rgb, gt) -> backward -> [grad all-reduce] -> optimizer.step -> lr *= decay.  The loss is that of
@@ -779,7 +902,17 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
     before anything is drawn.
 
     distortion: ``train_step``'s -- the loss becomes MSE + lambda / (B (tf - tn)) sum_rays D on the Nc + Nf guided positions.
-    Not with ``occupancy`` (RuntimeError before anything is drawn)."""
+    Not with ``occupancy`` (RuntimeError before anything is drawn).
+
+    controls: a ``Controls`` -- with ``occupancy`` the masked guided step with the three terms, as ``train_step(..., occupancy=,
+    controls=)`` on the guided positions (the noise is keyed by ``noise_seed`` and ``ray_id0``).  Without a grid it stands for
+    ``distortion`` alone (the dense guided step knows no background and no noise: RuntimeError); with the flat keyword:
+    ValueError."""
+    controls = _controls_arg(controls, distortion=distortion)
+    if controls is not None and occupancy is None:
+        if controls.background is not None or controls.sigma_noise:
+            raise RuntimeError("the dense guided step takes the distortion term only: background / sigma_noise need occupancy=")
+        distortion = controls.distortion
     lam = _check_distortion(distortion)
     _refuse_distortion(lam, occupancy=occupancy)
     _check_guided(net, proposal)
@@ -789,12 +922,17 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
         occ_mod.check_trainable(occupancy, net, rays, int(Nc) + int(Nf), precision)
     proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)   # before any draw: a refused call changes nothing
     if occupancy is not None:
+        mc = None
+        if controls is not None:
+            lam = controls.distortion
+            mc = _masked_controls(controls, rays.size(0), rays.device, ray_id0)        # the background's shape: before any draw
         net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
         rays = rays.detach().contiguous()
         ts, mark = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
                                    ray_id0=ray_id0, occupancy=occupancy, return_mark=True)
         optimizer.zero_grad(set_to_none=True)
-        outs = _masked_outputs(rays, net, int(Nc) + int(Nf), occupancy, None, ts, _lib.FLAG_TS_GIVEN, 0, 0, mark=mark)
+        outs = _masked_outputs(rays, net, int(Nc) + int(Nf), occupancy, None, ts, _lib.FLAG_TS_GIVEN, 0, 0, mark=mark,
+                               controls=mc)
     else:
         ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
                              ray_id0=ray_id0)
@@ -1075,7 +1213,17 @@ class _MaskedPass(_Pass):
         """The masked head (masked compositor + MSE gradient + backward, one kernel); ``pdf`` as the dense pass's."""
         ptr, s = _lib.ptr, self.step
         args = (ptr(self.raw), *self.jitter, ptr(self.mask), ptr(self.offsets), ptr(s.gt))
-        if pdf is None:
+        if pdf is None and (s._controls or s._distortion > 0):
+            # the masked head behind the stepper's background, with noise on the live rows and / or with the distortion term
+            # beside the MSE: still one launch.  The noise key is noise_seed + the step's offset in memory and its ray ids start
+            # at the stepper's ray_id0, whatever the jitter source is (given positions carry no ids of their own)
+            rays, jit, tbins, flags, seed, _ = self.jitter
+            _launch("nerf_amd_volume_render_masked_mse_backward_dist", ptr(self.raw), rays, jit, tbins, flags, seed, s.ray_id0,
+                    ptr(self.mask), ptr(self.offsets), ptr(s.gt), ptr(s.background), s._bg_stride, s.sigma_noise,
+                    _lib.FLAG_SEED_IN_MEMORY, s.noise_seed & (2 ** 64 - 1), s._seed_mem, s._t_far if s._distortion > 0 else 0.0,
+                    s._dist_coef if s._distortion > 0 else 0.0, ptr(self.rgb), ptr(s._loss_ray) if s._distortion > 0 else None,
+                    ptr(self.d_raw), self.P, s.B, self.N, st)
+        elif pdf is None:
             _launch("nerf_amd_volume_render_masked_mse_backward", *args, ptr(self.rgb), ptr(self.d_raw), self.P, s.B, self.N, st)
         else:
             u_f, ts_f, Nf = pdf
@@ -1175,6 +1323,9 @@ class GraphedTrainStep:
     lambda is fixed at capture (``stepper.distortion_weight``, read-only): a schedule on it is a recapture.  The dense single
     step and the guided step only: the masked and hierarchical steppers raise RuntimeError.
 
+    ``controls``: a ``Controls`` -- ``background``, ``sigma_noise``, ``noise_seed`` and ``distortion`` as ONE argument, bit for
+    bit the flat keywords (giving both raises ValueError); the masked steppers take the terms through it alone.
+
     ``check_every`` (default 16, 0 = never): every so many steps the forward's range flag is copied back without
     waiting; a later ``step`` raises FloatingPointError once such a copy shows non-finite values inside the network
     (NaN / inf weights or inputs: a diverged run) -- the reference would show a NaN loss there.
@@ -1191,13 +1342,21 @@ class GraphedTrainStep:
 
     def __init__(self, net, optimizer, n_rays, N, *, tn=2, tf=6, group=None, timing=False, buckets=1,
                  device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16",
-                 background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0):
+                 background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0, controls=None):
         from . import parallel
         from .utils.rendering import _background_arg, _check_sigma_noise
+        pair = self._samples if self._samples and len(self._samples) == 2 else None
         self._distortion = _check_distortion(distortion)
         # the masked and hierarchical steppers inherit this constructor: the term cannot slip through them
-        _refuse_distortion(self._distortion, **{"a coarse / fine pair": self._samples if self._samples and len(self._samples) == 2 else None,
-                                                "an occupancy grid": self._capacities})
+        _refuse_distortion(self._distortion, **{"a coarse / fine pair": pair, "an occupancy grid": self._capacities})
+        # the bundle: the flat keywords' meaning here, and the one way the three terms reach a masked pass
+        controls = _controls_arg(controls, background=background, sigma_noise=sigma_noise, noise_seed=noise_seed,
+                                 distortion=distortion)
+        if controls is not None:
+            if pair is not None:
+                _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__})")
+            background, sigma_noise, noise_seed, self._distortion = (controls.background, controls.sigma_noise,
+                                                                     controls.noise_seed, controls.distortion)
         self._check_modules(net, optimizer)
         self._sigma_noise, self.noise_seed = _check_sigma_noise(sigma_noise), int(noise_seed)
         if background is not None:           # this object's own buffer: the captured head reads it at every replay
@@ -1824,6 +1983,7 @@ class GraphedCameraTrainStep(_TableTrainStep):
                  camera_eps=1e-8, select_mode="train", group=None, buckets=1, storage="bf16", background=None, sigma_noise=0.0,
                  distortion=0.0, **kw):
         from .utils.cameras import CameraRefinement
+        _refuse_bundle(kw.pop("controls", None), "GraphedCameraTrainStep")
         if storage != "bf16":
             raise RuntimeError("GraphedCameraTrainStep: storage='e4m3' is not served (nerf_amd_input_gradients reads bf16 dY)")
         if buckets != 1:
@@ -1912,6 +2072,7 @@ class GraphedAppearanceTrainStep(_TableTrainStep):
     def __init__(self, net, optimizer, n_rays, N, appearance, *, rays_from, appearance_lr=1e-3, appearance_betas=(0.9, 0.999),
                  appearance_eps=1e-8, select_mode="train", group=None, **kw):
         from .utils.appearance import AppearanceCorrection
+        _refuse_bundle(kw.pop("controls", None), "GraphedAppearanceTrainStep")
         self._bind_table(appearance, AppearanceCorrection, optimizer, n_rays, rays_from, select_mode, group,
                          (kw.get("background"), kw.get("sigma_noise"), kw.get("distortion")), appearance_lr, appearance_betas,
                          appearance_eps)
@@ -2040,11 +2201,21 @@ class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
     ``occupancy``: an ``OccupancyGrid`` / ``TrainingOccupancyGrid`` on the module's device.  The address of its ``words``
     is baked into the graph (``step`` raises if the tensor was replaced); ``TrainingOccupancyGrid.update`` writes the bits
     in place, so an update between two replays simply takes effect.  Jitter and ``step`` as GraphedTrainStep.  bf16 storage,
-    N <= 512, the default network."""
+    N <= 512, the default network.
+
+    ``controls``: a ``Controls`` -- with any term on the head is
+    nerf_amd_volume_render_masked_mse_backward_dist, still one launch under the same clamp: the loss behind
+    ``stepper.background`` (the stepper's own buffer, overwritable in place between replays), Gaussian noise on the live rows
+    keyed by ``noise_seed`` + the step count read from device memory (step k draws what the eager masked step draws with
+    ``noise_seed + k``), and the distortion term, whose per-ray values the side branch sums into ``stepper.distortion`` while
+    ``step()`` returns the total -- GraphedTrainStep's machinery.  Without it the step is the one it was, kernel for kernel.
+    The flat ``distortion=`` keyword keeps refusing here."""
 
     def __init__(self, net, optimizer, n_rays, N, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
-                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0):
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0,
+                 controls=None):
         _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
+        controls = _controls_arg(controls)
         self._refuse(storage, buckets)
         B, N_ = int(n_rays), int(N)
         if B < 1 or N_ < 1:
@@ -2052,7 +2223,7 @@ class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
         self._bind_grid((net,), (N_,), B, optimizer, occupancy, capacity)
         self.capacity = self._capacities[0]
         super().__init__(net, optimizer, B, N_, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed, ray_id0=ray_id0,
-                         check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+                         check_every=check_every, rays_from=rays_from, select_mode=select_mode, controls=controls)
 
     def step(self, rays=None, gt=None, u=None, decay=1.0):
         self._watch_grid()
@@ -2110,8 +2281,9 @@ class GraphedHierarchicalTrainStep(_PairJitter, GraphedTrainStep):
     _one_bucket = True
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc=64, Nf=128, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
-                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", distortion=0.0):
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", distortion=0.0, controls=None):
         _refuse_distortion(_check_distortion(distortion), **{"a coarse / fine pair": (net_c, net_f)})
+        _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__})")
         _check_pair(net_c, net_f, Nc, Nf, None)
         self.net_c, self.net_f, self.Nc, self.Nf = net_c, net_f, int(Nc), int(Nf)
         # ``net`` / ``nets`` are the pair, as FusedAdam([net_c, net_f]).net / .nets hold it
@@ -2155,8 +2327,9 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc, Nf, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
                  seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
-                 distortion=0.0):
+                 distortion=0.0, controls=None):
         _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
+        _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__})")
         self._refuse(storage, buckets)
         _check_pair(net_c, net_f, Nc, Nf, None)
         B, Nc_, Nf_ = int(n_rays), int(Nc), int(Nf)
@@ -2192,10 +2365,15 @@ class GraphedGuidedTrainStep(_PairJitter, GraphedTrainStep):
     _one_bucket = True
 
     def __init__(self, net, optimizer, n_rays, Nc, Nf, proposal, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
-                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0):
+                 ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0,
+                 controls=None):
         from .utils.proposal import check_sizes
         lam = _check_distortion(distortion)
         _refuse_distortion(lam, **{"an occupancy grid": self._capacities})       # the masked guided stepper comes through here
+        controls = _controls_arg(controls, distortion=distortion)
+        if controls is not None and self._capacities is None and (controls.background is not None or controls.sigma_noise):
+            raise RuntimeError("the dense guided stepper takes the distortion term only: background / sigma_noise need the "
+                               "masked guided stepper (GraphedMaskedGuidedTrainStep)")
         _MaskedSteps._refuse(self, storage, buckets)
         _check_guided(net, proposal)
         self.Nc, self.Nf = check_sizes(Nc, Nf)
@@ -2207,7 +2385,8 @@ class GraphedGuidedTrainStep(_PairJitter, GraphedTrainStep):
         proposal.check(torch.empty((0, 6), dtype=torch.float32, device=proposal.sigma.device), self.Nc, self.Nf)
         self.proposal, self._sigma_ptr = proposal, proposal.sigma.data_ptr()
         super().__init__(net, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
-                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode, distortion=lam)
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode, distortion=lam,
+                         controls=controls)
 
     def _alloc_pass_buffers(self, tn, tf):
         """The dense pass reads given positions: ``ts_f``, which the sampler writes.  ``u`` is split as a pair's."""
@@ -2264,15 +2443,18 @@ class GraphedMaskedGuidedTrainStep(_MaskedSteps, GraphedGuidedTrainStep):
     ``rays_from`` are GraphedGuidedTrainStep's.  The addresses of ``occupancy.words`` and ``proposal.sigma`` are baked into
     the graph (``step`` raises if either tensor was replaced); ``TrainingOccupancyGrid.update`` and ``ProposalVolume.update``
     write in place, so an update between two replays simply takes effect.  With P' <= C at step k the step is the eager
-    ``train_step_guided(..., occupancy=, device_rng=True, seed=seed + k)``.  bf16 storage, the default network."""
+    ``train_step_guided(..., occupancy=, device_rng=True, seed=seed + k)``.  bf16 storage, the default network.
+    ``controls``: GraphedMaskedTrainStep's -- the same head with the three terms on the Nc + Nf guided positions; the eager
+    equivalent at step k is ``train_step_guided(..., occupancy=, controls=c.replace(noise_seed=c.noise_seed + k))``."""
 
     _masked_pass_type = _MarkedPass
 
     def __init__(self, net, optimizer, n_rays, Nc, Nf, proposal, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
                  seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
-                 distortion=0.0):
+                 distortion=0.0, controls=None):
         from .utils.proposal import check_sizes
         _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
+        controls = _controls_arg(controls)
         self._refuse(storage, buckets)
         _check_guided(net, proposal)
         Nc_, Nf_ = check_sizes(Nc, Nf)
@@ -2282,7 +2464,7 @@ class GraphedMaskedGuidedTrainStep(_MaskedSteps, GraphedGuidedTrainStep):
         self._bind_grid((net,), (Nc_ + Nf_,), B, optimizer, occupancy, capacity)
         self.capacity = self._capacities[0]
         super().__init__(net, optimizer, B, Nc_, Nf_, proposal, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
-                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode, controls=controls)
 
     def _before_forward(self, st):
         import ctypes

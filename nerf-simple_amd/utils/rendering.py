@@ -94,6 +94,27 @@ def _refuse_controls(background, sigma_noise, **paths):
                                "or without the grid)")
 
 
+def _inference_controls(controls, occupancy, terminate, **flat):
+    """``controls=`` of the inference renders -> (flat keywords to go on with, the masked render's background or None).  Without a grid the bundle is the flat keywords' equivalent (both given: ValueError); with ``occupancy`` it
+    brings the background alone -- the masked render, then the blend.  Refused before anything is drawn or launched: with
+    ``terminate``, a non-zero ``distortion`` (the term belongs to a training step), noise behind a grid."""
+    from ..training import _controls_arg
+    c = _controls_arg(controls, **flat)
+    if c is None:
+        return flat, None
+    if terminate is not None:
+        raise RuntimeError("controls= does not reach the terminated render yet: not with terminate=")
+    if c.distortion:
+        raise ValueError("the distortion term belongs to a training step (train_step(..., controls=)): a render takes "
+                         "controls.distortion == 0")
+    if occupancy is None:
+        return {k: getattr(c, k) for k in flat}, None
+    if c.sigma_noise > 0:
+        raise RuntimeError("sigma_noise is a training regulariser, not a render option: the masked inference render trains "
+                           "nothing")
+    return flat, c.background
+
+
 def _blend(rgb, acc, disp, bg, stride, pixels=False):
     """rgb + (1 - acc) bg through nerf_amd_background_blend: rgb_bg [B,3], or pixels [B,4] = [clip(rgb_bg, 0, 1), disp]."""
     B, dev = rgb.shape[0], rgb.device
@@ -140,7 +161,7 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS, background=None):
 
 def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUTS,
                 precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, terminate=None,
-                background=None, sigma_noise=0.0, noise_seed=0):
+                background=None, sigma_noise=0.0, noise_seed=0, controls=None):
     """Stratified sampling along rays, NeRF query, compositing
     (reference utils/rendering.py:13-45).
 
@@ -168,11 +189,23 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     ``noise_seed`` and the global sample id (``ray_id0``), whatever the jitter source; pass a new ``noise_seed`` per step.
     Both serve the dense path only: with ``occupancy`` or ``terminate`` they raise RuntimeError before anything is drawn
     or launched.
+
+    controls: a ``training.Controls`` -- without a grid the equivalent of the three keywords above (both given: ValueError);
+    with ``occupancy`` the background behind the masked render: rgb becomes rgb + (1 - acc) background through the same blend,
+    the other four outputs are what they were.  ``controls.sigma_noise > 0`` behind a grid raises the regulariser's
+    RuntimeError, a non-zero ``controls.distortion`` ValueError, ``terminate=`` with it RuntimeError.
     """
+    masked_bg = None
+    if controls is not None:
+        flat, masked_bg = _inference_controls(controls, occupancy, terminate, background=background, sigma_noise=sigma_noise,
+                                              noise_seed=noise_seed)
+        background, sigma_noise, noise_seed = flat["background"], flat["sigma_noise"], flat["noise_seed"]
     _refuse_controls(background, sigma_noise, occupancy=occupancy, terminate=terminate)
     std = _check_sigma_noise(sigma_noise) if sigma_noise else 0.0
     B, N = _lib.require_rays(rays), int(N)
     dev = rays.device
+    if masked_bg is not None:
+        masked_bg = _background_arg(masked_bg, B, dev)
     controls = None
     if background is not None or sigma_noise:
         bg = (None, 0) if background is None else _background_arg(background, B, dev)
@@ -219,7 +252,8 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
         try:
             if terminate is not None:
                 return render_terminated(terminate, occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
-            return render_masked(occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
+            out = render_masked(occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
+            return out if masked_bg is None else (_blend(out[0], out[3], None, *masked_bg),) + tuple(out[1:])
         finally:
             if pending_rng is not None:
                 pending_rng.finish()
@@ -471,7 +505,7 @@ def generate_rays(pose, cam_params, device, ray0=0, n_rays=None):
 
 
 def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_rays=None,
-                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None, background=None):
+                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None, background=None, controls=None):
     """One view (or the pixel range [ray0, ray0+n_rays) of it) in ONE library
     call: device ray generation -> render_nerf -> clip(rgb,0,1), i.e. the body of
     the reference's per-image loop (utils/rendering.py:139-151) without the
@@ -486,7 +520,15 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     without one, on an all-live grid.
     background: a colour [3] (or one per pixel of the range, [n,3]) behind the volume: pixels = [clip(rgb + (1 - acc)
     background, 0, 1), disparity], the clip behind the blend.  Device ray generation, nerf_amd_render_forward for rgb, disp
-    and acc, then one small blend launch (without a background: the one call it was).  Not with occupancy / terminate."""
+    and acc, then one small blend launch (without a background: the one call it was).  Not with occupancy / terminate.
+    controls: a ``training.Controls`` -- ``render_nerf``'s: without a grid it stands for ``background``; with ``occupancy`` the
+    masked render through the five-output masked compositor (so that acc exists), then the blend and the clip behind it."""
+    masked_bg = None
+    if controls is not None:
+        flat, masked_bg = _inference_controls(controls, occupancy, terminate, background=background)
+        if occupancy is None and controls.sigma_noise > 0:
+            raise RuntimeError("sigma_noise is a training regulariser, not a render option: render_view trains nothing")
+        background = flat["background"]
     _refuse_controls(background, 0.0, occupancy=occupancy, terminate=terminate)
     dev = next(net.parameters()).device
     if terminate is not None:
@@ -507,6 +549,8 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
                                              **({} if background is None else {"background": background}))
         return torch.cat([rgb.clamp(0., 1.), disp[:, None]], dim=1)
     bg = None if background is None else _background_arg(background, n, dev)
+    if masked_bg is not None:
+        masked_bg = _background_arg(masked_bg, n, dev)
     code = _lib.precision_of(net, precision)
     net.packed_weights(code)
     # the shape of ``u`` is looked at below, on the masked and background branches only (section 31)
@@ -522,6 +566,10 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         if terminate is not None:
             return render_terminated(terminate, occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
                                      code, (), pixels=True)
+        if masked_bg is not None:
+            rgb, disp, _, acc, _ = render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
+                                                 code, ())
+            return _blend(rgb, acc, disp, *masked_bg, pixels=True)
         return render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0, code, (),
                              pixels=True)
 
