@@ -1,7 +1,8 @@
 // composite_backward_device.h -- the per-ray backward walk of the compositor, shared by its kernels:
 // composite_backward_kernel<E> (composite.hip, dense raw[B, N, 4]), dense_head_kernel (composite_head.hip, the dense head
-// with its optional terms) and masked_backward_kernel<Up, E> (occupancy_train.hip, the masked samples: the five gradients,
-// or the MSE head under the capacity clamp, alone or with the fine pass's sampler behind it).
+// with its optional terms) and masked_backward_kernel<Up, NOISE, E> (occupancy_train.hip, the masked samples: the five
+// gradients, or the MSE head under the capacity clamp -- alone, with the fine pass's sampler behind it, or with the dense
+// head's terms).
 //
 // d loss / d raw given the upstream gradients of the five outputs.  With G_i = dL/dw_i gathered from every consumer of w,
 //   dL/dc_i     = w_i * g_rgb
@@ -15,7 +16,8 @@
 // samples.  The one fused pair is G T - suffix / f; everything else rounds separately.
 //
 // The three axes on which the callers differ are compile-time choices; a term a caller does not have is not computed.
-//   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd)
+//   Src  -- the ray's samples, asked chunk by chunk in ascending order (DenseSamples below; MaskedSamplesBwd; either in
+//           nerf_noise::Noisy<>, sigma_noise_device.h)
 //   Up   -- the upstream gradients (FiveGrads: five pointers, each may be NULL; LossHead<BG, DIST, AFFINE>: the MSE loss
 //           gradient formed here -- BG: behind a background colour, whose gradient to acc reaches every w_i; DIST: with the
 //           distortion loss of the ray's weights beside the MSE, whose gradient joins G_i where FiveGrads adds g_w; AFFINE:

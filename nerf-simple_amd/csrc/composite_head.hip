@@ -1,6 +1,6 @@
 // composite_head.hip -- the dense training head with its optional terms, ONE kernel: compositor + MSE gradient + compositor
 // backward on composite_backward_ray (composite_backward_device.h), one wavefront per ray, with any of
-//   NOISE    Gaussian noise on the raw density in front of the softplus (sigma_noise_device.h NoisySamples)
+//   NOISE    Gaussian noise on the raw density in front of the softplus (sigma_noise_device.h Noisy<Src>)
 //   BG       the loss behind a background colour                         (the stages: composite_bg.hip)
 //   DIST     the distortion loss of the ray's weights beside the MSE     (the stage: composite_dist.hip)
 //   AFFINE   the loss behind a per-image colour correction               (the stages: appearance.hip)
@@ -33,7 +33,8 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void dense_head_kernel(const D
     const nerf_composite::DenseSamples dense{a.ts + ray * N, reinterpret_cast<const f32x4*>(a.raw) + ray * N};
     if constexpr (NOISE) {
         nerf_composite::composite_backward_ray<MAX_CHUNKS>(
-            nerf_noise::NoisySamples{dense, a.std, nerf_noise::noise_key(a.seed, a.seed_mem), (unsigned long long)((a.ray_id0 + ray) * N)},
+            nerf_noise::Noisy<nerf_composite::DenseSamples>{dense, a.std, nerf_noise::noise_key(a.seed, a.seed_mem),
+                                                            (unsigned long long)((a.ray_id0 + ray) * N)},
             up, nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
     } else {
         nerf_composite::composite_backward_ray<MAX_CHUNKS>(dense, up, nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);

@@ -32,10 +32,12 @@ struct DenseHeadArgs {
     float* g_theta;                                    // and every ray's row of d loss / d theta [B,6]
 };
 
-// What the masked compositor backward reads beside the rays (occupancy_train.hip), filled by the three entry points that
-// reach it (api.hip: the eager backward; occupancy_graph.hip: the two capped heads).  The upstream gradients are the MSE
-// head's where target != NULL and the five pointers otherwise; the fine pass's sampler runs behind the sweep where
-// ts_out != NULL.
+// What the masked compositor backward reads beside the rays (occupancy_train.hip), filled by the entry points that reach it
+// (api.hip: the eager backward; occupancy_graph.hip and masked_controls.hip: the three capped heads, through
+// capped_head_args below).  The upstream gradients are the MSE head's where target != NULL and the five pointers otherwise.
+// Behind the MSE head either the fine pass's sampler runs (ts_out != NULL) or any of the head's terms is on, its fields as
+// DenseHeadArgs has them: std != 0 (noise; the ray ids are the jitter's, MlpArgs::ray_id0), bg != NULL, coef != 0.  A
+// term's fields are looked at only where the term is on.
 struct MaskedBackwardArgs {
     const unsigned long long* mask;                    // [B, ceil(N / 64)]
     const long long* offsets;                          // [B + 1]
@@ -46,27 +48,11 @@ struct MaskedBackwardArgs {
                                                        // the end of the zero fill; MASKED_NO_CLAMP: the rows are offsets[B]
     const float *g_rgb, *g_disp, *g_alpha, *g_acc, *g_w;   // each may be NULL
     const float* target;                               // the MSE head: [B,3]
-    float* rgb;                                        // [B,3]
+    float* rgb;                                        // [B,3] = the loss's prediction
     float scale;                                       // 1 / (3 B): the launcher's
     const float* u_f;                                  // the sampler: u_f[B, Nf] (unused with the counter RNG)
     float* ts_out;                                     // [B, N + Nf]
     int Nf;
-};
-constexpr long long MASKED_NO_CLAMP = 0x7fffffffffffffffll;
-
-// What the masked training head with its optional terms reads beside the rays (masked_controls.hip): the MSE head under the
-// capacity clamp, as MaskedBackwardArgs describes it, and the terms' fields as DenseHeadArgs has them.  A term's fields are
-// looked at only where the term is on: std != 0 (noise; the ray ids are the jitter's, MlpArgs::ray_id0), bg != NULL, coef != 0.
-struct MaskedHeadArgs {
-    const unsigned long long* mask;                    // [B, ceil(N / 64)]
-    const long long* offsets;                          // [B + 1]
-    const float* raw_live;
-    float* d_raw_live;
-    long long B;
-    long long capacity;                                // rows of raw_live / d_raw_live: the clamp and the end of the zero fill
-    const float* target;                               // [B,3]
-    float* rgb;                                        // [B,3] = the loss's prediction
-    float scale;                                       // 1 / (3 B): the launcher's
     const float* bg;                                   // one colour (bg_stride 0) or one per ray (bg_stride 3)
     long long bg_stride;
     float std;                                         // noise on sigma: keyed by noise_seed (+ *seed_mem)
@@ -75,6 +61,19 @@ struct MaskedHeadArgs {
     float t_far, coef;                                 // the distortion term; coef == 0: off, loss_ray gets zeros
     float* loss_ray;                                   // [B] or NULL
 };
+constexpr long long MASKED_NO_CLAMP = 0x7fffffffffffffffll;
+
+// the plain MSE head under the clamp `capacity`: what the three capped heads share; the sampler's and the terms' fields zero
+inline MaskedBackwardArgs capped_head_args(const float* raw_live, const uint64_t* mask, const int64_t* offsets, const float* gt,
+                                           float* rgb, float* d_raw_live, int64_t capacity, int64_t B) {
+    MaskedBackwardArgs b{};
+    b.mask = reinterpret_cast<const unsigned long long*>(mask);
+    b.offsets = reinterpret_cast<const long long*>(offsets);
+    b.raw_live = raw_live; b.d_raw_live = d_raw_live;
+    b.B = B; b.capacity = capacity;
+    b.target = gt; b.rgb = rgb;
+    return b;
+}
 
 extern "C" {
 int nerf_amd_launch_pack(const float*, void*, int, hipStream_t);
@@ -168,7 +167,6 @@ int nerf_amd_launch_distortion_loss(const float*, const float*, float, float, fl
 int nerf_amd_launch_sum_f32(const float*, float*, long long, hipStream_t);
 int nerf_amd_launch_sigma_noise_masked(const float*, float*, float, unsigned long long, const unsigned long long*, long long,
                                        const unsigned long long*, const long long*, long long, int, hipStream_t);
-int nerf_amd_launch_masked_head(const MlpArgs*, const MaskedHeadArgs*, hipStream_t);
 int nerf_amd_launch_camera_rays(const float*, const float*, const long long*, long long*, int, int, float, float*, long long,
                                 long long, hipStream_t);
 int nerf_amd_launch_camera_rays_backward(const float*, const float*, const long long*, const float*, int, int, float, float*,

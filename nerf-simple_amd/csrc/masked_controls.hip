@@ -1,24 +1,18 @@
 // masked_controls.hip -- the training controls of the dense path (background colour, noise on the raw density, distortion
 // loss; composite_bg.hip, composite_dist.hip, composite_head.hip) for the MASKED single-network steps: the noise stage on the
-// live rows, and the masked training head with any of the three terms in one launch under the capacity clamp.  Not in the
-// reference.  include/nerf_amd.h, "masked training controls"; DESIGN.md section 32.
+// live rows, and the entry point of the masked training head with any of the three terms in one launch under the capacity
+// clamp.  Not in the reference.  include/nerf_amd.h, "masked training controls"; DESIGN.md section 32.
 //
 //   sigma_noise_masked_kernel<NOISE> -- raw_live[P',4] -> out[P',4].  One wavefront per ray, lane = ORIGINAL sample index,
 //       row = offsets[ray] + rank, rank from popcounts of the mask words (as emit_ray_rows, occ_scan_device.h): the colours
 //       copied, sigma' = noisy_sigma(sigma, std, key, (ray_id0 + ray) N + i) (sigma_noise_device.h, the one definition).  The
 //       counter is the original sample index, so a live sample draws what nerf_amd_sigma_noise gives that sample in the dense
 //       raw[B,N,4].  A row is read and written by the same lane: out may be raw_live.  NOISE = false: the copy alone.
-//   masked_head_kernel<NOISE, BG, DIST> -- masked_backward_kernel<MseHead, 0>'s walk (occupancy_train.hip: the pad rows, the
-//       clamp, the empty ray, the positions into the wave's LDS slice, composite_backward_ray over MaskedSamplesBwd) with
-//       LossHead<BG, DIST, false> as the loss head and, with NOISE, NoisyMaskedSamples around the source.  It is a kernel of
-//       its own on the shared headers: occupancy_train.hip's six instantiations are pinned by name and by count and stay as
-//       they are.  Seven instantiations, the combinations the entry point reaches; with no term the launcher hands the launch
-//       on to nerf_amd_launch_masked_backward.
+//   the head -- masked_backward_kernel<LossHead<BG, DIST, false>, NOISE, 0> (occupancy_train.hip, the one walk of every
+//       masked backward and head); this source holds its entry point, which fills the terms' fields of MaskedBackwardArgs.
 //
-// No atomics; the kept rows and the pad rows are disjoint ranges and every row of d_raw_live[C,4] is written by exactly one
-// lane on every launch, so two runs write the same bytes.  The two entry points below are the C ABI themselves (argument
-// checking included, api_checks.h).
-#include "composite_backward_device.h"
+// No atomics; a row is written by exactly one lane, so two runs write the same bytes.  The two entry points below are the
+// C ABI themselves (argument checking included, api_checks.h).
 #include "sigma_noise_device.h"
 #include "occ_scan_device.h"
 #include "api_checks.h"
@@ -26,8 +20,7 @@
 
 namespace {
 
-constexpr int MAX_N = nerf_layout::COMPOSITE_BWD_MAX_N;                    // N <= 512, the plain masked head's limit
-constexpr int CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;
+constexpr int MAX_N = nerf_layout::COMPOSITE_BWD_MAX_N;                    // N <= 512, the masked head's limit
 
 template <bool NOISE>
 __global__ __launch_bounds__(MASKED_THREADS) void sigma_noise_masked_kernel(const f32x4* raw, f32x4* out, float std,
@@ -61,56 +54,6 @@ __global__ __launch_bounds__(MASKED_THREADS) void sigma_noise_masked_kernel(cons
     }
 }
 
-template <bool NOISE, bool BG, bool DIST>
-__global__ __launch_bounds__(MASKED_THREADS) void masked_head_kernel(MlpArgs a, MaskedHeadArgs b) {
-    __shared__ float lds[MASKED_RAYS_PER_BLOCK][MAX_N];
-    const int wv = threadIdx.x >> 6;
-    const long long ray = (long long)blockIdx.x * MASKED_RAYS_PER_BLOCK + wv;
-    const int lane = threadIdx.x & 63;
-    const int N = a.N;
-    {
-        // the surplus rows [min(P', C), C) of d_raw_live: exact zeros, grid-stride (no wave depends on another's rows)
-        const long long kept = min_ll(b.offsets[b.B], b.capacity);
-        f32x4* pad = reinterpret_cast<f32x4*>(b.d_raw_live) + kept;
-        for (long long r = (long long)blockIdx.x * MASKED_THREADS + threadIdx.x; r < b.capacity - kept;
-             r += (long long)gridDim.x * MASKED_THREADS)
-            pad[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    if (ray >= b.B) return;                    // whole wave leaves together; no workgroup barrier below
-    const long long first = min_ll(b.offsets[ray], b.capacity);
-    const long long n_kept = min_ll(b.offsets[ray + 1], b.capacity) - first;
-    const unsigned long long* m = b.mask + ray * ((N + 63) >> 6);
-    f32x4* rout = reinterpret_cast<f32x4*>(b.d_raw_live) + first;
-    float* rts = lds[wv];
-    const nerf_composite::LossHead<BG, DIST, false> up{b.target, b.rgb, b.scale, b.bg, b.bg_stride, b.t_far, b.coef, b.loss_ray,
-                                                       nullptr, 0, nullptr};
-    if constexpr (!DIST) {                     // coef == 0: the term's values are zeros
-        if (b.loss_ray && lane == 0) b.loss_ray[ray] = 0.f;
-    }
-    if (N == 1 || n_kept <= 0) {
-        // N == 1: the reference composites an EMPTY sample axis; nothing kept: every sample is (0, 0, 0, -inf), w = 0
-        // throughout.  Either way rgb = bg through the blend's own ops (0 without one), the ray has no weight (D = 0) and a
-        // kept row (N == 1) gets zeros: the dense head's empty ray, whose one row may not exist here.
-        if (n_kept > 0 && (m[0] & 1ull)) {
-            nerf_composite::loss_head_empty_ray(up, lane, ray, rout);
-        } else {
-            f32x4 none;                        // a register: the routine's store of the row goes nowhere
-            nerf_composite::loss_head_empty_ray(up, lane, ray, &none);
-        }
-        return;
-    }
-    fill_ray_positions(a, ray, lane, rts);
-    const nerf_composite::MaskedSamplesBwd src{rts, m, reinterpret_cast<const f32x4*>(b.raw_live) + first, n_kept};
-    if constexpr (NOISE) {
-        nerf_composite::composite_backward_ray<CHUNKS>(
-            nerf_noise::NoisyMaskedSamples{src, b.std, nerf_noise::noise_key(b.noise_seed, b.seed_mem),
-                                           (unsigned long long)((a.ray_id0 + ray) * N)},
-            up, nerf_composite::NoSink{}, N, lane, ray_dnorm(a, ray), ray, rout);
-    } else {
-        nerf_composite::composite_backward_ray<CHUNKS>(src, up, nerf_composite::NoSink{}, N, lane, ray_dnorm(a, ray), ray, rout);
-    }
-}
-
 }  // namespace
 
 extern "C" int nerf_amd_launch_sigma_noise_masked(const float* raw_live, float* out, float std, unsigned long long seed,
@@ -129,37 +72,6 @@ extern "C" int nerf_amd_launch_sigma_noise_masked(const float* raw_live, float* 
     else
         hipLaunchKernelGGL(sigma_noise_masked_kernel<true>, grid, block, 0, stream, in4, out4, std, seed, seed_mem, ray_id0, mask,
                            offsets, B, N);
-    return (int)hipGetLastError();
-}
-
-extern "C" int nerf_amd_launch_masked_head(const MlpArgs* args, const MaskedHeadArgs* head, hipStream_t stream) {
-    MaskedHeadArgs b = *head;
-    const bool noise = b.std != 0.f, bg = b.bg != nullptr, dist = b.coef != 0.f;
-    if (!noise && !bg && !dist) {              // no term: the plain masked head's launch itself (occupancy_train.hip)
-        if (b.loss_ray && b.B > 0) {
-            const hipError_t e = hipMemsetAsync(b.loss_ray, 0, (size_t)b.B * sizeof(float), stream);
-            if (e != hipSuccess) return (int)e;
-        }
-        MaskedBackwardArgs p{};
-        p.mask = b.mask; p.offsets = b.offsets; p.raw_live = b.raw_live; p.d_raw_live = b.d_raw_live;
-        p.B = b.B; p.capacity = b.capacity; p.target = b.target; p.rgb = b.rgb;
-        return nerf_amd_launch_masked_backward(args, &p, stream);
-    }
-    (void)hipGetLastError();
-    if (b.B == 0) return 0;
-    if (args->N > MAX_N) return -2;
-    b.scale = 1.0f / (3.0f * (float)b.B);
-    const dim3 grid((unsigned)((b.B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
-#define MASKED_HEAD(NOISE_, BG_, DIST_) \
-    hipLaunchKernelGGL((masked_head_kernel<NOISE_, BG_, DIST_>), grid, block, 0, stream, *args, b)
-    if (!dist && !noise) MASKED_HEAD(false, true, false);
-    else if (!dist && !bg) MASKED_HEAD(true, false, false);
-    else if (!dist) MASKED_HEAD(true, true, false);
-    else if (!noise && !bg) MASKED_HEAD(false, false, true);
-    else if (!noise) MASKED_HEAD(false, true, true);
-    else if (!bg) MASKED_HEAD(true, false, true);
-    else MASKED_HEAD(true, true, true);
-#undef MASKED_HEAD
     return (int)hipGetLastError();
 }
 
@@ -205,15 +117,10 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward_dist(const float* raw_
         misaligned(gt, 4) || misaligned(rgb, 4) || misaligned(bg, 4) || misaligned(loss_ray, 4))
         return NERF_AMD_EINVAL;
     const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
-    MaskedHeadArgs b{};
-    b.mask = reinterpret_cast<const unsigned long long*>(mask);
-    b.offsets = reinterpret_cast<const long long*>(offsets);
-    b.raw_live = raw_live; b.d_raw_live = d_raw_live;
-    b.B = B; b.capacity = capacity;
-    b.target = gt; b.rgb = rgb;
+    MaskedBackwardArgs b = capped_head_args(raw_live, mask, offsets, gt, rgb, d_raw_live, capacity, B);
     b.bg = bg; b.bg_stride = bg_stride;
     b.std = std; b.noise_seed = noise_seed;
     b.seed_mem = (noise_flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr;
     b.t_far = t_far; b.coef = coef; b.loss_ray = loss_ray;
-    return nerf_amd_launch_masked_head(&a, &b, reinterpret_cast<hipStream_t>(stream));
+    return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
 }

@@ -9,8 +9,9 @@
 //   the two fused heads -- masked compositor forward -> g_rgb = 2 (rgb - gt) / (3 B) -> masked compositor backward in one
 //       launch under the capacity clamp, and for the coarse head of the hierarchical pair the fine pass's sample placement
 //       behind it in the same wave (the fine pass's mark depends on ts_out, so in a captured step both have to come out of
-//       one node chain with no host in it).  Both are masked_backward_kernel<MseHead, E> (occupancy_train.hip) with
-//       capacity = C; this source holds their entry points.
+//       one node chain with no host in it).  Both are masked_backward_kernel<MseHead, false, E> (occupancy_train.hip) with
+//       capacity = C; this source holds their entry points, which fill MaskedBackwardArgs through capped_head_args
+//       (launchers.h) as the head with the training controls does (masked_controls.hip).
 //
 // No atomics; the kept rows and the pad rows are disjoint ranges, so no two lanes write one address and two runs write the
 // same bytes.  The host wrappers below are the C ABI themselves (argument checking included, api_checks.h).
@@ -52,19 +53,6 @@ int occg_check(const float* rays, const float* u, const float* tbins, uint32_t f
     return rc ? rc : capped_check(mask, offsets, C, B, N);
 }
 
-// the launch of a fused head, its arguments checked: the MSE head under the clamp, with the sampler where ts_out != NULL
-int capped_head(const MlpArgs& a, const float* raw_live, const uint64_t* mask, const int64_t* offsets, const float* gt, float* rgb,
-                float* d_raw_live, int64_t capacity, int64_t B, const float* u_f, float* ts_out, int Nf, void* stream) {
-    MaskedBackwardArgs b{};
-    b.mask = reinterpret_cast<const unsigned long long*>(mask);
-    b.offsets = reinterpret_cast<const long long*>(offsets);
-    b.raw_live = raw_live; b.d_raw_live = d_raw_live;
-    b.B = B; b.capacity = capacity;
-    b.target = gt; b.rgb = rgb;
-    b.u_f = u_f; b.ts_out = ts_out; b.Nf = Nf;
-    return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
-}
-
 }  // namespace
 
 extern "C" int nerf_amd_occupancy_points_capped(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed,
@@ -91,8 +79,9 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward(const float* raw_live,
     if (!raw_live || !gt || !rgb || !d_raw_live || misaligned(raw_live, 16) || misaligned(d_raw_live, 16) ||
         misaligned(gt, 4) || misaligned(rgb, 4))
         return NERF_AMD_EINVAL;
-    return capped_head(rays_args(rays, u, tbins, flags, seed, ray_id0, B, N), raw_live, mask, offsets, gt, rgb, d_raw_live, capacity,
-                       B, nullptr, nullptr, 0, stream);
+    const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, N);
+    const MaskedBackwardArgs b = capped_head_args(raw_live, mask, offsets, gt, rgb, d_raw_live, capacity, B);
+    return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int nerf_amd_volume_render_masked_mse_backward_pdf(const float* raw_live, const float* rays, const float* u,
@@ -109,6 +98,8 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward_pdf(const float* raw_l
     if (!raw_live || !gt || !rgb || !d_raw_live || !ts_out || misaligned(raw_live, 16) || misaligned(d_raw_live, 16) ||
         misaligned(gt, 4) || misaligned(rgb, 4) || misaligned(ts_out, 4) || misaligned(u_f, 4))
         return NERF_AMD_EINVAL;
-    return capped_head(rays_args(rays, u, tbins, flags, seed, ray_id0, B, Nc), raw_live, mask, offsets, gt, rgb, d_raw_live, capacity,
-                       B, u_f, ts_out, Nf, stream);
+    const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, Nc);
+    MaskedBackwardArgs b = capped_head_args(raw_live, mask, offsets, gt, rgb, d_raw_live, capacity, B);
+    b.u_f = u_f; b.ts_out = ts_out; b.Nf = Nf;
+    return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
 }

@@ -1,21 +1,28 @@
 // occupancy_train.hip -- training with empty-space skipping: the backward of the masked compositor, under every head that
 // runs it, and the running density volume a training occupancy grid is refreshed from.  Not in the reference.
 //
-//   masked_backward_kernel<Up, E> -- d loss / d raw_live of nerf_amd_volume_render_masked.  One wavefront per ray, lane =
-//       ORIGINAL sample index, N walked in chunks of 64 by composite_backward_ray (composite_backward_device.h), the walk of
-//       the dense raw[B, N, 4]: positions recomputed (fetch_point_rays) into the wave's LDS slice, the network's output read
-//       at the ray's first row + rank for a kept sample -- rank from popcounts of the mask words -- and (0, 0, 0, -inf) for
-//       a dead one.  A dead sample has softplus' = 0, alpha = 0 and w = 0 there: it receives nothing and adds exact zeros to
-//       the suffix sums.  The result is the rows at the kept samples of the dense backward on the overwritten raw, bit for
-//       bit.  No atomics: a row is written by exactly one lane, and two runs write the same bytes.  Three axes:
+//   masked_backward_kernel<Up, NOISE, E> -- d loss / d raw_live of nerf_amd_volume_render_masked, the one walk of every masked
+//       backward and head.  One wavefront per ray, lane = ORIGINAL sample index, N walked in chunks of 64 by
+//       composite_backward_ray (composite_backward_device.h), the walk of the dense raw[B, N, 4]: positions recomputed
+//       (fetch_point_rays) into the wave's LDS slice, the network's output read at the ray's first row + rank for a kept
+//       sample -- rank from popcounts of the mask words -- and (0, 0, 0, -inf) for a dead one.  A dead sample has
+//       softplus' = 0, alpha = 0 and w = 0 there: it receives nothing and adds exact zeros to the suffix sums.  The result is
+//       the rows at the kept samples of the dense backward on the overwritten raw, bit for bit.  No atomics: a row is written
+//       by exactly one lane, and two runs write the same bytes.  Thirteen instantiations, the combinations the launcher
+//       reaches, on four axes:
 //         Up        FiveGrads: the five upstream gradients are given (nerf_amd_volume_render_masked_backward);
 //                   MseHead: g_rgb = 2 (rgb - gt) / (3 B) is formed from the sweep's own forward, and rgb is written
 //                   (the graphed steps' heads, occupancy_graph.hip; DESIGN.md sections 14, 15);
-//         E         0: no sampler.  1, 2, 4, 8: the fine pass's sample placement (sample_pdf_device.h, E keys per lane) runs
-//                   in the same wave from the weights of the forward sweep, as composite.hip's dense coarse head does it:
-//                   wt = mul_rn(alpha, T) goes from registers to the wave's LDS slice beside the positions (a dead or
-//                   over-capacity sample carries exactly 0), and the sampler reads both there.  w never reaches HBM.
-//                   Nc <= 256: four chunks; LDS per block 4 * (6 KB + 256 E B), the dense head's figures;
+//                   LossHead<BG, DIST, false>: that head behind a background colour, with the distortion loss beside the
+//                   MSE, or both (the training controls, masked_controls.hip).  A head's empty ray is
+//                   the dense head's (loss_head_empty_ray), its row a register where the ray owns none;
+//         NOISE     Noisy<> around the source (sigma_noise_device.h): noise on the raw density of the kept samples;
+//         E         0: no sampler.  1, 2, 4, 8, behind the plain MseHead only: the fine pass's sample placement
+//                   (sample_pdf_device.h, E keys per lane) runs in the same wave from the weights of the forward sweep, as
+//                   composite.hip's dense coarse head does it: wt = mul_rn(alpha, T) goes from registers to the wave's LDS
+//                   slice beside the positions (a dead or over-capacity sample carries exactly 0), and the sampler reads
+//                   both there.  w never reaches HBM.  Nc <= 256: four chunks; LDS per block 4 * (6 KB + 256 E B), the
+//                   dense head's figures;
 //         capacity  a clamp C of every row index (wave-uniform): sample i of ray b is KEPT iff its mask bit is set and
 //                   offsets[b] + (set bits of the ray below i) < C, and the rows [min(P', C), C) are zero-filled, so every
 //                   row of d_raw_live[C, 4] is written by exactly one lane on every launch.  MASKED_NO_CLAMP: the kept rows
@@ -23,6 +30,7 @@
 //   occ_decay_max_kernel -- state = max(fl(state decay), softplus(sigma_now)), softplus as the compositor's.
 #include "composite_backward_device.h"
 #include "sample_pdf_device.h"
+#include "sigma_noise_device.h"
 #include "occ_scan_device.h"
 #include "launchers.h"
 
@@ -45,8 +53,10 @@ struct MaskedLds<0> {
     __device__ float* ts() { return t; }
 };
 
-template <class Up, int E>
+template <class Up, bool NOISE, int E>
 __global__ __launch_bounds__(MASKED_THREADS) void masked_backward_kernel(MlpArgs a, MaskedBackwardArgs b) {
+    static_assert(E == 0 || (Up::MSE && !Up::BG && !Up::DIST && !NOISE), "the sampler runs behind the plain MSE head only");
+    static_assert(Up::MSE || !NOISE, "the terms belong to the loss head");
     constexpr int CHUNKS = E ? nerf_pdf::MAXC / 64 : nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;
     __shared__ MaskedLds<E> lds[MASKED_RAYS_PER_BLOCK];
     const int wv = threadIdx.x >> 6;
@@ -70,23 +80,38 @@ __global__ __launch_bounds__(MASKED_THREADS) void masked_backward_kernel(MlpArgs
     const unsigned long long* m = b.mask + ray * ((N + 63) >> 6);
     f32x4* rout = reinterpret_cast<f32x4*>(b.d_raw_live) + first;
     float* rts = lds[wv].ts();
+    const auto up = [&] {
+        // loss = MSELoss(rgb, gt) (train.py:52), with the head's terms: only rgb (and, behind a background, acc) feeds it
+        if constexpr (Up::MSE)
+            return Up{b.target, b.rgb, b.scale, b.bg, b.bg_stride, b.t_far, b.coef, b.loss_ray, nullptr, 0, nullptr};
+        else return FiveGrads{b.g_rgb, b.g_disp, b.g_alpha, b.g_acc, b.g_w};
+    }();
     const bool empty = N == 1 || n_kept <= 0;
     if (empty) {
         // N == 1: the reference composites an EMPTY sample axis (composite_device.h), no output depends on raw.  Nothing
-        // kept: every sample is (0, 0, 0, -inf), w = 0 throughout.  Either way rgb = 0 and a kept row (N == 1) gets zeros.
-        if (lane == 0) {
-            if constexpr (Up::MSE) { b.rgb[ray * 3 + 0] = 0.f; b.rgb[ray * 3 + 1] = 0.f; b.rgb[ray * 3 + 2] = 0.f; }
-            if (n_kept > 0 && (m[0] & 1ull)) rout[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // kept: every sample is (0, 0, 0, -inf), w = 0 throughout.  Either way the ray has no weight and a kept row (N == 1)
+        // gets zeros: the dense head's empty ray (rgb = bg through the blend's own ops, 0 without one; D = 0), whose one row
+        // may not exist here.
+        const bool owns_row = n_kept > 0 && (m[0] & 1ull);
+        if constexpr (!Up::MSE) {
+            if (lane == 0 && owns_row) rout[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else if (owns_row) {
+            nerf_composite::loss_head_empty_ray(up, lane, ray, rout);
+        } else {
+            f32x4 none;                        // a register: the routine's store of the row goes nowhere
+            nerf_composite::loss_head_empty_ray(up, lane, ray, &none);
         }
         if constexpr (E == 0) return;
     }
     fill_ray_positions(a, ray, lane, rts);
-    const auto up = [&] {
-        // loss = MSELoss(rgb, gt) (train.py:52): only rgb feeds it
-        if constexpr (Up::MSE) return MseHead{b.target, b.rgb, b.scale};
-        else return FiveGrads{b.g_rgb, b.g_disp, b.g_alpha, b.g_acc, b.g_w};
+    const auto src = [&] {
+        using nerf_composite::MaskedSamplesBwd;
+        const auto masked = MaskedSamplesBwd{rts, m, reinterpret_cast<const f32x4*>(b.raw_live) + first, n_kept};
+        if constexpr (NOISE)
+            return nerf_noise::Noisy<MaskedSamplesBwd>{masked, b.std, nerf_noise::noise_key(b.noise_seed, b.seed_mem),
+                                                       (unsigned long long)((a.ray_id0 + ray) * N)};
+        else return masked;
     }();
-    const nerf_composite::MaskedSamplesBwd src{rts, m, reinterpret_cast<const f32x4*>(b.raw_live) + first, n_kept};
     if constexpr (E == 0) {
         nerf_composite::composite_backward_ray<CHUNKS>(src, up, nerf_composite::NoSink{}, N, lane, ray_dnorm(a, ray), ray, rout);
     } else {
@@ -121,23 +146,40 @@ __global__ __launch_bounds__(256) void occ_decay_max_kernel(float* __restrict__ 
 
 extern "C" int nerf_amd_occ_train_max_n(void) { return OCCT_MAX_N; }
 
+// The head's terms are on where std != 0 (noise), bg != NULL, coef != 0 (distortion); loss_ray without the distortion term
+// gets its zeros here, so no kernel carries code for a term it does not have.
 extern "C" int nerf_amd_launch_masked_backward(const MlpArgs* args, const MaskedBackwardArgs* head, hipStream_t stream) {
     (void)hipGetLastError();
     MaskedBackwardArgs b = *head;
     if (b.B == 0) return 0;
-    if (b.ts_out && !b.target) return -2;      // the sampler runs behind the MSE head only
+    const bool noise = b.std != 0.f, bg = b.bg != nullptr, dist = b.coef != 0.f, term = noise || bg || dist;
+    // the sampler and the terms run behind the MSE head only, and not together
+    if (((b.ts_out || term) && !b.target) || (b.ts_out && term)) return -2;
     if (b.ts_out ? nerf_pdf::unsupported_sizes(args->N, b.Nf) : args->N > OCCT_MAX_N) return -2;
+    if (b.loss_ray && !dist) {
+        const hipError_t e = hipMemsetAsync(b.loss_ray, 0, (size_t)b.B * sizeof(float), stream);
+        if (e != hipSuccess) return (int)e;
+    }
     b.scale = 1.0f / (3.0f * (float)b.B);
     const dim3 grid((unsigned)((b.B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
-#define MASKED_BACKWARD(UP_, E_) hipLaunchKernelGGL((masked_backward_kernel<UP_, E_>), grid, block, 0, stream, *args, b)
-    if (!b.target) MASKED_BACKWARD(FiveGrads, 0);
-    else if (!b.ts_out) MASKED_BACKWARD(MseHead, 0);
-    else switch (nerf_pdf::keys_per_lane(b.Nf)) {
-        case 1: MASKED_BACKWARD(MseHead, 1); break;
-        case 2: MASKED_BACKWARD(MseHead, 2); break;
-        case 4: MASKED_BACKWARD(MseHead, 4); break;
-        default: MASKED_BACKWARD(MseHead, 8); break;
+#define MASKED_BACKWARD(...) hipLaunchKernelGGL((masked_backward_kernel<__VA_ARGS__>), grid, block, 0, stream, *args, b)
+#define MASKED_HEAD(NOISE_, BG_, DIST_) MASKED_BACKWARD(nerf_composite::LossHead<BG_, DIST_, false>, NOISE_, 0)
+    if (!b.target) MASKED_BACKWARD(FiveGrads, false, 0);
+    else if (b.ts_out) switch (nerf_pdf::keys_per_lane(b.Nf)) {
+        case 1: MASKED_BACKWARD(MseHead, false, 1); break;
+        case 2: MASKED_BACKWARD(MseHead, false, 2); break;
+        case 4: MASKED_BACKWARD(MseHead, false, 4); break;
+        default: MASKED_BACKWARD(MseHead, false, 8); break;
     }
+    else if (!term) MASKED_BACKWARD(MseHead, false, 0);
+    else if (!dist && !noise) MASKED_HEAD(false, true, false);
+    else if (!dist && !bg) MASKED_HEAD(true, false, false);
+    else if (!dist) MASKED_HEAD(true, true, false);
+    else if (!noise && !bg) MASKED_HEAD(false, false, true);
+    else if (!noise) MASKED_HEAD(false, true, true);
+    else if (!bg) MASKED_HEAD(true, false, true);
+    else MASKED_HEAD(true, true, true);
+#undef MASKED_HEAD
 #undef MASKED_BACKWARD
     return (int)hipGetLastError();
 }

@@ -1,8 +1,8 @@
 // sigma_noise_device.h -- the sigma-noise regulariser (the NeRF paper's raw_noise_std; the reference leaves it as
 // `## TODO add gaussian noise regularizer`, utils/rendering.py:63): sigma' = sigma + std z in front of the softplus, z a
 // standard normal from the counter RNG.  Written ONCE: nerf_amd_sigma_noise and the training head (composite_head.hip) call
-// the routine below, and so do their masked counterparts (masked_controls.hip), so all write the same bits for the same
-// (key, sample).
+// the routine below, and so do their masked counterparts (masked_controls.hip, occupancy_train.hip), so all write the same
+// bits for the same (key, sample).
 //
 // Key: (noise_seed + the step's offset in memory) ^ NOISE_KEY -- the offset goes in front of the xor, as in the sampler's
 // seed (composite.hip, the coarse head), so a replayed graph at step k draws what an eager call with noise_seed + k draws.
@@ -46,29 +46,19 @@ __device__ __forceinline__ float noisy_sigma(float sigma, float std, unsigned lo
     return add_rn(sigma, mul_rn(std, standard_normal(key, sample)));
 }
 
-// DenseSamples with the routine above applied to sigma as a chunk is loaded, for the training head (composite_head.hip):
-// the forward sweep keeps sigma'-derived values per chunk and the backward sweep reuses them, so each sample's noise is
-// generated once.
-struct NoisySamples {
-    nerf_composite::DenseSamples dense;
+// A sample source (DenseSamples, MaskedSamplesBwd) with the routine above applied to sigma as a chunk is loaded, for the
+// training heads (composite_head.hip, occupancy_train.hip): the forward sweep keeps sigma'-derived values per chunk and the
+// backward sweep reuses them, so each sample's noise is generated once.  The noise goes only where the source returned a
+// row: every sample of a dense ray, and of a masked one the kept samples -- a dead or over-capacity sample stays
+// (0, 0, 0, -inf) whatever std is (-inf + NaN would not), so its alpha and w are exactly 0.  The counter is the ORIGINAL
+// sample index: a live sample draws what the dense stage gives that sample.
+template <class Src>
+struct Noisy {
+    Src src;
     float std;
     unsigned long long key, sample0;       // sample0 = (ray_id0 + ray) N
     __device__ __forceinline__ nerf_composite::BwdSample chunk(int ch, int i, int lane, bool valid, int N) {
-        nerf_composite::BwdSample s = dense.chunk(ch, i, lane, valid, N);
-        if (valid) s.c[3] = noisy_sigma(s.c[3], std, key, sample0 + (unsigned long long)i);
-        return s;
-    }
-};
-
-// MaskedSamplesBwd likewise, for the masked training head (masked_controls.hip).  The noise goes only where the source
-// returned a row: a dead or over-capacity sample stays (0, 0, 0, -inf) whatever std is (-inf + NaN would not), so its alpha and
-// w are exactly 0.  The counter is the ORIGINAL sample index: a live sample draws what the dense stage gives that sample.
-struct NoisyMaskedSamples {
-    nerf_composite::MaskedSamplesBwd masked;
-    float std;
-    unsigned long long key, sample0;       // sample0 = (ray_id0 + ray) N
-    __device__ __forceinline__ nerf_composite::BwdSample chunk(int ch, int i, int lane, bool valid, int N) {
-        nerf_composite::BwdSample s = masked.chunk(ch, i, lane, valid, N);
+        nerf_composite::BwdSample s = src.chunk(ch, i, lane, valid, N);
         if (s.row >= 0) s.c[3] = noisy_sigma(s.c[3], std, key, sample0 + (unsigned long long)i);
         return s;
     }

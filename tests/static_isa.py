@@ -31,11 +31,22 @@ def checked_kernels(source):
     return kernels
 
 
+_MASKED = re.compile(r"masked_backward_kernelIN14nerf_composite\d+(FiveGrads|LossHeadILb([01])ELb([01])ELb0EE)ELb([01])ELi(\d+)EEEv")
+
+
 def masked_backward_instantiations(kernels):
-    """[(upstream, E)] of the masked_backward_kernel<Up, E> symbols among `kernels`, sorted."""
+    """[(upstream, E)] of the masked_backward_kernel<Up, false, E> symbols with a plain upstream among `kernels`, sorted."""
     found = []
-    for name in kernels:
-        m = re.search(r"masked_backward_kernelIN14nerf_composite\d+(FiveGrads|LossHeadILb0ELb0ELb0EE)ELi(\d+)EEEv", name)
-        if m:
-            found.append(("FiveGrads" if m.group(1) == "FiveGrads" else "MseHead", int(m.group(2))))
+    for m in filter(None, map(_MASKED.search, kernels)):
+        if m.group(4) == "0" and m.group(2) in (None, "0") and m.group(3) in (None, "0"):
+            found.append(("FiveGrads" if m.group(1) == "FiveGrads" else "MseHead", int(m.group(5))))
+    return sorted(found)
+
+
+def masked_term_instantiations(kernels):
+    """[(NOISE, BG, DIST, E)] of the masked_backward_kernel<LossHead<BG, DIST, false>, NOISE, E> symbols with a term on, sorted."""
+    found = []
+    for m in filter(None, map(_MASKED.search, kernels)):
+        if m.group(1) != "FiveGrads" and "1" in (m.group(2), m.group(3), m.group(4)):
+            found.append((int(m.group(4)), int(m.group(2)), int(m.group(3)), int(m.group(5))))
     return sorted(found)

@@ -70,6 +70,12 @@ def test_exports_header_and_ctypes_agree(lib):
     assert open(os.path.join(csrc, "sigma_noise_device.h")).read().count("float noisy_sigma(") == 1
     text = open(os.path.join(csrc, "masked_controls.hip")).read()
     assert "noisy_sigma(" in text and "float noisy_sigma(" not in text and "philox" not in text
+    # the head is the one masked walk (occupancy_train.hip) over the one noise wrapper: no second kernel, struct or launcher
+    walk = open(os.path.join(csrc, "occupancy_train.hip")).read()
+    assert "__global__" in text and text.count("__global__") == 1 and "nerf_amd_launch_masked_backward(" in text
+    assert walk.count("MaskedSamplesBwd{") == 1 and "nerf_noise::Noisy<" in walk and "noisy_sigma(" not in walk
+    sources = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    assert "masked_head" not in sources and "MaskedHeadArgs" not in sources and sources.count("struct Noisy") == 1
     assert "masked_controls.hip" in open(os.path.join(csrc, "Makefile")).read()
 
 

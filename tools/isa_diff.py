@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do the kernels of the working tree compile to the machine code of another commit?
 
-    python tools/isa_diff.py [--base REV] [--show N] [file.hip[:-DFLAG] ...] > profiles/<name>_isa_diff.txt
+    python tools/isa_diff.py [--base REV] [--show N] [--map OLD=NEW ...] [file.hip[:-DFLAG] ...] > profiles/<name>_isa_diff.txt
 
 For a change that only moves source around (a shared header, a renamed helper) the proof that nothing happened to a
 kernel is that its instructions did not change.  The tool exports nerf-simple_amd/csrc and include/ of REV (default
@@ -10,7 +10,9 @@ from the working tree (tools/check_vmcnt.py assemble / kernels_of; 9-15 s per fi
 compares the instruction text kernel by kernel after normalisation:
   * comments and assembler directives are stripped;
   * local labels (.LBB<f>_<n>, ...) are renumbered in order of first appearance;
-  * kernel symbol names are NOT normalised: a kernel must keep its name.
+  * kernel symbol names are NOT normalised: a kernel must keep its name, unless --map OLD=NEW (regular expression and
+    replacement, applied to the base's symbols; repeatable) says how it was renamed.  A mapped kernel is looked up in
+    every listed file of the working tree, so it may have moved to another source.
 One line per kernel: instruction count, MFMA count, identical yes / no; --show N prints the first N differing lines of a
 kernel that is not identical.  Exit status 1 when any kernel differs, is missing or is new.  Needs hipcc and git; no GPU.
 """
@@ -60,6 +62,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--base", default="HEAD", help="the commit to compare the working tree against")
     ap.add_argument("--show", type=int, default=0, help="print this many differing lines of a kernel that differs")
+    ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW",
+                    help="a renamed kernel: re.sub(OLD, NEW) on the symbols of the base")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("files", nargs="*", default=DEFAULT)
     args = ap.parse_args()
@@ -70,8 +74,21 @@ def main():
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(base)
         with concurrent.futures.ThreadPoolExecutor(args.jobs) as pool:
             fut = {(tree, j): pool.submit(kernels, tree, *j) for j in jobs for tree in (base, ROOT)}
+            moved = {}                          # mapped kernels of the working tree, from whichever listed file holds them
             for src, flags in jobs:
                 old, new = fut[base, (src, flags)].result(), fut[ROOT, (src, flags)].result()
+                for name in list(old):
+                    to = name
+                    for rule in args.map:
+                        to = re.sub(*rule.split("=", 1), to)
+                    if to != name:
+                        old[to] = old.pop(name)
+                        moved[to] = None
+            for key in moved:
+                moved[key] = next((fut[ROOT, j].result().pop(key) for j in jobs if key in fut[ROOT, j].result()), None)
+            for src, flags in jobs:
+                old, new = fut[base, (src, flags)].result(), fut[ROOT, (src, flags)].result()
+                new.update({k: v for k, v in moved.items() if k in old and v is not None})
                 print(f"== {src} {' '.join(flags)}".rstrip())
                 for name in sorted(set(old) | set(new)):
                     if name not in old or name not in new:
