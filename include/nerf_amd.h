@@ -1126,6 +1126,35 @@ int nerf_amd_volume_render_masked_mse_backward_dist(const float* raw_live, const
                                                     float t_far, float coef, float* rgb, float* loss_ray, float* d_raw_live,
                                                     int64_t capacity, int64_t B, int N, void* stream);
 
+/* ---- scene box: a ray's samples placed inside an axis-aligned box (csrc/ray_box.hip, csrc/ray_box_device.h) ---------------
+ * Not in the reference, whose samples lie in linspace(tn, tf, N + 1) bins whatever the ray (utils/rendering.py:24-30): this
+ * generalises that line to a per-ray interval.  tests/box_model.py restates it op for op; DESIGN.md section 33.
+ *
+ * nerf_amd_box_positions: ts[B,N], the positions of N samples per ray inside the box [h_lo, h_hi] (HOST float[3] each, finite,
+ * lo < hi on every axis).  Per ray (o, d), d un-normalised as render_nerf uses it; fp32, every operation rounded on its own
+ * (no fma contraction); min / max are comparisons that let a NaN through:
+ *   1. slabs, per axis a: d_a != 0 -- ta = (lo_a - o_a) / d_a, tb = (hi_a - o_a) / d_a, near_a = min(ta, tb), far_a = max(ta, tb);
+ *      d_a == 0 (either sign) with lo_a <= o_a <= hi_a -- the axis constrains nothing; d_a == 0 otherwise -- the ray misses.
+ *   2. interval: t0 = max(tn, near_x, near_y, near_z), t1 = min(tf, far_x, far_y, far_z), folded in that order;
+ *      hit = (t0 < t1), false for a NaN: a ray with a NaN component is a miss.
+ *   3. a miss keeps the whole interval, t0 = tn, t1 = tf: it renders as it does without a box (and is dead as a whole behind a
+ *      grid whose outside is empty).  No special values, no NaN.
+ *   4. unit positions c[N]: bit for bit the ts nerf_amd_query_points forms for this ray's (u, flags, seed, ray_id0) on
+ *      tbins01 = linspace(0, 1, N + 1) -- every jitter mode of that rule: u, NERF_AMD_DEVICE_RNG, with NERF_AMD_SEED_IN_MEMORY
+ *      (then `u` is the address of the offset), and NERF_AMD_TS_GIVEN, where u[B,N] holds unit positions of the caller's own
+ *      and tbins01 is not looked at.
+ *   5. ts_i = min(t0 + (t1 - t0) c_i, t1): ascending whenever c is; a position may land one rounding outside the box.
+ * Outputs: ts[B,N]; span[B,2] = (t0, t1) and hit[B] (int32 0 / 1), each skipped when NULL.  Feed ts to any entry point under
+ * NERF_AMD_TS_GIVEN.  One wavefront per ray, every element written by exactly one lane, no atomics: two runs write the same
+ * bytes.  Nothing here carries a gradient: the positions are constants of the render, as the fine sampler's are.
+ * Rules in order -- NERF_AMD_EINVAL: h_lo / h_hi NULL, not finite or lo_a >= hi_a; tn or tf not finite or !(tn < tf);
+ * B < 0 or N <= 0; unknown flags, NERF_AMD_TS_GIVEN without u, no u without the counter RNG, a seed address missing or off
+ * 8 bytes, tbins01 NULL unless NERF_AMD_TS_GIVEN.  NERF_AMD_EUNSUP: N > 768 or B > 2^32 (the masked entry points that read ts).
+ * NERF_AMD_EINVAL: rays NULL with B > 0, ts NULL with B > 0, a buffer off 4 bytes.  B == 0: nothing is launched or written. */
+int nerf_amd_box_positions(const float* rays, const float* u, const float* tbins01, uint32_t flags, uint64_t seed,
+                           int64_t ray_id0, const float* h_lo, const float* h_hi, float tn, float tf, float* ts, float* span,
+                           int32_t* hit, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

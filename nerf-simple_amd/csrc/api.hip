@@ -1068,4 +1068,20 @@ int nerf_amd_occupancy_decay_max(float* state, const float* sigma_now, float dec
     return nerf_amd_launch_occ_decay_max(state, sigma_now, decay, n, S(stream));
 }
 
+// the scene box: the box and the global interval first (host scalars, as the terminated render's eps and slab), then the
+// rays / jitter / size rules of the masked stages -- the entry points that read ts[B,N] -- then the outputs
+int nerf_amd_box_positions(const float* rays, const float* u, const float* tbins01, uint32_t flags, uint64_t seed,
+                           int64_t ray_id0, const float* h_lo, const float* h_hi, float tn, float tf, float* ts, float* span,
+                           int32_t* hit, int64_t B, int N, void* stream) {
+    if (bad_box(h_lo, h_hi)) return NERF_AMD_EINVAL;
+    if (!(tn < tf) || !(tn >= -3.402823466e38f) || !(tf <= 3.402823466e38f)) return NERF_AMD_EINVAL;       // also NaN
+    const int rc = masked_rays_check(rays, u, tbins01, flags, B, N, N > MASKED_MAX_N);
+    if (rc) return rc;
+    if (misaligned(rays, 4) || misaligned(u, 4) || misaligned(tbins01, 4)) return NERF_AMD_EINVAL;
+    if ((B > 0 && !ts) || misaligned(ts, 4) || misaligned(span, 4) || misaligned(hit, 4)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    const MlpArgs a = rays_args(rays, u, tbins01, flags, seed, ray_id0, B, N);
+    return nerf_amd_launch_box_positions(&a, h_lo, h_hi, tn, tf, ts, span, hit, B, S(stream));
+}
+
 }  // extern "C"

@@ -49,6 +49,16 @@ inline bool bad_distortion(float t_far, float coef) {
 // a background: one colour (stride 0) or one per ray (stride 3), in floats; looked at whether or not `bg` is given
 inline bool bad_bg_stride(int64_t bg_stride) { return bg_stride != 0 && bg_stride != 3; }
 
+// a scene box (nerf_amd_box_positions): two HOST vectors of three floats, finite, lo < hi on every axis
+inline bool bad_box(const float* h_lo, const float* h_hi) {
+    if (!h_lo || !h_hi) return true;
+    for (int i = 0; i < 3; ++i) {
+        if (!(h_lo[i] >= -3.402823466e38f) || !(h_hi[i] <= 3.402823466e38f)) return true;       // -inf / +inf / NaN
+        if (!(h_lo[i] < h_hi[i])) return true;                                                   // also the other infinity
+    }
+    return false;
+}
+
 // the rays and jitter of a rays-mode launch whose kernels form the sample positions themselves
 inline MlpArgs rays_args(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0,
                          int64_t B, int N) {

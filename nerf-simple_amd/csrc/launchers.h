@@ -182,4 +182,6 @@ int nerf_amd_launch_appearance_apply_backward(const float*, const float*, const 
                                               hipStream_t);
 int nerf_amd_launch_appearance_reduce(const float*, const long long*, long long, const float*, float, const int*, float*,
                                       long long, long long, hipStream_t);
+int nerf_amd_launch_box_positions(const MlpArgs*, const float*, const float*, float, float, float*, float*, int*, long long,
+                                  hipStream_t);
 }

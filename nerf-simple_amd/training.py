@@ -650,7 +650,7 @@ def _masked_controls(controls, B, dev, ray_id0):
 
 
 def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0,
-                       return_ts=False, controls=None):
+                       return_ts=False, controls=None, box=None):
     """``render_nerf`` through an occupancy grid WITH gradients to the parameters of ``net``: the network is evaluated
     (fused bf16 training kernels, points mode) at the live samples only, a dead sample is (0, 0, 0, -inf) -- it contributes
     exactly nothing and receives no gradient.  Returns the same 5-tuple; alpha / w are dense [B,N], zero at dead samples.
@@ -664,8 +664,12 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     ``controls``: a ``Controls`` -- Gaussian noise on the live rows of the raw density (nerf_amd_sigma_noise_masked: a live
     sample draws what the dense render gives that sample; a dead one stays dead) and rgb + (1 - acc) background behind the
     masked compositor; ``w.ts`` then holds the sample positions.  The distortion term belongs to the step: a non-zero
-    ``controls.distortion`` raises ValueError."""
-    from .utils import jitter, occupancy as occ_mod
+    ``controls.distortion`` raises ValueError.
+    ``box``: a ``SceneBox`` (utils/box.py) -- the samples are placed inside the box (``box.positions`` with this call's jitter
+    arguments, formed once where the jitter would be drawn) and the call goes on as its ``ts=`` path; the positions carry no
+    gradient.  Together with ``ts=``: ValueError."""
+    from .utils import box as box_mod, jitter, occupancy as occ_mod
+    box_mod.check_box(box, ts=ts)
     controls = _controls_arg(controls)
     if controls is not None and controls.distortion:
         raise ValueError("render_nerf_masked renders: the distortion term belongs to the step (train_step(..., occupancy=, "
@@ -678,7 +682,12 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     _lib.require_same_device("occupancy grid", occupancy.words, dev)
     controls = _masked_controls(controls, B, dev, ray_id0)     # the background's shape: before the jitter is drawn
     net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
-    jit, flags, pending = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
+    if box is not None:                       # the box's positions, then the ts= path
+        jitter.check(B, N, u=u)
+        box_mod.check_interval(N, tn, tf)
+        jit, flags, pending = box_mod.single(box, rays, N, tn, tf, u=u, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+    else:
+        jit, flags, pending = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
     try:
         rays = rays.detach().contiguous()
         tbins = jitter.tbins(tn, tf, N, dev, flags)
@@ -715,7 +724,7 @@ def _optimise(loss, params, optimizer, decay, group):
 
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, background=None, sigma_noise=0.0,
-               noise_seed=0, distortion=0.0, controls=None):
+               noise_seed=0, distortion=0.0, controls=None, box=None):
     """zero_grad -> render_nerf -> MSELoss(rgb, gt) -> backward -> [grad all-reduce]
     -> optimizer.step -> lr *= decay.  Returns the (detached) loss.
     Only ``rgb`` feeds the loss, as in the reference (train.py:52).
@@ -733,8 +742,13 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     lambda > 0 ``.distortion`` on it holds the weighted term.
     controls: a ``Controls`` -- the same four as ONE argument, on the dense path (bit for bit the flat keywords; giving both
     raises ValueError) AND with ``occupancy``: the masked step with the noise on its live rows, the loss behind the background
-    and the distortion term on the masked compositor's weights, assembled as the dense step assembles them."""
+    and the distortion term on the masked compositor's weights, assembled as the dense step assembles them.
+    box: a ``SceneBox`` (utils/box.py) -- the samples are placed inside the box: the step is this step on
+    ``render_nerf(..., box=box)`` / ``render_nerf_masked(..., box=box)``, dense or with ``occupancy``, with the controls, at
+    every precision.  The positions carry no gradient; the distortion term keeps the global ``tf`` and its coefficient."""
+    from .utils.box import check_box
     from .utils.rendering import render_nerf, _refuse_controls
+    bkw = {} if check_box(box) is None else {"box": box}       # off by default: a call without it is the call it was
     controls = _controls_arg(controls, background=background, sigma_noise=sigma_noise, noise_seed=noise_seed,
                              distortion=distortion)
     if controls is not None and occupancy is None:       # the dense step: the flat keywords' meaning
@@ -752,13 +766,14 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     optimizer.zero_grad(set_to_none=True)
     if occupancy is not None:
         rgb, _, _, _, w = render_nerf_masked(rays, net, N, occupancy, tn, tf, u=u, device_rng=device_rng, seed=seed,
-                                             ray_id0=ray_id0, controls=None if controls is None else controls.replace(distortion=0.0))
+                                             ray_id0=ray_id0, controls=None if controls is None else controls.replace(distortion=0.0),
+                                             **bkw)
     else:
         kw = {}
         if background is not None or sigma_noise:          # off by default: a call without them is the call it was
             kw = dict(background=background, sigma_noise=sigma_noise, noise_seed=noise_seed)
         rgb, _, _, _, w = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
-                                      device_rng=device_rng, seed=seed, ray_id0=ray_id0, **kw)
+                                      device_rng=device_rng, seed=seed, ray_id0=ray_id0, **kw, **bkw)
     loss, term = mse_loss(rgb, gt), None
     if lam > 0:
         term = _distortion_term(w, getattr(w, "ts", None), lam, tn, tf)
@@ -814,7 +829,7 @@ def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray
 
 def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
                             decay=1.0, group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None,
-                            controls=None):
+                            controls=None, box=None):
     """One optimisation step of the coarse / fine pair (the NeRF paper's objective; the reference has no hierarchical
     path, its CoarseNet / FineNet are empty): zero_grad -> coarse render_nerf with gradients (Nc stratified samples) ->
     sample_pdf on the DETACHED coarse weights (the coarse net learns from its own loss only) -> fine render_nerf of
@@ -835,7 +850,9 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     requires_grad; refused before any jitter is drawn."""
     from .optim import FusedAdam
     from .utils import jitter
+    from .utils.box import refuse_box
     from .utils.rendering import render_nerf, sample_pdf
+    refuse_box(box, "the coarse + fine pair (train_step_hierarchical)")
     _refuse_bundle(controls, "the coarse + fine pair (train_step_hierarchical)")
     _check_pair(net_c, net_f, Nc, Nf, precision)
     Nc, Nf = int(Nc), int(Nf)
@@ -886,7 +903,7 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
 # --------------------------------------------------------------------------
 def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, ts_c=None, u_f=None, decay=1.0,
                       group=None, precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, distortion=0.0,
-                      controls=None):
+                      controls=None, box=None):
     """One optimisation step of ONE network on grid-guided positions: ts = ``proposal.sample(rays, Nc, Nf, ...)`` (a
     ``ProposalVolume``, utils/proposal.py: no network evaluation, no gradient) -> zero_grad -> render_nerf with gradients on those
     Nc + Nf positions -> MSE(rgb, gt) -> backward -> [grad all-reduce] -> optimizer.step -> lr *= decay.  The loss is that of
@@ -907,7 +924,10 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
     controls: a ``Controls`` -- with ``occupancy`` the masked guided step with the three terms, as ``train_step(..., occupancy=,
     controls=)`` on the guided positions (the noise is keyed by ``noise_seed`` and ``ray_id0``).  Without a grid it stands for
     ``distortion`` alone (the dense guided step knows no background and no noise: RuntimeError); with the flat keyword:
-    ValueError."""
+    ValueError.
+    box: refused (RuntimeError before anything is drawn): the guided placement has its own interval."""
+    from .utils.box import refuse_box
+    refuse_box(box, "the guided step (train_step_guided)")
     controls = _controls_arg(controls, distortion=distortion)
     if controls is not None and occupancy is None:
         if controls.background is not None or controls.sigma_noise:
@@ -1983,6 +2003,8 @@ class GraphedCameraTrainStep(_TableTrainStep):
                  camera_eps=1e-8, select_mode="train", group=None, buckets=1, storage="bf16", background=None, sigma_noise=0.0,
                  distortion=0.0, **kw):
         from .utils.cameras import CameraRefinement
+        from .utils.box import refuse_box
+        refuse_box(kw.pop("box", None), "GraphedCameraTrainStep")
         _refuse_bundle(kw.pop("controls", None), "GraphedCameraTrainStep")
         if storage != "bf16":
             raise RuntimeError("GraphedCameraTrainStep: storage='e4m3' is not served (nerf_amd_input_gradients reads bf16 dY)")
@@ -2072,6 +2094,8 @@ class GraphedAppearanceTrainStep(_TableTrainStep):
     def __init__(self, net, optimizer, n_rays, N, appearance, *, rays_from, appearance_lr=1e-3, appearance_betas=(0.9, 0.999),
                  appearance_eps=1e-8, select_mode="train", group=None, **kw):
         from .utils.appearance import AppearanceCorrection
+        from .utils.box import refuse_box
+        refuse_box(kw.pop("box", None), "GraphedAppearanceTrainStep")
         _refuse_bundle(kw.pop("controls", None), "GraphedAppearanceTrainStep")
         self._bind_table(appearance, AppearanceCorrection, optimizer, n_rays, rays_from, select_mode, group,
                          (kw.get("background"), kw.get("sigma_noise"), kw.get("distortion")), appearance_lr, appearance_betas,
@@ -2230,6 +2254,77 @@ class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
         return super().step(rays, gt, u=u, decay=decay)
 
     __call__ = step
+
+
+class _BoxSteps:
+    """What the two scene-box steppers share (listed in front of their stepper base): the stepper's own
+    jitter arguments become the PLACEMENT's (on the unit bins ``tbins01``; with ``device_rng`` the seed offset is read from
+    device memory, as before), the one pass reads the placed positions ``ts_box`` under NERF_AMD_TS_GIVEN, and
+    nerf_amd_box_positions is one more node of graph A in front of the forward.  ``box.lo`` / ``box.hi`` are baked into the
+    graph by value: a SceneBox is frozen, another box is another stepper."""
+
+    def _bind_box(self, box, N, tn, tf):
+        from .utils.box import check_box, check_interval
+        from .utils.mesh import _host_f32x3
+        if check_box(box) is None:
+            raise TypeError(f"{type(self).__name__} needs a utils.box.SceneBox")
+        check_interval(N, tn, tf)
+        self.box, self._box_args = box, (_host_f32x3(box.lo), _host_f32x3(box.hi), float(tn), float(tf))
+
+    def _alloc_pass_buffers(self, tn, tf):
+        from .utils.rendering import _tbins
+        super()._alloc_pass_buffers(tn, tf)
+        ptr, first = _lib.ptr, self.passes[0]
+        rays, jit, _, flags, seed, rid = first.jitter
+        self.tbins01 = _tbins(0, 1, first.N, self.dev)
+        self.ts_box = torch.empty((self.B, first.N), dtype=torch.float32, device=self.dev)
+        self._box_jitter = (rays, jit, ptr(self.tbins01), flags, seed, rid)
+        first.jitter = (ptr(self.rays), ptr(self.ts_box), None, _lib.FLAG_TS_GIVEN, 0, 0)
+        if not hasattr(self, "ts"):              # a masked pass keeps no positions of its own: the placed ones are the step's
+            self.ts = self.ts_box
+
+    def _before_forward(self, st):
+        super()._before_forward(st)
+        _launch("nerf_amd_box_positions", *self._box_jitter, *self._box_args, _lib.ptr(self.ts_box), None, None, self.B,
+                self.passes[0].N, st)
+
+
+class GraphedBoxTrainStep(_BoxSteps, GraphedTrainStep):
+    """``train_step(..., box=box)`` as captured hipGraphs: GraphedTrainStep with its one dense pass under
+    NERF_AMD_TS_GIVEN and ONE more node in graph A:
+
+        graph A: hyper fetch -> placement (nerf_amd_box_positions: the stepper's jitter on unit bins, each ray's interval
+                 clipped to ``box``; writes ``ts_box`` [B, N]) -> training forward on ts_box -> head -> ...: the rest is
+                 GraphedTrainStep's, and so are graph B, the exchange seam, ``rays_from``, ``controls`` and ``check_every``.
+
+    Jitter and ``step`` as GraphedTrainStep; step k (1-based) equals the eager ``train_step(..., box=box, device_rng=True,
+    seed=seed + k)``, or ``train_step(..., box=box, u=u)`` for a given ``u``.  ``stepper.ts`` holds the positions the forward
+    read (the forward's own copy, bit for bit ``ts_box``).  The positions carry no gradient; the distortion term keeps the
+    global ``tf``."""
+
+    def __init__(self, net, optimizer, n_rays, N, box, *, tn=2, tf=6, **kw):
+        self._bind_box(box, int(N), tn, tf)
+        super().__init__(net, optimizer, n_rays, N, tn=tn, tf=tf, **kw)
+
+    def _range_check(self):
+        """The reference's |x| > 1 warning on the first / last PLACED position of every ray."""
+        from .utils.xyz import range_check_rays
+        range_check_rays(self.rays, self.ts_box, None, _lib.FLAG_TS_GIVEN, 0, 0, self.N)
+
+
+class GraphedMaskedBoxTrainStep(_BoxSteps, GraphedMaskedTrainStep):
+    """``train_step(..., occupancy=, box=box)`` as captured hipGraphs: GraphedMaskedTrainStep on the box's positions --
+
+        graph A: hyper fetch -> placement (nerf_amd_box_positions; writes ``ts_box`` [B, N]) -> mark + scan, capped emit,
+                 training forward on the C points and the masked head, all under NERF_AMD_TS_GIVEN on ts_box -> ...
+
+    Capacity, overflow reporting, ``counts()``, ``rays_from``, ``controls`` and ``check_every`` are GraphedMaskedTrainStep's;
+    with P' <= C step k equals the eager ``train_step(..., occupancy=, box=box, device_rng=True, seed=seed + k)``.  A tight box
+    (``SceneBox.from_occupancy``) raises the live share of the batch: size the capacity for it."""
+
+    def __init__(self, net, optimizer, n_rays, N, box, occupancy, capacity, *, tn=2, tf=6, **kw):
+        self._bind_box(box, int(N), tn, tf)
+        super().__init__(net, optimizer, n_rays, N, occupancy, capacity, tn=tn, tf=tf, **kw)
 
 
 class _PairJitter:

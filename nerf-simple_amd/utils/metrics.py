@@ -173,7 +173,7 @@ def evaluate(net, rg, im_set='val', idxs=None, *, N=128, render=None, ssim=True,
     """Metrics of a trained model over the views of ``rg.samples[im_set]`` (all of them, or ``idxs``): the pose of view i is
     ``rg.samples[im_set][i]['transform']``, its ground truth the rows ``rg.colours[im_set][i H W:(i+1) H W]``, which are
     resident and are not copied.  The default render is ``render_view(net, pose, rg.cam_params, N=N, **render_kw)``, so
-    ``occupancy=``, ``terminate=``, ``background=``, ``device_rng=``, ``precision=`` pass through; ``render=`` -- a function
+    ``occupancy=``, ``terminate=``, ``background=``, ``box=``, ``device_rng=``, ``precision=`` pass through; ``render=`` -- a function
     pose -> pixels [H W, >= 3] -- takes the other paths, e.g.
     ``lambda pose: render_guided_view(net, pose, rg.cam_params, 64, 128, prop, occupancy=occ)``.  Returns what
     ``evaluate_views`` returns, plus 'idxs'."""

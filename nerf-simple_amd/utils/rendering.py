@@ -161,7 +161,7 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS, background=None):
 
 def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUTS,
                 precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, terminate=None,
-                background=None, sigma_noise=0.0, noise_seed=0, controls=None):
+                background=None, sigma_noise=0.0, noise_seed=0, controls=None, box=None):
     """Stratified sampling along rays, NeRF query, compositing
     (reference utils/rendering.py:13-45).
 
@@ -194,7 +194,16 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     with ``occupancy`` the background behind the masked render: rgb becomes rgb + (1 - acc) background through the same blend,
     the other four outputs are what they were.  ``controls.sigma_noise > 0`` behind a grid raises the regulariser's
     RuntimeError, a non-zero ``controls.distortion`` ValueError, ``terminate=`` with it RuntimeError.
+
+    box: a ``SceneBox`` (utils/box.py) -- each ray's N samples are placed inside the box instead of in
+    [tn, tf] (a ray that misses keeps [tn, tf]): ``box.positions(rays, N, tn, tf, u=, device_rng=, seed=, ray_id0=)`` is formed
+    once, where the jitter would be drawn, and the call goes on as its ``ts=`` path -- so it composes with everything that
+    path serves (``occupancy``, ``terminate``, the controls, every precision, foreign nets).  The positions are constants:
+    no gradient, and d loss / d rays ignores the dependence of the interval on the ray (the fine sampler's rule).
+    ``box=`` together with ``ts=`` is a ValueError.
     """
+    from . import box as box_mod
+    box_mod.check_box(box, ts=ts)
     masked_bg = None
     if controls is not None:
         flat, masked_bg = _inference_controls(controls, occupancy, terminate, background=background, sigma_noise=sigma_noise,
@@ -232,11 +241,16 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     # everything that can raise cheaply is checked BEFORE the jitter is drawn, so a failed call
     # leaves torch's CPU generator untouched
     jitter.check(B, N, u=u, ts=ts)
+    if box is not None:
+        box_mod.check_interval(N, tn, tf)
     code = None
     if fused and not training:
         code = _lib.precision_of(net, precision)
         net.packed_weights(code)              # packs now if it has to: errors surface before the jitter is drawn
-    jit, flags, pending_rng = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
+    if box is not None:                       # the box's positions, then the ts= path
+        jit, flags, pending_rng = box_mod.single(box, rays, N, tn, tf, u=u, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
+    else:
+        jit, flags, pending_rng = jitter.single(B, N, dev, u=u, ts=ts, device_rng=device_rng)
     # the reference's |x| > 1 warning (utils/xyz.py:8-9, raised inside net.forward's positional_encoder): verdict formed on
     # the device from the first / last sample of every ray, raised lazily (xyz.range_check_rays); a foreign net encodes
     # its own inputs and warns (or not) by itself
@@ -471,6 +485,8 @@ def render_rays_sharded(net, rays, batch_size, *, N=128, tn=2, tf=6, u=None, gro
     every rank's GPU.  Jitter is indexed by global ray id, so the image does
     not depend on the number of ranks."""
     from .. import parallel
+    from .box import refuse_box
+    refuse_box(kw.get("box"), "the sharded render (render_rays_sharded)")
     dev = next(net.parameters()).device
 
     def render_fn(r, us, ray_id0):
@@ -505,7 +521,8 @@ def generate_rays(pose, cam_params, device, ray0=0, n_rays=None):
 
 
 def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_rays=None,
-                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None, background=None, controls=None):
+                precision=None, device_rng=False, seed=0, occupancy=None, terminate=None, background=None, controls=None,
+                box=None):
     """One view (or the pixel range [ray0, ray0+n_rays) of it) in ONE library
     call: device ray generation -> render_nerf -> clip(rgb,0,1), i.e. the body of
     the reference's per-image loop (utils/rendering.py:139-151) without the
@@ -522,7 +539,13 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     background, 0, 1), disparity], the clip behind the blend.  Device ray generation, nerf_amd_render_forward for rgb, disp
     and acc, then one small blend launch (without a background: the one call it was).  Not with occupancy / terminate.
     controls: a ``training.Controls`` -- ``render_nerf``'s: without a grid it stands for ``background``; with ``occupancy`` the
-    masked render through the five-output masked compositor (so that acc exists), then the blend and the clip behind it."""
+    masked render through the five-output masked compositor (so that acc exists), then the blend and the clip behind it.
+    box: a ``SceneBox`` -- device ray generation -> the box's positions (nerf_amd_box_positions, jitter keyed by global pixel
+    id) -> the render, the background render or the masked / terminated render on the materialised rays under those given
+    positions, as the ``occupancy=`` branch already runs; by definition ``render_nerf(generate_rays(...), ..., box=box)`` and
+    the clip.  Not inside the one-launch image kernel."""
+    from . import box as box_mod
+    box_mod.check_box(box)
     masked_bg = None
     if controls is not None:
         flat, masked_bg = _inference_controls(controls, occupancy, terminate, background=background)
@@ -546,15 +569,24 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         with torch.no_grad():
             rgb, disp, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, outputs=("rgb", "disp", "acc"),
                                              device_rng=device_rng, seed=seed, ray_id0=ray0,
-                                             **({} if background is None else {"background": background}))
+                                             **({} if background is None else {"background": background}),
+                                             **({} if box is None else {"box": box}))
         return torch.cat([rgb.clamp(0., 1.), disp[:, None]], dim=1)
     bg = None if background is None else _background_arg(background, n, dev)
     if masked_bg is not None:
         masked_bg = _background_arg(masked_bg, n, dev)
     code = _lib.precision_of(net, precision)
     net.packed_weights(code)
-    # the shape of ``u`` is looked at below, on the masked and background branches only (section 31)
-    jit, flags, pending_rng = jitter.single(n, N, dev, u=u, device_rng=device_rng, shape_error=None)
+    rays = None
+    if box is not None:
+        # the materialised rays, the box's positions on them, then a branch below under NERF_AMD_TS_GIVEN
+        box_mod.check_interval(N, tn, tf)
+        jitter.check(n, int(N), u=u, shape_error="u must be [n_rays, N]")
+        rays = generate_rays(pose, cam_params, dev, ray0, n)
+        jit, flags, pending_rng = box_mod.single(box, rays, int(N), tn, tf, u=u, device_rng=device_rng, seed=seed, ray_id0=ray0)
+    else:
+        # the shape of ``u`` is looked at below, on the masked and background branches only (section 31)
+        jit, flags, pending_rng = jitter.single(n, N, dev, u=u, device_rng=device_rng, shape_error=None)
     if pending_rng is not None:
         pending_rng.finish()
     lib = _lib.lib()
@@ -562,7 +594,8 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         from .occupancy import render_masked, render_terminated
         if jit is not None and tuple(jit.shape) != (n, int(N)):
             raise RuntimeError("u must be [n_rays, N]")
-        rays = generate_rays(pose, cam_params, dev, ray0, n)
+        if rays is None:
+            rays = generate_rays(pose, cam_params, dev, ray0, n)
         if terminate is not None:
             return render_terminated(terminate, occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
                                      code, (), pixels=True)
@@ -580,8 +613,20 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     if bg is not None:
         if jit is not None and tuple(jit.shape) != (n, int(N)):
             raise RuntimeError("u must be [n_rays, N]")
-        rays = generate_rays(pose, cam_params, dev, ray0, n)
+        if rays is None:
+            rays = generate_rays(pose, cam_params, dev, ray0, n)
         return guarded_launch([net], code, launch_bg)
+    if box is not None:
+        def launch_given(code, packed):       # the render's pixel head on the given positions (render_guided_view's launch)
+            pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            ws = _lib.workspace(lib.nerf_amd_render_workspace_bytes(code, n, int(N)), dev, floor=0)
+            with torch.cuda.device(dev):
+                _lib.check(lib.nerf_amd_render_pixels_forward(
+                    _lib.ptr(rays), _lib.ptr(jit), None, _lib.ptr(packed[0]), code, flags, int(seed), int(ray0),
+                    _lib.ptr(pixels), _lib.ptr(ws), n, int(N), _lib.stream_ptr(dev)), "nerf_amd_render_pixels_forward")
+            return pixels
+
+        return guarded_launch([net], code, launch_given)
     h_pose = _host_pose(pose)
 
     def launch(code, packed):
@@ -652,7 +697,7 @@ def _masked_pair_args(occupancy, net_coarse, net_fine, B, Nc, Nf, u_c, u_f, prec
 
 
 def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *, u_c=None, u_f=None,
-                        precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
+                        precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, box=None):
     """Coarse + fine render (BASELINE config 4: 64 + 128 samples).  The reference
     only has the single-pass render_nerf (its CoarseNet / FineNet are empty
     classes), so this composition is new: a coarse render_nerf pass with Nc
@@ -665,7 +710,10 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
     occupancy: ONE ``OccupancyGrid`` masks both passes: masked coarse pass -> sample_pdf on its
     weights (exactly 0 at a dead sample; a ray with no live coarse sample gets uniform fine samples) -> masked fine pass
     on the merged positions; each network sees live samples only, two host synchronisations per call, both passes at one
-    precision under one range guard.  Inference only (``torch.no_grad()``), default network shape only."""
+    precision under one range guard.  Inference only (``torch.no_grad()``), default network shape only.
+    box: refused (RuntimeError before anything is drawn): the scene box serves the single-network renders."""
+    from .box import refuse_box
+    refuse_box(box, "the coarse + fine pair (render_hierarchical)")
     _lib.require_cuda_f32(rays, "rays")
     dev, B = rays.device, rays.size(0)
     if occupancy is not None:
@@ -712,7 +760,7 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
 
 
 def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
-                             ray0=0, n_rays=None, precision=None, device_rng=False, seed=0, occupancy=None):
+                             ray0=0, n_rays=None, precision=None, device_rng=False, seed=0, occupancy=None, box=None):
     """BASELINE config 4 for one view (or its pixel range [ray0, ray0+n_rays)) in ONE library call:
     device ray generation -> coarse pass (Nc stratified samples) -> sample_pdf -> fine pass on the
     Nc+Nf merged positions -> clip(rgb,0,1)  (nerf_amd_render_hierarchical_forward: four launches,
@@ -721,7 +769,10 @@ def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=1
     draws torch.rand(n,Nc) then torch.rand(n,Nf); device_rng=True: counter RNG keyed by global pixel id.
     Parity unpinned (no reference counterpart).
     occupancy: an ``OccupancyGrid`` for both passes -- device ray generation, then the composition of
-    ``render_hierarchical(..., occupancy=)``, then the clip (not one library call: two host reads, one per pass)."""
+    ``render_hierarchical(..., occupancy=)``, then the clip (not one library call: two host reads, one per pass).
+    box: refused (RuntimeError before anything is drawn)."""
+    from .box import refuse_box
+    refuse_box(box, "the coarse + fine pair (render_hierarchical_view)")
     dev = next(net_coarse.parameters()).device
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
     n = H * W - ray0 if n_rays is None else int(n_rays)
@@ -779,7 +830,7 @@ def _check_guided(net, proposal):
 
 
 def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=None, u_f=None, outputs=ALL_OUTPUTS,
-                  precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None):
+                  precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, box=None):
     """Grid-guided render: ONE network on Nc + Nf positions per ray, the Nf new ones placed by
     ``proposal`` (a ``ProposalVolume``, utils/proposal.py) from its sigma volume instead of by a coarse network.  It is
     ``render_nerf(rays, net, Nc + Nf, ts=proposal.sample(rays, Nc, Nf, ...))``; jitter arguments as ``ProposalVolume.sample``
@@ -790,7 +841,10 @@ def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=Non
     coarse samples weigh nothing; the merged positions come back marked) and the masked render on those positions under
     that mark, which is not formed a second time.  By definition ``render_nerf(rays, net, Nc + Nf, ts=ts, occupancy=occupancy)``
     on the placement's ``ts``; inference only (call it under ``torch.no_grad()``), one host synchronisation, sets
-    ``occupancy.last_stats``."""
+    ``occupancy.last_stats``.
+    box: refused (RuntimeError before anything is drawn): the guided placement has its own interval."""
+    from .box import refuse_box
+    refuse_box(box, "the guided render (render_guided)")
     _check_guided(net, proposal)
     if occupancy is not None:
         return _render_guided_masked(rays, net, Nc, Nf, proposal, tn, tf, u_c, ts_c, u_f, outputs, precision, device_rng, seed,
@@ -820,7 +874,7 @@ def _render_guided_masked(rays, net, Nc, Nf, proposal, tn, tf, u_c, ts_c, u_f, o
 
 
 def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u_c=None, u_f=None, ray0=0, n_rays=None,
-                       precision=None, device_rng=False, seed=0, occupancy=None):
+                       precision=None, device_rng=False, seed=0, occupancy=None, box=None):
     """One view (or its pixel range [ray0, ray0 + n_rays)) through the grid-guided render: device ray generation ->
     ``proposal.sample`` (counter RNG keyed by global pixel id with device_rng=True) -> the fused render on the given
     positions -> clip(rgb, 0, 1).  Returns pixels [n, 4] = [r, g, b, disparity] on the GPU.  u_c [n, Nc] / u_f [n, Nf]:
@@ -828,7 +882,10 @@ def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u
 
     occupancy: an ``OccupancyGrid`` -- device ray generation -> the masked guided placement -> the
     masked render's pixel head (nerf_amd_volume_render_masked_pixels) on its positions under its mark; under
-    ``torch.no_grad()``, one host synchronisation."""
+    ``torch.no_grad()``, one host synchronisation.
+    box: refused (RuntimeError before anything is drawn)."""
+    from .box import refuse_box
+    refuse_box(box, "the guided render (render_guided_view)")
     _check_guided(net, proposal)
     if occupancy is not None:
         from .occupancy import check_renderable
