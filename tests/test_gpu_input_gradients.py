@@ -1,6 +1,18 @@
 """Gradients with respect to the inputs on the GPU: the encoder, Nerf.forward(v), render_nerf's rays and a camera pose
 recovered through them.  Yardsticks and tolerances: tests/input_grad_model.py (float64 oracle autograd; fp32 paths within
-FACTOR_32 of the fp32 oracle's own error, bf16 paths within FACTOR_16 of an emulation of the kernels' numerics)."""
+FACTOR_32 of the fp32 oracle's own error, bf16 paths within FACTOR_16 of an emulation of the kernels' numerics).
+
+What this end-to-end rule sees, and what it does not.  ``rel_err`` is max |got - want| over the whole [P, 6] (or [B, 6]) tensor
+divided by max |want|.  The encoder's Jacobian multiplies level l by 2^l, so the position columns at level 9 set that scale
+(4562.8 on the inputs of test_nerf_forward_input_gradient) and the three direction columns (at most 2^3; 3.62 there) and the
+low levels sit far below it; and at that amplification the bf16 emulation is itself far from float64, so the allowance is a
+large share of the maximum (0.375).  The rule therefore catches a gradient that is wrong at the top of its range -- a lost
+high level, a wrong scale, a mis-ordered chain -- and answers whether the whole bf16 path is as good as bf16 can be.  It does
+NOT see the direction outputs (zeroed altogether: rel_err 7.9e-4), the raw columns or encoder levels 0..7 of the position (all
+removed together: 0.358), nor a column mapped to the wrong coordinate or trig function at a low level.  Those are pinned
+element by element, against the float64 evaluation of the kernel's own stored operands and under a bound counted from its
+roundings, by tests/test_gpu_input_grad_stage.py (model: tests/input_grad_stage_model.py; the figures above are reproduced
+without a GPU by tests/test_input_grad_stage_cpu.py::test_the_end_to_end_rule_cannot_see_the_direction_columns)."""
 import pytest
 import torch
 
