@@ -216,6 +216,31 @@ def stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def launch(name, *args, dev=None, stream=None):
+    """Enqueue the C entry point ``name``: the one way the package calls into the library.  ``args``
+    are the ABI's arguments in the ABI's order without the trailing stream: a tensor goes as its device pointer, None as
+    NULL, everything else (ints, floats, raw addresses, host float triples) as it is, for the declared argtypes to convert.
+    ``stream`` (a stream pointer): the caller has fixed device and stream, as a captured sequence has.  Without one the
+    launch goes on the current stream of ``dev``, under its device guard.  A non-zero status raises under ``name``."""
+    argv = [a.data_ptr() if torch.is_tensor(a) else a for a in args]
+    if stream is not None:
+        return check(getattr(lib(), name)(*argv, stream), name)
+    with torch.cuda.device(dev):
+        check(getattr(lib(), name)(*argv, torch.cuda.current_stream(dev).cuda_stream), name)
+
+
+def host_f32x3(v):
+    """Three host floats as a launcher's ``const float*`` argument (read before the call returns)."""
+    return (ctypes.c_float * 3)(*[float(x) for x in v])
+
+
+def grad_bucket_range(bucket):
+    """(first, count) of exchange bucket ``bucket`` inside the flat gradient vector (nerf_amd_grad_bucket_range)."""
+    first, count = ctypes.c_int64(), ctypes.c_int64()
+    check(lib().nerf_amd_grad_bucket_range(bucket, ctypes.byref(first), ctypes.byref(count)), "nerf_amd_grad_bucket_range")
+    return first.value, count.value
+
+
 def require_cuda_f32(t, name):
     """The kernels take fp32, contiguous, device-resident tensors; anything
     else is an error (the reference's callers do .cuda() themselves,

@@ -78,13 +78,8 @@ class FusedAdam:
         g = self._flat_grad()
         pg = self.param_groups[0]
         self.step_count += 1
-        lib = _lib.lib()
-        dev = self.flat.device
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_adam_step(
-                _lib.ptr(self.flat), _lib.ptr(g), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
-                self.flat.numel(), float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]),
-                float(pg["eps"]), self.step_count, _lib.stream_ptr(dev)), "nerf_amd_adam_step")
+        _lib.launch("nerf_amd_adam_step", self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), float(pg["lr"]),
+                    float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), self.step_count, dev=self.flat.device)
         # the kernel wrote through the flat buffer (the parameters' _version did not move):
         # re-derive the packed images now and stamp the cache with the current versions
         if self.nets is None:

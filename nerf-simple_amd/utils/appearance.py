@@ -34,8 +34,8 @@ class _Appearance(torch.autograd.Function):
         theta_ray = torch.empty((B, 6), dtype=torch.float32, device=dev)
         out = torch.empty((B, 3), dtype=torch.float32, device=dev)
         if B:
-            app._launch("nerf_amd_appearance_gather", theta, ids, None, app.HW, theta_ray, B, app.M)
-            app._launch("nerf_amd_appearance_apply", rgb, theta_ray, 6, out, B)
+            _lib.launch("nerf_amd_appearance_gather", theta, ids, None, app.HW, theta_ray, B, app.M, dev=dev)
+            _lib.launch("nerf_amd_appearance_apply", rgb, theta_ray, 6, out, B, dev=dev)
         ctx.app, ctx.ids = app, ids
         ctx.save_for_backward(rgb, theta, theta_ray)
         return out
@@ -49,8 +49,9 @@ class _Appearance(torch.autograd.Function):
         g_rgb, g_ray = torch.empty_like(rgb), torch.empty_like(theta_ray)
         g_theta = torch.zeros_like(theta)
         if B:
-            app._launch("nerf_amd_appearance_apply_backward", g_out, rgb, theta_ray, 6, g_rgb, g_ray, B)
-            app._launch("nerf_amd_appearance_reduce", g_ray, ids, app.HW, theta, app.reg, app._frozen_arg, g_theta, B, app.M)
+            _lib.launch("nerf_amd_appearance_apply_backward", g_out, rgb, theta_ray, 6, g_rgb, g_ray, B, dev=theta.device)
+            _lib.launch("nerf_amd_appearance_reduce", g_ray, ids, app.HW, theta, app.reg, app._frozen_arg, g_theta, B, app.M,
+                        dev=theta.device)
         return g_rgb, g_theta, None, None
 
 
@@ -98,12 +99,6 @@ class AppearanceCorrection(torch.nn.Module):
     @property
     def _frozen_arg(self):
         return self.frozen_mask if self.frozen else None
-
-    def _launch(self, name, *args, stream=None):
-        dev = self.theta.device
-        with torch.cuda.device(dev):
-            _lib.check(getattr(_lib.lib(), name)(*[_lib.ptr(a) if torch.is_tensor(a) or a is None else a for a in args],
-                                                 stream if stream is not None else _lib.stream_ptr(dev)), name)
 
     def forward(self, rgb, ray_ids):
         """c' [B,3] of the colours ``rgb`` [B,3] of the rays with global ids ``ray_ids`` [B] (int64), differentiable in ``rgb``

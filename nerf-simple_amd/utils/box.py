@@ -23,7 +23,6 @@ import torch
 
 from .. import _lib
 from . import jitter
-from .mesh import _host_f32x3
 
 MAX_N = 768                             # samples per ray of the entry points that read the positions (the masked stages)
 
@@ -155,11 +154,8 @@ def place(box, rays, jit, flags, seed, ray_id0, N, tn, tf, want_span=False):
     span = torch.empty((B, 2), dtype=torch.float32, device=dev) if want_span else None
     hit = torch.empty((B,), dtype=torch.int32, device=dev) if want_span else None
     tb = None if flags & _lib.FLAG_TS_GIVEN else _tbins(0, 1, N, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_box_positions(
-            _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tb), flags, int(seed), int(ray_id0), _host_f32x3(box.lo), _host_f32x3(box.hi),
-            float(tn), float(tf), _lib.ptr(ts), _lib.ptr(span), _lib.ptr(hit), B, N, _lib.stream_ptr(dev)),
-            "nerf_amd_box_positions")
+    _lib.launch("nerf_amd_box_positions", rays, jit, tb, flags, int(seed), int(ray_id0), _lib.host_f32x3(box.lo),
+                _lib.host_f32x3(box.hi), float(tn), float(tf), ts, span, hit, B, N, dev=dev)
     return ts, span, hit
 
 

@@ -85,19 +85,12 @@ class CameraRefinement(torch.nn.Module):
 
     # ---- the three entry points --------------------------------------------------------------------------------------
     def _launch_rays(self, xi, ids, ids_copy, rays, stream=None):
-        dev = self.poses0.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_camera_rays(
-                _lib.ptr(self.poses0), _lib.ptr(xi), _lib.ptr(ids), _lib.ptr(ids_copy), self.H, self.W, self.f, _lib.ptr(rays),
-                int(ids.shape[0]), self.M, stream if stream is not None else _lib.stream_ptr(dev)), "nerf_amd_camera_rays")
+        _lib.launch("nerf_amd_camera_rays", self.poses0, xi, ids, ids_copy, self.H, self.W, self.f, rays, int(ids.shape[0]),
+                    self.M, dev=self.poses0.device, stream=stream)
 
     def _launch_backward(self, xi, ids, d_rays, g_xi, stream=None):
-        dev = self.poses0.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_camera_rays_backward(
-                _lib.ptr(self.poses0), _lib.ptr(xi), _lib.ptr(ids), _lib.ptr(d_rays), self.H, self.W, self.f, _lib.ptr(g_xi),
-                None, int(ids.shape[0]), self.M, stream if stream is not None else _lib.stream_ptr(dev)),
-                "nerf_amd_camera_rays_backward")
+        _lib.launch("nerf_amd_camera_rays_backward", self.poses0, xi, ids, d_rays, self.H, self.W, self.f, g_xi, None,
+                    int(ids.shape[0]), self.M, dev=self.poses0.device, stream=stream)
 
     def rays(self, ray_ids):
         """Rays [B,6] of the global ray ids [B] (int64, on the cameras' device), differentiable in ``xi``.  An id outside
@@ -113,9 +106,7 @@ class CameraRefinement(torch.nn.Module):
         """The corrected poses [M,4,4] (for ``render_view``): the bits the rays are formed from."""
         dev = self.poses0.device
         top = torch.empty((self.M, 3, 4), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_camera_poses(_lib.ptr(self.poses0), _lib.ptr(self.xi), _lib.ptr(top), self.M,
-                                                        _lib.stream_ptr(dev)), "nerf_amd_camera_poses")
+        _lib.launch("nerf_amd_camera_poses", self.poses0, self.xi, top, self.M, dev=dev)
         out = torch.zeros((self.M, 4, 4), dtype=torch.float32, device=dev)
         out[:, :3] = top
         out[:, 3, 3] = 1.0

@@ -137,13 +137,10 @@ class RayGenerator:
         return self._ws[key]
 
     def launch(self, mode, B, draws, seed, seed_mem, rays, gt, ids, stream=None, workspace=None):
-        """nerf_amd_select_rays on the current stream (or ``stream``, a ctypes stream pointer: graph capture);
+        """nerf_amd_select_rays on the current stream (or ``stream``, a stream pointer: graph capture);
         ``workspace``: the caller's own (a captured launch keeps its address), default one cached per batch size."""
         table = self.rays_dataset[mode]
         cols = self.colours.get(mode) if gt is not None else None
         dev = table.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_select_rays(
-                _lib.ptr(draws), int(seed) & 0xffffffffffffffff, seed_mem, int(table.shape[0]), int(B), _lib.ptr(table),
-                _lib.ptr(cols), _lib.ptr(rays), _lib.ptr(gt), _lib.ptr(ids), _lib.ptr(workspace if workspace is not None else self.workspace(B, dev)),
-                stream if stream is not None else _lib.stream_ptr(dev)), "nerf_amd_select_rays")
+        _lib.launch("nerf_amd_select_rays", draws, int(seed) & 0xffffffffffffffff, seed_mem, int(table.shape[0]), int(B), table,
+                    cols, rays, gt, ids, workspace if workspace is not None else self.workspace(B, dev), dev=dev, stream=stream)

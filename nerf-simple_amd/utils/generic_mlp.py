@@ -34,10 +34,8 @@ def _gemm(A, sa_i, sa_k, B, sb_k, sb_j, C, ldc, M, N, K, *, mask=None, bias=None
     dev = C.device
     pa = A.data_ptr() + 4 * a_off
     pm = 0 if mask is None else mask.data_ptr() + 4 * a_off
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_linear_f32(pa, sa_i, sa_k, pm or None, B.data_ptr() + 4 * b_off, sb_k, sb_j,
-                                                  _lib.ptr(bias), C.data_ptr() + 4 * c_off, ldc, M, N, K, flags,
-                                                  _lib.stream_ptr(dev)), "nerf_amd_linear_f32")
+    _lib.launch("nerf_amd_linear_f32", pa, sa_i, sa_k, pm or None, B.data_ptr() + 4 * b_off, sb_k, sb_j, bias,
+                C.data_ptr() + 4 * c_off, ldc, M, N, K, flags, dev=dev)
 
 
 def _linear(x, w, b, out, *, relu, w_col0=0, accumulate=False, out_col0=0):
@@ -177,10 +175,7 @@ class _GenericMlp(torch.autograd.Function):
             xgrad(d_h, H, H, w[0], d_posx, mask=acts[0], accumulate=True)                 # layers_0.0
             d_v = torch.empty((P, 6), dtype=torch.float32, device=dev)
             Lp, Ld = ctx.L
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib().nerf_amd_positional_encoder_backward(
-                    _lib.ptr(v), _lib.ptr(d_posx), _lib.ptr(d_posd), _lib.ptr(d_v), P, Lp, Ld, _lib.stream_ptr(dev)),
-                    "nerf_amd_positional_encoder_backward")
+            _lib.launch("nerf_amd_positional_encoder_backward", v, d_posx, d_posd, d_v, P, Lp, Ld, dev=dev)
         grads = []
         for L in range(12):
             grads += [gw[L], gb[L]] if need_w else [None, None]

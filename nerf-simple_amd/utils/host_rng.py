@@ -124,7 +124,6 @@ def segment_plan(next0, n, levels, seg_words, n_short, short_words):
 
 def _launch_uniform(words_dev, next0, out, n, state_out, device):
     """nerf_amd_mt19937_uniform, or its multi-workgroup form when the draw spans several segments."""
-    lib = _lib.lib()
     st = _lib.stream_ptr(device)
     jp = _jump_polys(device)
     if jp is not None:
@@ -133,13 +132,11 @@ def _launch_uniform(words_dev, next0, out, n, state_out, device):
         if table is not None:
             polys = short if table == "short" else long_polys
             ws = torch.empty((S, _N), dtype=torch.int32, device=device)
-            _lib.check(lib.nerf_amd_mt19937_uniform_par(_lib.ptr(words_dev), int(next0), _lib.ptr(out), int(n),
-                                                        _lib.ptr(state_out), _lib.ptr(polys), levels, seg_words,
-                                                        _lib.ptr(ws), st), "nerf_amd_mt19937_uniform_par")
+            _lib.launch("nerf_amd_mt19937_uniform_par", words_dev, int(next0), out, int(n), state_out, polys, levels, seg_words,
+                        ws, stream=st)
             ws.record_stream(torch.cuda.current_stream(device))
             return
-    _lib.check(lib.nerf_amd_mt19937_uniform(_lib.ptr(words_dev), int(next0), _lib.ptr(out), int(n), _lib.ptr(state_out), st),
-               "nerf_amd_mt19937_uniform")
+    _lib.launch("nerf_amd_mt19937_uniform", words_dev, int(next0), out, int(n), state_out, stream=st)
 
 
 _side_streams = {}
@@ -205,7 +202,6 @@ class GeneratorSession:
         n, B = int(n), int(B)
         total = max(n - 1, 0)
         first = min(B, total)
-        lib = _lib.lib()
         draws = torch.empty(max(first, 1), dtype=torch.int32, device=self.device)
         if total == 0:
             return draws[:0]
@@ -216,15 +212,12 @@ class GeneratorSession:
                 # a short permutation: draw all of it (one workgroup, 0.6 us per block) and keep the head
                 everything = torch.empty(total, dtype=torch.int32, device=self.device)
                 state_out = torch.empty(_N, dtype=torch.int32, device=self.device)
-                _lib.check(lib.nerf_amd_mt19937_raw(_lib.ptr(self.words_dev), self._first_unread(), _lib.ptr(everything), total,
-                                                    _lib.ptr(state_out), st), "nerf_amd_mt19937_raw")
+                _lib.launch("nerf_amd_mt19937_raw", self.words_dev, self._first_unread(), everything, total, state_out, stream=st)
                 draws = everything[:first]
             else:
-                _lib.check(lib.nerf_amd_mt19937_raw(_lib.ptr(self.words_dev), self._first_unread(), _lib.ptr(draws), first, None, st),
-                           "nerf_amd_mt19937_raw")
+                _lib.launch("nerf_amd_mt19937_raw", self.words_dev, self._first_unread(), draws, first, None, stream=st)
                 state_out = torch.empty(_N, dtype=torch.int32, device=self.device)
-                _lib.check(lib.nerf_amd_mt19937_advance(_lib.ptr(self.words_dev), _lib.ptr(advance_poly(blocks - 1, self.device)),
-                                                        _lib.ptr(state_out), st), "nerf_amd_mt19937_advance")
+                _lib.launch("nerf_amd_mt19937_advance", self.words_dev, advance_poly(blocks - 1, self.device), state_out, stream=st)
             self._moved(state_out, left, nxt, blocks)
         return draws[:first]
 
@@ -244,7 +237,6 @@ class GeneratorSession:
         S = _segments(next1, nj, short_words)
         if S > 256:
             return self.randperm_draws(n, B_sel), self.rand(B, N, out=out)
-        lib = _lib.lib()
         first = min(B_sel, total)
         draws = torch.empty(max(first, 1), dtype=torch.int32, device=self.device)
         u = torch.empty((B, N), dtype=torch.float32, device=self.device) if out is None else out
@@ -254,11 +246,9 @@ class GeneratorSession:
         left2, nxt2, _blocks2 = _advance(left1, nxt1, nj)
         with torch.cuda.device(self.device):
             st = _lib.stream_ptr(self.device)
-            _lib.check(lib.nerf_amd_mt19937_raw(_lib.ptr(self.words_dev), self._first_unread(), _lib.ptr(draws), first, None, st),
-                       "nerf_amd_mt19937_raw")
-            _lib.check(lib.nerf_amd_mt19937_uniform_after(_lib.ptr(self.words_dev), _lib.ptr(polys), S, next1, _lib.ptr(u), nj,
-                                                          _lib.ptr(state_out), short_words, _lib.ptr(seg_states), st),
-                       "nerf_amd_mt19937_uniform_after")
+            _lib.launch("nerf_amd_mt19937_raw", self.words_dev, self._first_unread(), draws, first, None, stream=st)
+            _lib.launch("nerf_amd_mt19937_uniform_after", self.words_dev, polys, S, next1, u, nj, state_out, short_words,
+                        seg_states, stream=st)
             seg_states.record_stream(torch.cuda.current_stream(self.device))
             self._moved(state_out, left2, nxt2, 1)          # the shuffle alone has regenerated: the words are new
         return draws[:first], u

@@ -15,7 +15,6 @@
 Grid coordinates, per axis: ``step = fl32((hi - lo) / (R - 1))`` and ``x(i) = fl32(lo + fl32(i * step))`` -- the same
 numbers as torch's float32 ``lo + torch.arange(R) * step``.
 """
-import ctypes
 import warnings
 
 import numpy as np
@@ -45,10 +44,6 @@ def grid_axes(resolution, bounds=DEFAULT_BOUNDS):
     return lo, step
 
 
-def _host_f32x3(a):
-    return (ctypes.c_float * 3)(*[float(x) for x in a])
-
-
 def _warn_if_out_of_range(R, lo, step, stacklevel=3):
     """The reference's range warning (utils/xyz.py:8-9), decided on the host: Nerf.forward on the grid points (direction
     (0, 0, 1)) raises it iff a coordinate lies outside [-1, 1], and x(i) is monotone in i, so the two ends tell."""
@@ -70,19 +65,17 @@ def density_grid(net, resolution, bounds=DEFAULT_BOUNDS, *, precision=None):
     if dev.type != "cuda":
         raise RuntimeError("Nerf must be moved to the GPU (.cuda()) before use; there is no CPU path")
     _warn_if_out_of_range(R, lo, step)
-    lib = _lib.lib()
-    h_lo, h_step = _host_f32x3(lo), _host_f32x3(step)
+    h_lo, h_step = _lib.host_f32x3(lo), _lib.host_f32x3(step)
     n = R[0] * R[1] * R[2]
 
     def by_chunks(forward):
         sigma = torch.empty(R, dtype=torch.float32, device=dev)
         flat = sigma.view(-1)
         pts = torch.empty((min(n, _CHUNK), 6), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):         # stays: the chunks' forward and the slice copy run under it too
             for first in range(0, n, _CHUNK):
                 cnt = min(_CHUNK, n - first)
-                _lib.check(lib.nerf_amd_grid_points(h_lo, h_step, R[0], R[1], R[2], first, cnt, _lib.ptr(pts),
-                                                    _lib.stream_ptr(dev)), "nerf_amd_grid_points")
+                _lib.launch("nerf_amd_grid_points", h_lo, h_step, R[0], R[1], R[2], first, cnt, pts, dev=dev)
                 flat[first:first + cnt] = forward(pts[:cnt])[:, 3]
         return sigma
 
@@ -96,9 +89,7 @@ def density_grid(net, resolution, bounds=DEFAULT_BOUNDS, *, precision=None):
             if code == _lib.F32:
                 return by_chunks(lambda p: net.forward_inference(p, precision="fp32"))
             sigma = torch.empty(R, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_amd_density_grid(h_lo, h_step, R[0], R[1], R[2], _lib.ptr(packed[0]), code,
-                                                     _lib.ptr(sigma), _lib.stream_ptr(dev)), "nerf_amd_density_grid")
+            _lib.launch("nerf_amd_density_grid", h_lo, h_step, R[0], R[1], R[2], packed[0], code, sigma, dev=dev)
             return sigma
 
         code = _lib.precision_of(net, precision)
@@ -123,19 +114,16 @@ def marching_cubes(volume, level, bounds=DEFAULT_BOUNDS):
         raise RuntimeError(f"marching_cubes: unsupported volume shape {R}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
-    lvl = ctypes.c_float(float(level))
-    with torch.cuda.device(dev):
-        _lib.check(lib.nerf_amd_marching_cubes_count(_lib.ptr(volume), *R, lvl, _lib.ptr(ws), _lib.ptr(counts),
-                                                     _lib.stream_ptr(dev)), "nerf_amd_marching_cubes_count")
-        nv, nf = (int(x) for x in counts.cpu())
-        if nv >= 1 << 31:
-            raise RuntimeError(f"marching_cubes: {nv} vertices do not fit int32 face indices")
-        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-        _lib.check(lib.nerf_amd_marching_cubes_emit(_lib.ptr(volume), *R, lvl, _host_f32x3(lo), _host_f32x3(step),
-                                                    _lib.ptr(ws), _lib.ptr(verts), _lib.ptr(normals), _lib.ptr(faces),
-                                                    nv, nf, _lib.stream_ptr(dev)), "nerf_amd_marching_cubes_emit")
+    lvl = float(level)
+    _lib.launch("nerf_amd_marching_cubes_count", volume, *R, lvl, ws, counts, dev=dev)
+    nv, nf = (int(x) for x in counts.cpu())
+    if nv >= 1 << 31:
+        raise RuntimeError(f"marching_cubes: {nv} vertices do not fit int32 face indices")
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    _lib.launch("nerf_amd_marching_cubes_emit", volume, *R, lvl, _lib.host_f32x3(lo), _lib.host_f32x3(step), ws, verts,
+                normals, faces, nv, nf, dev=dev)
     return verts, faces, normals
 
 

@@ -87,11 +87,7 @@ def _workspace(M, H, W, dev):
 def _launch(pred, gt, M, H, W, sums, ssim_rgb, ssim_map, workspace):
     p2, ps = _rows(pred)
     g2, gs = _rows(gt)
-    dev = p2.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_image_metrics(_lib.ptr(p2), ps, _lib.ptr(g2), gs, _lib.ptr(sums), _lib.ptr(ssim_rgb),
-                                                     _lib.ptr(ssim_map), _lib.ptr(workspace), M, H, W, _lib.stream_ptr(dev)),
-                   "nerf_amd_image_metrics")
+    _lib.launch("nerf_amd_image_metrics", p2, ps, g2, gs, sums, ssim_rgb, ssim_map, workspace, M, H, W, dev=p2.device)
 
 
 def _derive(sums, ssim_rgb, H, W, ssim_map=None):

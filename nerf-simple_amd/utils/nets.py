@@ -210,9 +210,7 @@ class Nerf(nn.Module):
         if flat.numel() != lib.nerf_amd_param_count():
             raise RuntimeError("unexpected parameter count")
         packed = torch.empty(lib.nerf_amd_packed_bytes(code), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_pack_weights(_lib.ptr(flat), _lib.ptr(packed), code,
-                                                 _lib.stream_ptr(dev)), "nerf_amd_pack_weights")
+        _lib.launch("nerf_amd_pack_weights", flat, packed, code, dev=dev)
         self._packed[key] = _Packed(stamp, packed)
         return self._packed[key]
 
@@ -237,26 +235,22 @@ class Nerf(nn.Module):
         (optim.FusedAdam): no per-tensor concatenation, cache stays valid."""
         if not self._fused_ok():
             return                                   # sizes on the layer-by-layer path read the parameters themselves
-        lib = _lib.lib()
         dev = flat.device
         stamp = tuple((p.data_ptr(), p._version) for p in self._param_list())
         codes = {code for (d, code) in self._packed if d == dev} or {_lib.precision_code(self.precision)}
-        with torch.cuda.device(dev):
-            if _lib.BF16 in codes and _lib.BF16_BWD in codes:
-                # the training pair in one launch
-                a, b = self._packed[(dev, _lib.BF16)].buf, self._packed[(dev, _lib.BF16_BWD)].buf
-                _lib.check(lib.nerf_amd_pack_weights_train(_lib.ptr(flat), _lib.ptr(a), _lib.ptr(b), _lib.stream_ptr(dev)),
-                           "nerf_amd_pack_weights_train")
-                self._packed[(dev, _lib.BF16)] = _Packed(stamp, a)
-                self._packed[(dev, _lib.BF16_BWD)] = _Packed(stamp, b)
-                codes = codes - {_lib.BF16, _lib.BF16_BWD}
-            for code in codes:
-                hit = self._packed.get((dev, code))
-                packed = hit.buf if hit is not None else torch.empty(
-                    lib.nerf_amd_packed_bytes(code), dtype=torch.uint8, device=dev)
-                _lib.check(lib.nerf_amd_pack_weights(_lib.ptr(flat), _lib.ptr(packed), code,
-                                                     _lib.stream_ptr(dev)), "nerf_amd_pack_weights")
-                self._packed[(dev, code)] = _Packed(stamp, packed)       # new weights: the range guard starts over
+        if _lib.BF16 in codes and _lib.BF16_BWD in codes:
+            # the training pair in one launch
+            a, b = self._packed[(dev, _lib.BF16)].buf, self._packed[(dev, _lib.BF16_BWD)].buf
+            _lib.launch("nerf_amd_pack_weights_train", flat, a, b, dev=dev)
+            self._packed[(dev, _lib.BF16)] = _Packed(stamp, a)
+            self._packed[(dev, _lib.BF16_BWD)] = _Packed(stamp, b)
+            codes = codes - {_lib.BF16, _lib.BF16_BWD}
+        for code in codes:
+            hit = self._packed.get((dev, code))
+            packed = hit.buf if hit is not None else torch.empty(
+                _lib.lib().nerf_amd_packed_bytes(code), dtype=torch.uint8, device=dev)
+            _lib.launch("nerf_amd_pack_weights", flat, packed, code, dev=dev)
+            self._packed[(dev, code)] = _Packed(stamp, packed)       # new weights: the range guard starts over
 
     def drop_packed(self, dev, keep=()):
         """Forget the packed images of device ``dev`` except the precision codes in ``keep``: for callers that
@@ -295,10 +289,7 @@ class Nerf(nn.Module):
 
         def launch(code, packed):
             out = torch.empty((P, 4), dtype=torch.float32, device=v.device)
-            with torch.cuda.device(v.device):
-                _lib.check(_lib.lib().nerf_amd_mlp_forward(_lib.ptr(v), _lib.ptr(packed[0]), _lib.ptr(out),
-                                                           P, code, _lib.stream_ptr(v.device)),
-                           "nerf_amd_mlp_forward")
+            _lib.launch("nerf_amd_mlp_forward", v, packed[0], out, P, code, dev=v.device)
             return out
 
         return guarded_launch([self], code, launch)
@@ -327,10 +318,7 @@ class Nerf(nn.Module):
                 v = x if x.shape[1] == 6 else torch.cat([x, torch.zeros_like(x[:, :2]), torch.ones_like(x[:, :1])], 1)
                 return self.forward_inference(v, precision="fp32")[:, 3]
             sigma = torch.empty(P, dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib().nerf_amd_density_forward(_lib.ptr(x), x.shape[1], _lib.ptr(packed[0]), code,
-                                                               _lib.ptr(sigma), P, _lib.stream_ptr(x.device)),
-                           "nerf_amd_density_forward")
+            _lib.launch("nerf_amd_density_forward", x, x.shape[1], packed[0], code, sigma, P, dev=x.device)
             return sigma
 
         return guarded_launch([self], code, launch)
@@ -352,10 +340,7 @@ class Nerf(nn.Module):
         bf16_bytes = 10 * ((P + 255) // 256) * 256 * 512            # the point-blocked bf16 region (nerf_amd.h)
         acts = torch.zeros(nbytes, dtype=torch.uint8, device=v.device)
         out = torch.empty((P, 4), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(lib.nerf_amd_mlp_forward_train_points(_lib.ptr(v), _lib.ptr(self.packed_weights(_lib.BF16)),
-                                                             _lib.ptr(out), _lib.ptr(acts), P, _lib.stream_ptr(v.device)),
-                       "nerf_amd_mlp_forward_train_points")
+        _lib.launch("nerf_amd_mlp_forward_train_points", v, self.packed_weights(_lib.BF16), out, acts, P, dev=v.device)
         return float(acts[:bf16_bytes].view(torch.bfloat16).float().abs().max()) / 65504.0
 
 

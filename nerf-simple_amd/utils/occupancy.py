@@ -37,14 +37,12 @@ The coarse + fine pair through ONE grid (``render_masked_pair`` below: ``render_
 ``training.train_step_hierarchical(..., occupancy=)`` / ``training.GraphedMaskedHierarchicalTrainStep``) -- DESIGN.md
 section 15.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from . import jitter
-from .mesh import DEFAULT_BOUNDS, _host_f32x3, _resolution, density_grid, grid_axes
+from .mesh import DEFAULT_BOUNDS, _resolution, density_grid, grid_axes
 
 _POLICIES = ("live", "empty")
 MAX_N = 768                             # samples per ray the mask layout and the masked compositor serve
@@ -96,9 +94,7 @@ class OccupancyGrid:
         cells = (mask != 0).to(torch.uint8).contiguous()
         lib = _lib.lib()
         words = torch.empty(_grid_words(lib, R), dtype=torch.int32, device=mask.device)
-        with torch.cuda.device(mask.device):
-            _lib.check(lib.nerf_amd_occupancy_from_mask(_lib.ptr(cells), *R, _lib.ptr(words), _lib.stream_ptr(mask.device)),
-                       "nerf_amd_occupancy_from_mask")
+        _lib.launch("nerf_amd_occupancy_from_mask", cells, *R, words, dev=mask.device)
         return cls(words, R, bounds, outside)
 
     @classmethod
@@ -114,10 +110,7 @@ class OccupancyGrid:
         sigma = sigma.detach().contiguous()
         lib = _lib.lib()
         words = torch.empty(_grid_words(lib, R), dtype=torch.int32, device=sigma.device)
-        with torch.cuda.device(sigma.device):
-            _lib.check(lib.nerf_amd_occupancy_from_density(_lib.ptr(sigma), *R, ctypes.c_float(float(level)), int(dilate),
-                                                           _lib.ptr(words), _lib.stream_ptr(sigma.device)),
-                       "nerf_amd_occupancy_from_density")
+        _lib.launch("nerf_amd_occupancy_from_density", sigma, *R, float(level), int(dilate), words, dev=sigma.device)
         return cls(words, R, bounds, outside)
 
     # ---- inspection ---------------------------------------------------------------------------------------------------
@@ -188,14 +181,10 @@ class TrainingOccupancyGrid(OccupancyGrid):
             sigma = density_grid(net, self.resolution, self.bounds, precision=precision)
         if sigma.device != self.state.device:
             raise RuntimeError(f"the occupancy grid lives on {self.state.device}, the network on {sigma.device}")
-        lib, dev = _lib.lib(), self.state.device
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            _lib.check(lib.nerf_amd_occupancy_decay_max(_lib.ptr(self.state), _lib.ptr(sigma), ctypes.c_float(float(decay)),
-                                                        self.state.numel(), st), "nerf_amd_occupancy_decay_max")
-            _lib.check(lib.nerf_amd_occupancy_from_density(_lib.ptr(self.state), *self.resolution,
-                                                           ctypes.c_float(float(softplus_level(level))), int(dilate),
-                                                           _lib.ptr(self.words), st), "nerf_amd_occupancy_from_density")
+        dev = self.state.device
+        _lib.launch("nerf_amd_occupancy_decay_max", self.state, sigma, float(decay), self.state.numel(), dev=dev)
+        _lib.launch("nerf_amd_occupancy_from_density", self.state, *self.resolution, float(softplus_level(level)), int(dilate),
+                    self.words, dev=dev)
         self.cell_fraction = self._count() / float(np.prod([r - 1 for r in self.resolution]))
         self.updates += 1
         return self
@@ -261,12 +250,9 @@ def _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N):
     offsets = torch.empty(B + 1, dtype=torch.int64, device=dev)
     ws = _lib.workspace(lib.nerf_amd_occupancy_workspace_bytes(B), dev)
     mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-    with torch.cuda.device(dev):
-        _lib.check(lib.nerf_amd_occupancy_mark(
-            _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), mflags, int(seed), int(ray_id0), _lib.ptr(occ.words),
-            *occ.resolution, _host_f32x3(occ.lo), _host_f32x3(occ.inv_step), _lib.ptr(mask), _lib.ptr(offsets), None,
-            _lib.ptr(ws), B, N, _lib.stream_ptr(dev)), "nerf_amd_occupancy_mark")
-        live = int(offsets[B])          # the one host synchronisation of a masked render
+    _lib.launch("nerf_amd_occupancy_mark", rays, jit, tbins, mflags, int(seed), int(ray_id0), occ.words, *occ.resolution,
+                _lib.host_f32x3(occ.lo), _lib.host_f32x3(occ.inv_step), mask, offsets, None, ws, B, N, dev=dev)
+    live = int(offsets[B])              # the one host synchronisation of a masked render
     return MarkResult(mask, offsets, live, B, N)
 
 
@@ -275,10 +261,8 @@ def _points(m, rays, jit, tbins, flags, seed, ray_id0):
     dev = rays.device
     pts = torch.empty((m.live, 6), dtype=torch.float32, device=dev)
     if m.live:
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_occupancy_points(
-                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0), _lib.ptr(m.mask),
-                _lib.ptr(m.offsets), _lib.ptr(pts), m.live, m.B, m.N, _lib.stream_ptr(dev)), "nerf_amd_occupancy_points")
+        _lib.launch("nerf_amd_occupancy_points", rays, jit, tbins, flags, int(seed), int(ray_id0), m.mask, m.offsets, pts,
+                    m.live, m.B, m.N, dev=dev)
     return pts
 
 
@@ -290,37 +274,39 @@ def sample_positions(rays, jit, tbins, flags, seed, ray_id0, N):
     return _query_points(rays, jit, tbins, flags, seed, ray_id0, N)[1]
 
 
+def _masked_composite(raw, head, m, outputs, pixels, st):
+    """The masked compositor on the live rows ``raw`` (None: no live row) of a MarkResult, enqueued on ``st``: pixels [B, 4],
+    or the 5-tuple.  ``head`` = (rays, jitter, tbins, flags, seed, ray_id0)."""
+    from .rendering import _five_outputs, _per_sample
+    B, N, dev = m.B, m.N, head[0].device
+    chead = (raw, *head, m.mask, m.offsets)
+    if pixels:
+        px = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        _lib.launch("nerf_amd_volume_render_masked_pixels", *chead, px, B, N, stream=st)
+        return px
+    rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
+    _lib.launch("nerf_amd_volume_render_masked", *chead, rgb, disp, alpha, acc, w, B, N, stream=st)
+    return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+
+
 def _masked_pass(occ, rays, N, tbins, jit, flags, seed, ray_id0, outputs, pixels, mark=None):
     """mark + emit of one masked pass, now (one host read) -> (MarkResult, stats, launch); ``launch(code, image)`` enqueues
     the network on the live points and the masked compositor and returns the 5-tuple, or pixels [B, 4].  ``mark``: the
     ready MarkResult of these positions (the masked guided placement produces it with them): no mark is launched."""
-    from .rendering import _five_outputs, _per_sample
     B, dev = rays.size(0), rays.device
-    lib = _lib.lib()
     m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N) if mark is None else mark
     pts = _points(m, rays, jit, tbins, flags, seed, ray_id0)
     stats = {"rays": B, "samples": B * N, "live": m.live, "network_launches": 0}
 
     def launch(code, image):
         raw = None
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):          # one guard and one stream lookup for the pass's two launches
             st = _lib.stream_ptr(dev)
             if m.live:
                 raw = torch.empty((m.live, 4), dtype=torch.float32, device=dev)
-                _lib.check(lib.nerf_amd_mlp_forward(_lib.ptr(pts), _lib.ptr(image), _lib.ptr(raw), m.live, code, st),
-                           "nerf_amd_mlp_forward")
+                _lib.launch("nerf_amd_mlp_forward", pts, image, raw, m.live, code, stream=st)
                 stats["network_launches"] += 1
-            head = (_lib.ptr(raw), _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0),
-                    _lib.ptr(m.mask), _lib.ptr(m.offsets))
-            if pixels:
-                px = torch.empty((B, 4), dtype=torch.float32, device=dev)
-                _lib.check(lib.nerf_amd_volume_render_masked_pixels(*head, _lib.ptr(px), B, N, st),
-                           "nerf_amd_volume_render_masked_pixels")
-                return px
-            rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
-            _lib.check(lib.nerf_amd_volume_render_masked(*head, _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha), _lib.ptr(acc),
-                                                         _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
-        return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+            return _masked_composite(raw, (rays, jit, tbins, flags, int(seed), int(ray_id0)), m, outputs, pixels, st)
 
     return m, stats, launch
 
@@ -418,11 +404,9 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
     them (nothing when the slab is empty), advance (retire the rows into raw0, T, select the next slab) -> the masked
     compositor on (raw0, M0): at most K + 1 host reads.  ``occ`` None: the all-live grid."""
     from .nets import guarded_launch
-    from .rendering import _five_outputs, _per_sample
     B, dev = rays.size(0), rays.device
     if occ is None:
         occ = all_live_grid(dev)
-    lib = _lib.lib()
     S, K, W = term.slab, (N + term.slab - 1) // term.slab, (N + 63) // 64
     m = _mark(occ, rays, jit, tbins, flags, seed, ray_id0, N)          # M0; raises for N > MAX_N
     trans = torch.ones((B, K), dtype=torch.float32, device=dev)
@@ -434,20 +418,18 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
     masks = [torch.empty((B, W), dtype=torch.int64, device=dev) for _ in range(2)]
     offs = [torch.empty(B + 1, dtype=torch.int64, device=dev) for _ in range(2)]
     totals = torch.zeros(2, dtype=torch.int64, device=dev)
-    ws = _lib.workspace(lib.nerf_amd_termination_workspace_bytes(B), dev)
+    ws = _lib.workspace(_lib.lib().nerf_amd_termination_workspace_bytes(B), dev)
     dead_row = torch.tensor([0.0, 0.0, 0.0, -np.inf], dtype=torch.float32, device=dev) if B else None
-    head = (_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0))
+    head = (rays, jit, tbins, flags, int(seed), int(ray_id0))
 
     def advance(raw, cur, rows, s0, s1, s2, raw0, st):
-        _lib.check(lib.nerf_amd_termination_advance(
-            _lib.ptr(raw), _lib.ptr(masks[cur]) if raw is not None else None, _lib.ptr(offs[cur]) if raw is not None else None,
-            rows, *head, _lib.ptr(m.mask), _lib.ptr(m.offsets), _lib.ptr(raw0), m.live, ctypes.c_float(term.eps), S, s0, s1, s2,
-            _lib.ptr(trans), _lib.ptr(masks[1 - cur]), _lib.ptr(offs[1 - cur]), _lib.ptr(totals), _lib.ptr(ws), B, N, st),
-            "nerf_amd_termination_advance")
+        _lib.launch("nerf_amd_termination_advance", raw, masks[cur] if raw is not None else None,
+                    offs[cur] if raw is not None else None, rows, *head, m.mask, m.offsets, raw0, m.live, term.eps, S, s0, s1, s2,
+                    trans, masks[1 - cur], offs[1 - cur], totals, ws, B, N, stream=st)
 
     def launch(code, image):
         raw0 = None
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):          # one guard and one stream lookup for the slab loop (host reads between its launches)
             st = _lib.stream_ptr(dev)
             if B:
                 raw0 = dead_row.repeat(max(m.live, 1), 1)
@@ -470,11 +452,9 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
                     raw = None
                     if count:
                         pts = torch.empty((count, 6), dtype=torch.float32, device=dev)
-                        _lib.check(lib.nerf_amd_occupancy_points(*head, _lib.ptr(masks[cur]), _lib.ptr(offs[cur]), _lib.ptr(pts),
-                                                                 count, B, N, st), "nerf_amd_occupancy_points")
+                        _lib.launch("nerf_amd_occupancy_points", *head, masks[cur], offs[cur], pts, count, B, N, stream=st)
                         raw = torch.empty((count, 4), dtype=torch.float32, device=dev)
-                        _lib.check(lib.nerf_amd_mlp_forward(_lib.ptr(pts), _lib.ptr(image), _lib.ptr(raw), count, code, st),
-                                   "nerf_amd_mlp_forward")
+                        _lib.launch("nerf_amd_mlp_forward", pts, image, raw, count, code, stream=st)
                         stats["network_launches"] += 1
                         stats["evaluated"] += count
                         evaluated_mask.bitwise_or_(masks[cur])
@@ -482,16 +462,7 @@ def render_terminated(term, occ, rays, net, N, tbins, jit, flags, seed, ray_id0,
                     advance(raw, cur, count, k * S, s1, min(s1 + S, N), raw0, st)
                     stats["slabs_run"] += 1
                     cur = 1 - cur
-            chead = (_lib.ptr(raw0 if m.live else None), *head, _lib.ptr(m.mask), _lib.ptr(m.offsets))
-            if pixels:
-                px = torch.empty((B, 4), dtype=torch.float32, device=dev)
-                _lib.check(lib.nerf_amd_volume_render_masked_pixels(*chead, _lib.ptr(px), B, N, st),
-                           "nerf_amd_volume_render_masked_pixels")
-                return px
-            rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
-            _lib.check(lib.nerf_amd_volume_render_masked(*chead, _lib.ptr(rgb), _lib.ptr(disp), _lib.ptr(alpha), _lib.ptr(acc),
-                                                         _lib.ptr(w), B, N, st), "nerf_amd_volume_render_masked")
-        return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+            return _masked_composite(raw0 if m.live else None, head, m, outputs, pixels, st)
 
     if B == 0 or m.live == 0:
         # nothing to evaluate: no network launch, hence nothing for the range guard to look at

@@ -23,7 +23,7 @@ import torch
 
 from .. import _lib
 from . import jitter
-from .mesh import DEFAULT_BOUNDS, _host_f32x3, _resolution, _warn_if_out_of_range, density_grid, grid_axes
+from .mesh import DEFAULT_BOUNDS, _resolution, _warn_if_out_of_range, density_grid, grid_axes
 
 MIN_NC, MAX_NC, MAX_TOTAL = 3, 256, 512           # the sampler's sizes (csrc/sample_pdf_device.h)
 
@@ -54,7 +54,7 @@ class ProposalVolume:
         self.bounds = (tuple(float(x) for x in bounds[0]), tuple(float(x) for x in bounds[1]))
         self.lo, self.step = grid_axes(R, self.bounds)
         self.inv_step = (np.float32(1) / self.step).astype(np.float32)
-        self._h_lo, self._h_inv_step = _host_f32x3(self.lo), _host_f32x3(self.inv_step)
+        self._h_lo, self._h_inv_step = _lib.host_f32x3(self.lo), _lib.host_f32x3(self.inv_step)
         self.updates = 0
 
     @classmethod
@@ -82,15 +82,13 @@ class ProposalVolume:
         code = _lib.precision_of(net, precision)
         R = self.resolution
         _warn_if_out_of_range(R, self.lo, self.step)
-        lib, h_lo, h_step = _lib.lib(), _host_f32x3(self.lo), _host_f32x3(self.step)
+        h_lo, h_step = _lib.host_f32x3(self.lo), _lib.host_f32x3(self.step)
 
         def launch(code, packed):
             if code == _lib.F32:
                 self.sigma.copy_(density_grid(net, R, self.bounds, precision="fp32"))
             else:
-                with torch.cuda.device(dev):
-                    _lib.check(lib.nerf_amd_density_grid(h_lo, h_step, R[0], R[1], R[2], _lib.ptr(packed[0]), code,
-                                                         _lib.ptr(self.sigma), _lib.stream_ptr(dev)), "nerf_amd_density_grid")
+                _lib.launch("nerf_amd_density_grid", h_lo, h_step, R[0], R[1], R[2], packed[0], code, self.sigma, dev=dev)
             return self.sigma
 
         with torch.no_grad():
@@ -101,25 +99,17 @@ class ProposalVolume:
     # ---- the sampler ------------------------------------------------------------------------------------------------------
     def _launch(self, rays, jit, tbins, flags, seed, ray_id0, u_f, ts_out, sigma_c, w_c, B, Nc, Nf):
         """Enqueue nerf_amd_sample_pdf_volume on the current stream of the volume's device (no allocation, no sync)."""
-        dev = self.sigma.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_sample_pdf_volume(
-                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed), int(ray_id0), _lib.ptr(self.sigma),
-                *self.resolution, self._h_lo, self._h_inv_step, _lib.ptr(u_f), _lib.ptr(ts_out), _lib.ptr(sigma_c),
-                _lib.ptr(w_c), B, Nc, Nf, _lib.stream_ptr(dev)), "nerf_amd_sample_pdf_volume")
+        _lib.launch("nerf_amd_sample_pdf_volume", rays, jit, tbins, flags, int(seed), int(ray_id0), self.sigma,
+                    *self.resolution, self._h_lo, self._h_inv_step, u_f, ts_out, sigma_c, w_c, B, Nc, Nf, dev=self.sigma.device)
 
     def _launch_masked(self, occ, rays, jit, tbins, flags, seed, ray_id0, u_f, ts_out, sigma_c, w_c, mask, offsets, live, ws,
                        B, Nc, Nf):
         """Enqueue nerf_amd_sample_pdf_volume_masked (placement + mark + scan through ``occ``) likewise."""
-        dev = self.sigma.device
         mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_sample_pdf_volume_masked(
-                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), mflags, int(seed), int(ray_id0), _lib.ptr(self.sigma),
-                *self.resolution, self._h_lo, self._h_inv_step, _lib.ptr(occ.words), *occ.resolution, _host_f32x3(occ.lo),
-                _host_f32x3(occ.inv_step), _lib.ptr(u_f), _lib.ptr(ts_out), _lib.ptr(sigma_c), _lib.ptr(w_c), _lib.ptr(mask),
-                _lib.ptr(offsets), _lib.ptr(live), _lib.ptr(ws), B, Nc, Nf, _lib.stream_ptr(dev)),
-                "nerf_amd_sample_pdf_volume_masked")
+        _lib.launch("nerf_amd_sample_pdf_volume_masked", rays, jit, tbins, mflags, int(seed), int(ray_id0), self.sigma,
+                    *self.resolution, self._h_lo, self._h_inv_step, occ.words, *occ.resolution, _lib.host_f32x3(occ.lo),
+                    _lib.host_f32x3(occ.inv_step), u_f, ts_out, sigma_c, w_c, mask, offsets, live, ws, B, Nc, Nf,
+                    dev=self.sigma.device)
 
     def check(self, rays, Nc, Nf, u_c=None, ts_c=None, u_f=None, device_rng=False, *, occupancy=None):
         """The preconditions of ``sample``; raises before any jitter is drawn.  -> (B, Nc, Nf)"""

@@ -119,11 +119,8 @@ def _blend(rgb, acc, disp, bg, stride, pixels=False):
     """rgb + (1 - acc) bg through nerf_amd_background_blend: rgb_bg [B,3], or pixels [B,4] = [clip(rgb_bg, 0, 1), disp]."""
     B, dev = rgb.shape[0], rgb.device
     out = torch.empty((B, 4 if pixels else 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_background_blend(
-            _lib.ptr(rgb), _lib.ptr(acc), _lib.ptr(disp) if pixels else None, _lib.ptr(bg), stride,
-            None if pixels else _lib.ptr(out), _lib.ptr(out) if pixels else None, B, _lib.stream_ptr(dev)),
-            "nerf_amd_background_blend")
+    _lib.launch("nerf_amd_background_blend", rgb, acc, disp if pixels else None, bg, stride, None if pixels else out,
+                out if pixels else None, B, dev=dev)
     return out
 
 
@@ -149,11 +146,7 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS, background=None):
     dev = nerf_outs.device
     raw, ts, dirs = nerf_outs.detach().contiguous(), ts.detach().contiguous(), dirs.detach().contiguous()
     rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_volume_render(
-            _lib.ptr(raw), _lib.ptr(ts), _lib.ptr(dirs), 3, _lib.ptr(rgb), _lib.ptr(disp),
-            _lib.ptr(alpha), _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)),
-            "nerf_amd_volume_render")
+    _lib.launch("nerf_amd_volume_render", raw, ts, dirs, 3, rgb, disp, alpha, acc, w, B, N, dev=dev)
     if bg is not None:
         rgb = _blend(rgb, acc, None, *bg)
     return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
@@ -303,13 +296,11 @@ render_rays = render_nerf      # the name BASELINE.json uses for the same functi
 def _render_forward(rays, jit, tbins, image, code, flags, seed, ray_id0, N, outputs):
     """nerf_amd_render_forward with its outputs and its workspace: the five buffers of ``_five_outputs``, as the kernel left
     them (``render_nerf`` and ``render_view(background=)`` differ in the outputs they ask for and in the blend behind)."""
-    B, dev, lib = rays.size(0), rays.device, _lib.lib()
+    B, dev = rays.size(0), rays.device
     out = _five_outputs(B, N, outputs, dev)
-    ws = _lib.workspace(lib.nerf_amd_render_workspace_bytes(code, B, N), dev, floor=0)     # 0 bytes: the one-launch render
-    with torch.cuda.device(dev):
-        _lib.check(lib.nerf_amd_render_forward(
-            _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), _lib.ptr(image), code, flags, int(seed), int(ray_id0),
-            *[_lib.ptr(t_) for t_ in out], _lib.ptr(ws), B, N, _lib.stream_ptr(dev)), "nerf_amd_render_forward")
+    ws = _lib.workspace(_lib.lib().nerf_amd_render_workspace_bytes(code, B, N), dev, floor=0)     # 0 bytes: the one-launch render
+    _lib.launch("nerf_amd_render_forward", rays, jit, tbins, image, code, flags, int(seed), int(ray_id0), *out, ws, B, N,
+                dev=dev)
     return out
 
 
@@ -325,7 +316,6 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, co
         rays = rays.detach()
     else:
         q, ts = _query_points(rays, jit, _tbins(tn, tf, N, dev), flags, seed, ray_id0, N)
-    lib = _lib.lib()
     out = net.forward(q).reshape(B, N, 4).float()
     if torch.is_grad_enabled() and out.requires_grad:
         from ..training import composite_with_controls
@@ -334,10 +324,7 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, co
         raise RuntimeError("sigma_noise is a training regulariser: the net's output carries no gradient")
     out = out.detach().contiguous()
     rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.nerf_amd_volume_render_rays(_lib.ptr(out), _lib.ptr(ts), _lib.ptr(rays), _lib.ptr(rgb), _lib.ptr(disp),
-                                                   _lib.ptr(alpha), _lib.ptr(acc), _lib.ptr(w), B, N, _lib.stream_ptr(dev)),
-                   "nerf_amd_volume_render_rays")
+    _lib.launch("nerf_amd_volume_render_rays", out, ts, rays, rgb, disp, alpha, acc, w, B, N, dev=dev)
     if controls is not None:
         rgb = _blend(rgb, acc, None, controls[0], controls[1])
     return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
@@ -348,10 +335,7 @@ def _query_points(rays, jit, tbins, flags, seed, ray_id0, N):
     B, dev = rays.size(0), rays.device
     q = torch.empty((B * N, 6), dtype=torch.float32, device=dev)
     ts = torch.empty((B, N), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_query_points(_lib.ptr(rays), _lib.ptr(jit), _lib.ptr(tbins), flags, int(seed),
-                                                    int(ray_id0), _lib.ptr(q), _lib.ptr(ts), B, N, _lib.stream_ptr(dev)),
-                   "nerf_amd_query_points")
+    _lib.launch("nerf_amd_query_points", rays, jit, tbins, flags, int(seed), int(ray_id0), q, ts, B, N, dev=dev)
     return q, ts
 
 
@@ -373,10 +357,7 @@ class _QueryPoints(torch.autograd.Function):
         B, dev = rays.size(0), rays.device
         d_rays = torch.empty((B, 6), dtype=torch.float32, device=dev)
         g_q = g_q.contiguous().float()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_query_points_backward(_lib.ptr(rays), _lib.ptr(ts), _lib.ptr(g_q),
-                                                                 _lib.ptr(d_rays), B, ctx.N, _lib.stream_ptr(dev)),
-                       "nerf_amd_query_points_backward")
+        _lib.launch("nerf_amd_query_points_backward", rays, ts, g_q, d_rays, B, ctx.N, dev=dev)
         return d_rays, None, None, None, None, None, None
 
 
@@ -513,10 +494,7 @@ def generate_rays(pose, cam_params, device, ray0=0, n_rays=None):
     n = H * W - ray0 if n_rays is None else int(n_rays)
     h_pose = _host_pose(pose)
     rays = torch.empty((n, 6), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().nerf_amd_generate_rays(
-            h_pose.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(rays), _lib.stream_ptr(device)),
-            "nerf_amd_generate_rays")
+    _lib.launch("nerf_amd_generate_rays", h_pose.ctypes.data, H, W, f, int(ray0), n, rays, dev=device)
     return rays
 
 
@@ -620,10 +598,8 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         def launch_given(code, packed):       # the render's pixel head on the given positions (render_guided_view's launch)
             pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
             ws = _lib.workspace(lib.nerf_amd_render_workspace_bytes(code, n, int(N)), dev, floor=0)
-            with torch.cuda.device(dev):
-                _lib.check(lib.nerf_amd_render_pixels_forward(
-                    _lib.ptr(rays), _lib.ptr(jit), None, _lib.ptr(packed[0]), code, flags, int(seed), int(ray0),
-                    _lib.ptr(pixels), _lib.ptr(ws), n, int(N), _lib.stream_ptr(dev)), "nerf_amd_render_pixels_forward")
+            _lib.launch("nerf_amd_render_pixels_forward", rays, jit, None, packed[0], code, flags, int(seed), int(ray0), pixels,
+                        ws, n, int(N), dev=dev)
             return pixels
 
         return guarded_launch([net], code, launch_given)
@@ -632,11 +608,8 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
         ws = _lib.workspace(lib.nerf_amd_render_image_workspace_bytes(code, n, N), dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_render_image_forward(
-                h_pose.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, N, dev)),
-                _lib.ptr(packed[0]), code, flags, int(seed), _lib.ptr(pixels), _lib.ptr(ws), int(N),
-                _lib.stream_ptr(dev)), "nerf_amd_render_image_forward")
+        _lib.launch("nerf_amd_render_image_forward", h_pose.ctypes.data, H, W, f, int(ray0), n, jit, _tbins(tn, tf, N, dev),
+                    packed[0], code, flags, int(seed), pixels, ws, int(N), dev=dev)
         return pixels
 
     return guarded_launch([net], code, launch)
@@ -672,10 +645,8 @@ def sample_pdf(ts, w, Nf, *, u=None, device_rng=False, seed=0, ray_id0=0):
     if pending_rng is not None:
         pending_rng.finish()
     out = torch.empty((B, Nc + Nf), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nerf_amd_sample_pdf(
-            _lib.ptr(ts.contiguous()), _lib.ptr(w.contiguous()), _lib.ptr(jit), flags, int(seed), int(ray_id0),
-            _lib.ptr(out), B, int(Nc), int(Nf), _lib.stream_ptr(dev)), "nerf_amd_sample_pdf")
+    _lib.launch("nerf_amd_sample_pdf", ts.contiguous(), w.contiguous(), jit, flags, int(seed), int(ray_id0), out, B, int(Nc),
+                int(Nf), dev=dev)
     return out
 
 
@@ -738,19 +709,13 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
     if pending_rng is not None:
         pending_rng.finish()
     # the coarse pass through the stage-1 entry point: the sampler needs the positions the kernel drew
-    lib = _lib.lib()
-
     def launch(code, packed):
         raw = torch.empty((B, Nc, 4), dtype=torch.float32, device=dev)
         ts_c = torch.empty((B, Nc), dtype=torch.float32, device=dev)
         outs = [torch.empty(s_, dtype=torch.float32, device=dev) for s_ in ((B, 3), (B,), (B, Nc), (B,), (B, Nc))]
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            _lib.check(lib.nerf_amd_mlp_forward_rays(
-                _lib.ptr(rays), _lib.ptr(jit), _lib.ptr(_tbins(tn, tf, Nc, dev)), _lib.ptr(packed[0]), code, flags, int(seed),
-                int(ray_id0), _lib.ptr(raw), _lib.ptr(ts_c), B, Nc, st), "nerf_amd_mlp_forward_rays")
-            _lib.check(lib.nerf_amd_volume_render_rays(_lib.ptr(raw), _lib.ptr(ts_c), _lib.ptr(rays),
-                                                       *[_lib.ptr(x) for x in outs], B, Nc, st), "nerf_amd_volume_render_rays")
+        _lib.launch("nerf_amd_mlp_forward_rays", rays, jit, _tbins(tn, tf, Nc, dev), packed[0], code, flags, int(seed),
+                    int(ray_id0), raw, ts_c, B, Nc, dev=dev)
+        _lib.launch("nerf_amd_volume_render_rays", raw, ts_c, rays, *outs, B, Nc, dev=dev)
         return ts_c, tuple(outs)
 
     ts_c, coarse = guarded_launch([net_coarse], code, launch)
@@ -793,11 +758,8 @@ def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=1
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
         ws = _lib.workspace(lib.nerf_amd_render_hierarchical_workspace_bytes(n, Nc, Nf), dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_render_hierarchical_forward(
-                h_pose.ctypes.data, H, W, f, int(ray0), n, _lib.ptr(u_c), _lib.ptr(u_f), _lib.ptr(_tbins(tn, tf, Nc, dev)),
-                _lib.ptr(packed[0]), _lib.ptr(packed[-1]), code, flags, int(seed), _lib.ptr(pixels), _lib.ptr(ws), int(Nc),
-                int(Nf), _lib.stream_ptr(dev)), "nerf_amd_render_hierarchical_forward")
+        _lib.launch("nerf_amd_render_hierarchical_forward", h_pose.ctypes.data, H, W, f, int(ray0), n, u_c, u_f,
+                    _tbins(tn, tf, Nc, dev), packed[0], packed[-1], code, flags, int(seed), pixels, ws, int(Nc), int(Nf), dev=dev)
         return pixels
 
     # one precision for both passes: if either network left the fp16 range, both render with bf16 operands
@@ -908,10 +870,8 @@ def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u
     def launch(code, packed):
         pixels = torch.empty((n, 4), dtype=torch.float32, device=dev)
         ws = _lib.workspace(lib.nerf_amd_render_workspace_bytes(code, n, N), dev, floor=0)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nerf_amd_render_pixels_forward(
-                _lib.ptr(rays), _lib.ptr(ts), None, _lib.ptr(packed[0]), code, _lib.FLAG_TS_GIVEN, int(seed), int(ray0),
-                _lib.ptr(pixels), _lib.ptr(ws), n, N, _lib.stream_ptr(dev)), "nerf_amd_render_pixels_forward")
+        _lib.launch("nerf_amd_render_pixels_forward", rays, ts, None, packed[0], code, _lib.FLAG_TS_GIVEN, int(seed), int(ray0),
+                    pixels, ws, n, N, dev=dev)
         return pixels
 
     with torch.no_grad():

@@ -68,24 +68,21 @@ def range_check_values(x, stacklevel=4):
     w = _watch(x.device)
     w.poll(stacklevel=stacklevel)
     x = x.detach().contiguous()
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().nerf_amd_range_check(None, _lib.ptr(x), None, None, 0, 0, 0, _lib.ptr(w.word), x.numel(), 0,
-                                                   _lib.stream_ptr(x.device)), "nerf_amd_range_check")
+    with torch.cuda.device(x.device):         # stays: the word's copy home (after_launch) runs under it too
+        _lib.launch("nerf_amd_range_check", None, x, None, None, 0, 0, 0, w.word, x.numel(), 0, stream=_lib.stream_ptr(x.device))
         w.after_launch()
 
 
 def range_check_rays(rays, jit, tbins, flags, seed, ray_id0, N, stacklevel=4):
     """The same for the points render_nerf forms from its rays (first and last sample of every ray: a coordinate is
-    monotone along its ray): ``jit`` is a tensor, a ctypes pointer (seed-in-memory form) or None."""
+    monotone along its ray): ``jit`` is a tensor, an address (seed-in-memory form) or None."""
     if rays.shape[0] == 0:
         return
     w = _watch(rays.device)
     w.poll(stacklevel=stacklevel)
-    jp = _lib.ptr(jit) if (jit is None or torch.is_tensor(jit)) else jit
     with torch.cuda.device(rays.device):
-        _lib.check(_lib.lib().nerf_amd_range_check(_lib.ptr(rays), None, jp, _lib.ptr(tbins), int(flags), int(seed), int(ray_id0),
-                                                   _lib.ptr(w.word), rays.shape[0], int(N), _lib.stream_ptr(rays.device)),
-                   "nerf_amd_range_check")
+        _lib.launch("nerf_amd_range_check", rays, None, jit, tbins, int(flags), int(seed), int(ray_id0), w.word, rays.shape[0],
+                    int(N), stream=_lib.stream_ptr(rays.device))
         w.after_launch()
 
 
@@ -112,15 +109,13 @@ def gamma(x, L=4):
 
 def _gamma(x, L):
     P, C = x.shape
-    lib = _lib.lib()
     cols = []
     with torch.cuda.device(x.device):
         st = _lib.stream_ptr(x.device)
         for c in range(C):
             xc = x[:, c]
             out = torch.empty((P, 2 * L), dtype=torch.float32, device=x.device)
-            _lib.check(lib.nerf_amd_gamma(_lib.ptr(xc), xc.stride(0) if P > 1 else 1,
-                                          _lib.ptr(out), P, L, st), "nerf_amd_gamma")
+            _lib.launch("nerf_amd_gamma", xc, xc.stride(0) if P > 1 else 1, out, P, L, stream=st)
             cols.append(out)
     if C == 1:
         return cols[0]
@@ -142,15 +137,13 @@ class _Gamma(torch.autograd.Function):
         L = ctx.L
         P, C = x.shape
         g = g.float().reshape(P, 2 * L, C)            # output column (2i + trig) * C + c
-        lib = _lib.lib()
         cols = []
         with torch.cuda.device(x.device):
             st = _lib.stream_ptr(x.device)
             for c in range(C):
                 xc, gc = x[:, c], g[:, :, c].contiguous()
                 dx = torch.empty((P,), dtype=torch.float32, device=x.device)
-                _lib.check(lib.nerf_amd_gamma_backward(_lib.ptr(xc), xc.stride(0) if P > 1 else 1, _lib.ptr(gc),
-                                                       _lib.ptr(dx), P, L, st), "nerf_amd_gamma_backward")
+                _lib.launch("nerf_amd_gamma_backward", xc, xc.stride(0) if P > 1 else 1, gc, dx, P, L, stream=st)
                 cols.append(dx)
         return torch.stack(cols, dim=1), None
 
@@ -173,10 +166,7 @@ def _positional_encoder(vec, Lp, Ld):
     P = vec.shape[0]
     posx = torch.empty((P, 3 + 6 * Lp), dtype=torch.float32, device=vec.device)
     posd = torch.empty((P, 3 + 6 * Ld), dtype=torch.float32, device=vec.device)
-    with torch.cuda.device(vec.device):
-        _lib.check(_lib.lib().nerf_amd_positional_encoder(
-            _lib.ptr(vec), _lib.ptr(posx), _lib.ptr(posd), P, Lp, Ld,
-            _lib.stream_ptr(vec.device)), "nerf_amd_positional_encoder")
+    _lib.launch("nerf_amd_positional_encoder", vec, posx, posd, P, Lp, Ld, dev=vec.device)
     return posx, posd
 
 
@@ -197,10 +187,7 @@ class _PositionalEncoder(torch.autograd.Function):
         g_posx = torch.zeros((P, 3 + 6 * Lp), device=dev) if g_posx is None else g_posx.float().contiguous()
         g_posd = torch.zeros((P, 3 + 6 * Ld), device=dev) if g_posd is None else g_posd.float().contiguous()
         d_vec = torch.empty((P, 6), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nerf_amd_positional_encoder_backward(
-                _lib.ptr(vec), _lib.ptr(g_posx), _lib.ptr(g_posd), _lib.ptr(d_vec), P, Lp, Ld, _lib.stream_ptr(dev)),
-                "nerf_amd_positional_encoder_backward")
+        _lib.launch("nerf_amd_positional_encoder_backward", vec, g_posx, g_posd, d_vec, P, Lp, Ld, dev=dev)
         return d_vec, None, None
 
 

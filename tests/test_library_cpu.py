@@ -592,3 +592,80 @@ def test_reference_jitter_segment_plan():
     assert segment_plan(0, 4096 * 64, levels, long_words, n_short, short_words)[0] == 7
     assert segment_plan(0, 16000 * 128, levels, long_words, n_short, short_words)[0] == 52
     assert segment_plan(0, 640000 * 128, levels, long_words, n_short, short_words)[:2] == (129, "long")
+
+
+class _StubLibrary:
+    """Stands in for the loaded library: every entry point notes its arguments and returns ``rc``."""
+
+    def __init__(self, rc=0):
+        self.rc, self.calls = rc, []
+
+    def __getattr__(self, name):
+        return lambda *a: (self.calls.append((name, a)), self.rc)[1]
+
+
+def test_launch_converts_arguments_and_appends_the_stream(monkeypatch):
+    """_lib.launch with an explicit stream needs no device: a tensor arrives as its data_ptr(), None as NULL, ints, floats and
+    a raw address as given, the stream last, under the name asked for."""
+    import torch
+    from nerf_simple_amd import _lib
+    stub = _StubLibrary()
+    monkeypatch.setattr(_lib, "lib", lambda: stub)
+    t, empty = torch.arange(6, dtype=torch.float32), torch.empty(0)
+    view = t[2:]                                         # a view arrives as ITS first element, not its storage's
+    triple = _lib.host_f32x3((1.0, 2.0, 3.5))
+    stream = ctypes.c_void_p(0x5EED)
+    assert _lib.launch("nerf_amd_sum_f32", t, None, 3, 0.25, 0xABCDE0, view, empty, triple, stream=stream) is None
+    (name, args), = stub.calls
+    assert name == "nerf_amd_sum_f32"
+    assert args[0] == t.data_ptr() and args[0] != 0
+    assert args[1] is None
+    assert args[2] == 3 and type(args[2]) is int
+    assert args[3] == 0.25 and type(args[3]) is float
+    assert args[4] == 0xABCDE0
+    assert args[5] == t.data_ptr() + 8
+    assert not args[6]                                   # an empty tensor has no storage: NULL
+    assert args[7] is triple and list(triple) == [1.0, 2.0, 3.5]
+    assert args[-1] is stream and len(args) == 9
+    # stream 0 (the default stream's pointer) is a stream given, not "no stream": no device is asked for
+    _lib.launch("nerf_amd_sum_f32", t, stream=0)
+    assert stub.calls[-1] == ("nerf_amd_sum_f32", (t.data_ptr(), 0))
+
+
+@pytest.mark.parametrize("rc, message", [(-1, "nerf_amd_mse_loss failed: invalid argument"),
+                                         (-2, "nerf_amd_mse_loss failed: unsupported configuration"),
+                                         (700, "nerf_amd_mse_loss failed: hipError_t 700")])
+def test_launch_raises_on_a_status_under_the_entry_points_name(monkeypatch, rc, message):
+    from nerf_simple_amd import _lib
+    monkeypatch.setattr(_lib, "lib", lambda: _StubLibrary(rc))
+    with pytest.raises(RuntimeError) as err:
+        _lib.launch("nerf_amd_mse_loss", None, 1, stream=0)
+    assert str(err.value) == message
+
+
+def test_training_launch_takes_the_stream_last(monkeypatch):
+    """training._launch, the captured sequences' spelling (tests and tools reach it): the last argument is the stream."""
+    import torch
+    from nerf_simple_amd import _lib, training
+    stub = _StubLibrary()
+    monkeypatch.setattr(_lib, "lib", lambda: stub)
+    t = torch.zeros(3)
+    training._launch("nerf_amd_sum_f32", t, _lib.ptr(t), 3, 77)
+    assert stub.calls == [("nerf_amd_sum_f32", (t.data_ptr(), stub.calls[0][1][1], 3, 77))]
+    assert stub.calls[0][1][1].value == t.data_ptr()     # a pointer the caller wrapped already goes through as it is
+
+
+def test_grad_bucket_range(lib):
+    from nerf_simple_amd import _lib
+    (f1, c1), (f2, c2) = _lib.grad_bucket_range(1), _lib.grad_bucket_range(2)
+    assert f2 == 0 and f1 == c2 and f1 + c1 == lib.nerf_amd_param_count()      # bucket 2 = the head, bucket 1 = the tail
+    with pytest.raises(RuntimeError, match="nerf_amd_grad_bucket_range failed: invalid argument"):
+        _lib.grad_bucket_range(3)
+
+
+def test_ctypes_is_confined_to_the_binding():
+    pkg = os.path.join(ROOT, "nerf-simple_amd")
+    files = [os.path.join(d, f) for d, _, fs in os.walk(pkg) for f in fs if f.endswith(".py")]
+    assert len(files) >= 20
+    users = [os.path.relpath(f, pkg) for f in files if re.search(r"^\s*(import ctypes|from ctypes)\b", open(f).read(), re.M)]
+    assert users == ["_lib.py"]

@@ -29,7 +29,6 @@ from nerf_simple_amd.training import (GraphedBoxTrainStep, GraphedMaskedBoxTrain
                                       GraphedTrainStep)
 from nerf_simple_amd.utils import synthetic                                                          # noqa: E402
 from nerf_simple_amd.utils.box import SceneBox                                                       # noqa: E402
-from nerf_simple_amd.utils.mesh import _host_f32x3                                                   # noqa: E402
 from nerf_simple_amd.utils.rendering import generate_rays, render_view                               # noqa: E402
 from nerf_simple_amd.utils.xyz import spherical_to_pose                                              # noqa: E402
 from time_masked_controls import BOUNDS, alternate, ball_grid, net_on                                # noqa: E402
@@ -93,7 +92,7 @@ def main():
         ts = torch.empty((rows, n), dtype=torch.float32, device=dev)
         u = torch.rand((rows, n), dtype=torch.float32, device=dev)
         tb01 = torch.linspace(0, 1, n + 1).to(dev)
-        box_args = (_host_f32x3(tight.lo), _host_f32x3(tight.hi), 2.0, 6.0, _lib.ptr(ts), None, None, rows, n, _lib.stream_ptr(dev))
+        box_args = (_lib.host_f32x3(tight.lo), _lib.host_f32x3(tight.hi), 2.0, 6.0, _lib.ptr(ts), None, None, rows, n, _lib.stream_ptr(dev))
         # the three sources of the unit positions: ten Philox rounds per sample, or 4 N more bytes per ray read
         calls = {"counter RNG": (_lib.ptr(r), None, _lib.ptr(tb01), _lib.FLAG_DEVICE_RNG, 3, 0, *box_args),
                  "explicit u": (_lib.ptr(r), _lib.ptr(u), _lib.ptr(tb01), 0, 0, 0, *box_args),

@@ -27,7 +27,6 @@ from nerf_simple_amd.optim import FusedAdam                                     
 from nerf_simple_amd.training import (GraphedGuidedTrainStep, GraphedMaskedGuidedTrainStep,          # noqa: E402
                                       GraphedMaskedHierarchicalTrainStep, train_step_guided, train_step_hierarchical)
 from nerf_simple_amd.utils import synthetic                                                          # noqa: E402
-from nerf_simple_amd.utils.mesh import _host_f32x3                                                   # noqa: E402
 from nerf_simple_amd.utils.nets import Nerf                                                          # noqa: E402
 from nerf_simple_amd.utils.occupancy import OccupancyGrid                                            # noqa: E402
 from nerf_simple_amd.utils.proposal import ProposalVolume                                            # noqa: E402
@@ -109,7 +108,7 @@ def main():
     off_a, off_b, off_c = (torch.empty(B + 1, **i64) for _ in range(3))
     ws = torch.empty(max(int(lib.nerf_amd_occupancy_workspace_bytes(B)), 256), dtype=torch.uint8, device=dev)
     RNG, GIVEN, EMPTY = _lib.FLAG_DEVICE_RNG, _lib.FLAG_TS_GIVEN, _lib.FLAG_OUTSIDE_EMPTY
-    g_lo, g_inv, st = _host_f32x3(occ.lo), _host_f32x3(occ.inv_step), _lib.stream_ptr(dev)
+    g_lo, g_inv, st = _lib.host_f32x3(occ.lo), _lib.host_f32x3(occ.inv_step), _lib.stream_ptr(dev)
 
     def masked():
         prop._launch_masked(occ, rays, None, tbins, RNG, 1, 0, None, ts_a, None, None, mask_a, off_a, None, ws, B, Nc, Nf)

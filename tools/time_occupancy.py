@@ -118,7 +118,7 @@ def main():
             raw = torch.empty((max(P, 1), 4), dtype=torch.float32, device=dev)
             px = torch.empty((B, 4), dtype=torch.float32, device=dev)
             mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-            lo, inv = occupancy._host_f32x3(occ.lo), occupancy._host_f32x3(occ.inv_step)
+            lo, inv = _lib.host_f32x3(occ.lo), _lib.host_f32x3(occ.inv_step)
             stages = {
                 "mark_scan": lambda: lib.nerf_amd_occupancy_mark(_lib.ptr(rays), None, _lib.ptr(tb), mflags, seed, 0, _lib.ptr(occ.words),
                                                                  *occ.resolution, lo, inv, _lib.ptr(mask), _lib.ptr(offsets), None,

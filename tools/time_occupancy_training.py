@@ -133,7 +133,7 @@ def main():
         rgb, disp, acc = (torch.empty(s, dtype=torch.float32, device=dev) for s in ((B, 3), (B,), (B,)))
         g_rgb = torch.randn(B, 3, device=dev) / B
         mflags = flags | (_lib.FLAG_OUTSIDE_EMPTY if occ.outside == "empty" else 0)
-        lo, inv = occupancy._host_f32x3(occ.lo), occupancy._host_f32x3(occ.inv_step)
+        lo, inv = _lib.host_f32x3(occ.lo), _lib.host_f32x3(occ.inv_step)
         head = (_lib.ptr(rays), None, _lib.ptr(tb), flags, seed, 0, _lib.ptr(m.mask), _lib.ptr(m.offsets))
 
         def mark_scan_read():
