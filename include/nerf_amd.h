@@ -1038,6 +1038,25 @@ int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, co
                                            const uint64_t* seed_mem, int64_t ray_id0, float* rgb, float* d_raw, int64_t B, int N,
                                            void* stream);
 
+/* nerf_amd_volume_render_mse_backward_pdf_bg: the COARSE head of the coarse + fine pair with both controls, ONE launch:
+ *   nerf_amd_volume_render_mse_backward_pdf with the term block (bg, bg_stride, std, noise_flags, noise_seed, seed_mem) of
+ *   nerf_amd_volume_render_mse_backward_bg in front of the sampler's arguments.  By definition, bit for bit
+ *   (tests/test_gpu_pair_controls.py), rgb[B,3] = rgb_bg and d_raw[B,Nc,4] are the chain of that entry point at N = Nc, and
+ *   ts_out[B,Nc+Nf] is nerf_amd_sample_pdf (u, flags, seed, ray_id0) on the w of that chain's compositor: the sampler sees
+ *   the weights of the NOISY compositor, the background never touches them, and w never reaches HBM.  ray_id0 is shared by
+ *   the sampler and the noise; the noise has flags, seed and seed_mem of its own (a pair's fine pass draws its noise under
+ *   noise_seed + 2^63: two streams, since the counter (ray_id0 + ray) N + i of two passes with different N would share words
+ *   across rays under one key).  The distortion term is not offered here: it belongs on the final weights.
+ *   bg == NULL: no background (bg_stride is still checked); std == 0: no noise; with both it IS
+ *   nerf_amd_volume_render_mse_backward_pdf (the same launch).  3 <= Nc <= 256, Nc + Nf <= 512 (NERF_AMD_EUNSUP beyond).
+ *   Rules in order: sizes and the sampler's jitter arguments as nerf_amd_volume_render_mse_backward_pdf; the noise arguments
+ *   as in nerf_amd_sigma_noise; bg_stride; B == 0; the size limit; the pointers. */
+int nerf_amd_volume_render_mse_backward_pdf_bg(const float* raw, const float* ts, const float* rays, const float* target,
+                                               const float* bg, int64_t bg_stride, float std, uint32_t noise_flags,
+                                               uint64_t noise_seed, const uint64_t* seed_mem, const float* u, uint32_t flags,
+                                               uint64_t seed, int64_t ray_id0, float* rgb, float* d_raw, float* ts_out, int64_t B,
+                                               int Nc, int Nf, void* stream);
+
 /* ---- distortion loss for the dense training path -------------------------------------------------------------------------
  * mip-NeRF 360's regulariser on a ray's compositing weights (the w of utils/rendering.py:68), which pulls them together into
  * one compact interval.  For one ray with positions t_0 <= ... <= t_{N-1} and the far plane t_far:
@@ -1081,7 +1100,7 @@ int nerf_amd_volume_render_mse_backward_dist(const float* raw, const float* ts, 
 
 /* ---- masked training controls: background, sigma noise and distortion loss for the masked steps (csrc/masked_controls.hip) --
  * The three terms of the dense training path for the masked single-network steps (one network behind an occupancy grid,
- * plain or on guided positions; not the masked coarse + fine pair).  Definitions of mask, offsets, the live rows raw_live[P',4]
+ * plain or on guided positions), and the background and the noise for the coarse head of the masked pair.  Definitions of mask, offsets, the live rows raw_live[P',4]
  * and the capacity clamp: "training with the occupancy grid" and "graphed masked training step" above.
  *
  * nerf_amd_sigma_noise_masked: the noise stage on live rows, raw_live[P',4] -> out[P',4] (out may be raw_live).  Row
@@ -1125,6 +1144,25 @@ int nerf_amd_volume_render_masked_mse_backward_dist(const float* raw_live, const
                                                     float std, uint32_t noise_flags, uint64_t noise_seed, const uint64_t* seed_mem,
                                                     float t_far, float coef, float* rgb, float* loss_ray, float* d_raw_live,
                                                     int64_t capacity, int64_t B, int N, void* stream);
+
+/* nerf_amd_volume_render_masked_mse_backward_pdf_bg: the COARSE head of the masked pair with the background and the noise,
+ *   ONE launch under the capacity clamp: nerf_amd_volume_render_masked_mse_backward_pdf with the term block (bg, bg_stride,
+ *   std, noise_flags, noise_seed, seed_mem) of the head above behind gt.  By definition, bit for bit
+ *   (tests/test_gpu_pair_controls.py), rgb and d_raw_live are the head above with coef = 0 at N = Nc, and ts_out[B,Nc+Nf] is
+ *   nerf_amd_sample_pdf (u_f, the jitter's flags, seed, ray_id0) on the w of that chain's masked compositor under mask_C:
+ *   the weights of the NOISY compositor, exactly 0 at a dead or over-capacity sample whatever std is; a ray with nothing kept
+ *   gets rgb = bg and the sampler's uniform placement.  The distortion term is not offered (it belongs on the final weights).
+ *   bg == NULL and std == 0: it IS nerf_amd_volume_render_masked_mse_backward_pdf (the same launch).
+ *   Rules in order: as nerf_amd_volume_render_masked_mse_backward_pdf up to the jitter arguments; the noise arguments as in
+ *   nerf_amd_sigma_noise; bg_stride; then that entry point's again: NERF_AMD_EUNSUP for the sampler's sizes (or B > 2^32);
+ *   NERF_AMD_EINVAL for missing rays, capacity > B Nc (so B == 0), a missing or misaligned mask / offsets, a missing raw_live /
+ *   gt / rgb / d_raw_live / ts_out, raw_live or d_raw_live off 16 bytes. */
+int nerf_amd_volume_render_masked_mse_backward_pdf_bg(const float* raw_live, const float* rays, const float* u, const float* tbins,
+                                                      uint32_t flags, uint64_t seed, int64_t ray_id0, const uint64_t* mask,
+                                                      const int64_t* offsets, const float* gt, const float* bg, int64_t bg_stride,
+                                                      float std, uint32_t noise_flags, uint64_t noise_seed,
+                                                      const uint64_t* seed_mem, const float* u_f, float* rgb, float* d_raw_live,
+                                                      float* ts_out, int64_t capacity, int64_t B, int Nc, int Nf, void* stream);
 
 /* ---- scene box: a ray's samples placed inside an axis-aligned box (csrc/ray_box.hip, csrc/ray_box_device.h) ---------------
  * Not in the reference, whose samples lie in linspace(tn, tf, N + 1) bins whatever the ray (utils/rendering.py:24-30): this

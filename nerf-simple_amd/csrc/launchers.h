@@ -32,12 +32,23 @@ struct DenseHeadArgs {
     float* g_theta;                                    // and every ray's row of d loss / d theta [B,6]
 };
 
+// What the dense COARSE head of the pair reads beside DenseHeadArgs (composite_pair.hip): the fine pass's sampler, as the plain
+// coarse head takes it (composite.hip).  The sampler's ray ids start at DenseHeadArgs::ray_id0, as the noise's do.
+struct DensePdfArgs {
+    const float* u;                                    // u[B,Nf]; with seed_in_mem the DEVICE ADDRESS of the 64-bit seed offset
+    float* ts_out;                                     // [B, Nc+Nf]
+    int Nf;
+    int device_rng;
+    int seed_in_mem;
+    unsigned long long seed;
+};
+
 // What the masked compositor backward reads beside the rays (occupancy_train.hip), filled by the entry points that reach it
 // (api.hip: the eager backward; occupancy_graph.hip and masked_controls.hip: the three capped heads, through
 // capped_head_args below).  The upstream gradients are the MSE head's where target != NULL and the five pointers otherwise.
-// Behind the MSE head either the fine pass's sampler runs (ts_out != NULL) or any of the head's terms is on, its fields as
-// DenseHeadArgs has them: std != 0 (noise; the ray ids are the jitter's, MlpArgs::ray_id0), bg != NULL, coef != 0.  A
-// term's fields are looked at only where the term is on.
+// Behind the MSE head the fine pass's sampler may run (ts_out != NULL) and any of the head's terms may be on, its fields as
+// DenseHeadArgs has them: std != 0 (noise; the ray ids are the jitter's, MlpArgs::ray_id0), bg != NULL, coef != 0 (not with
+// the sampler).  A term's fields are looked at only where the term is on.
 struct MaskedBackwardArgs {
     const unsigned long long* mask;                    // [B, ceil(N / 64)]
     const long long* offsets;                          // [B + 1]
@@ -156,6 +167,7 @@ int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const lo
 int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
 int nerf_amd_occ_train_max_n(void);
 int nerf_amd_launch_masked_backward(const MlpArgs*, const MaskedBackwardArgs*, hipStream_t);
+int nerf_amd_launch_masked_backward_pair(const MlpArgs*, const MaskedBackwardArgs*, hipStream_t);
 int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
 int nerf_amd_launch_sigma_noise(const float*, float*, float, unsigned long long, const unsigned long long*, long long, long long,
                                 int, hipStream_t);
@@ -163,6 +175,7 @@ int nerf_amd_launch_background_blend(const float*, const float*, const float*, c
                                      long long, hipStream_t);
 int nerf_amd_launch_background_blend_backward(const float*, const float*, long long, float*, long long, hipStream_t);
 int nerf_amd_launch_dense_head(const DenseHeadArgs*, hipStream_t);
+int nerf_amd_launch_dense_head_pdf(const DenseHeadArgs*, const DensePdfArgs*, hipStream_t);
 int nerf_amd_launch_distortion_loss(const float*, const float*, float, float, float*, float*, long long, int, hipStream_t);
 int nerf_amd_launch_sum_f32(const float*, float*, long long, hipStream_t);
 int nerf_amd_launch_sigma_noise_masked(const float*, float*, float, unsigned long long, const unsigned long long*, long long,

@@ -11,7 +11,10 @@
 //   the head -- masked_backward_kernel<LossHead<BG, DIST, false>, NOISE, 0> (occupancy_train.hip, the one walk of every
 //       masked backward and head); this source holds its entry point, which fills the terms' fields of MaskedBackwardArgs.
 //
-// No atomics; a row is written by exactly one lane, so two runs write the same bytes.  The two entry points below are the
+//   the coarse head of the masked pair -- the same walk with the sampler behind it, masked_backward_kernel<LossHead<BG, false,
+//       false>, NOISE, E> (the second translation unit of occupancy_train.hip); its entry point is the last one below.
+//
+// No atomics; a row is written by exactly one lane, so two runs write the same bytes.  The three entry points below are the
 // C ABI themselves (argument checking included, api_checks.h).
 #include "sigma_noise_device.h"
 #include "occ_scan_device.h"
@@ -122,5 +125,40 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward_dist(const float* raw_
     b.std = std; b.noise_seed = noise_seed;
     b.seed_mem = (noise_flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr;
     b.t_far = t_far; b.coef = coef; b.loss_ray = loss_ray;
+    return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The coarse head of the masked pair behind a background and / or with noise on the live rows: the plain masked coarse head
+// (occupancy_graph.hip) with the term block of the head above, the distortion term left out.  Order of
+// the rules: the plain coarse head's (Nf and capacity; the sampler's uniforms; sizes; the jitter arguments), then the noise
+// arguments and the background's stride, then the plain head's again (the size limit, NERF_AMD_EUNSUP; the rays; C <= B Nc,
+// mask and offsets; the buffers).
+extern "C" int nerf_amd_volume_render_masked_mse_backward_pdf_bg(const float* raw_live, const float* rays, const float* u,
+                                                                 const float* tbins, uint32_t flags, uint64_t seed,
+                                                                 int64_t ray_id0, const uint64_t* mask, const int64_t* offsets,
+                                                                 const float* gt, const float* bg, int64_t bg_stride, float std,
+                                                                 uint32_t noise_flags, uint64_t noise_seed,
+                                                                 const uint64_t* seed_mem, const float* u_f, float* rgb,
+                                                                 float* d_raw_live, float* ts_out, int64_t capacity, int64_t B,
+                                                                 int Nc, int Nf, void* stream) {
+    if (Nf < 0 || capacity < 1) return NERF_AMD_EINVAL;
+    if (!(flags & NERF_AMD_DEVICE_RNG) && !u_f && Nf > 0) return NERF_AMD_EINVAL;
+    if (B < 0 || Nc <= 0) return NERF_AMD_EINVAL;
+    if (bad_jitter(flags, u, tbins)) return NERF_AMD_EINVAL;
+    if (bad_sigma_noise(std, noise_flags, seed_mem)) return NERF_AMD_EINVAL;
+    if (bad_bg_stride(bg_stride)) return NERF_AMD_EINVAL;
+    if (nerf_pdf::unsupported_sizes(Nc, Nf) || B > MASKED_MAX_RAYS) return NERF_AMD_EUNSUP;
+    if (B > 0 && !rays) return NERF_AMD_EINVAL;
+    const int rc = capped_check(mask, offsets, capacity, B, Nc);
+    if (rc) return rc;
+    if (!raw_live || !gt || !rgb || !d_raw_live || !ts_out || misaligned(raw_live, 16) || misaligned(d_raw_live, 16) ||
+        misaligned(gt, 4) || misaligned(rgb, 4) || misaligned(ts_out, 4) || misaligned(u_f, 4) || misaligned(bg, 4))
+        return NERF_AMD_EINVAL;
+    const MlpArgs a = rays_args(rays, u, tbins, flags, seed, ray_id0, B, Nc);
+    MaskedBackwardArgs b = capped_head_args(raw_live, mask, offsets, gt, rgb, d_raw_live, capacity, B);
+    b.u_f = u_f; b.ts_out = ts_out; b.Nf = Nf;
+    b.bg = bg; b.bg_stride = bg_stride;
+    b.std = std; b.noise_seed = noise_seed;
+    b.seed_mem = (noise_flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr;
     return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
 }

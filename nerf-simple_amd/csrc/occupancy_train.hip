@@ -8,8 +8,8 @@
 //       sample -- rank from popcounts of the mask words -- and (0, 0, 0, -inf) for a dead one.  A dead sample has
 //       softplus' = 0, alpha = 0 and w = 0 there: it receives nothing and adds exact zeros to the suffix sums.  The result is
 //       the rows at the kept samples of the dense backward on the overwritten raw, bit for bit.  No atomics: a row is written
-//       by exactly one lane, and two runs write the same bytes.  Thirteen instantiations, the combinations the launcher
-//       reaches, on four axes:
+//       by exactly one lane, and two runs write the same bytes.  Thirteen instantiations here and twelve in this source's second
+//       translation unit (NERF_MASKED_PAIR, below), the combinations the launchers reach, on four axes:
 //         Up        FiveGrads: the five upstream gradients are given (nerf_amd_volume_render_masked_backward);
 //                   MseHead: g_rgb = 2 (rgb - gt) / (3 B) is formed from the sweep's own forward, and rgb is written
 //                   (the graphed steps' heads, occupancy_graph.hip; DESIGN.md sections 14, 15);
@@ -17,7 +17,9 @@
 //                   MSE, or both (the training controls, masked_controls.hip).  A head's empty ray is
 //                   the dense head's (loss_head_empty_ray), its row a register where the ray owns none;
 //         NOISE     Noisy<> around the source (sigma_noise_device.h): noise on the raw density of the kept samples;
-//         E         0: no sampler.  1, 2, 4, 8, behind the plain MseHead only: the fine pass's sample placement
+//         E         0: no sampler.  1, 2, 4, 8, behind the MseHead -- plain, or behind a background and / or with noise (the
+//                   coarse head of the masked pair with its controls, DESIGN.md section 35: the sampler sees the weights of
+//                   the NOISY masked compositor, the background never touches them) -- : the fine pass's sample placement
 //                   (sample_pdf_device.h, E keys per lane) runs in the same wave from the weights of the forward sweep, as
 //                   composite.hip's dense coarse head does it: wt = mul_rn(alpha, T) goes from registers to the wave's LDS
 //                   slice beside the positions (a dead or over-capacity sample carries exactly 0), and the sampler reads
@@ -55,7 +57,7 @@ struct MaskedLds<0> {
 
 template <class Up, bool NOISE, int E>
 __global__ __launch_bounds__(MASKED_THREADS) void masked_backward_kernel(MlpArgs a, MaskedBackwardArgs b) {
-    static_assert(E == 0 || (Up::MSE && !Up::BG && !Up::DIST && !NOISE), "the sampler runs behind the plain MSE head only");
+    static_assert(E == 0 || (Up::MSE && !Up::DIST && !Up::AFFINE), "the sampler runs behind the MSE head, plain or with background / noise");
     static_assert(Up::MSE || !NOISE, "the terms belong to the loss head");
     constexpr int CHUNKS = E ? nerf_pdf::MAXC / 64 : nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;
     __shared__ MaskedLds<E> lds[MASKED_RAYS_PER_BLOCK];
@@ -131,6 +133,7 @@ __global__ __launch_bounds__(MASKED_THREADS) void masked_backward_kernel(MlpArgs
     }
 }
 
+#ifndef NERF_MASKED_PAIR
 __global__ __launch_bounds__(256) void occ_decay_max_kernel(float* __restrict__ state, const float* __restrict__ sigma_now,
                                                             float decay, long long n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -141,8 +144,36 @@ __global__ __launch_bounds__(256) void occ_decay_max_kernel(float* __restrict__ 
         state[i] = (dcy != dcy) ? dcy : (sp != sp) ? sp : (dcy > sp ? dcy : sp);
     }
 }
+#endif
 
 }  // namespace
+
+#define MASKED_BACKWARD(...) hipLaunchKernelGGL((masked_backward_kernel<__VA_ARGS__>), grid, block, 0, stream, *args, b)
+
+#ifdef NERF_MASKED_PAIR
+// The second translation unit of this source (Makefile: build/occupancy_train_pair.o), as mlp_bf16_16.hip has one for fp16: the
+// twelve instantiations LossHead<BG, false, false> x NOISE x E of the masked COARSE head of the pair behind a background and /
+// or with noise and the launcher that reaches them, so the first unit holds the kernels it held.  `head`
+// comes checked and scaled from nerf_amd_launch_masked_backward below, which hands on to this for a sampler with a term.
+extern "C" int nerf_amd_launch_masked_backward_pair(const MlpArgs* args, const MaskedBackwardArgs* head, hipStream_t stream) {
+    const MaskedBackwardArgs b = *head;
+    const bool noise = b.std != 0.f, bg = b.bg != nullptr;
+    if (!b.ts_out || !b.target || b.coef != 0.f || !(noise || bg)) return -2;
+    const dim3 grid((unsigned)((b.B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
+#define MASKED_HEAD_PDF(NOISE_, BG_)                                                                       \
+    switch (nerf_pdf::keys_per_lane(b.Nf)) {                                                               \
+        case 1: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 1); break;            \
+        case 2: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 2); break;            \
+        case 4: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 4); break;            \
+        default: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 8); break;           \
+    }
+    if (!noise) MASKED_HEAD_PDF(false, true)
+    else if (!bg) MASKED_HEAD_PDF(true, false)
+    else MASKED_HEAD_PDF(true, true)
+#undef MASKED_HEAD_PDF
+    return (int)hipGetLastError();
+}
+#else
 
 extern "C" int nerf_amd_occ_train_max_n(void) { return OCCT_MAX_N; }
 
@@ -153,8 +184,9 @@ extern "C" int nerf_amd_launch_masked_backward(const MlpArgs* args, const Masked
     MaskedBackwardArgs b = *head;
     if (b.B == 0) return 0;
     const bool noise = b.std != 0.f, bg = b.bg != nullptr, dist = b.coef != 0.f, term = noise || bg || dist;
-    // the sampler and the terms run behind the MSE head only, and not together
-    if (((b.ts_out || term) && !b.target) || (b.ts_out && term)) return -2;
+    // the sampler and the terms run behind the MSE head only; the sampler with the background and the noise, not with the
+    // distortion term
+    if (((b.ts_out || term) && !b.target) || (b.ts_out && dist)) return -2;
     if (b.ts_out ? nerf_pdf::unsupported_sizes(args->N, b.Nf) : args->N > OCCT_MAX_N) return -2;
     if (b.loss_ray && !dist) {
         const hipError_t e = hipMemsetAsync(b.loss_ray, 0, (size_t)b.B * sizeof(float), stream);
@@ -162,7 +194,7 @@ extern "C" int nerf_amd_launch_masked_backward(const MlpArgs* args, const Masked
     }
     b.scale = 1.0f / (3.0f * (float)b.B);
     const dim3 grid((unsigned)((b.B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
-#define MASKED_BACKWARD(...) hipLaunchKernelGGL((masked_backward_kernel<__VA_ARGS__>), grid, block, 0, stream, *args, b)
+    if (b.ts_out && term) return nerf_amd_launch_masked_backward_pair(args, &b, stream);      // the coarse head with a term
 #define MASKED_HEAD(NOISE_, BG_, DIST_) MASKED_BACKWARD(nerf_composite::LossHead<BG_, DIST_, false>, NOISE_, 0)
     if (!b.target) MASKED_BACKWARD(FiveGrads, false, 0);
     else if (b.ts_out) switch (nerf_pdf::keys_per_lane(b.Nf)) {
@@ -180,7 +212,6 @@ extern "C" int nerf_amd_launch_masked_backward(const MlpArgs* args, const Masked
     else if (!bg) MASKED_HEAD(true, false, true);
     else MASKED_HEAD(true, true, true);
 #undef MASKED_HEAD
-#undef MASKED_BACKWARD
     return (int)hipGetLastError();
 }
 
@@ -192,3 +223,5 @@ extern "C" int nerf_amd_launch_occ_decay_max(float* state, const float* sigma_no
     hipLaunchKernelGGL(occ_decay_max_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, state, sigma_now, decay, n);
     return (int)hipGetLastError();
 }
+#endif
+#undef MASKED_BACKWARD

@@ -338,6 +338,29 @@ def _controls_arg(controls, *, background=None, sigma_noise=0.0, noise_seed=0, d
     return controls
 
 
+# The coarse + fine pair: both passes draw their sigma noise with ``controls.sigma_noise``, the coarse one
+# under ``noise_seed``, the fine one under (noise_seed + FINE_NOISE_OFFSET) mod 2^64.  The noise counter is (ray_id0 + ray) N + i
+# with N = Nc or Nc + Nf: under ONE key the two passes would share words across different rays.  A graphed stepper adds its step
+# count to the seed, which never crosses 2^63.
+FINE_NOISE_OFFSET = 1 << 63
+
+
+def _pair_controls(controls, what):
+    """``controls=`` of a coarse + fine entry point, the FIRST thing it looks at: None, or a Controls (TypeError) whose
+    distortion term is off (RuntimeError, before any look at the networks, the optimiser, the grid or the generator) -- the
+    regulariser belongs on the final weights, not on what places the samples.  -> (coarse Controls, fine Controls), or None
+    where nothing is on."""
+    controls = _controls_arg(controls)
+    if controls is None:
+        return None
+    if controls.distortion > 0:
+        raise RuntimeError(f"controls= brings the background and the sigma noise to {what}: the distortion term "
+                           "(controls.distortion) is not offered on the coarse + fine pair")
+    if controls.background is None and not controls.sigma_noise:
+        return None
+    return controls, controls.replace(noise_seed=(controls.noise_seed + FINE_NOISE_OFFSET) % (1 << 64))
+
+
 def _refuse_bundle(controls, what):
     """The paths ``controls=`` does not reach yet: refused before any launch and any RNG draw."""
     if controls is not None:
@@ -755,8 +778,9 @@ def _pair_stats(coarse, fine):
     return out
 
 
-def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0):
-    """render_nerf_autograd that also hands back the sample positions it drew (the coarse pass of the pair)."""
+def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0, controls=None):
+    """render_nerf_autograd that also hands back the sample positions it drew (the coarse pass of the pair).
+    ``controls``: the background / sigma noise of ``composite_with_controls``, None = neither."""
     from .utils.rendering import _tbins
     from .utils.xyz import range_check_rays
     dev, B = rays.device, rays.size(0)
@@ -771,6 +795,8 @@ def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray
     else:
         params = [p for _, p in net.named_parameters()]
         raw, ts = _FusedDense.apply(net, rays, jit, tbins, flags, seed, ray_id0, N, None, *params)
+    if controls is not None:
+        return composite_with_controls(raw, ts, rays, True, controls, ray_id0), ts
     return _VolumeRender.apply(raw, ts, rays, True), ts
 
 
@@ -794,13 +820,20 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     sample gets uniform fine samples), the fine pass is ``render_nerf_masked(ts=ts_f)`` through the same grid.  Two host
     synchronisations per step (one live count per pass); ``occupancy.last_stats`` holds the sums and the two passes'
     own reports under 'coarse' / 'fine'.  The default network and the bf16 training kernels only, rays without
-    requires_grad; refused before any jitter is drawn."""
+    requires_grad; refused before any jitter is drawn.
+
+    controls: a ``Controls`` with a background and / or sigma noise, dense or with ``occupancy``: the
+    loss is MSE(rgb_c + (1 - acc_c) bg, gt) + MSE(rgb_f + (1 - acc_f) bg, gt) and both passes carry Gaussian noise of
+    ``controls.sigma_noise`` on the raw density -- the coarse pass keyed by ``noise_seed``, the fine pass by ``noise_seed +
+    FINE_NOISE_OFFSET`` (mod 2^64), both with this call's ``ray_id0``.  The sampler sees the (detached) weights of the noisy
+    coarse compositor; the background never touches them.  ``controls.distortion > 0`` raises RuntimeError before anything
+    else is looked at: the term belongs on the final weights, not on what places the samples."""
     from .optim import FusedAdam
     from .utils import jitter
     from .utils.box import refuse_box
-    from .utils.rendering import render_nerf, sample_pdf
+    from .utils.rendering import render_nerf, sample_pdf, _background_arg
+    pair = _pair_controls(controls, "train_step_hierarchical")
     refuse_box(box, "the coarse + fine pair (train_step_hierarchical)")
-    _refuse_bundle(controls, "the coarse + fine pair (train_step_hierarchical)")
     _check_pair(net_c, net_f, Nc, Nf, precision)
     Nc, Nf = int(Nc), int(Nf)
     params = list(net_c.parameters()) + list(net_f.parameters())
@@ -819,24 +852,31 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
         check_trainable(occupancy, net_c, rays, Nc, precision)       # before any draw: a refused call changes nothing
         check_trainable(occupancy, net_f, rays, Nc + Nf, precision)
         _lib.require_same_device("occupancy grid", occupancy.words, dev)
+    kw_c, kw_f, dense_c = {}, {}, None
+    if pair is not None:                 # off by default: a call without it is the call it was
+        bg = (None, 0) if pair[0].background is None else _background_arg(pair[0].background, B, dev)   # its shape: before any draw
+        kw_c, kw_f = {"controls": pair[0]}, {"controls": pair[1], "ray_id0": ray_id0}
+        dense_c = (*bg, pair[0].sigma_noise, pair[0].noise_seed)
     rays = rays.detach().contiguous()
     jit_c, flags, u_f = jitter.pair(B, Nc, Nf, dev, u_c=u_c, u_f=u_f, device_rng=device_rng)
 
     optimizer.zero_grad(set_to_none=True)
     if occupancy is not None:
         coarse, ts_c = render_nerf_masked(rays, net_c, Nc, occupancy, tn, tf, u=jit_c, device_rng=jit_c is None, seed=seed,
-                                          ray_id0=ray_id0, return_ts=True)
+                                          ray_id0=ray_id0, return_ts=True, **kw_c)
         stats_c = occupancy.last_stats
     else:
         coarse, ts_c = _render_train_with_ts(rays, net_c, Nc, tn, tf, jit_c, flags,
-                                             net_c.precision if precision is None else precision, seed, ray_id0)
-    # the fine positions carry no gradient: w.detach() -- the coarse net learns from MSE(rgb_c, gt) alone
+                                             net_c.precision if precision is None else precision, seed, ray_id0,
+                                             *(() if dense_c is None else (dense_c,)))
+    # the fine positions carry no gradient: w.detach() -- the coarse net learns from MSE(rgb_c, gt) alone.  With sigma noise
+    # these are the weights of the noisy compositor; a background never touches them
     ts_f = sample_pdf(ts_c, coarse[4].detach(), Nf, u=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
     if occupancy is not None:
-        fine = render_nerf_masked(rays, net_f, Nc + Nf, occupancy, tn, tf, ts=ts_f)
+        fine = render_nerf_masked(rays, net_f, Nc + Nf, occupancy, tn, tf, ts=ts_f, **kw_f)
         occupancy.last_stats = _pair_stats(stats_c, occupancy.last_stats)
     else:
-        fine = render_nerf(rays, net_f, Nc + Nf, tn, tf, ts=ts_f, precision=precision)
+        fine = render_nerf(rays, net_f, Nc + Nf, tn, tf, ts=ts_f, precision=precision, **kw_f)
     loss_c = mse_loss(coarse[0], gt)
     loss_f = mse_loss(fine[0], gt)
     loss = loss_c + loss_f
@@ -1067,6 +1107,12 @@ class _Pass:
     it the rest before the first launch: ``net`` and its images ``fwd`` / ``bwd``, ``grads`` (its slice of the flat gradient
     vector), ``loss`` (its loss slot) and ``jitter`` = (rays, jitter, tbins, flags, seed, ray_id0) as the kernels take them."""
 
+    noise_offset = 0             # what this pass adds to the stepper's noise_seed (the fine pass of a pair: FINE_NOISE_OFFSET)
+
+    def noise_seed(self):
+        """The seed argument of this pass's sigma noise (the step's offset in memory comes on top)."""
+        return (self.step.noise_seed + self.noise_offset) & (2 ** 64 - 1)
+
     def __init__(self, step, N, P, rows, e4m3=False):
         lib, dev = _lib.lib(), step.dev
         f32, u8 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.uint8, device=dev)
@@ -1125,16 +1171,24 @@ class _DensePass(_Pass):
             # the head with the distortion term beside the MSE (and behind the same controls, if any): still one launch; the
             # per-ray loss values go to the side branch's sum
             _launch("nerf_amd_volume_render_mse_backward_dist", self.raw, self.ts, rays, s.gt, s.background,
-                    s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, s.noise_seed & (2 ** 64 - 1), s._seed_mem, s.ray_id0,
+                    s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, self.noise_seed(), s._seed_mem, s.ray_id0,
                     s._t_far, s._dist_coef, self.rgb, s._loss_ray, self.d_raw, s.B, self.N, st)
         elif pdf is None and s._controls:
             # the same head behind the stepper's background and / or with noise on sigma; the noise key is noise_seed + the
             # step's offset in memory, whatever the jitter source is
             _launch("nerf_amd_volume_render_mse_backward_bg", self.raw, self.ts, rays, s.gt, s.background,
-                    s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, s.noise_seed & (2 ** 64 - 1), s._seed_mem, s.ray_id0,
+                    s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, self.noise_seed(), s._seed_mem, s.ray_id0,
                     self.rgb, self.d_raw, s.B, self.N, st)
         elif pdf is None:
             _launch("nerf_amd_volume_render_mse_backward", self.raw, self.ts, rays, s.gt, self.rgb, self.d_raw, s.B, self.N, st)
+        elif s._controls:
+            # the coarse head of a pair behind the stepper's background and / or with noise on sigma: the sampler sees the
+            # weights of the noisy compositor.  The sampler and the noise share the stepper's ray_id0 (the sampler reads it with
+            # the counter RNG only, where it is the jitter's own)
+            u_f, ts_f, Nf = pdf
+            _launch("nerf_amd_volume_render_mse_backward_pdf_bg", self.raw, self.ts, rays, s.gt, s.background, s._bg_stride,
+                    s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY, self.noise_seed(), s._seed_mem, jit if u_f is None else u_f,
+                    flags, seed, s.ray_id0, self.rgb, self.d_raw, ts_f, s.B, self.N, Nf, st)
         else:
             u_f, ts_f, Nf = pdf
             _launch("nerf_amd_volume_render_mse_backward_pdf", self.raw, self.ts, rays, s.gt,
@@ -1178,11 +1232,19 @@ class _MaskedPass(_Pass):
             rays, jit, tbins, flags, seed, _ = self.jitter
             _launch("nerf_amd_volume_render_masked_mse_backward_dist", self.raw, rays, jit, tbins, flags, seed, s.ray_id0,
                     self.mask, self.offsets, s.gt, s.background, s._bg_stride, s.sigma_noise,
-                    _lib.FLAG_SEED_IN_MEMORY, s.noise_seed & (2 ** 64 - 1), s._seed_mem, s._t_far if s._distortion > 0 else 0.0,
+                    _lib.FLAG_SEED_IN_MEMORY, self.noise_seed(), s._seed_mem, s._t_far if s._distortion > 0 else 0.0,
                     s._dist_coef if s._distortion > 0 else 0.0, self.rgb, s._loss_ray if s._distortion > 0 else None,
                     self.d_raw, self.P, s.B, self.N, st)
         elif pdf is None:
             _launch("nerf_amd_volume_render_masked_mse_backward", *args, self.rgb, self.d_raw, self.P, s.B, self.N, st)
+        elif s._controls:
+            # the masked coarse head of a pair behind the stepper's background and / or with noise on the live rows: the
+            # sampler sees the weights of the noisy masked compositor under the clamp; ray ids as in the branch above
+            u_f, ts_f, Nf = pdf
+            rays, jit, tbins, flags, seed, _ = self.jitter
+            _launch("nerf_amd_volume_render_masked_mse_backward_pdf_bg", self.raw, rays, jit, tbins, flags, seed, s.ray_id0,
+                    self.mask, self.offsets, s.gt, s.background, s._bg_stride, s.sigma_noise, _lib.FLAG_SEED_IN_MEMORY,
+                    self.noise_seed(), s._seed_mem, u_f, self.rgb, self.d_raw, ts_f, self.P, s.B, self.N, Nf, st)
         else:
             u_f, ts_f, Nf = pdf
             _launch("nerf_amd_volume_render_masked_mse_backward_pdf", *args, u_f, self.rgb, self.d_raw, ts_f,
@@ -1310,8 +1372,8 @@ class GraphedTrainStep:
         controls = _controls_arg(controls, background=background, sigma_noise=sigma_noise, noise_seed=noise_seed,
                                  distortion=distortion)
         if controls is not None:
-            if pair is not None:
-                _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__})")
+            if pair is not None and controls.distortion > 0:       # the pair steppers refuse it first (_pair_controls)
+                _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__}) with the distortion term")
             background, sigma_noise, noise_seed, self._distortion = (controls.background, controls.sigma_noise,
                                                                      controls.noise_seed, controls.distortion)
         self._check_modules(net, optimizer)
@@ -1437,6 +1499,7 @@ class GraphedTrainStep:
             self.ts_f = torch.empty((B, samples[1]), dtype=torch.float32, device=dev)     # the coarse head's output:
             self.passes[1].jitter = (ptr(self.rays), ptr(self.ts_f), None, _lib.FLAG_TS_GIVEN, 0, 0)   # the fine positions
             self._pdf = (None if self.device_rng else ptr(self.u_f), ptr(self.ts_f), Nf)
+            self.passes[1].noise_offset = FINE_NOISE_OFFSET     # one noise stream per pass
         off = 0
         for k, (p, net) in enumerate(zip(self.passes, self.opt.nets or (self.net,))):
             n = sum(q.numel() for q in net.parameters())
@@ -2297,21 +2360,31 @@ class GraphedHierarchicalTrainStep(_PairJitter, GraphedTrainStep):
     device); ``device_rng=True`` keys both draws by seed + step (the eager step's values with ``seed=seed + k`` at step k).
     ``step(rays=None, gt=None, u_c=None, u_f=None, decay=1.0)`` returns the total loss as a 0-d device tensor (no sync);
     ``losses`` holds [coarse, fine]; ``net_c`` / ``net_f`` are the two modules, ``net`` = ``nets`` the pair (as
-    ``FusedAdam([net_c, net_f]).net``).  bf16 storage, one exchange bucket."""
+    ``FusedAdam([net_c, net_f]).net``).  bf16 storage, one exchange bucket.
+
+    ``controls``: a ``Controls`` with a background and / or sigma noise -- the coarse head becomes
+    nerf_amd_volume_render_mse_backward_pdf_bg and the fine head nerf_amd_volume_render_mse_backward_bg: the same number of
+    launches.  ``stepper.background`` is the stepper's own buffer (one colour or [n_rays, 3]), overwritable in place between
+    replays; ``stepper.sigma_noise`` is read-only.  Step k (1-based) draws the coarse noise under ``noise_seed + k`` and the
+    fine noise under ``noise_seed + FINE_NOISE_OFFSET + k``, both with the stepper's ``ray_id0``: the eager
+    ``train_step_hierarchical(..., seed=seed + k, controls=controls.replace(noise_seed=noise_seed + k))``.
+    ``controls.distortion > 0`` raises RuntimeError before anything else is looked at; the flat ``distortion=`` keyword keeps
+    its refusal.  Without ``controls`` the step is the one it was, launch for launch."""
 
     _one_bucket = True
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc=64, Nf=128, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
                  ray_id0=0, check_every=16, rays_from=None, select_mode="train", distortion=0.0, controls=None):
+        pair = _pair_controls(controls, type(self).__name__)
         _refuse_distortion(_check_distortion(distortion), **{"a coarse / fine pair": (net_c, net_f)})
-        _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__})")
         _check_pair(net_c, net_f, Nc, Nf, None)
         self.net_c, self.net_f, self.Nc, self.Nf = net_c, net_f, int(Nc), int(Nf)
         # ``net`` / ``nets`` are the pair, as FusedAdam([net_c, net_f]).net / .nets hold it
         self.nets = (net_c, net_f)
         self._samples = (self.Nc, self.Nc + self.Nf)
         super().__init__(self.nets, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng,
-                         seed=seed, ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+                         seed=seed, ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode,
+                         **({} if pair is None else {"controls": pair[0]}))
 
     def _check_modules(self, net, optimizer):
         from .optim import FusedAdam
@@ -2344,13 +2417,17 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
 
     ``occupancy``: ONE grid for both passes; its ``words`` address is baked into the graph (``step`` raises if the tensor was
     replaced; an in-place ``TrainingOccupancyGrid.update(net_f, ...)`` takes effect on the next replay).  ``losses`` holds
-    [coarse, fine].  bf16 storage, the default network, 3 <= Nc <= 256, Nc + Nf <= 512."""
+    [coarse, fine].  bf16 storage, the default network, 3 <= Nc <= 256, Nc + Nf <= 512.
+
+    ``controls``: as GraphedHierarchicalTrainStep's -- the masked coarse head becomes
+    nerf_amd_volume_render_masked_mse_backward_pdf_bg (the sampler sees the weights of the noisy masked compositor under the
+    clamp) and the fine head nerf_amd_volume_render_masked_mse_backward_dist with the distortion term's scalars zero."""
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc, Nf, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
                  seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
                  distortion=0.0, controls=None):
+        _pair_controls(controls, type(self).__name__)
         _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
-        _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__})")
         self._refuse(storage, buckets)
         _check_pair(net_c, net_f, Nc, Nf, None)
         B, Nc_, Nf_ = int(n_rays), int(Nc), int(Nf)
@@ -2359,7 +2436,8 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
         self._bind_grid((net_c, net_f), (Nc_, Nc_ + Nf_), B, optimizer, occupancy, capacity)
         self.capacity = self._capacities
         super().__init__(net_c, net_f, optimizer, B, Nc_, Nf_, tn=tn, tf=tf, group=group, device_rng=device_rng, seed=seed,
-                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode)
+                         ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode,
+                         controls=controls)
 
     def step(self, rays=None, gt=None, u_c=None, u_f=None, decay=1.0):
         self._watch_grid()

@@ -115,6 +115,22 @@ def _inference_controls(controls, occupancy, terminate, **flat):
     return flat, c.background
 
 
+def _pair_background(controls):
+    """``controls=`` of the coarse + fine inference renders, the first thing they look at -> the background or None.
+    ``render_nerf``'s rules: TypeError for anything but a Controls, ValueError for a distortion term (a render is no step),
+    the regulariser's RuntimeError for sigma noise (an inference render trains nothing)."""
+    from ..training import _controls_arg
+    c = _controls_arg(controls)
+    if c is None:
+        return None
+    if c.distortion:
+        raise ValueError("the distortion term belongs to a training step: a render takes controls.distortion == 0")
+    if c.sigma_noise > 0:
+        raise RuntimeError("sigma_noise is a training regulariser, not a render option: the coarse + fine inference render "
+                           "trains nothing")
+    return c.background
+
+
 def _blend(rgb, acc, disp, bg, stride, pixels=False):
     """rgb + (1 - acc) bg through nerf_amd_background_blend: rgb_bg [B,3], or pixels [B,4] = [clip(rgb_bg, 0, 1), disp]."""
     B, dev = rgb.shape[0], rgb.device
@@ -668,7 +684,7 @@ def _masked_pair_args(occupancy, net_coarse, net_fine, B, Nc, Nf, u_c, u_f, prec
 
 
 def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *, u_c=None, u_f=None,
-                        precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, box=None):
+                        precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, box=None, controls=None):
     """Coarse + fine render (BASELINE config 4: 64 + 128 samples).  The reference
     only has the single-pass render_nerf (its CoarseNet / FineNet are empty
     classes), so this composition is new: a coarse render_nerf pass with Nc
@@ -682,11 +698,22 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
     weights (exactly 0 at a dead sample; a ray with no live coarse sample gets uniform fine samples) -> masked fine pass
     on the merged positions; each network sees live samples only, two host synchronisations per call, both passes at one
     precision under one range guard.  Inference only (``torch.no_grad()``), default network shape only.
-    box: refused (RuntimeError before anything is drawn): the scene box serves the single-network renders."""
+    box: refused (RuntimeError before anything is drawn): the scene box serves the single-network renders.
+    controls: a ``training.Controls`` with a background, with or without ``occupancy``: ``rgb`` of the
+    fine and of the coarse 5-tuple becomes rgb + (1 - acc) background through nerf_amd_background_blend; every other output,
+    ``ts_fine`` included, is bit for bit what it was.  ``controls.sigma_noise > 0`` raises RuntimeError (a regulariser: this
+    render trains nothing), a non-zero ``controls.distortion`` ValueError."""
     from .box import refuse_box
+    background = _pair_background(controls)
     refuse_box(box, "the coarse + fine pair (render_hierarchical)")
     _lib.require_cuda_f32(rays, "rays")
     dev, B = rays.device, rays.size(0)
+    if background is not None:
+        bg = _background_arg(background, _lib.require_rays(rays), dev)        # its shape: before anything is drawn
+        fine, coarse, ts_f = render_hierarchical(rays, net_coarse, net_fine, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, precision=precision,
+                                                 device_rng=device_rng, seed=seed, ray_id0=ray_id0, occupancy=occupancy)
+        return ((_blend(fine[0], fine[3], None, *bg),) + tuple(fine[1:]),
+                (_blend(coarse[0], coarse[3], None, *bg),) + tuple(coarse[1:]), ts_f)
     if occupancy is not None:
         from .occupancy import render_masked_pair
         _lib.require_rays(rays)
@@ -725,7 +752,8 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
 
 
 def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=128, *, tn=2, tf=6, u_c=None, u_f=None,
-                             ray0=0, n_rays=None, precision=None, device_rng=False, seed=0, occupancy=None, box=None):
+                             ray0=0, n_rays=None, precision=None, device_rng=False, seed=0, occupancy=None, box=None,
+                             controls=None):
     """BASELINE config 4 for one view (or its pixel range [ray0, ray0+n_rays)) in ONE library call:
     device ray generation -> coarse pass (Nc stratified samples) -> sample_pdf -> fine pass on the
     Nc+Nf merged positions -> clip(rgb,0,1)  (nerf_amd_render_hierarchical_forward: four launches,
@@ -735,14 +763,28 @@ def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=1
     Parity unpinned (no reference counterpart).
     occupancy: an ``OccupancyGrid`` for both passes -- device ray generation, then the composition of
     ``render_hierarchical(..., occupancy=)``, then the clip (not one library call: two host reads, one per pass).
-    box: refused (RuntimeError before anything is drawn)."""
+    box: refused (RuntimeError before anything is drawn).
+    controls: a ``training.Controls`` with a background -- device ray generation, the composition of
+    ``render_hierarchical(..., controls=)`` on those rays (jitter ids from ``ray0``), then clip(rgb + (1 - acc) background,
+    0, 1) beside the fine disparity (the clip behind the blend).  Sigma noise / a distortion term: as ``render_hierarchical``.
+    Without it the dense call stays the one library call it is."""
     from .box import refuse_box
+    background = _pair_background(controls)
     refuse_box(box, "the coarse + fine pair (render_hierarchical_view)")
     dev = next(net_coarse.parameters()).device
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
     n = H * W - ray0 if n_rays is None else int(n_rays)
     if device_rng:
         u_c = u_f = None                 # this entry point's own rule (section 31): device_rng drops given uniforms
+    if background is not None:
+        bg = _background_arg(background, n, dev)                # its shape: before anything is drawn
+        _lib.require_shape(u_c, "u_c", (n, int(Nc)))
+        _lib.require_shape(u_f, "u_f", (n, int(Nf)))
+        rays = generate_rays(pose, cam_params, dev, ray0, n)
+        with torch.no_grad():
+            fine = render_hierarchical(rays, net_coarse, net_fine, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, precision=precision,
+                                       device_rng=device_rng, seed=seed, ray_id0=ray0, occupancy=occupancy)[0]
+        return _blend(fine[0], fine[3], fine[1], *bg, pixels=True)
     if occupancy is not None:
         from .occupancy import render_masked_pair
         Nc, Nf = int(Nc), int(Nf)

@@ -2,7 +2,7 @@
 """Register / LDS / spill numbers of the gfx950 kernels from the code object's own metadata (hipcc -S: the
 .amdhsa_* directives and the amdhsa.kernels YAML) -- what rocprofv3's trace columns do not report faithfully.
 
-    python tools/kernel_meta.py [source.hip ...] > profiles/r03_kernel_meta.txt
+    python tools/kernel_meta.py [source.hip[:-DFLAG] ...] > profiles/r03_kernel_meta.txt
 
 Dynamic LDS is requested at launch (csrc: LDS_TOTAL / LDS_TOTAL_COMP / LDS_BYTES) and is printed from the
 source constants the launchers use."""
@@ -61,7 +61,7 @@ def lane_moves(asm, mangled):
 
 
 def main():
-    srcs = [(a, []) for a in sys.argv[1:]] or DEFAULT
+    srcs = [(a.split(":")[0], a.split(":")[1:]) for a in sys.argv[1:]] or DEFAULT
     for src, defs in srcs:
         asm = assemble(src, defs)
         ks = list(kernels(asm))
