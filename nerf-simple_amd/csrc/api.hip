@@ -321,13 +321,7 @@ int nerf_amd_volume_render_mse_backward_pdf(const float* raw, const float* ts, c
                                             float* rgb, float* d_raw, float* ts_out, int64_t B, int Nc, int Nf,
                                             void* stream) {
     if (B < 0 || Nc <= 0 || Nf < 0) return NERF_AMD_EINVAL;
-    if (flags & ~(NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return NERF_AMD_EINVAL;
-    if (flags & NERF_AMD_SEED_IN_MEMORY) {
-        // `u` is the address of the 64-bit seed offset (the graphed step's hyper vector)
-        if (!(flags & NERF_AMD_DEVICE_RNG) || !u || (reinterpret_cast<uintptr_t>(u) & 7)) return NERF_AMD_EINVAL;
-    } else if (!(flags & NERF_AMD_DEVICE_RNG) && !u && Nf > 0) {
-        return NERF_AMD_EINVAL;
-    }
+    if (bad_pdf_jitter(flags, u, Nf)) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
     if (nerf_pdf::unsupported_sizes(Nc, Nf)) return NERF_AMD_EUNSUP;
     if (!raw || !ts || !rays || !target || !d_raw || !ts_out) return NERF_AMD_EINVAL;
@@ -344,8 +338,7 @@ int nerf_amd_sigma_noise(const float* raw, float* out, float std, uint32_t flags
     if (bad_sigma_noise(std, flags, seed_mem)) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
     if (!raw || !out) return NERF_AMD_EINVAL;
-    return nerf_amd_launch_sigma_noise(raw, out, std, seed, (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                                       ray_id0, B, N, S(stream));
+    return nerf_amd_launch_sigma_noise(raw, out, std, seed, noise_seed_mem(flags, seed_mem), ray_id0, B, N, S(stream));
 }
 
 int nerf_amd_background_blend(const float* rgb, const float* acc, const float* disp, const float* bg, int64_t bg_stride,
@@ -378,12 +371,11 @@ int nerf_amd_volume_render_mse_backward_bg(const float* raw, const float* ts, co
     if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
     const DenseHeadArgs a{.raw = raw, .ts = ts, .rays = rays, .target = target, .rgb = rgb, .d_raw = d_raw, .B = B, .N = N,
                           .bg = bg, .bg_stride = bg_stride, .std = std, .seed = seed,
-                          .seed_mem = (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                          .ray_id0 = ray_id0};
+                          .seed_mem = noise_seed_mem(flags, seed_mem), .ray_id0 = ray_id0};
     return nerf_amd_launch_dense_head(&a, S(stream));          // bg == NULL and std == 0: the plain head's launch
 }
 
-// The coarse head of the pair behind a background and / or with noise on sigma (composite_pair.hip).  Order of the rules: the
+// The coarse head of the pair behind a background and / or with noise on sigma (composite_head.hip).  Order of the rules: the
 // plain coarse head's (sizes; the sampler's jitter arguments), then the noise arguments and the background's stride, then the
 // plain head's again (the empty problem; the size limit, NERF_AMD_EUNSUP; the pointers).
 int nerf_amd_volume_render_mse_backward_pdf_bg(const float* raw, const float* ts, const float* rays, const float* target,
@@ -392,12 +384,7 @@ int nerf_amd_volume_render_mse_backward_pdf_bg(const float* raw, const float* ts
                                                uint64_t seed, int64_t ray_id0, float* rgb, float* d_raw, float* ts_out, int64_t B,
                                                int Nc, int Nf, void* stream) {
     if (B < 0 || Nc <= 0 || Nf < 0) return NERF_AMD_EINVAL;
-    if (flags & ~(NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return NERF_AMD_EINVAL;
-    if (flags & NERF_AMD_SEED_IN_MEMORY) {
-        if (!(flags & NERF_AMD_DEVICE_RNG) || !u || misaligned(u, 8)) return NERF_AMD_EINVAL;
-    } else if (!(flags & NERF_AMD_DEVICE_RNG) && !u && Nf > 0) {
-        return NERF_AMD_EINVAL;
-    }
+    if (bad_pdf_jitter(flags, u, Nf)) return NERF_AMD_EINVAL;
     if (bad_sigma_noise(std, noise_flags, seed_mem)) return NERF_AMD_EINVAL;
     if (bad_bg_stride(bg_stride)) return NERF_AMD_EINVAL;
     if (B == 0) return 0;
@@ -405,8 +392,7 @@ int nerf_amd_volume_render_mse_backward_pdf_bg(const float* raw, const float* ts
     if (!raw || !ts || !rays || !target || !d_raw || !ts_out) return NERF_AMD_EINVAL;
     const DenseHeadArgs a{.raw = raw, .ts = ts, .rays = rays, .target = target, .rgb = rgb, .d_raw = d_raw, .B = B, .N = Nc,
                           .bg = bg, .bg_stride = bg_stride, .std = std, .seed = noise_seed,
-                          .seed_mem = (noise_flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                          .ray_id0 = ray_id0};
+                          .seed_mem = noise_seed_mem(noise_flags, seed_mem), .ray_id0 = ray_id0};
     const DensePdfArgs p{u, ts_out, Nf, (flags & NERF_AMD_DEVICE_RNG) ? 1 : 0, (flags & NERF_AMD_SEED_IN_MEMORY) ? 1 : 0, seed};
     return nerf_amd_launch_dense_head_pdf(&a, &p, S(stream));  // bg == NULL and std == 0: the plain coarse head's launch
 }
@@ -441,8 +427,8 @@ int nerf_amd_volume_render_mse_backward_dist(const float* raw, const float* ts, 
     if (!raw || !ts || !rays || !target || !d_raw) return NERF_AMD_EINVAL;
     const DenseHeadArgs a{.raw = raw, .ts = ts, .rays = rays, .target = target, .rgb = rgb, .d_raw = d_raw, .B = B, .N = N,
                           .bg = bg, .bg_stride = bg_stride, .std = std, .seed = seed,
-                          .seed_mem = (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                          .ray_id0 = ray_id0, .dist = true, .t_far = t_far, .coef = coef, .loss_ray = loss_ray};
+                          .seed_mem = noise_seed_mem(flags, seed_mem), .ray_id0 = ray_id0, .dist = true, .t_far = t_far,
+                          .coef = coef, .loss_ray = loss_ray};
     return nerf_amd_launch_dense_head(&a, S(stream));
 }
 

@@ -40,6 +40,18 @@ inline bool bad_sigma_noise(float std, uint32_t flags, const uint64_t* seed_mem)
     if (flags & ~NERF_AMD_SEED_IN_MEMORY) return true;
     return (flags & NERF_AMD_SEED_IN_MEMORY) && (!seed_mem || misaligned(seed_mem, 8));
 }
+// the step offset a noise launch reads: `seed_mem` with NERF_AMD_SEED_IN_MEMORY, nothing without it
+inline const unsigned long long* noise_seed_mem(uint32_t flags, const uint64_t* seed_mem) {
+    return (flags & NERF_AMD_SEED_IN_MEMORY) ? reinterpret_cast<const unsigned long long*>(seed_mem) : nullptr;
+}
+// the jitter arguments of the dense coarse heads' sampler (nerf_amd_volume_render_mse_backward_pdf, .._pdf_bg): the uniforms
+// u[B, Nf], the counter RNG, or the counter RNG with its seed offset in device memory (then `u` is that 8-byte aligned address,
+// the graphed step's hyper vector).  No positions are given and no bins are needed, unlike bad_jitter.
+inline bool bad_pdf_jitter(uint32_t flags, const float* u, int Nf) {
+    if (flags & ~(NERF_AMD_DEVICE_RNG | NERF_AMD_SEED_IN_MEMORY)) return true;
+    if (flags & NERF_AMD_SEED_IN_MEMORY) return !(flags & NERF_AMD_DEVICE_RNG) || !u || misaligned(u, 8);
+    return !(flags & NERF_AMD_DEVICE_RNG) && !u && Nf > 0;
+}
 // the distortion term's scalars (nerf_amd_distortion_loss, nerf_amd_volume_render_mse_backward_dist): the far plane finite,
 // the coefficient finite and >= 0 (0 switches the term off: its gradient and loss values are zeros)
 inline bool bad_distortion(float t_far, float coef) {

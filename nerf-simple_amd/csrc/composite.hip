@@ -50,15 +50,12 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_kernel(
 constexpr int MAX_CHUNKS = nerf_layout::COMPOSITE_BWD_MAX_CHUNKS;          // N <= 512
 
 // The coarse training head (E > 0): the same kernel also places the fine pass's samples from the weights of its
-// forward sweep (sample_pdf_device.h).  The weights go from registers to the wave's LDS slice with the positions; the
-// sampler reads them there after the backward sweep, so neither ts nor w is read from HBM a second time.
-struct PdfHead {
-    const float* u;                    // u[B,Nf]; with seed_in_mem the DEVICE ADDRESS of the 64-bit seed offset
-    float* ts_out;                     // [B, Nc+Nf]
-    int Nf;
-    int device_rng;
-    int seed_in_mem;
-    unsigned long long seed;
+// forward sweep (sample_pdf_device.h sample_behind_walk).  The weights go from registers to the wave's LDS slice with the
+// positions; the sampler reads them there after the backward sweep, so neither ts nor w is read from HBM a second time.
+// The sampler's arguments (launchers.h) and the ray id of ray 0 are ONE kernel argument: as a scalar argument of its own the
+// ray id would be loaded at the kernel's entry, not beside the sampler's fields, and the kernel's text would move.
+struct CoarsePdf {
+    DensePdfArgs args;
     long long ray_id0;
 };
 
@@ -70,7 +67,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
     long long dirs_stride, const float* __restrict__ g_rgb, const float* __restrict__ g_disp,
     const float* __restrict__ g_alpha, const float* __restrict__ g_acc, const float* __restrict__ g_w,
     float* __restrict__ d_raw, long long B, int N, int normalize_dirs,
-    const float* __restrict__ mse_target, float* __restrict__ rgb_out, float mse_scale, PdfHead pdf) {
+    const float* __restrict__ mse_target, float* __restrict__ rgb_out, float mse_scale, CoarsePdf pdf) {
     constexpr int CHUNKS = E > 0 ? nerf_pdf::MAXC / 64 : MAX_CHUNKS;
     __shared__ nerf_pdf::WaveLds<(E > 0 ? E : 1)> s_pdf[E > 0 ? RAYS_PER_BLOCK : 1];
     __shared__ float s_pdf_w[E > 0 ? RAYS_PER_BLOCK : 1][nerf_pdf::MAXC];
@@ -94,16 +91,7 @@ __global__ __launch_bounds__(64 * RAYS_PER_BLOCK) void composite_backward_kernel
     if constexpr (E > 0) {
         nerf_composite::composite_backward_ray<CHUNKS>(src, mse, nerf_composite::PdfSink{s_pdf[wv].ts, s_pdf_w[wv]}, N, lane, dnorm,
                                                        ray, rout);
-        // the fine pass's positions from this ray's weights (nerf_amd_sample_pdf's body, same draws)
-        wave_lds_fence();
-        unsigned long long seed = pdf.seed;
-        if (pdf.seed_in_mem) {
-            const unsigned long long v = *reinterpret_cast<const unsigned long long*>(pdf.u);
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-            seed += ((unsigned long long)hi << 32) | lo;
-        }
-        nerf_pdf::sample_ray<E>(s_pdf[wv], s_pdf_w[wv], N, pdf.Nf, lane, pdf.u, pdf.device_rng != 0, seed, pdf.ray_id0, ray,
-                                pdf.ts_out + ray * (N + pdf.Nf));
+        nerf_pdf::sample_behind_walk<E>(s_pdf[wv], s_pdf_w[wv], N, lane, pdf.args, pdf.ray_id0, ray);
     } else if (mse_target) {
         nerf_composite::composite_backward_ray<CHUNKS>(src, mse, nerf_composite::NoSink{}, N, lane, dnorm, ray, rout);
     } else {
@@ -147,7 +135,7 @@ extern "C" int nerf_amd_launch_composite_backward(const float* raw, const float*
     const long long blocks = (B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
     hipLaunchKernelGGL(composite_backward_kernel<0>, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
                        raw, ts, dirs, dirs_stride, g_rgb, g_disp, g_alpha, g_acc, g_w, d_raw, B, N,
-                       normalize_dirs, nullptr, nullptr, 0.f, PdfHead{});
+                       normalize_dirs, nullptr, nullptr, 0.f, CoarsePdf{});
     return (int)hipGetLastError();
 }
 
@@ -161,7 +149,7 @@ extern "C" int nerf_amd_launch_composite_mse_backward(const float* raw, const fl
     const long long blocks = (B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK;
     hipLaunchKernelGGL(composite_backward_kernel<0>, dim3((unsigned)blocks), dim3(64 * RAYS_PER_BLOCK), 0, stream,
                        raw, ts, rays + 3, 6ll, nullptr, nullptr, nullptr, nullptr, nullptr, d_raw, B, N, 1,
-                       target, rgb, 1.0f / (3.0f * (float)B), PdfHead{});
+                       target, rgb, 1.0f / (3.0f * (float)B), CoarsePdf{});
     return (int)hipGetLastError();
 }
 
@@ -175,18 +163,12 @@ extern "C" int nerf_amd_launch_composite_mse_backward_pdf(const float* raw, cons
     if (B == 0) return 0;
     if (Nf < 0 || nerf_pdf::unsupported_sizes(Nc, Nf)) return -2;
     const dim3 grid((unsigned)((B + RAYS_PER_BLOCK - 1) / RAYS_PER_BLOCK)), block(64 * RAYS_PER_BLOCK);
-    const PdfHead pdf{u, ts_out, Nf, device_rng, seed_in_mem, seed, ray_id0};
+    const CoarsePdf pdf{{u, ts_out, Nf, device_rng, seed_in_mem, seed}, ray_id0};
     const float scale = 1.0f / (3.0f * (float)B);
-#define NERF_PDF_HEAD(E_)                                                                                             \
-    hipLaunchKernelGGL(composite_backward_kernel<E_>, grid, block, 0, stream, raw, ts, rays + 3, 6ll, nullptr, nullptr, \
-                       nullptr, nullptr, nullptr, d_raw, B, Nc, 1, target, rgb, scale, pdf)
-    switch (nerf_pdf::keys_per_lane(Nf)) {
-        case 1: NERF_PDF_HEAD(1); break;
-        case 2: NERF_PDF_HEAD(2); break;
-        case 4: NERF_PDF_HEAD(4); break;
-        default: NERF_PDF_HEAD(8); break;
-    }
-#undef NERF_PDF_HEAD
+    nerf_pdf::with_keys_per_lane(Nf, [&](auto e) {
+        hipLaunchKernelGGL(composite_backward_kernel<e()>, grid, block, 0, stream, raw, ts, rays + 3, 6ll, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, d_raw, B, Nc, 1, target, rgb, scale, pdf);
+    });
     return (int)hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
 // composite_backward_device.h -- the per-ray backward walk of the compositor, shared by its kernels:
-// composite_backward_kernel<E> (composite.hip, dense raw[B, N, 4]), dense_head_kernel (composite_head.hip, the dense head
-// with its optional terms) and masked_backward_kernel<Up, NOISE, E> (occupancy_train.hip, the masked samples: the five
-// gradients, or the MSE head under the capacity clamp -- alone, with the fine pass's sampler behind it, or with the dense
-// head's terms).
+// composite_backward_kernel<E> (composite.hip, dense raw[B, N, 4]), dense_head_kernel<.., E> (composite_head.hip, the dense
+// head with its optional terms) and masked_backward_kernel<Up, NOISE, E> (occupancy_train.hip, the masked samples: the five
+// gradients, or the MSE head under the capacity clamp, with the dense head's terms).  Behind each of the three the fine
+// pass's sampler may run in the same wave (E > 0: the coarse head of a pair).
 //
 // d loss / d raw given the upstream gradients of the five outputs.  With G_i = dL/dw_i gathered from every consumer of w,
 //   dL/dc_i     = w_i * g_rgb

@@ -4,7 +4,8 @@
 //   sigma'  = sigma + std z                 in front of the softplus (sigma_noise_device.h)
 //   rgb_bg  = rgb + (1 - acc) bg            two rounded ops per channel, no fma: torch's fp32 expression gives the same bits
 // Three small stages (noise, blend, the blend's backward).  The training head is BY DEFINITION their composition with the
-// compositor, the MSE gradient and the compositor's backward, in one launch: dense_head_kernel<NOISE, BG, ..> (composite_head.hip).
+// compositor, the MSE gradient and the compositor's backward, in one launch: dense_head_kernel<NOISE, BG, .., E>
+// (composite_head.hip; E > 0: the coarse head of the pair, the fine pass's sampler behind the same walk).
 #include "composite_device.h"
 #include "launchers.h"
 #include "sigma_noise_device.h"

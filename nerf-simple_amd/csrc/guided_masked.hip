@@ -89,17 +89,11 @@ extern "C" int nerf_amd_launch_sample_pdf_volume_masked(const MlpArgs* args, con
         const OccGrid og = occ_grid_args(bits, gx, gy, gz, g_lo, g_inv_step, outside_live);
         int* counts = occ_ws_counts(ws);
         const dim3 grid((unsigned)((B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
-        // keys per lane of the register sort: ceil_pow2(Nf) / 64 (nerf_pdf::keys_per_lane)
-#define GUIDED_MASKED_LAUNCH(E)                                                                                                  \
-    hipLaunchKernelGGL(guided_masked_kernel<E>, grid, block, 0, stream, *args, g, volume, og, u_f, ts_out, sigma_c, w_c, mask,   \
-                       counts, B, Nf)
-        switch (nerf_pdf::keys_per_lane(Nf)) {
-        case 1: GUIDED_MASKED_LAUNCH(1); break;
-        case 2: GUIDED_MASKED_LAUNCH(2); break;
-        case 4: GUIDED_MASKED_LAUNCH(4); break;
-        default: GUIDED_MASKED_LAUNCH(8); break;
-        }
-#undef GUIDED_MASKED_LAUNCH
+        // keys per lane of the register sort: ceil_pow2(Nf) / 64
+        nerf_pdf::with_keys_per_lane(Nf, [&](auto e) {
+            hipLaunchKernelGGL(guided_masked_kernel<e()>, grid, block, 0, stream, *args, g, volume, og, u_f, ts_out, sigma_c, w_c,
+                               mask, counts, B, Nf);
+        });
     }
     return nerf_amd_launch_occ_scan(ws, offsets, live, B, stream);
 }

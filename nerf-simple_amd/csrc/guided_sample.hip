@@ -70,13 +70,10 @@ extern "C" int nerf_amd_launch_sample_pdf_volume(const MlpArgs* args, const floa
     if (Nf < 0 || nerf_pdf::unsupported_sizes(Nc, Nf) || nx < 2 || ny < 2 || nz < 2) return -2;
     const SigmaVolume g = sigma_volume_args(nx, ny, nz, h_lo, h_inv_step);
     const dim3 grid((unsigned)((B + GUIDED_RAYS_PER_BLOCK - 1) / GUIDED_RAYS_PER_BLOCK)), block(64 * GUIDED_RAYS_PER_BLOCK);
-    // keys per lane of the register sort: ceil_pow2(Nf) / 64 (nerf_pdf::keys_per_lane)
-    switch (nerf_pdf::keys_per_lane(Nf)) {
-    case 1: hipLaunchKernelGGL(guided_sample_kernel<1>, grid, block, 0, stream, *args, g, volume, u_f, ts_out, sigma_c, w_c, B, Nf); break;
-    case 2: hipLaunchKernelGGL(guided_sample_kernel<2>, grid, block, 0, stream, *args, g, volume, u_f, ts_out, sigma_c, w_c, B, Nf); break;
-    case 4: hipLaunchKernelGGL(guided_sample_kernel<4>, grid, block, 0, stream, *args, g, volume, u_f, ts_out, sigma_c, w_c, B, Nf); break;
-    default: hipLaunchKernelGGL(guided_sample_kernel<8>, grid, block, 0, stream, *args, g, volume, u_f, ts_out, sigma_c, w_c, B, Nf); break;
-    }
+    // keys per lane of the register sort: ceil_pow2(Nf) / 64
+    nerf_pdf::with_keys_per_lane(Nf, [&](auto e) {
+        hipLaunchKernelGGL(guided_sample_kernel<e()>, grid, block, 0, stream, *args, g, volume, u_f, ts_out, sigma_c, w_c, B, Nf);
+    });
     return (int)hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 struct MlpArgs;          // nerf_device.h
 struct DensityArgs;
@@ -32,8 +33,9 @@ struct DenseHeadArgs {
     float* g_theta;                                    // and every ray's row of d loss / d theta [B,6]
 };
 
-// What the dense COARSE head of the pair reads beside DenseHeadArgs (composite_pair.hip): the fine pass's sampler, as the plain
-// coarse head takes it (composite.hip).  The sampler's ray ids start at DenseHeadArgs::ray_id0, as the noise's do.
+// The fine pass's sampler behind a dense walk (sample_pdf_device.h sample_behind_walk): what both dense coarse heads read beside
+// their own arguments -- composite_backward_kernel<E> (composite.hip), which takes the ray id of ray 0 beside it, and
+// dense_head_kernel<.., E> (composite_head.hip), where the ray ids start at DenseHeadArgs::ray_id0 as the noise's do.
 struct DensePdfArgs {
     const float* u;                                    // u[B,Nf]; with seed_in_mem the DEVICE ADDRESS of the 64-bit seed offset
     float* ts_out;                                     // [B, Nc+Nf]
@@ -84,6 +86,15 @@ inline MaskedBackwardArgs capped_head_args(const float* raw_live, const uint64_t
     b.B = B; b.capacity = capacity;
     b.target = gt; b.rgb = rgb;
     return b;
+}
+
+// The (NOISE, BG) ladder of the training heads' launchers (composite_head.hip, occupancy_train.hip), one of the two terms being
+// on: f is called once with the pair as std::bool_constant, e.g. with_noise_bg(noise, bg, [&](auto n, auto b) { ..<n(), b()>.. }).
+template <class F>
+inline void with_noise_bg(bool noise, bool bg, F&& f) {
+    if (!noise) f(std::false_type{}, std::true_type{});
+    else if (!bg) f(std::true_type{}, std::false_type{});
+    else f(std::true_type{}, std::true_type{});
 }
 
 extern "C" {
@@ -167,7 +178,6 @@ int nerf_amd_launch_occ_emit(const MlpArgs*, const unsigned long long*, const lo
 int nerf_amd_launch_occ_composite(const MlpArgs*, const unsigned long long*, const long long*, const float*, long long, hipStream_t);
 int nerf_amd_occ_train_max_n(void);
 int nerf_amd_launch_masked_backward(const MlpArgs*, const MaskedBackwardArgs*, hipStream_t);
-int nerf_amd_launch_masked_backward_pair(const MlpArgs*, const MaskedBackwardArgs*, hipStream_t);
 int nerf_amd_launch_occ_decay_max(float*, const float*, float, long long, hipStream_t);
 int nerf_amd_launch_sigma_noise(const float*, float*, float, unsigned long long, const unsigned long long*, long long, long long,
                                 int, hipStream_t);

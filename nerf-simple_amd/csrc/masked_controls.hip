@@ -12,7 +12,7 @@
 //       masked backward and head); this source holds its entry point, which fills the terms' fields of MaskedBackwardArgs.
 //
 //   the coarse head of the masked pair -- the same walk with the sampler behind it, masked_backward_kernel<LossHead<BG, false,
-//       false>, NOISE, E> (the second translation unit of occupancy_train.hip); its entry point is the last one below.
+//       false>, NOISE, E> (occupancy_train.hip likewise); its entry point is the last one below.
 //
 // No atomics; a row is written by exactly one lane, so two runs write the same bytes.  The three entry points below are the
 // C ABI themselves (argument checking included, api_checks.h).
@@ -90,9 +90,8 @@ extern "C" int nerf_amd_sigma_noise_masked(const float* raw_live, float* out, fl
     if (!mask || !offsets || misaligned(mask, 8) || misaligned(offsets, 8)) return NERF_AMD_EINVAL;
     if (!raw_live != !out || misaligned(raw_live, 16) || misaligned(out, 16)) return NERF_AMD_EINVAL;
     if (!raw_live) return 0;
-    return nerf_amd_launch_sigma_noise_masked(raw_live, out, std, seed,
-                                              (flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr,
-                                              ray_id0, reinterpret_cast<const unsigned long long*>(mask),
+    return nerf_amd_launch_sigma_noise_masked(raw_live, out, std, seed, noise_seed_mem(flags, seed_mem), ray_id0,
+                                              reinterpret_cast<const unsigned long long*>(mask),
                                               reinterpret_cast<const long long*>(offsets), B, N, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -123,7 +122,7 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward_dist(const float* raw_
     MaskedBackwardArgs b = capped_head_args(raw_live, mask, offsets, gt, rgb, d_raw_live, capacity, B);
     b.bg = bg; b.bg_stride = bg_stride;
     b.std = std; b.noise_seed = noise_seed;
-    b.seed_mem = (noise_flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr;
+    b.seed_mem = noise_seed_mem(noise_flags, seed_mem);
     b.t_far = t_far; b.coef = coef; b.loss_ray = loss_ray;
     return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
 }
@@ -159,6 +158,6 @@ extern "C" int nerf_amd_volume_render_masked_mse_backward_pdf_bg(const float* ra
     b.u_f = u_f; b.ts_out = ts_out; b.Nf = Nf;
     b.bg = bg; b.bg_stride = bg_stride;
     b.std = std; b.noise_seed = noise_seed;
-    b.seed_mem = (noise_flags & NERF_AMD_SEED_IN_MEMORY) ? (const unsigned long long*)seed_mem : nullptr;
+    b.seed_mem = noise_seed_mem(noise_flags, seed_mem);
     return nerf_amd_launch_masked_backward(&a, &b, reinterpret_cast<hipStream_t>(stream));
 }

@@ -8,8 +8,8 @@
 //       sample -- rank from popcounts of the mask words -- and (0, 0, 0, -inf) for a dead one.  A dead sample has
 //       softplus' = 0, alpha = 0 and w = 0 there: it receives nothing and adds exact zeros to the suffix sums.  The result is
 //       the rows at the kept samples of the dense backward on the overwritten raw, bit for bit.  No atomics: a row is written
-//       by exactly one lane, and two runs write the same bytes.  Thirteen instantiations here and twelve in this source's second
-//       translation unit (NERF_MASKED_PAIR, below), the combinations the launchers reach, on four axes:
+//       by exactly one lane, and two runs write the same bytes.  Twenty-five instantiations, the combinations the one launcher
+//       below reaches, on four axes:
 //         Up        FiveGrads: the five upstream gradients are given (nerf_amd_volume_render_masked_backward);
 //                   MseHead: g_rgb = 2 (rgb - gt) / (3 B) is formed from the sweep's own forward, and rgb is written
 //                   (the graphed steps' heads, occupancy_graph.hip; DESIGN.md sections 14, 15);
@@ -133,7 +133,6 @@ __global__ __launch_bounds__(MASKED_THREADS) void masked_backward_kernel(MlpArgs
     }
 }
 
-#ifndef NERF_MASKED_PAIR
 __global__ __launch_bounds__(256) void occ_decay_max_kernel(float* __restrict__ state, const float* __restrict__ sigma_now,
                                                             float decay, long long n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -144,36 +143,8 @@ __global__ __launch_bounds__(256) void occ_decay_max_kernel(float* __restrict__ 
         state[i] = (dcy != dcy) ? dcy : (sp != sp) ? sp : (dcy > sp ? dcy : sp);
     }
 }
-#endif
 
 }  // namespace
-
-#define MASKED_BACKWARD(...) hipLaunchKernelGGL((masked_backward_kernel<__VA_ARGS__>), grid, block, 0, stream, *args, b)
-
-#ifdef NERF_MASKED_PAIR
-// The second translation unit of this source (Makefile: build/occupancy_train_pair.o), as mlp_bf16_16.hip has one for fp16: the
-// twelve instantiations LossHead<BG, false, false> x NOISE x E of the masked COARSE head of the pair behind a background and /
-// or with noise and the launcher that reaches them, so the first unit holds the kernels it held.  `head`
-// comes checked and scaled from nerf_amd_launch_masked_backward below, which hands on to this for a sampler with a term.
-extern "C" int nerf_amd_launch_masked_backward_pair(const MlpArgs* args, const MaskedBackwardArgs* head, hipStream_t stream) {
-    const MaskedBackwardArgs b = *head;
-    const bool noise = b.std != 0.f, bg = b.bg != nullptr;
-    if (!b.ts_out || !b.target || b.coef != 0.f || !(noise || bg)) return -2;
-    const dim3 grid((unsigned)((b.B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
-#define MASKED_HEAD_PDF(NOISE_, BG_)                                                                       \
-    switch (nerf_pdf::keys_per_lane(b.Nf)) {                                                               \
-        case 1: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 1); break;            \
-        case 2: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 2); break;            \
-        case 4: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 4); break;            \
-        default: MASKED_BACKWARD(nerf_composite::LossHead<BG_, false, false>, NOISE_, 8); break;           \
-    }
-    if (!noise) MASKED_HEAD_PDF(false, true)
-    else if (!bg) MASKED_HEAD_PDF(true, false)
-    else MASKED_HEAD_PDF(true, true)
-#undef MASKED_HEAD_PDF
-    return (int)hipGetLastError();
-}
-#else
 
 extern "C" int nerf_amd_occ_train_max_n(void) { return OCCT_MAX_N; }
 
@@ -194,24 +165,19 @@ extern "C" int nerf_amd_launch_masked_backward(const MlpArgs* args, const Masked
     }
     b.scale = 1.0f / (3.0f * (float)b.B);
     const dim3 grid((unsigned)((b.B + MASKED_RAYS_PER_BLOCK - 1) / MASKED_RAYS_PER_BLOCK)), block(MASKED_THREADS);
-    if (b.ts_out && term) return nerf_amd_launch_masked_backward_pair(args, &b, stream);      // the coarse head with a term
-#define MASKED_HEAD(NOISE_, BG_, DIST_) MASKED_BACKWARD(nerf_composite::LossHead<BG_, DIST_, false>, NOISE_, 0)
+#define MASKED_BACKWARD(...) hipLaunchKernelGGL((masked_backward_kernel<__VA_ARGS__>), grid, block, 0, stream, *args, b)
+#define MASKED_HEAD(NOISE_, BG_, DIST_, E_) MASKED_BACKWARD(nerf_composite::LossHead<BG_, DIST_, false>, NOISE_, E_)
     if (!b.target) MASKED_BACKWARD(FiveGrads, false, 0);
-    else if (b.ts_out) switch (nerf_pdf::keys_per_lane(b.Nf)) {
-        case 1: MASKED_BACKWARD(MseHead, false, 1); break;
-        case 2: MASKED_BACKWARD(MseHead, false, 2); break;
-        case 4: MASKED_BACKWARD(MseHead, false, 4); break;
-        default: MASKED_BACKWARD(MseHead, false, 8); break;
-    }
+    else if (b.ts_out) nerf_pdf::with_keys_per_lane(b.Nf, [&](auto e) {        // the coarse head of a pair: term = noise || bg
+        if (!term) MASKED_BACKWARD(MseHead, false, e());
+        else with_noise_bg(noise, bg, [&](auto n, auto g) { MASKED_HEAD(n(), g(), false, e()); });
+    });
     else if (!term) MASKED_BACKWARD(MseHead, false, 0);
-    else if (!dist && !noise) MASKED_HEAD(false, true, false);
-    else if (!dist && !bg) MASKED_HEAD(true, false, false);
-    else if (!dist) MASKED_HEAD(true, true, false);
-    else if (!noise && !bg) MASKED_HEAD(false, false, true);
-    else if (!noise) MASKED_HEAD(false, true, true);
-    else if (!bg) MASKED_HEAD(true, false, true);
-    else MASKED_HEAD(true, true, true);
+    else if (dist && !noise && !bg) MASKED_HEAD(false, false, true, 0);
+    else if (dist) with_noise_bg(noise, bg, [&](auto n, auto g) { MASKED_HEAD(n(), g(), true, 0); });
+    else with_noise_bg(noise, bg, [&](auto n, auto g) { MASKED_HEAD(n(), g(), false, 0); });
 #undef MASKED_HEAD
+#undef MASKED_BACKWARD
     return (int)hipGetLastError();
 }
 
@@ -223,5 +189,4 @@ extern "C" int nerf_amd_launch_occ_decay_max(float* state, const float* sigma_no
     hipLaunchKernelGGL(occ_decay_max_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, state, sigma_now, decay, n);
     return (int)hipGetLastError();
 }
-#endif
-#undef MASKED_BACKWARD
+

@@ -43,10 +43,9 @@ extern "C" int nerf_amd_launch_sample_pdf(const float* ts, const float* w, const
     if (B == 0) return 0;
     if (Nf < 0 || nerf_pdf::unsupported_sizes(Nc, Nf)) return -2;
     const dim3 grid((unsigned)((B + RPB - 1) / RPB)), block(64 * RPB);
-    // keys per lane of the register sort: ceil_pow2(Nf) / 64 (nerf_pdf::keys_per_lane)
-    if (Nf <= 64) hipLaunchKernelGGL(sample_pdf_kernel<1>, grid, block, 0, stream, ts, w, u, out, B, Nc, Nf, seed, ray_id0, device_rng);
-    else if (Nf <= 128) hipLaunchKernelGGL(sample_pdf_kernel<2>, grid, block, 0, stream, ts, w, u, out, B, Nc, Nf, seed, ray_id0, device_rng);
-    else if (Nf <= 256) hipLaunchKernelGGL(sample_pdf_kernel<4>, grid, block, 0, stream, ts, w, u, out, B, Nc, Nf, seed, ray_id0, device_rng);
-    else hipLaunchKernelGGL(sample_pdf_kernel<8>, grid, block, 0, stream, ts, w, u, out, B, Nc, Nf, seed, ray_id0, device_rng);
+    // keys per lane of the register sort: ceil_pow2(Nf) / 64
+    nerf_pdf::with_keys_per_lane(Nf, [&](auto e) {
+        hipLaunchKernelGGL(sample_pdf_kernel<e()>, grid, block, 0, stream, ts, w, u, out, B, Nc, Nf, seed, ray_id0, device_rng);
+    });
     return (int)hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // sample_pdf_device.h -- the per-ray body of hierarchical sample placement (BASELINE config 4), shared by
-// sample_pdf.hip (positions and weights read from HBM) and the coarse training head in composite.hip (weights
-// handed over from the compositor's registers through the wave's LDS slice).  ABSENT from the reference
+// sample_pdf.hip (positions and weights read from HBM), the guided samplers and the coarse training heads (composite.hip,
+// composite_head.hip, occupancy_train.hip: weights handed over from the compositor's registers through the wave's LDS
+// slice; the two dense ones through sample_behind_walk below), and the launchers' Nf -> E dispatch.  ABSENT from the reference
 // (README.md:3, configs/lego.yaml:7): parity UNPINNED; the NeRF paper's sample_pdf over interior bins, checked
 // against oracle/nerf_oracle.sample_pdf.
 //
@@ -17,6 +18,7 @@
 // merged by rank: a coarse position lands at i + #{z < ts[i]}, a new one at j + #{ts <= z[j]} (two binary
 // searches per element).  Nc <= 256, Nf <= 512, Nc + Nf <= 512.
 #pragma once
+#include "launchers.h"
 #include "nerf_device.h"
 
 namespace nerf_pdf {
@@ -164,6 +166,35 @@ __device__ __forceinline__ void sample_ray(WaveLds<E>& s, const float* rw, int N
     wave_lds_fence();
     const int M = Nc + Nf;
     for (int i = lane; i < M; i += 64) out[i] = all[i];
+}
+
+// The sampler behind a dense walk of the same wave (composite_backward_kernel<E>, composite.hip; dense_head_kernel<.., E>,
+// composite_head.hip): the walk's PdfSink left the ray's positions in s.ts and its weights in rw, both LDS.  Fences them,
+// resolves a seed whose offset is held in device memory (p.seed_in_mem: p.u is its address) and places the samples --
+// nerf_amd_sample_pdf's body, same draws.
+template <int E>
+__device__ __forceinline__ void sample_behind_walk(WaveLds<E>& s, const float* rw, int Nc, int lane, const DensePdfArgs& p,
+                                                   long long ray_id0, long long ray) {
+    wave_lds_fence();
+    unsigned long long seed = p.seed;
+    if (p.seed_in_mem) {
+        const unsigned long long v = *reinterpret_cast<const unsigned long long*>(p.u);
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+        seed += ((unsigned long long)hi << 32) | lo;
+    }
+    sample_ray<E>(s, rw, Nc, p.Nf, lane, p.u, p.device_rng != 0, seed, ray_id0, ray, p.ts_out + ray * (Nc + p.Nf));
+}
+
+// Host: Nf -> the compile-time E of a launch, the one place keys_per_lane is switched over.  f is called once with
+// std::integral_constant<int, E>, e.g. with_keys_per_lane(Nf, [&](auto e) { launch(kernel<e()>) ... });
+template <class F>
+inline void with_keys_per_lane(int Nf, F&& f) {
+    switch (keys_per_lane(Nf)) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 8>{}); break;
+    }
 }
 
 }  // namespace nerf_pdf

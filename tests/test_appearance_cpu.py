@@ -284,8 +284,9 @@ def _scratch_of(source):
 
 
 def test_appearance_kernels_use_no_scratch():
-    """For gfx950: csrc/appearance.hip is the four stages, and csrc/composite_head.hip exactly the eight instantiations
-    (NOISE, BG, DIST, AFFINE) of the dense head the entry points reach, the affine one among them; none with a byte of
+    """For gfx950: csrc/appearance.hip is the four stages, and csrc/composite_head.hip exactly the instantiations
+    (NOISE, BG, DIST, AFFINE, E) of the dense head the entry points reach -- the eight without a sampler (E = 0), the affine one
+    among them, and the twelve of the pair's coarse head, (NOISE, BG) with a term on at E = 1, 2, 4, 8 --; none with a byte of
     scratch (the head keeps its 8 chunks of per-sample state and the six floats of the ray's row in registers)."""
     if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("hipcc not available")
@@ -297,8 +298,11 @@ def test_appearance_kernels_use_no_scratch():
     want = {flags(0, 1, 0, 0), flags(1, 0, 0, 0), flags(1, 1, 0, 0),         # background and noise
             flags(0, 0, 1, 0), flags(0, 1, 1, 0), flags(1, 0, 1, 0), flags(1, 1, 1, 0),      # with the distortion term
             flags(0, 0, 0, 1)}                                               # the affine head
-    got = {re.search(r"dense_head_kernel<([^>]*)>", n).group(1) for n in heads}
-    assert len(heads) == 8 and got == want, heads
+    got = [re.search(r"dense_head_kernel<([^>]*)>", n).group(1) for n in heads]
+    assert {g[:-len(", 0")] for g in got if g.endswith(", 0")} == want, heads
+    assert {g for g in got if not g.endswith(", 0")} == \
+        {f"{flags(n, b, 0, 0)}, {e}" for n, b in ((0, 1), (1, 0), (1, 1)) for e in (1, 2, 4, 8)}, heads
+    assert len(heads) == 20 and len(set(got)) == 20, heads
     assert set(heads.values()) == {0}, heads
-    affine = [n for n in heads if f"<{flags(0, 0, 0, 1)}>" in n]
+    affine = [n for n in heads if f"<{flags(0, 0, 0, 1)}, 0>" in n]
     assert len(affine) == 1 and heads[affine[0]] == 0, heads

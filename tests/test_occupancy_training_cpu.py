@@ -243,11 +243,13 @@ def test_new_kernels_pass_the_static_isa_checks():
     """tools/check_vmcnt.py on csrc/occupancy_train.hip (tests/static_isa.py): no counted vmcnt wait is short, no wide store
     has its data registers overwritten by the next instruction, no atomic.  The source holds the six plain instantiations of
     the masked compositor backward -- the eager backward's is (FiveGrads, 0) --, the seven of the head with a training control
-    on (noise, background, distortion; no sampler), and occ_decay_max_kernel, and nothing else."""
+    on (noise, background, distortion; no sampler), the twelve of the pair's coarse head with a control on (noise, background;
+    the sampler at E = 1, 2, 4, 8), and occ_decay_max_kernel, and nothing else."""
     import static_isa
     kernels = static_isa.checked_kernels("occupancy_train.hip")
     assert static_isa.masked_backward_instantiations(kernels) == \
         [("FiveGrads", 0), ("MseHead", 0), ("MseHead", 1), ("MseHead", 2), ("MseHead", 4), ("MseHead", 8)], list(kernels)
     assert static_isa.masked_term_instantiations(kernels) == \
-        [(n, b, d, 0) for n in (0, 1) for b in (0, 1) for d in (0, 1) if n or b or d], list(kernels)
-    assert len(kernels) == 14 and sum("occ_decay_max_kernel" in k for k in kernels) == 1, list(kernels)
+        sorted([(n, b, d, 0) for n in (0, 1) for b in (0, 1) for d in (0, 1) if n or b or d] +
+               [(n, b, 0, e) for n, b in ((0, 1), (1, 0), (1, 1)) for e in (1, 2, 4, 8)]), list(kernels)
+    assert len(kernels) == 26 and sum("occ_decay_max_kernel" in k for k in kernels) == 1, list(kernels)

@@ -1,4 +1,4 @@
-"""The training controls of the coarse + fine pair without a GPU (csrc/composite_pair.hip, csrc/masked_controls.hip,
+"""The training controls of the coarse + fine pair without a GPU (csrc/composite_head.hip, csrc/masked_controls.hip,
 training.train_step_hierarchical / the two graphed pair steppers / rendering.render_hierarchical[_view] with ``controls=``;
 DESIGN.md section 35): the exports and prototypes of the two coarse heads, their argument rules call by call
 (tests/golden/abi_refusals_pair_controls.json, written from the rules in include/nerf_amd.h: every call is refused or is an empty
@@ -80,12 +80,37 @@ def test_exports_header_and_ctypes_agree(lib):
     sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
     assert sum(t.count("int nerf_amd_launch_dense_head_pdf(") for t in sources.values()) == 2          # declaration + definition
     assert "int nerf_amd_launch_dense_head_pdf(" in sources["launchers.h"]
-    pair = sources["composite_pair.hip"]
+    pair = sources["composite_head.hip"]
     assert pair.count("__global__") == 1 and "composite_backward_ray<" in pair and "nerf_noise::Noisy<" in pair
-    assert "PdfSink" in pair and "sample_ray<E>" in pair and "philox" not in pair and "atomicAdd" not in pair
-    assert "composite_pair.hip" in open(os.path.join(csrc, "Makefile")).read()
+    assert "PdfSink" in pair and "philox" not in pair and "atomicAdd" not in pair
+    # the sampler is reached through the routine the plain coarse head shares, and only there
+    assert "sample_behind_walk<E>" in pair and "sample_behind_walk<E>" in sources["composite.hip"]
+    assert "sample_ray<E>" in sources["sample_pdf_device.h"] and "void sample_behind_walk(" in sources["sample_pdf_device.h"]
+    assert "sample_ray<" not in pair and "sample_ray<" not in sources["composite.hip"]
+    # the old layout is gone: no source, Makefile rule or comment under csrc/ names it
+    everything = dict(sources, Makefile=open(os.path.join(csrc, "Makefile")).read())
+    assert "composite_head.hip" in everything["Makefile"] and not os.path.exists(os.path.join(csrc, "composite_pair.hip"))
+    for f, text in everything.items():
+        assert "composite_pair.hip" not in text and "NERF_MASKED_PAIR" not in text, f
     walk = sources["occupancy_train.hip"]
     assert "E == 0 || (Up::MSE && !Up::DIST && !Up::AFFINE)" in walk
+
+
+def test_keys_per_lane_is_switched_over_once():
+    """Nf -> the compile-time E of a launch is one host helper (sample_pdf_device.h with_keys_per_lane): under csrc/ a
+    `switch` over keys_per_lane( occurs exactly once, there, and every launcher with a sampler goes through the helper (the
+    masked walk's once for its plain and its term heads)."""
+    csrc = os.path.join(ROOT, "nerf-simple_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    switches = {f: len(re.findall(r"\bswitch\s*\([^)]*keys_per_lane\(", t)) for f, t in sources.items()}
+    assert {f: n for f, n in switches.items() if n} == {"sample_pdf_device.h": 1}, switches
+    helper = sources["sample_pdf_device.h"]
+    assert helper.index("void with_keys_per_lane(") < helper.index("switch (keys_per_lane(")
+    calls = {f: t.count("with_keys_per_lane(") for f, t in sources.items() if f.endswith(".hip")}
+    assert {f: n for f, n in calls.items() if n} == {"composite.hip": 1, "composite_head.hip": 1, "occupancy_train.hip": 1,
+                                                     "sample_pdf.hip": 1, "guided_sample.hip": 1, "guided_masked.hip": 1}, calls
+    # no other ladder over the four buckets: a kernel's E is never spelled as a literal 1, 2, 4 or 8 at a launch
+    assert not [f for f, t in sources.items() if re.search(r"_kernel<[^>;]*\b[1248]>\)?, grid", t)], sources.keys()
 
 
 def test_fixture_covers_every_rule():

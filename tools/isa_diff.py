@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do the kernels of the working tree compile to the machine code of another commit?
 
-    python tools/isa_diff.py [--base REV] [--show N] [--map OLD=NEW ...] [file.hip[:-DFLAG] ...] > profiles/<name>_isa_diff.txt
+    python tools/isa_diff.py [--base REV] [--show N] [--map OLD=NEW ...] [[base:]file.hip[:-DFLAG] ...] > profiles/<name>_isa_diff.txt
 
 For a change that only moves source around (a shared header, a renamed helper) the proof that nothing happened to a
 kernel is that its instructions did not change.  The tool exports nerf-simple_amd/csrc and include/ of REV (default
@@ -12,7 +12,9 @@ compares the instruction text kernel by kernel after normalisation:
   * local labels (.LBB<f>_<n>, ...) are renumbered in order of first appearance;
   * kernel symbol names are NOT normalised: a kernel must keep its name, unless --map OLD=NEW (regular expression and
     replacement, applied to the base's symbols; repeatable) says how it was renamed.  A mapped kernel is looked up in
-    every listed file of the working tree, so it may have moved to another source.
+    every listed file of the working tree, so it may have moved to another source.  A file or flag set that the working
+    tree no longer has is listed as base:file.hip[:-DFLAG]: it is assembled from the base alone, and every kernel of it has
+    to be mapped into a listed file of the working tree.
 One line per kernel: instruction count, MFMA count, identical yes / no; --show N prints the first N differing lines of a
 kernel that is not identical.  Exit status 1 when any kernel differs, is missing or is new.  Needs hipcc and git; no GPU.
 """
@@ -54,6 +56,10 @@ def count(lines):
 
 
 def kernels(tree, src, flags):
+    if src.startswith("base:"):
+        if tree == ROOT:
+            return {}
+        src = src[len("base:"):]
     asm = check_vmcnt.assemble(os.path.join(tree, CSRC, src), flags)
     return {k: normalise(v) for k, v in check_vmcnt.kernels_of(asm).items()}
 
@@ -67,7 +73,7 @@ def main():
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("files", nargs="*", default=DEFAULT)
     args = ap.parse_args()
-    jobs = [(f.split(":")[0], tuple(f.split(":")[1:])) for f in args.files]
+    jobs = [(f.split(":-")[0], tuple("-" + x for x in f.split(":-")[1:])) for f in args.files]
     rc = 0
     with tempfile.TemporaryDirectory() as base:
         tar = subprocess.run(["git", "-C", ROOT, "archive", args.base, CSRC, "include"], check=True, stdout=subprocess.PIPE).stdout
@@ -81,7 +87,7 @@ def main():
                     to = name
                     for rule in args.map:
                         to = re.sub(*rule.split("=", 1), to)
-                    if to != name:
+                    if to != name or src.startswith("base:"):
                         old[to] = old.pop(name)
                         moved[to] = None
             for key in moved:

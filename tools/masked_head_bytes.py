@@ -4,7 +4,9 @@
     python tools/masked_head_bytes.py --parent /path/to/other/libnerf_amd.so > profiles/<name>_bytes.txt
 
 Both libraries are loaded with ctypes in one process and the four entry points that run the masked compositor's backward walk
-(csrc/occupancy_train.hip) are called on the same inputs, so that all thirteen instantiations of the kernel run:
+(csrc/occupancy_train.hip) are called on the same inputs, so that thirteen of the kernel's twenty-five instantiations run (the
+other twelve, the pair's coarse head with a control on, are compared with their chain of stages bit for bit by
+tests/test_gpu_pair_controls.py):
   nerf_amd_volume_render_masked_backward           the five gradients, all given
   nerf_amd_volume_render_masked_mse_backward       the MSE head under the clamp
   nerf_amd_volume_render_masked_mse_backward_pdf   ... with the sampler, Nf = 3, 64, 128, 256 and 512 - N (keys per lane 1, 1, 2,
