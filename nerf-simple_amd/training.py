@@ -29,7 +29,10 @@ the reference's autograd to 1e-5; long dW / db reductions are summed with float 
 import torch
 
 from . import _lib
-from .utils.rendering import _check_guided
+from .utils import controls as controls_mod
+from .utils.controls import FINE_NOISE_OFFSET, Background as _Background, Controls       # noqa: F401  (the public names)
+from .utils.jitter import tbins as _tbins
+from .utils.rendering import ALL_OUTPUTS, _check_guided, _five_outputs, _render_generic, _render_nerf, sample_pdf
 
 
 def img_mse(gt, pred):
@@ -83,11 +86,6 @@ def mse_loss(pred, target):
 # --------------------------------------------------------------------------
 # compositor with a HIP backward
 # --------------------------------------------------------------------------
-def _five_outputs(B, N, dev):
-    """rgb [B,3], disp [B], alpha [B,N], acc [B], w [B,N]: the compositor's outputs, in its order"""
-    return tuple(torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((B, 3), (B,), (B, N), (B,), (B, N)))
-
-
 def _grad_arg(g):
     """An upstream gradient as the backward kernels take it: fp32 contiguous, or None for a missing or empty one"""
     return None if (g is None or g.numel() == 0) else g.contiguous().float()
@@ -102,7 +100,7 @@ class _VolumeRender(torch.autograd.Function):
         B, N = raw.shape[0], raw.shape[1]
         dev = raw.device
         raw, ts, dirs = raw.contiguous(), ts.contiguous(), dirs.contiguous()
-        rgb, disp, alpha, acc, w = _five_outputs(B, N, dev)
+        rgb, disp, alpha, acc, w = _five_outputs(B, N, ALL_OUTPUTS, dev)
         if from_rays:
             _lib.launch("nerf_amd_volume_render_rays", raw, ts, dirs, rgb, disp, alpha, acc, w, B, N, dev=dev)
         else:
@@ -157,67 +155,26 @@ class _SigmaNoise(torch.autograd.Function):
         return g, None, None, None
 
 
-class _Background(torch.autograd.Function):
-    """(rgb [B,3], acc [B]) -> rgb_bg = rgb + (1 - acc) bg (nerf_amd_background_blend); backward: g_rgb passes through,
-    g_acc from nerf_amd_background_blend_backward -- autograd adds it to whatever else reaches acc, and the sum enters
-    the compositor's backward, which already takes g_acc.  ``bg`` [3] (stride 0) or [B,3] (stride 3) carries no gradient."""
-
-    @staticmethod
-    def forward(ctx, rgb, acc, bg, stride):
-        from .utils.rendering import _blend
-        rgb, acc = rgb.contiguous(), acc.contiguous()
-        ctx.save_for_backward(bg)
-        ctx.stride = stride
-        return _blend(rgb, acc, None, bg, stride)
-
-    @staticmethod
-    def backward(ctx, g):
-        (bg,) = ctx.saved_tensors
-        g = g.contiguous().float()
-        B, dev = g.shape[0], g.device
-        g_acc = torch.empty((B,), dtype=torch.float32, device=dev)
-        _lib.launch("nerf_amd_background_blend_backward", g, bg, ctx.stride, g_acc, B, dev=dev)
-        return g, g_acc, None, None
-
-
-def composite_with_controls(raw, ts, dirs, from_rays, controls, ray_id0=0):
-    """_VolumeRender with the training controls around it.  ``controls`` = (bg, stride, sigma_noise, noise_seed) or None."""
-    if controls is None:
-        out = _VolumeRender.apply(raw, ts, dirs, from_rays)
-        out[4].ts = ts                # the positions the weights belong to: what a distortion term on w needs beside it
-        return out
-    bg, stride, std, noise_seed = controls
-    if std:
-        raw = _SigmaNoise.apply(raw, std, noise_seed, ray_id0)
-    out = _VolumeRender.apply(raw, ts, dirs, from_rays)
-    out[4].ts = ts
-    if bg is not None:
-        out = (_Background.apply(out[0], out[3], bg, stride),) + tuple(out[1:])
+def composite_with_controls(raw, ts, dirs, from_rays, c, masked=None):
+    """The one place the controls are applied with gradients: noise on the raw density -> the compositor -> ``w.ts`` = the sample
+    positions (what a distortion term on w needs beside it) -> the blend.  ``c``: a ``Resolved`` or None.
+    Two heads.  Dense: _VolumeRender(raw [B,N,4], ts, dirs, from_rays) behind _SigmaNoise.  Masked (``masked`` = the (head, B, N) of
+    _MaskedVolumeRender): raw is raw_live [P',4], the noise is _MaskedSigmaNoise's, and ``ts`` is None (``w.ts`` is not set) or a
+    callable that forms the positions, called behind the compositor."""
+    if c is not None and c.std:
+        raw = (_SigmaNoise.apply(raw, c.std, c.noise_seed, c.noise_ray_id0) if masked is None else
+               _MaskedSigmaNoise.apply(raw, c.std, c.noise_seed, c.noise_ray_id0, masked[0][6:8] + masked[1:]))
+    out = _VolumeRender.apply(raw, ts, dirs, from_rays) if masked is None else _MaskedVolumeRender.apply(raw, *masked)
+    if ts is not None:
+        out[4].ts = ts() if callable(ts) else ts
+    if c is not None and c.bg is not None:
+        out = (_Background.apply(out[0], out[3], c.bg, c.stride),) + tuple(out[1:])
     return out
 
 
 # --------------------------------------------------------------------------
 # the distortion loss on the compositor's weights (DESIGN.md section 25)
 # --------------------------------------------------------------------------
-def _check_distortion(distortion):
-    """``distortion=`` as a weight: a finite float >= 0 (0 = off), else ValueError."""
-    import math
-    lam = float(distortion)
-    if not (lam >= 0.0) or math.isinf(lam):
-        raise ValueError(f"distortion is the weight of the distortion loss: finite and >= 0, got {distortion!r}")
-    return lam
-
-
-def _refuse_distortion(lam, **paths):
-    """The masked, hierarchical and sharded paths do not know the term: refused before any launch and any RNG draw."""
-    if not lam:
-        return
-    for name, v in paths.items():
-        if v is not None:
-            raise RuntimeError(f"distortion serves the dense and guided steps only: not with {name} (train without the term, "
-                               "or on the dense path)")
-
-
 def _distortion_launch(w, ts, t_far, coef, want_loss, want_grad):
     """nerf_amd_distortion_loss on w [B,N], ts [B,N]: (coef D per ray [B], coef dD/dw [B,N]); the reference's empty sample
     axis (w [B,0] at N == 1) has D = 0 and no gradient."""
@@ -287,85 +244,6 @@ def _distortion_term(w, ts, lam, tn, tf):
     if ts is None:
         raise RuntimeError("distortion: this render did not hand back its sample positions (the net does not train)")
     return _DistortionTerm.apply(w, ts.detach(), float(tf), _distortion_coef(lam, ts.shape[0], tn, tf))
-
-
-# --------------------------------------------------------------------------
-# the three terms as ONE argument: what the masked steps take, and the dense ones beside their flat keywords
-# --------------------------------------------------------------------------
-class Controls:
-    """``Controls(background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0)``: the training controls as one frozen value --
-    a background colour ([3], or one per ray [B,3]) behind the volume, the standard deviation of Gaussian noise on the raw
-    density with the counter RNG's ``noise_seed``, and the weight of the distortion loss (``train_step`` describes each).
-    Validated here as the flat keywords are (ValueError for a negative or non-finite ``sigma_noise`` / ``distortion``); the
-    background's shape is checked where the number of rays is known.  ``controls=`` is the one keyword the masked steps take
-    them through; on the dense steps it is the equivalent of the flat keywords, so a grid can be toggled without respelling
-    the call."""
-
-    __slots__ = ("background", "sigma_noise", "noise_seed", "distortion")
-
-    def __init__(self, background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0):
-        from .utils.rendering import _check_sigma_noise
-        set_ = object.__setattr__
-        set_(self, "background", background)
-        set_(self, "sigma_noise", _check_sigma_noise(sigma_noise))
-        set_(self, "noise_seed", int(noise_seed))
-        set_(self, "distortion", _check_distortion(distortion))
-
-    def __setattr__(self, name, value=None):
-        raise AttributeError(f"Controls is frozen: build a new one to change {name!r}")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self):
-        return (f"Controls(background={self.background!r}, sigma_noise={self.sigma_noise!r}, noise_seed={self.noise_seed!r}, "
-                f"distortion={self.distortion!r})")
-
-    def replace(self, **changes):
-        """A new Controls with some fields changed."""
-        return Controls(**{**{n: getattr(self, n) for n in self.__slots__}, **changes})
-
-
-def _controls_arg(controls, *, background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0):
-    """``controls=`` of an entry point: None, or a Controls -- TypeError for anything else, ValueError where the flat keywords of
-    the same call (passed on here by those entry points that have them) say something too."""
-    if controls is None:
-        return None
-    if not isinstance(controls, Controls):
-        raise TypeError(f"controls must be a training.Controls (or None), got {type(controls).__name__}")
-    if background is not None or sigma_noise or noise_seed or distortion:
-        raise ValueError("controls= and the flat keywords background / sigma_noise / noise_seed / distortion say the same thing: "
-                         "give one of the two")
-    return controls
-
-
-# The coarse + fine pair (DESIGN.md section 35): both passes draw their sigma noise with ``controls.sigma_noise``, the coarse one
-# under ``noise_seed``, the fine one under (noise_seed + FINE_NOISE_OFFSET) mod 2^64.  The noise counter is (ray_id0 + ray) N + i
-# with N = Nc or Nc + Nf: under ONE key the two passes would share words across different rays.  A graphed stepper adds its step
-# count to the seed, which never crosses 2^63.
-FINE_NOISE_OFFSET = 1 << 63
-
-
-def _pair_controls(controls, what):
-    """``controls=`` of a coarse + fine entry point, the FIRST thing it looks at: None, or a Controls (TypeError) whose
-    distortion term is off (RuntimeError, before any look at the networks, the optimiser, the grid or the generator) -- the
-    regulariser belongs on the final weights, not on what places the samples.  -> (coarse Controls, fine Controls), or None
-    where nothing is on."""
-    controls = _controls_arg(controls)
-    if controls is None:
-        return None
-    if controls.distortion > 0:
-        raise RuntimeError(f"controls= brings the background and the sigma noise to {what}: the distortion term "
-                           "(controls.distortion) is not offered on the coarse + fine pair")
-    if controls.background is None and not controls.sigma_noise:
-        return None
-    return controls, controls.replace(noise_seed=(controls.noise_seed + FINE_NOISE_OFFSET) % (1 << 64))
-
-
-def _refuse_bundle(controls, what):
-    """The paths ``controls=`` does not reach yet: refused before any launch and any RNG draw."""
-    if controls is not None:
-        _controls_arg(controls)
-        raise RuntimeError(f"controls= serves the dense and the masked single-network steps: not {what}")
 
 
 # --------------------------------------------------------------------------
@@ -487,27 +365,25 @@ def nerf_forward_autograd(net, v, precision):
     return raw.reshape(-1, 4)
 
 
-def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0, controls=None):
+def render_nerf_autograd(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0, c=None):
     """render_nerf (reference utils/rendering.py:13-45) with gradients to the
     parameters of ``net`` and, when ``rays`` requires grad, to the rays; returns the same 5-tuple.
-    ``controls``: the background / sigma noise of ``composite_with_controls``, None = neither."""
-    from .utils.rendering import _tbins
+    ``c``: the ``Resolved`` controls of ``composite_with_controls``, None = none."""
     if _lib.precision_code(precision) == _lib.F32:
         # exact fp32: the reference's own composition (sampling -> net.forward -> volume_render), each stage a HIP kernel
         from .utils import generic_mlp
-        from .utils.rendering import ALL_OUTPUTS, _render_generic
 
         class _Exact:
             @staticmethod
             def forward(q):
                 return generic_mlp.forward(net, q)
 
-        return _render_generic(rays, _Exact, N, tn, tf, jit, flags, ALL_OUTPUTS, seed, ray_id0, controls)
+        return _render_generic(rays, _Exact, N, tn, tf, jit, flags, ALL_OUTPUTS, seed, ray_id0, c)
     dev = rays.device
     params = [p for _, p in net.named_parameters()]
     raw, ts = _FusedDense.apply(net, rays, jit, _tbins(tn, tf, N, dev), flags, seed, ray_id0, N, None, *params)
     # the compositor's |d_hat| factor carries no gradient (|d_hat| == 1): the rays enter it detached
-    return composite_with_controls(raw, ts, rays.detach(), True, controls, ray_id0)
+    return composite_with_controls(raw, ts, rays.detach(), True, c)
 
 
 # --------------------------------------------------------------------------
@@ -522,7 +398,7 @@ class _MaskedVolumeRender(torch.autograd.Function):
         rays, jit, tbins, flags, seed, ray_id0, mask, offsets = head
         dev = rays.device
         raw_live = raw_live.contiguous()
-        rgb, disp, alpha, acc, w = _five_outputs(B, N, dev)
+        rgb, disp, alpha, acc, w = _five_outputs(B, N, ALL_OUTPUTS, dev)
         _lib.launch("nerf_amd_volume_render_masked", raw_live if raw_live.numel() else None, rays, jit, tbins, flags, int(seed),
                     int(ray_id0), mask, offsets, rgb, disp, alpha, acc, w, B, N, dev=dev)
         ctx.save_for_backward(raw_live, rays, jit, tbins, mask, offsets)
@@ -579,12 +455,12 @@ class _ZeroParamGrads(torch.autograd.Function):
         return tuple(torch.zeros_like(p) for p in ctx.like)
 
 
-def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, mark=None, controls=None):
+def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, mark=None, c=None):
     """The stages of ``render_nerf_masked`` once rays and jitter are settled: mark (or ``mark``, the ready MarkResult of these
     positions: the masked guided placement produces it with them) -> emit -> training forward on the live points -> masked
     compositor, with gradients.  Sets ``occupancy.last_stats``.
-    ``controls`` = (bg, stride, sigma_noise, noise_seed, ray id of the first ray) or None: the noise stage on the live rows in
-    front of the compositor, the blend behind it, and the sample positions attached to the weights as ``w.ts``."""
+    ``c``: the ``Resolved`` controls or None: the noise stage on the live rows in front of the compositor, the blend behind it,
+    and the sample positions attached to the weights as ``w.ts`` (``composite_with_controls``)."""
     from .utils import occupancy as occ_mod
     B = rays.size(0)
     m = occ_mod._mark(occupancy, rays, jit, tbins, flags, seed, ray_id0, N) if mark is None else mark
@@ -601,25 +477,9 @@ def _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, m
         stats["network_launches"] = 1
     else:
         raw_live = _ZeroParamGrads.apply(*params)
-    if controls is None:
-        return _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
-    bg, stride, std, noise_seed, noise_ray_id0 = controls
-    if std:
-        raw_live = _MaskedSigmaNoise.apply(raw_live, std, noise_seed, noise_ray_id0, (m.mask, m.offsets, B, N))
-    out = _MaskedVolumeRender.apply(raw_live, (rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N)
-    out[4].ts = occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
-    if bg is not None:
-        out = (_Background.apply(out[0], out[3], bg, stride),) + tuple(out[1:])
-    return out
-
-
-def _masked_controls(controls, B, dev, ray_id0):
-    """A Controls as ``_masked_outputs`` takes it (None passes); the distortion term is the step's, not the render's."""
-    if controls is None:
-        return None
-    from .utils.rendering import _background_arg
-    bg = (None, 0) if controls.background is None else _background_arg(controls.background, B, dev)
-    return (*bg, controls.sigma_noise, controls.noise_seed, int(ray_id0))
+    positions = None if c is None else lambda: occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
+    return composite_with_controls(raw_live, positions, None, None, c,
+                                   masked=((rays, jit, tbins, flags, seed, ray_id0, m.mask, m.offsets), B, N))
 
 
 def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0,
@@ -641,19 +501,29 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     ``box``: a ``SceneBox`` (utils/box.py) -- the samples are placed inside the box (``box.positions`` with this call's jitter
     arguments, formed once where the jitter would be drawn) and the call goes on as its ``ts=`` path; the positions carry no
     gradient.  Together with ``ts=``: ValueError."""
-    from .utils import box as box_mod, jitter, occupancy as occ_mod
-    box_mod.check_box(box, ts=ts)
-    controls = _controls_arg(controls)
+    from .utils.box import check_box
+    check_box(box, ts=ts)
+    controls = controls_mod.bundle(controls)
     if controls is not None and controls.distortion:
         raise ValueError("render_nerf_masked renders: the distortion term belongs to the step (train_step(..., occupancy=, "
                          "controls=), or distortion_loss on the weights it returns)")
+    return _render_nerf_masked(rays, net, N, occupancy, tn, tf, controls, u=u, ts=ts, device_rng=device_rng, seed=seed,
+                               ray_id0=ray_id0, return_ts=return_ts, box=box)
+
+
+def _render_nerf_masked(rays, net, N, occupancy, tn, tf, c, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0,
+                        return_ts=False, box=None):
+    """The body of ``render_nerf_masked`` behind its preamble.  ``c``: a Controls, resolved here where the parent looked at the
+    background's shape (behind the grid's checks, before the jitter is drawn), or a ``Resolved`` as a train step hands it down."""
+    from .utils import box as box_mod, jitter, occupancy as occ_mod
     B, N = _lib.require_rays(rays), int(N)
     dev = rays.device
     occ_mod.check_trainable(occupancy, net, rays, N)
     if N < 1:
         raise RuntimeError(f"masked training serves 1 <= N <= {occ_mod.MAX_N_TRAIN} samples per ray, got N = {N}")
     _lib.require_same_device("occupancy grid", occupancy.words, dev)
-    controls = _masked_controls(controls, B, dev, ray_id0)     # the background's shape: before the jitter is drawn
+    if isinstance(c, Controls):
+        c = controls_mod.resolve(c, B, dev, ray_id0)       # the background's shape: before the jitter is drawn
     net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
     if box is not None:                       # the box's positions, then the ts= path
         jitter.check(B, N, u=u)
@@ -664,7 +534,7 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     try:
         rays = rays.detach().contiguous()
         tbins = jitter.tbins(tn, tf, N, dev, flags)
-        out = _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, controls=controls)
+        out = _masked_outputs(rays, net, N, occupancy, tbins, jit, flags, seed, ray_id0, c=c)
         if return_ts:
             return out, occ_mod.sample_positions(rays, jit, tbins, flags, seed, ray_id0, N)
         return out
@@ -695,6 +565,19 @@ def _optimise(loss, params, optimizer, decay, group):
     return loss.detach()
 
 
+def _optimise_with_term(rgb, gt, w, ts, lam, tn, tf, params, optimizer, decay, group):
+    """MSE(rgb, gt), with ``lam`` > 0 plus the distortion term on the weights ``w`` at ``ts`` (one fp32 add), through
+    ``_optimise``; the detached total, ``.distortion`` on it the weighted term."""
+    loss, term = mse_loss(rgb, gt), None
+    if lam > 0:
+        term = _distortion_term(w, ts, lam, tn, tf)
+        loss = loss + term
+    out = _optimise(loss, params, optimizer, decay, group)
+    if term is not None:
+        out.distortion = term.detach()
+    return out
+
+
 def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, group=None,
                precision=None, device_rng=False, seed=0, ray_id0=0, occupancy=None, background=None, sigma_noise=0.0,
                noise_seed=0, distortion=0.0, controls=None, box=None):
@@ -720,41 +603,23 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     ``render_nerf(..., box=box)`` / ``render_nerf_masked(..., box=box)``, dense or with ``occupancy``, with the controls, at
     every precision.  The positions carry no gradient; the distortion term keeps the global ``tf`` and its coefficient."""
     from .utils.box import check_box
-    from .utils.rendering import render_nerf, _refuse_controls
     bkw = {} if check_box(box) is None else {"box": box}       # off by default: a call without it is the call it was
-    controls = _controls_arg(controls, background=background, sigma_noise=sigma_noise, noise_seed=noise_seed,
-                             distortion=distortion)
-    if controls is not None and occupancy is None:       # the dense step: the flat keywords' meaning
-        background, sigma_noise, noise_seed, distortion = (controls.background, controls.sigma_noise, controls.noise_seed,
-                                                           controls.distortion)
-    lam = _check_distortion(distortion)
-    _refuse_distortion(lam, occupancy=occupancy)
-    _refuse_controls(background, sigma_noise, occupancy=occupancy)
+    c = controls_mod.from_keywords(controls, {"occupancy": occupancy}, background=background, sigma_noise=sigma_noise,
+                                   noise_seed=noise_seed, distortion=distortion)
     if occupancy is not None:
         from .utils.occupancy import check_trainable
         check_trainable(occupancy, net, rays, N, precision)      # before zero_grad: a refused call changes nothing
-        if controls is not None:
-            lam = controls.distortion
-            _masked_controls(controls, _lib.require_rays(rays), rays.device, ray_id0)      # the background's shape, likewise
+    if c is not None:
+        c = controls_mod.resolve(c, _lib.require_rays(rays), rays.device, ray_id0)     # the background's shape, likewise
     optimizer.zero_grad(set_to_none=True)
     if occupancy is not None:
-        rgb, _, _, _, w = render_nerf_masked(rays, net, N, occupancy, tn, tf, u=u, device_rng=device_rng, seed=seed,
-                                             ray_id0=ray_id0, controls=None if controls is None else controls.replace(distortion=0.0),
-                                             **bkw)
+        rgb, _, _, _, w = _render_nerf_masked(rays, net, N, occupancy, tn, tf, c, u=u, device_rng=device_rng, seed=seed,
+                                              ray_id0=ray_id0, **bkw)
     else:
-        kw = {}
-        if background is not None or sigma_noise:          # off by default: a call without them is the call it was
-            kw = dict(background=background, sigma_noise=sigma_noise, noise_seed=noise_seed)
-        rgb, _, _, _, w = render_nerf(rays, net, N, tn, tf, u=u, precision=precision,
-                                      device_rng=device_rng, seed=seed, ray_id0=ray_id0, **kw, **bkw)
-    loss, term = mse_loss(rgb, gt), None
-    if lam > 0:
-        term = _distortion_term(w, getattr(w, "ts", None), lam, tn, tf)
-        loss = loss + term
-    out = _optimise(loss, net.parameters(), optimizer, decay, group)
-    if term is not None:
-        out.distortion = term.detach()
-    return out
+        rgb, _, _, _, w = _render_nerf(rays, net, N, tn, tf, c, u=u, precision=precision, device_rng=device_rng, seed=seed,
+                                       ray_id0=ray_id0, **bkw)
+    return _optimise_with_term(rgb, gt, w, getattr(w, "ts", None), 0.0 if c is None else c.lam, tn, tf, net.parameters(), optimizer,
+                               decay, group)
 
 
 # --------------------------------------------------------------------------
@@ -778,10 +643,9 @@ def _pair_stats(coarse, fine):
     return out
 
 
-def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0, controls=None):
+def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray_id0, c=None):
     """render_nerf_autograd that also hands back the sample positions it drew (the coarse pass of the pair).
-    ``controls``: the background / sigma noise of ``composite_with_controls``, None = neither."""
-    from .utils.rendering import _tbins
+    ``c``: the ``Resolved`` controls of ``composite_with_controls``; None = none, and ``w.ts`` is not set."""
     from .utils.xyz import range_check_rays
     dev, B = rays.device, rays.size(0)
     tbins = _tbins(tn, tf, N, dev)
@@ -795,8 +659,8 @@ def _render_train_with_ts(rays, net, N, tn, tf, jit, flags, precision, seed, ray
     else:
         params = [p for _, p in net.named_parameters()]
         raw, ts = _FusedDense.apply(net, rays, jit, tbins, flags, seed, ray_id0, N, None, *params)
-    if controls is not None:
-        return composite_with_controls(raw, ts, rays, True, controls, ray_id0), ts
+    if c is not None:
+        return composite_with_controls(raw, ts, rays, True, c), ts
     return _VolumeRender.apply(raw, ts, rays, True), ts
 
 
@@ -831,8 +695,7 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
     from .optim import FusedAdam
     from .utils import jitter
     from .utils.box import refuse_box
-    from .utils.rendering import render_nerf, sample_pdf, _background_arg
-    pair = _pair_controls(controls, "train_step_hierarchical")
+    c = controls_mod.pair(controls, "train_step_hierarchical")
     refuse_box(box, "the coarse + fine pair (train_step_hierarchical)")
     _check_pair(net_c, net_f, Nc, Nf, precision)
     Nc, Nf = int(Nc), int(Nf)
@@ -852,31 +715,28 @@ def train_step_hierarchical(net_c, net_f, optimizer, rays, gt, Nc=64, Nf=128, *,
         check_trainable(occupancy, net_c, rays, Nc, precision)       # before any draw: a refused call changes nothing
         check_trainable(occupancy, net_f, rays, Nc + Nf, precision)
         _lib.require_same_device("occupancy grid", occupancy.words, dev)
-    kw_c, kw_f, dense_c = {}, {}, None
-    if pair is not None:                 # off by default: a call without it is the call it was
-        bg = (None, 0) if pair[0].background is None else _background_arg(pair[0].background, B, dev)   # its shape: before any draw
-        kw_c, kw_f = {"controls": pair[0]}, {"controls": pair[1], "ray_id0": ray_id0}
-        dense_c = (*bg, pair[0].sigma_noise, pair[0].noise_seed)
+    c = controls_mod.resolve(c, B, dev, ray_id0)        # the background's shape: before any draw
+    # off by default: a call without controls is the call it was, the fine pass's default ray_id0 included
+    c_f, kw_f = (None, {}) if c is None else (c.fine(), {"ray_id0": ray_id0})
     rays = rays.detach().contiguous()
     jit_c, flags, u_f = jitter.pair(B, Nc, Nf, dev, u_c=u_c, u_f=u_f, device_rng=device_rng)
 
     optimizer.zero_grad(set_to_none=True)
     if occupancy is not None:
-        coarse, ts_c = render_nerf_masked(rays, net_c, Nc, occupancy, tn, tf, u=jit_c, device_rng=jit_c is None, seed=seed,
-                                          ray_id0=ray_id0, return_ts=True, **kw_c)
+        coarse, ts_c = _render_nerf_masked(rays, net_c, Nc, occupancy, tn, tf, c, u=jit_c, device_rng=jit_c is None, seed=seed,
+                                           ray_id0=ray_id0, return_ts=True)
         stats_c = occupancy.last_stats
     else:
         coarse, ts_c = _render_train_with_ts(rays, net_c, Nc, tn, tf, jit_c, flags,
-                                             net_c.precision if precision is None else precision, seed, ray_id0,
-                                             *(() if dense_c is None else (dense_c,)))
+                                             net_c.precision if precision is None else precision, seed, ray_id0, c)
     # the fine positions carry no gradient: w.detach() -- the coarse net learns from MSE(rgb_c, gt) alone.  With sigma noise
     # these are the weights of the noisy compositor; a background never touches them
     ts_f = sample_pdf(ts_c, coarse[4].detach(), Nf, u=u_f, device_rng=device_rng, seed=seed, ray_id0=ray_id0)
     if occupancy is not None:
-        fine = render_nerf_masked(rays, net_f, Nc + Nf, occupancy, tn, tf, ts=ts_f, **kw_f)
+        fine = _render_nerf_masked(rays, net_f, Nc + Nf, occupancy, tn, tf, c_f, ts=ts_f, **kw_f)
         occupancy.last_stats = _pair_stats(stats_c, occupancy.last_stats)
     else:
-        fine = render_nerf(rays, net_f, Nc + Nf, tn, tf, ts=ts_f, precision=precision, **kw_f)
+        fine = _render_nerf(rays, net_f, Nc + Nf, tn, tf, c_f, ts=ts_f, precision=precision, **kw_f)
     loss_c = mse_loss(coarse[0], gt)
     loss_f = mse_loss(fine[0], gt)
     loss = loss_c + loss_f
@@ -915,13 +775,10 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
     box: refused (RuntimeError before anything is drawn): the guided placement has its own interval."""
     from .utils.box import refuse_box
     refuse_box(box, "the guided step (train_step_guided)")
-    controls = _controls_arg(controls, distortion=distortion)
-    if controls is not None and occupancy is None:
-        if controls.background is not None or controls.sigma_noise:
-            raise RuntimeError("the dense guided step takes the distortion term only: background / sigma_noise need occupancy=")
-        distortion = controls.distortion
-    lam = _check_distortion(distortion)
-    _refuse_distortion(lam, occupancy=occupancy)
+    c = controls_mod.from_keywords(controls, {"occupancy": occupancy}, distortion=distortion)
+    if controls is not None and occupancy is None and (c.background is not None or c.sigma_noise):
+        raise RuntimeError("the dense guided step takes the distortion term only: background / sigma_noise need occupancy=")
+    lam = 0.0 if c is None else c.distortion
     _check_guided(net, proposal)
     _lib.precision_of(net, precision)             # a precision the kernels do not know: ValueError before anything else
     if occupancy is not None:
@@ -929,17 +786,13 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
         occ_mod.check_trainable(occupancy, net, rays, int(Nc) + int(Nf), precision)
     proposal.check(rays, Nc, Nf, u_c, ts_c, u_f, device_rng, occupancy=occupancy)   # before any draw: a refused call changes nothing
     if occupancy is not None:
-        mc = None
-        if controls is not None:
-            lam = controls.distortion
-            mc = _masked_controls(controls, rays.size(0), rays.device, ray_id0)        # the background's shape: before any draw
+        c = controls_mod.resolve(c, rays.size(0), rays.device, ray_id0)        # the background's shape: before any draw
         net.packed_weights(_lib.BF16)             # packs now if it has to: errors surface before the jitter is drawn
         rays = rays.detach().contiguous()
         ts, mark = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
                                    ray_id0=ray_id0, occupancy=occupancy, return_mark=True)
         optimizer.zero_grad(set_to_none=True)
-        outs = _masked_outputs(rays, net, int(Nc) + int(Nf), occupancy, None, ts, _lib.FLAG_TS_GIVEN, 0, 0, mark=mark,
-                               controls=mc)
+        outs = _masked_outputs(rays, net, int(Nc) + int(Nf), occupancy, None, ts, _lib.FLAG_TS_GIVEN, 0, 0, mark=mark, c=c)
     else:
         ts = proposal.sample(rays, Nc, Nf, tn, tf, u_c=u_c, ts_c=ts_c, u_f=u_f, device_rng=device_rng, seed=seed,
                              ray_id0=ray_id0)
@@ -947,14 +800,8 @@ def train_step_guided(net, optimizer, rays, gt, Nc, Nf, proposal, *, tn=2, tf=6,
         optimizer.zero_grad(set_to_none=True)
         outs, _ = _render_train_with_ts(rays, net, int(Nc) + int(Nf), tn, tf, ts, _lib.FLAG_TS_GIVEN,
                                         net.precision if precision is None else precision, seed, ray_id0)
-    loss, term = mse_loss(outs[0], gt), None
-    if lam > 0:
-        term = _distortion_term(outs[4], ts, lam, tn, tf)
-        loss = loss + term
-    out = _optimise(loss, net.parameters(), optimizer, decay, group)
+    out = _optimise_with_term(outs[0], gt, outs[4], ts, lam, tn, tf, net.parameters(), optimizer, decay, group)
     out.ts = ts
-    if term is not None:
-        out.distortion = term.detach()
     return out
 
 
@@ -1363,24 +1210,21 @@ class GraphedTrainStep:
                  device_rng=False, seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", storage="bf16",
                  background=None, sigma_noise=0.0, noise_seed=0, distortion=0.0, controls=None):
         from . import parallel
-        from .utils.rendering import _background_arg, _check_sigma_noise
         pair = self._samples if self._samples and len(self._samples) == 2 else None
-        self._distortion = _check_distortion(distortion)
-        # the masked and hierarchical steppers inherit this constructor: the term cannot slip through them
-        _refuse_distortion(self._distortion, **{"a coarse / fine pair": pair, "an occupancy grid": self._capacities})
-        # the bundle: the flat keywords' meaning here, and the one way the three terms reach a masked pass
-        controls = _controls_arg(controls, background=background, sigma_noise=sigma_noise, noise_seed=noise_seed,
-                                 distortion=distortion)
-        if controls is not None:
-            if pair is not None and controls.distortion > 0:       # the pair steppers refuse it first (_pair_controls)
-                _refuse_bundle(controls, f"the coarse + fine pair ({type(self).__name__}) with the distortion term")
-            background, sigma_noise, noise_seed, self._distortion = (controls.background, controls.sigma_noise,
-                                                                     controls.noise_seed, controls.distortion)
+        controls_mod.check_distortion(distortion)        # looked at before the bundle's type, as it always was
+        # the flat keywords' meaning here, and the one way the three terms reach a masked pass; the masked and hierarchical
+        # steppers inherit this constructor: the flat term cannot slip through them
+        c = controls_mod.from_keywords(controls, {"a coarse / fine pair": pair, "an occupancy grid": self._capacities},
+                                       background=background, sigma_noise=sigma_noise, noise_seed=noise_seed, distortion=distortion)
+        if controls is not None and pair is not None and c.distortion > 0:       # the pair steppers refuse it first (pair)
+            controls_mod.refuse_bundle(c, f"the coarse + fine pair ({type(self).__name__}) with the distortion term")
         self._check_modules(net, optimizer)
-        self._sigma_noise, self.noise_seed = _check_sigma_noise(sigma_noise), int(noise_seed)
-        if background is not None:           # this object's own buffer: the captured head reads it at every replay
-            bg, self._bg_stride = _background_arg(background, int(n_rays), optimizer.flat.device)
-            self.background = bg.clone()
+        self.noise_seed = int(noise_seed) if controls is None else c.noise_seed       # kept whatever is on
+        c = controls_mod.resolve(c, int(n_rays), optimizer.flat.device, ray_id0)
+        if c is not None:
+            self._bg_stride, self._sigma_noise, self._distortion = c.stride, c.std, c.lam
+            if c.bg is not None:             # this object's own buffer: the captured head reads it at every replay
+                self.background = c.bg.clone()
         self._controls = self.background is not None or self._sigma_noise > 0
         self.net, self.opt, self.group = net, optimizer, group
         if buckets not in (1, 2):
@@ -1469,7 +1313,6 @@ class GraphedTrainStep:
         """``passes`` with their buffers, each pass's module, gradient slice, loss slot and jitter arguments.  A pair
         (coarse, fine) shares ONE jitter draw: ``u`` [B, Nc+Nf] of the reference stream, whose first B*Nc values are
         torch.rand(B,Nc) = ``u_c`` and the rest torch.rand(B,Nf) = ``u_f`` -- the same numbers as the two draws in a row."""
-        from .utils.rendering import _tbins
         lib, dev, ptr, B = _lib.lib(), self.dev, _lib.ptr, self.B
         samples = self._samples or (self.N,)
         pair = len(samples) == 2
@@ -1871,12 +1714,10 @@ class _TableTrainStep(GraphedTrainStep):
     table, and the stepper's first launch keeps the ids a step ran on in ``_ids_used``.  ``_words``: what differs between
     the steppers' messages (``spans`` is formatted with the object); ``_baked_now()``: the addresses the graph holds."""
 
-    def _bind_table(self, obj, kind, optimizer, n_rays, rays_from, select_mode, group, controls, lr, betas, eps):
+    def _bind_table(self, obj, kind, optimizer, n_rays, rays_from, select_mode, group, lr, betas, eps):
         """The refusals the table steppers share, in their order, before any launch or RNG draw; then the table's optimiser."""
         from . import parallel
         name, w = type(self).__name__, self._words
-        if controls[0] is not None or controls[1] or controls[2]:
-            raise RuntimeError(f"{name} does not take background / sigma_noise / distortion yet")
         if parallel.collectives_active(group):
             raise RuntimeError(f"{name} trains on one replica: the {w['gradient']} gradient has no exchange yet")
         if not isinstance(obj, kind):
@@ -1995,13 +1836,14 @@ class GraphedCameraTrainStep(_TableTrainStep):
         from .utils.cameras import CameraRefinement
         from .utils.box import refuse_box
         refuse_box(kw.pop("box", None), "GraphedCameraTrainStep")
-        _refuse_bundle(kw.pop("controls", None), "GraphedCameraTrainStep")
+        controls_mod.refuse_bundle(kw.pop("controls", None), "GraphedCameraTrainStep")
         if storage != "bf16":
             raise RuntimeError("GraphedCameraTrainStep: storage='e4m3' is not served (nerf_amd_input_gradients reads bf16 dY)")
         if buckets != 1:
             raise RuntimeError("GraphedCameraTrainStep: one exchange bucket only (buckets=1)")
-        self._bind_table(cameras, CameraRefinement, optimizer, n_rays, rays_from, select_mode, group,
-                         (background, sigma_noise, distortion), camera_lr, camera_betas, camera_eps)
+        controls_mod.refuse_flat(type(self).__name__, background, sigma_noise, distortion)
+        self._bind_table(cameras, CameraRefinement, optimizer, n_rays, rays_from, select_mode, group, camera_lr, camera_betas,
+                         camera_eps)
         self.cameras = cameras
         self._baked = self._baked_now()
         f32 = dict(dtype=torch.float32, device=cameras.xi.device)
@@ -2086,10 +1928,10 @@ class GraphedAppearanceTrainStep(_TableTrainStep):
         from .utils.appearance import AppearanceCorrection
         from .utils.box import refuse_box
         refuse_box(kw.pop("box", None), "GraphedAppearanceTrainStep")
-        _refuse_bundle(kw.pop("controls", None), "GraphedAppearanceTrainStep")
-        self._bind_table(appearance, AppearanceCorrection, optimizer, n_rays, rays_from, select_mode, group,
-                         (kw.get("background"), kw.get("sigma_noise"), kw.get("distortion")), appearance_lr, appearance_betas,
-                         appearance_eps)
+        controls_mod.refuse_bundle(kw.pop("controls", None), "GraphedAppearanceTrainStep")
+        controls_mod.refuse_flat(type(self).__name__, kw.get("background"), kw.get("sigma_noise"), kw.get("distortion"))
+        self._bind_table(appearance, AppearanceCorrection, optimizer, n_rays, rays_from, select_mode, group, appearance_lr,
+                         appearance_betas, appearance_eps)
         self.appearance = appearance
         self._baked = self._baked_now()
         f32 = dict(dtype=torch.float32, device=appearance.theta.device)
@@ -2228,8 +2070,8 @@ class GraphedMaskedTrainStep(_MaskedSteps, GraphedTrainStep):
     def __init__(self, net, optimizer, n_rays, N, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
                  ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0,
                  controls=None):
-        _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
-        controls = _controls_arg(controls)
+        controls_mod.check_distortion(distortion, {"an occupancy grid": occupancy})
+        controls = controls_mod.bundle(controls)
         self._refuse(storage, buckets)
         B, N_ = int(n_rays), int(N)
         if B < 1 or N_ < 1:
@@ -2261,7 +2103,6 @@ class _BoxSteps:
         self.box, self._box_args = box, (_lib.host_f32x3(box.lo), _lib.host_f32x3(box.hi), float(tn), float(tf))
 
     def _alloc_pass_buffers(self, tn, tf):
-        from .utils.rendering import _tbins
         super()._alloc_pass_buffers(tn, tf)
         ptr, first = _lib.ptr, self.passes[0]
         rays, jit, _, flags, seed, rid = first.jitter
@@ -2375,8 +2216,8 @@ class GraphedHierarchicalTrainStep(_PairJitter, GraphedTrainStep):
 
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc=64, Nf=128, *, tn=2, tf=6, group=None, device_rng=False, seed=0,
                  ray_id0=0, check_every=16, rays_from=None, select_mode="train", distortion=0.0, controls=None):
-        pair = _pair_controls(controls, type(self).__name__)
-        _refuse_distortion(_check_distortion(distortion), **{"a coarse / fine pair": (net_c, net_f)})
+        c = controls_mod.pair(controls, type(self).__name__)
+        controls_mod.check_distortion(distortion, {"a coarse / fine pair": (net_c, net_f)})
         _check_pair(net_c, net_f, Nc, Nf, None)
         self.net_c, self.net_f, self.Nc, self.Nf = net_c, net_f, int(Nc), int(Nf)
         # ``net`` / ``nets`` are the pair, as FusedAdam([net_c, net_f]).net / .nets hold it
@@ -2384,7 +2225,7 @@ class GraphedHierarchicalTrainStep(_PairJitter, GraphedTrainStep):
         self._samples = (self.Nc, self.Nc + self.Nf)
         super().__init__(self.nets, optimizer, n_rays, self.Nc + self.Nf, tn=tn, tf=tf, group=group, device_rng=device_rng,
                          seed=seed, ray_id0=ray_id0, check_every=check_every, rays_from=rays_from, select_mode=select_mode,
-                         **({} if pair is None else {"controls": pair[0]}))
+                         **({} if c is None else {"controls": c}))
 
     def _check_modules(self, net, optimizer):
         from .optim import FusedAdam
@@ -2426,8 +2267,8 @@ class GraphedMaskedHierarchicalTrainStep(_MaskedSteps, GraphedHierarchicalTrainS
     def __init__(self, net_c, net_f, optimizer, n_rays, Nc, Nf, occupancy, capacity, *, tn=2, tf=6, group=None, device_rng=False,
                  seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
                  distortion=0.0, controls=None):
-        _pair_controls(controls, type(self).__name__)
-        _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
+        controls_mod.pair(controls, type(self).__name__)
+        controls_mod.check_distortion(distortion, {"an occupancy grid": occupancy})
         self._refuse(storage, buckets)
         _check_pair(net_c, net_f, Nc, Nf, None)
         B, Nc_, Nf_ = int(n_rays), int(Nc), int(Nf)
@@ -2467,9 +2308,8 @@ class GraphedGuidedTrainStep(_PairJitter, GraphedTrainStep):
                  ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16", distortion=0.0,
                  controls=None):
         from .utils.proposal import check_sizes
-        lam = _check_distortion(distortion)
-        _refuse_distortion(lam, **{"an occupancy grid": self._capacities})       # the masked guided stepper comes through here
-        controls = _controls_arg(controls, distortion=distortion)
+        lam = controls_mod.check_distortion(distortion, {"an occupancy grid": self._capacities})   # the masked guided stepper too
+        controls = controls_mod.bundle(controls, distortion=distortion)
         if controls is not None and self._capacities is None and (controls.background is not None or controls.sigma_noise):
             raise RuntimeError("the dense guided stepper takes the distortion term only: background / sigma_noise need the "
                                "masked guided stepper (GraphedMaskedGuidedTrainStep)")
@@ -2489,7 +2329,6 @@ class GraphedGuidedTrainStep(_PairJitter, GraphedTrainStep):
 
     def _alloc_pass_buffers(self, tn, tf):
         """The dense pass reads given positions: ``ts_f``, which the sampler writes.  ``u`` is split as a pair's."""
-        from .utils.rendering import _tbins
         super()._alloc_pass_buffers(tn, tf)
         ptr, B, Nc, Nf, dev = _lib.ptr, self.B, self.Nc, self.Nf, self.dev
         self.tbins = _tbins(tn, tf, Nc, dev)                        # of the COARSE positions, the only ones drawn from bins
@@ -2550,8 +2389,8 @@ class GraphedMaskedGuidedTrainStep(_MaskedSteps, GraphedGuidedTrainStep):
                  seed=0, ray_id0=0, check_every=16, rays_from=None, select_mode="train", buckets=1, storage="bf16",
                  distortion=0.0, controls=None):
         from .utils.proposal import check_sizes
-        _refuse_distortion(_check_distortion(distortion), **{"an occupancy grid": occupancy})
-        controls = _controls_arg(controls)
+        controls_mod.check_distortion(distortion, {"an occupancy grid": occupancy})
+        controls = controls_mod.bundle(controls)
         self._refuse(storage, buckets)
         _check_guided(net, proposal)
         Nc_, Nf_ = check_sizes(Nc, Nf)

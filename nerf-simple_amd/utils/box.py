@@ -148,12 +148,11 @@ def check_interval(N, tn, tf):
 
 def place(box, rays, jit, flags, seed, ray_id0, N, tn, tf, want_span=False):
     """One launch of nerf_amd_box_positions for settled jitter arguments -> (ts, span or None, hit or None)."""
-    from .rendering import _tbins
     B, dev = rays.size(0), rays.device
     ts = torch.empty((B, N), dtype=torch.float32, device=dev)
     span = torch.empty((B, 2), dtype=torch.float32, device=dev) if want_span else None
     hit = torch.empty((B,), dtype=torch.int32, device=dev) if want_span else None
-    tb = None if flags & _lib.FLAG_TS_GIVEN else _tbins(0, 1, N, dev)
+    tb = jitter.tbins(0, 1, N, dev, flags)
     _lib.launch("nerf_amd_box_positions", rays, jit, tb, flags, int(seed), int(ray_id0), _lib.host_f32x3(box.lo),
                 _lib.host_f32x3(box.hi), float(tn), float(tf), ts, span, hit, B, N, dev=dev)
     return ts, span, hit

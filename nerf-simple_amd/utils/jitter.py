@@ -5,9 +5,12 @@ Precedence: explicit positions ``ts`` (FLAG_TS_GIVEN) > explicit uniforms ``u`` 
 no tensor) > one ``torch.rand(B, N)`` of torch's CPU generator, continued on the device (``host_rng.reference_rand``).
 Nothing here raises after a draw: a refused call leaves the generator where it was.
 """
+import torch
+
 from .. import _lib
 from . import host_rng
 
+_tbins_cache = {}
 SHAPE_ERROR = "u / ts must be [B, N]"       # render_nerf's, OccupancyGrid.mark's and render_nerf_masked's message
 
 
@@ -54,7 +57,18 @@ def pair(B, Nc, Nf, dev, *, u_c=None, u_f=None, device_rng=False):
     return jit_c, flags_c, u_f
 
 
-def tbins(tn, tf, N, dev, flags):
-    """The bin edges the kernels jitter in, or None when the positions are given."""
-    from .rendering import _tbins
-    return None if flags & _lib.FLAG_TS_GIVEN else _tbins(tn, tf, N, dev)
+def tbins(tn, tf, N, device, flags=0):
+    """The bin edges the kernels jitter in (one cached tensor per interval, count and device), or None when the positions are
+    given."""
+    if flags & _lib.FLAG_TS_GIVEN:
+        return None
+    key = (float(tn), float(tf), int(N), device)
+    t = _tbins_cache.get(key)
+    if t is None:
+        # computed on the host by torch.linspace so bin edges are bit-identical
+        # to the reference's (utils/rendering.py:25)
+        t = torch.linspace(tn, tf, N + 1).to(device)
+        if len(_tbins_cache) > 64:
+            _tbins_cache.clear()
+        _tbins_cache[key] = t
+    return t

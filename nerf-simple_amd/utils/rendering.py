@@ -25,26 +25,14 @@ import torch
 from tqdm import tqdm
 
 from .. import _lib
-from . import jitter
+from . import box as box_mod, controls as controls_mod, jitter
+from .controls import background_arg as _background_arg      # the name tests/test_background_cpu.py holds the shape rule by
 from .host_rng import ReferenceJitter
+from .jitter import tbins as _tbins
 from .nets import Nerf, guarded_launch
 
 ALL_OUTPUTS = ("rgb", "disp", "alpha", "acc", "w")
 _FUSED_MAX_N = 768          # csrc/nerf_layout.h FUSED_RENDER_MAX_N: rays the one-launch render composites in its LDS ring
-_tbins_cache = {}
-
-
-def _tbins(tn, tf, N, device):
-    key = (float(tn), float(tf), int(N), device)
-    t = _tbins_cache.get(key)
-    if t is None:
-        # computed on the host by torch.linspace so bin edges are bit-identical
-        # to the reference's (utils/rendering.py:25)
-        t = torch.linspace(tn, tf, N + 1).to(device)
-        if len(_tbins_cache) > 64:
-            _tbins_cache.clear()
-        _tbins_cache[key] = t
-    return t
 
 
 def _per_sample(t_, N):
@@ -62,84 +50,6 @@ def _five_outputs(B, N, outputs, dev):
     return rgb, disp, buf(B, N) if "alpha" in outputs else None, acc, buf(B, N) if "w" in outputs else None
 
 
-# ---- the two training controls of the dense path: a background colour and noise on the raw density -------------------------
-def _background_arg(background, B, dev):
-    """``background`` as the kernels take it: (fp32 contiguous tensor on ``dev``, stride) -- one colour [3] (stride 0) or one
-    per ray [B,3] (stride 3).  A sequence of three numbers is a colour.  It carries no gradient."""
-    if not torch.is_tensor(background):
-        background = torch.tensor([float(x) for x in background], dtype=torch.float32)
-    bg = background.detach().to(device=dev, dtype=torch.float32).contiguous()
-    if tuple(bg.shape) == (3,):
-        return bg, 0
-    if tuple(bg.shape) == (B, 3):
-        return bg, 3
-    raise RuntimeError(f"background must be one colour [3] or one per ray [{B}, 3], got {tuple(bg.shape)}")
-
-
-def _check_sigma_noise(sigma_noise):
-    import math
-    std = float(sigma_noise)
-    if not (std >= 0.0) or math.isinf(std):
-        raise ValueError(f"sigma_noise is a standard deviation: finite and >= 0, got {sigma_noise!r}")
-    return std
-
-
-def _refuse_controls(background, sigma_noise, **paths):
-    """The masked and terminated renders know neither control: refused before any launch and any RNG draw."""
-    if background is None and not sigma_noise:
-        return
-    for name, v in paths.items():
-        if v is not None:
-            raise RuntimeError(f"background / sigma_noise serve the dense path only: not with {name}= (render without them, "
-                               "or without the grid)")
-
-
-def _inference_controls(controls, occupancy, terminate, **flat):
-    """``controls=`` of the inference renders -> (flat keywords to go on with, the masked render's background or None).  Without a grid the bundle is the flat keywords' equivalent (both given: ValueError); with ``occupancy`` it
-    brings the background alone -- the masked render, then the blend.  Refused before anything is drawn or launched: with
-    ``terminate``, a non-zero ``distortion`` (the term belongs to a training step), noise behind a grid."""
-    from ..training import _controls_arg
-    c = _controls_arg(controls, **flat)
-    if c is None:
-        return flat, None
-    if terminate is not None:
-        raise RuntimeError("controls= does not reach the terminated render yet: not with terminate=")
-    if c.distortion:
-        raise ValueError("the distortion term belongs to a training step (train_step(..., controls=)): a render takes "
-                         "controls.distortion == 0")
-    if occupancy is None:
-        return {k: getattr(c, k) for k in flat}, None
-    if c.sigma_noise > 0:
-        raise RuntimeError("sigma_noise is a training regulariser, not a render option: the masked inference render trains "
-                           "nothing")
-    return flat, c.background
-
-
-def _pair_background(controls):
-    """``controls=`` of the coarse + fine inference renders, the first thing they look at -> the background or None.
-    ``render_nerf``'s rules: TypeError for anything but a Controls, ValueError for a distortion term (a render is no step),
-    the regulariser's RuntimeError for sigma noise (an inference render trains nothing)."""
-    from ..training import _controls_arg
-    c = _controls_arg(controls)
-    if c is None:
-        return None
-    if c.distortion:
-        raise ValueError("the distortion term belongs to a training step: a render takes controls.distortion == 0")
-    if c.sigma_noise > 0:
-        raise RuntimeError("sigma_noise is a training regulariser, not a render option: the coarse + fine inference render "
-                           "trains nothing")
-    return c.background
-
-
-def _blend(rgb, acc, disp, bg, stride, pixels=False):
-    """rgb + (1 - acc) bg through nerf_amd_background_blend: rgb_bg [B,3], or pixels [B,4] = [clip(rgb_bg, 0, 1), disp]."""
-    B, dev = rgb.shape[0], rgb.device
-    out = torch.empty((B, 4 if pixels else 3), dtype=torch.float32, device=dev)
-    _lib.launch("nerf_amd_background_blend", rgb, acc, disp if pixels else None, bg, stride, None if pixels else out,
-                out if pixels else None, B, dev=dev)
-    return out
-
-
 def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS, background=None):
     """nerf_outs [B,N,4], ts [B,N], dirs [B,3] -> (rgb [B,3], disp [B], alpha [B,N],
     acc [B], w [B,N])  (reference utils/rendering.py:47-85).  The second output is
@@ -154,18 +64,17 @@ def volume_render(nerf_outs, ts, dirs, *, outputs=ALL_OUTPUTS, background=None):
     B, N = nerf_outs.shape[0], nerf_outs.shape[1]
     if tuple(ts.shape) != (B, N) or tuple(dirs.shape) != (B, 3):
         raise RuntimeError("ts must be [B, N] and dirs [B, 3]")
-    bg = None if background is None else _background_arg(background, B, nerf_outs.device)
+    c = None if background is None else controls_mod.resolve(controls_mod.Controls(background), B, nerf_outs.device)
     if torch.is_grad_enabled() and nerf_outs.requires_grad:
-        from ..training import _Background, volume_render_autograd
+        from ..training import volume_render_autograd
         out = volume_render_autograd(nerf_outs, ts, dirs)
-        return out if bg is None else (_Background.apply(out[0], out[3], *bg),) + tuple(out[1:])
+        return out if c is None else (controls_mod.Background.apply(out[0], out[3], c.bg, c.stride),) + tuple(out[1:])
     dev = nerf_outs.device
     raw, ts, dirs = nerf_outs.detach().contiguous(), ts.detach().contiguous(), dirs.detach().contiguous()
     rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
     _lib.launch("nerf_amd_volume_render", raw, ts, dirs, 3, rgb, disp, alpha, acc, w, B, N, dev=dev)
-    if bg is not None:
-        rgb = _blend(rgb, acc, None, *bg)
-    return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+    out = rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+    return controls_mod.blended(out, c)
 
 
 def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUTS,
@@ -211,23 +120,28 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     no gradient, and d loss / d rays ignores the dependence of the interval on the ray (the fine sampler's rule).
     ``box=`` together with ``ts=`` is a ValueError.
     """
-    from . import box as box_mod
     box_mod.check_box(box, ts=ts)
-    masked_bg = None
+    c = controls_mod.from_keywords(controls, {"occupancy": occupancy, "terminate": terminate}, background=background,
+                                   sigma_noise=sigma_noise, noise_seed=noise_seed)
     if controls is not None:
-        flat, masked_bg = _inference_controls(controls, occupancy, terminate, background=background, sigma_noise=sigma_noise,
-                                              noise_seed=noise_seed)
-        background, sigma_noise, noise_seed = flat["background"], flat["sigma_noise"], flat["noise_seed"]
-    _refuse_controls(background, sigma_noise, occupancy=occupancy, terminate=terminate)
-    std = _check_sigma_noise(sigma_noise) if sigma_noise else 0.0
+        controls_mod.render_only(c, terminate, " (train_step(..., controls=))")
+        if occupancy is not None and c.sigma_noise > 0:
+            controls_mod.refuse_noise("the masked inference render trains nothing")
+    if c is not None:
+        c = controls_mod.resolve(c, _lib.require_rays(rays), rays.device, ray_id0)
+    return _render_nerf(rays, net, N, tn, tf, c, u=u, ts=ts, outputs=outputs, precision=precision, device_rng=device_rng, seed=seed,
+                        ray_id0=ray_id0, occupancy=occupancy, terminate=terminate, box=box)
+
+
+render_rays = render_nerf      # the name BASELINE.json uses for the same function
+
+
+def _render_nerf(rays, net, N, tn, tf, c, *, u=None, ts=None, outputs=ALL_OUTPUTS, precision=None, device_rng=False, seed=0,
+                 ray_id0=0, occupancy=None, terminate=None, box=None):
+    """The body of ``render_nerf`` behind its controls preamble.  ``c``: the ``Resolved`` controls or None -- without a grid the
+    background and / or the noise; with ``occupancy`` the background behind the masked render."""
     B, N = _lib.require_rays(rays), int(N)
     dev = rays.device
-    if masked_bg is not None:
-        masked_bg = _background_arg(masked_bg, B, dev)
-    controls = None
-    if background is not None or sigma_noise:
-        bg = (None, 0) if background is None else _background_arg(background, B, dev)
-        controls = (*bg, std, int(noise_seed))
     # d loss / d rays (utils/rendering.py:31-40 is differentiable in the rays): autograd runs even for a frozen net
     rays_grad = torch.is_grad_enabled() and rays.requires_grad
     rays_in = rays.contiguous() if rays_grad else None
@@ -235,12 +149,11 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
 
     fused = isinstance(net, Nerf) and net._fused_ok()
     training = fused and torch.is_grad_enabled() and (rays_grad or any(p.requires_grad for p in net.parameters()))
-    if controls is not None and controls[2] > 0:
+    if c is not None and c.std > 0:
         trains = training or (not fused and torch.is_grad_enabled() and (
             rays_grad or any(p.requires_grad for p in getattr(net, "parameters", lambda: ())())))
         if not trains:
-            raise RuntimeError("sigma_noise is a training regulariser, not a render option: this call trains nothing (no_grad, "
-                               "or no parameter and no ray requires grad)")
+            controls_mod.refuse_noise("this call trains nothing (no_grad, or no parameter and no ray requires grad)")
     if terminate is not None:
         from .occupancy import check_terminable
         check_terminable(terminate, occupancy, net, rays_grad)
@@ -276,7 +189,7 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
             if terminate is not None:
                 return render_terminated(terminate, occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
             out = render_masked(occupancy, rays, net, N, tb, jit, flags, seed, ray_id0, code, outputs)
-            return out if masked_bg is None else (_blend(out[0], out[3], None, *masked_bg),) + tuple(out[1:])
+            return controls_mod.blended(out, c)
         finally:
             if pending_rng is not None:
                 pending_rng.finish()
@@ -285,28 +198,25 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
         try:
             return render_nerf_autograd(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags,
                                         net.precision if precision is None else precision,
-                                        seed, ray_id0, *(() if controls is None else (controls,)))
+                                        seed, ray_id0, c)
         finally:
             if pending_rng is not None:
                 pending_rng.finish()          # the forward is enqueued behind the generator kernel: only that is awaited
     if not fused:
-        return _render_generic(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, controls)
+        return _render_generic(rays_in if rays_grad else rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, c)
 
     def launch(code, packed):
         rgb, disp, alpha, acc, w = _render_forward(rays, jit, _tbins(tn, tf, N, dev), packed[0], code, flags, seed, ray_id0, N,
                                                    outputs)
-        if controls is not None:              # the same one-launch render, then the blend (acc is always among the outputs)
-            rgb = _blend(rgb, acc, None, controls[0], controls[1])
-        return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+        out = rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+        # with a background: the same one-launch render, then the blend (acc is always among the outputs)
+        return controls_mod.blended(out, c)
 
     try:
         return guarded_launch([net], code, launch)     # fp16: range guard (nets.guarded_launch)
     finally:
         if pending_rng is not None:
             pending_rng.finish()              # the render is enqueued behind it: only the generator kernel is awaited
-
-
-render_rays = render_nerf      # the name BASELINE.json uses for the same function
 
 
 def _render_forward(rays, jit, tbins, image, code, flags, seed, ray_id0, N, outputs):
@@ -320,7 +230,7 @@ def _render_forward(rays, jit, tbins, image, code, flags, seed, ray_id0, N, outp
     return out
 
 
-def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, controls=None):
+def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, c=None):
     """Any other net object: sampling and query-point assembly in one HIP kernel (nerf_amd_query_points =
     utils/rendering.py:24-40; the same jitter sources as the fused path, counter RNG included), the net's own
     forward exactly as the reference calls it (:41), compositing by the HIP kernel with the directions taken
@@ -335,15 +245,14 @@ def _render_generic(rays, net, N, tn, tf, jit, flags, outputs, seed, ray_id0, co
     out = net.forward(q).reshape(B, N, 4).float()
     if torch.is_grad_enabled() and out.requires_grad:
         from ..training import composite_with_controls
-        return composite_with_controls(out, ts, rays, True, controls, ray_id0)
-    if controls is not None and controls[2] > 0:
+        return composite_with_controls(out, ts, rays, True, c)
+    if c is not None and c.std > 0:
         raise RuntimeError("sigma_noise is a training regulariser: the net's output carries no gradient")
     out = out.detach().contiguous()
     rgb, disp, alpha, acc, w = _five_outputs(B, N, outputs, dev)
     _lib.launch("nerf_amd_volume_render_rays", out, ts, rays, rgb, disp, alpha, acc, w, B, N, dev=dev)
-    if controls is not None:
-        rgb = _blend(rgb, acc, None, controls[0], controls[1])
-    return rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+    out = rgb, disp, _per_sample(alpha, N), acc, _per_sample(w, N)
+    return controls_mod.blended(out, c)
 
 
 def _query_points(rays, jit, tbins, flags, seed, ray_id0, N):
@@ -388,7 +297,7 @@ def _render_batched(rays, net, batch_size, N, tn, tf, u, progress, id_base=0, **
     background = kw.pop("background", None)          # one colour, or one per ray of this table: its rows follow the batches
     per_ray = torch.is_tensor(background) and background.dim() == 2
     if per_ray and background.shape[0] != n:
-        raise RuntimeError(f"background must be one colour [3] or one per ray [{n}, 3], got {tuple(background.shape)}")
+        raise controls_mod.background_shape(n, background.shape)
     if isinstance(net, Nerf) and net._fused_ok() and rays.is_cuda and 0 < n and N <= _FUSED_MAX_N:
         # The reference's batch_size bounds the [batch, N, ...] tensors of its per-sample path.  The fused render keeps
         # nothing per sample in HBM and its pixels do not depend on how the rays are batched (jitter rows follow the rays;
@@ -482,8 +391,7 @@ def render_rays_sharded(net, rays, batch_size, *, N=128, tn=2, tf=6, u=None, gro
     every rank's GPU.  Jitter is indexed by global ray id, so the image does
     not depend on the number of ranks."""
     from .. import parallel
-    from .box import refuse_box
-    refuse_box(kw.get("box"), "the sharded render (render_rays_sharded)")
+    box_mod.refuse_box(kw.get("box"), "the sharded render (render_rays_sharded)")
     dev = next(net.parameters()).device
 
     def render_fn(r, us, ray_id0):
@@ -538,15 +446,13 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     id) -> the render, the background render or the masked / terminated render on the materialised rays under those given
     positions, as the ``occupancy=`` branch already runs; by definition ``render_nerf(generate_rays(...), ..., box=box)`` and
     the clip.  Not inside the one-launch image kernel."""
-    from . import box as box_mod
     box_mod.check_box(box)
-    masked_bg = None
+    c = controls_mod.from_keywords(controls, {"occupancy": occupancy, "terminate": terminate}, background=background)
     if controls is not None:
-        flat, masked_bg = _inference_controls(controls, occupancy, terminate, background=background)
-        if occupancy is None and controls.sigma_noise > 0:
-            raise RuntimeError("sigma_noise is a training regulariser, not a render option: render_view trains nothing")
-        background = flat["background"]
-    _refuse_controls(background, 0.0, occupancy=occupancy, terminate=terminate)
+        controls_mod.render_only(c, terminate, " (train_step(..., controls=))")
+        if c.sigma_noise > 0:
+            controls_mod.refuse_noise("render_view trains nothing" if occupancy is None else
+                                      "the masked inference render trains nothing")
     dev = next(net.parameters()).device
     if terminate is not None:
         from .occupancy import check_terminable
@@ -563,12 +469,10 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         with torch.no_grad():
             rgb, disp, _, _, _ = render_nerf(rays, net, N, tn, tf, u=u, outputs=("rgb", "disp", "acc"),
                                              device_rng=device_rng, seed=seed, ray_id0=ray0,
-                                             **({} if background is None else {"background": background}),
+                                             **({} if c is None or c.background is None else {"background": c.background}),
                                              **({} if box is None else {"box": box}))
         return torch.cat([rgb.clamp(0., 1.), disp[:, None]], dim=1)
-    bg = None if background is None else _background_arg(background, n, dev)
-    if masked_bg is not None:
-        masked_bg = _background_arg(masked_bg, n, dev)
+    c = controls_mod.resolve(c, n, dev, ray0)         # the background, dense or behind the masked render
     code = _lib.precision_of(net, precision)
     net.packed_weights(code)
     rays = None
@@ -593,18 +497,17 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
         if terminate is not None:
             return render_terminated(terminate, occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
                                      code, (), pixels=True)
-        if masked_bg is not None:
-            rgb, disp, _, acc, _ = render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
-                                                 code, ())
-            return _blend(rgb, acc, disp, *masked_bg, pixels=True)
+        if c is not None:
+            return controls_mod.blended(render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0,
+                                                      code, ()), c, pixels=True)
         return render_masked(occupancy, rays, net, int(N), _tbins(tn, tf, N, dev), jit, flags, seed, ray0, code, (),
                              pixels=True)
 
     def launch_bg(code, packed):
-        rgb, disp, _, acc, _ = _render_forward(rays, jit, _tbins(tn, tf, N, dev), packed[0], code, flags, seed, ray0, int(N), ())
-        return _blend(rgb, acc, disp, *bg, pixels=True)
+        return controls_mod.blended(_render_forward(rays, jit, _tbins(tn, tf, N, dev), packed[0], code, flags, seed, ray0, int(N), ()),
+                                    c, pixels=True)
 
-    if bg is not None:
+    if c is not None:
         if jit is not None and tuple(jit.shape) != (n, int(N)):
             raise RuntimeError("u must be [n_rays, N]")
         if rays is None:
@@ -666,6 +569,17 @@ def sample_pdf(ts, w, Nf, *, u=None, device_rng=False, seed=0, ray_id0=0):
     return out
 
 
+def _pair_render_controls(controls):
+    """``controls=`` of the coarse + fine inference renders, the first thing they look at -> a Controls with a background, or None.
+    ``render_nerf``'s rules: TypeError for anything but a Controls, ValueError for a distortion term (a render is no step),
+    the regulariser's RuntimeError for sigma noise (an inference render trains nothing)."""
+    c = controls_mod.bundle(controls)
+    controls_mod.render_only(c)
+    if c is not None and c.sigma_noise > 0:
+        controls_mod.refuse_noise("the coarse + fine inference render trains nothing")
+    return None if c is None or c.background is None else c
+
+
 def _masked_pair_args(occupancy, net_coarse, net_fine, B, Nc, Nf, u_c, u_f, precision, device_rng, dev):
     """What ``render_hierarchical[_view](..., occupancy=)`` settles before anything is launched or drawn: the grid's and
     the sampler's preconditions, then the jitter (u_c, then u_f, from torch's CPU generator unless given / device_rng).
@@ -703,17 +617,15 @@ def render_hierarchical(rays, net_coarse, net_fine, Nc=64, Nf=128, tn=2, tf=6, *
     fine and of the coarse 5-tuple becomes rgb + (1 - acc) background through nerf_amd_background_blend; every other output,
     ``ts_fine`` included, is bit for bit what it was.  ``controls.sigma_noise > 0`` raises RuntimeError (a regulariser: this
     render trains nothing), a non-zero ``controls.distortion`` ValueError."""
-    from .box import refuse_box
-    background = _pair_background(controls)
-    refuse_box(box, "the coarse + fine pair (render_hierarchical)")
+    c = _pair_render_controls(controls)
+    box_mod.refuse_box(box, "the coarse + fine pair (render_hierarchical)")
     _lib.require_cuda_f32(rays, "rays")
     dev, B = rays.device, rays.size(0)
-    if background is not None:
-        bg = _background_arg(background, _lib.require_rays(rays), dev)        # its shape: before anything is drawn
+    if c is not None:
+        c = controls_mod.resolve(c, _lib.require_rays(rays), dev, ray_id0)        # the background's shape: before anything is drawn
         fine, coarse, ts_f = render_hierarchical(rays, net_coarse, net_fine, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, precision=precision,
                                                  device_rng=device_rng, seed=seed, ray_id0=ray_id0, occupancy=occupancy)
-        return ((_blend(fine[0], fine[3], None, *bg),) + tuple(fine[1:]),
-                (_blend(coarse[0], coarse[3], None, *bg),) + tuple(coarse[1:]), ts_f)
+        return controls_mod.blended(fine, c), controls_mod.blended(coarse, c), ts_f
     if occupancy is not None:
         from .occupancy import render_masked_pair
         _lib.require_rays(rays)
@@ -768,23 +680,22 @@ def render_hierarchical_view(net_coarse, net_fine, pose, cam_params, Nc=64, Nf=1
     ``render_hierarchical(..., controls=)`` on those rays (jitter ids from ``ray0``), then clip(rgb + (1 - acc) background,
     0, 1) beside the fine disparity (the clip behind the blend).  Sigma noise / a distortion term: as ``render_hierarchical``.
     Without it the dense call stays the one library call it is."""
-    from .box import refuse_box
-    background = _pair_background(controls)
-    refuse_box(box, "the coarse + fine pair (render_hierarchical_view)")
+    c = _pair_render_controls(controls)
+    box_mod.refuse_box(box, "the coarse + fine pair (render_hierarchical_view)")
     dev = next(net_coarse.parameters()).device
     H, W, f = int(cam_params[0]), int(cam_params[1]), float(cam_params[2])
     n = H * W - ray0 if n_rays is None else int(n_rays)
     if device_rng:
         u_c = u_f = None                 # this entry point's own rule (section 31): device_rng drops given uniforms
-    if background is not None:
-        bg = _background_arg(background, n, dev)                # its shape: before anything is drawn
+    if c is not None:
+        c = controls_mod.resolve(c, n, dev, ray0)               # the background's shape: before anything is drawn
         _lib.require_shape(u_c, "u_c", (n, int(Nc)))
         _lib.require_shape(u_f, "u_f", (n, int(Nf)))
         rays = generate_rays(pose, cam_params, dev, ray0, n)
         with torch.no_grad():
             fine = render_hierarchical(rays, net_coarse, net_fine, Nc, Nf, tn, tf, u_c=u_c, u_f=u_f, precision=precision,
                                        device_rng=device_rng, seed=seed, ray_id0=ray0, occupancy=occupancy)[0]
-        return _blend(fine[0], fine[3], fine[1], *bg, pixels=True)
+        return controls_mod.blended(fine, c, pixels=True)
     if occupancy is not None:
         from .occupancy import render_masked_pair
         Nc, Nf = int(Nc), int(Nf)
@@ -847,8 +758,7 @@ def render_guided(rays, net, Nc, Nf, proposal, tn=2, tf=6, *, u_c=None, ts_c=Non
     on the placement's ``ts``; inference only (call it under ``torch.no_grad()``), one host synchronisation, sets
     ``occupancy.last_stats``.
     box: refused (RuntimeError before anything is drawn): the guided placement has its own interval."""
-    from .box import refuse_box
-    refuse_box(box, "the guided render (render_guided)")
+    box_mod.refuse_box(box, "the guided render (render_guided)")
     _check_guided(net, proposal)
     if occupancy is not None:
         return _render_guided_masked(rays, net, Nc, Nf, proposal, tn, tf, u_c, ts_c, u_f, outputs, precision, device_rng, seed,
@@ -888,8 +798,7 @@ def render_guided_view(net, pose, cam_params, Nc, Nf, proposal, *, tn=2, tf=6, u
     masked render's pixel head (nerf_amd_volume_render_masked_pixels) on its positions under its mark; under
     ``torch.no_grad()``, one host synchronisation.
     box: refused (RuntimeError before anything is drawn)."""
-    from .box import refuse_box
-    refuse_box(box, "the guided render (render_guided_view)")
+    box_mod.refuse_box(box, "the guided render (render_guided_view)")
     _check_guided(net, proposal)
     if occupancy is not None:
         from .occupancy import check_renderable

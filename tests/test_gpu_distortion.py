@@ -295,19 +295,20 @@ def test_train_step_bf16(dev, scene, synthetic):
     calls agree to compare_gradients only).  With the term: the loss against the float64 total on the training forward's own
     raw, the gradients against the same composition built by hand from the public pieces, alone and behind both controls."""
     from nerf_simple_amd import training
+    from nerf_simple_amd.utils.controls import Resolved
     from nerf_simple_amd.utils.rendering import _tbins
     rays, gt, u, N, B = (scene[k] for k in ("rays", "gt", "u", "N", "B"))
     la, ga, _ = _eager(dev, synthetic, scene, u=u)
     lb, gb, _ = _eager(dev, synthetic, scene, u=u, distortion=0.0)
     assert same(la, lb) and not hasattr(lb, "distortion")
     compare_gradients(gb, ga, "distortion=0.0")
-    for controls in (None, (scene["bgB"], 3, 0.5, 77)):
+    for controls in (None, Resolved(scene["bgB"], 3, 0.5, 77, RAY0, 0.0)):
         kw = {} if controls is None else dict(background=controls[0], sigma_noise=controls[2], noise_seed=controls[3])
         lc, gc, _ = _eager(dev, synthetic, scene, u=u, distortion=LAM_STEP, ray_id0=RAY0, **kw)
         net = fresh(dev, synthetic)
         params = [p for _, p in net.named_parameters()]
         raw, ts = training._FusedDense.apply(net, rays, u, _tbins(2, 6, N, dev), 0, 0, 0, N, None, *params)
-        out = training.composite_with_controls(raw, ts, rays, True, controls, RAY0)
+        out = training.composite_with_controls(raw, ts, rays, True, controls)
         per_ray = training.distortion_loss(out[4], ts)
         assert per_ray.shape == (B,) and bool((per_ray > 0).all())
         want = training.mse_loss(out[0], gt) + (LAM_STEP / B) * per_ray.sum()

@@ -156,9 +156,13 @@ def test_the_fine_noise_offset():
     from nerf_simple_amd import training as T
     assert T.FINE_NOISE_OFFSET == 1 << 63
     c = T.Controls(sigma_noise=0.5, noise_seed=(1 << 63) + 5)
-    coarse, fine = T._pair_controls(c, "a test")
-    assert coarse is c and fine.noise_seed == 5 and fine.sigma_noise == 0.5            # mod 2^64
-    assert T._pair_controls(None, "a test") is None and T._pair_controls(T.Controls(), "a test") is None
+    from nerf_simple_amd.utils.controls import pair, resolve
+    assert pair(c, "a test") is c                 # the coarse pass takes the bundle as it is ...
+    coarse = resolve(c, 2, torch.device("cpu"), 9)
+    fine = coarse.fine()                                      # ... the fine pass its record under the offset key
+    assert coarse.noise_seed == (1 << 63) + 5 and fine.noise_seed == 5 and fine.std == 0.5            # mod 2^64
+    assert fine._replace(noise_seed=coarse.noise_seed) == coarse and fine.noise_ray_id0 == 9
+    assert pair(None, "a test") is None and pair(T.Controls(), "a test") is None
 
 
 def _calls(c):

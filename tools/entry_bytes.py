@@ -13,6 +13,9 @@ the repository.
 The train rows end in the flat gradient, which is NOT hashed: the dW products combine their split-K partial sums with float
 atomics (csrc/dw_gemm.hip), so its last bits differ between two runs of one tree.  Its largest magnitude is printed to three
 digits instead; the loss, which every sample feeds, is hashed like everything else.
+
+``CONTROL_ROWS`` are the same entry points with the training controls on; ``main`` prints them behind
+``ROWS``.
 """
 import hashlib
 import os
@@ -121,6 +124,46 @@ ROWS = (
     ("train_step_guided occupancy=", True, PAIR, lambda s, **j: _train_guided(s, s.occ, **j)),
 )
 
+# The same entry points with the training controls on: one fixed bundle, each row with the pieces its
+# entry point accepts.  ``train_step`` appears with the four flat keywords and with ``controls=``: the two rows print the same
+# digests.
+BG, LAM = (0.2, 0.4, 0.6), 0.01
+C_BG = T.Controls(background=BG)
+C_NOISE = T.Controls(background=BG, sigma_noise=0.5, noise_seed=11)
+C_ALL = C_NOISE.replace(distortion=LAM)
+
+
+def _per_ray(s):
+    """One colour per ray [B,3], different on every ray."""
+    return T.Controls(background=torch.rand(B, 3, generator=torch.Generator().manual_seed(2)).to(s.dev))
+
+
+CONTROL_ROWS = (
+    ("render_nerf background=", False, ONE, lambda s, **j: R.render_nerf(s.rays, s.net, N, background=BG, **j)),
+    ("render_nerf controls= occupancy=", False, ONE,
+     lambda s, **j: R.render_nerf(s.rays, s.net, N, occupancy=s.occ, controls=_per_ray(s), **j)),
+    ("render_view controls= occupancy=", False, ONE,
+     lambda s, **j: R.render_view(s.net, s.pose, s.cam, N=N, n_rays=B, occupancy=s.occ, controls=C_BG, **j)),
+    ("render_hierarchical controls=", False, PAIR,
+     lambda s, **j: R.render_hierarchical(s.rays, s.net_c, s.net_f, NC, NF, controls=C_BG, **j)),
+    ("render_hierarchical controls= occupancy=", False, PAIR,
+     lambda s, **j: R.render_hierarchical(s.rays, s.net_c, s.net_f, NC, NF, occupancy=s.occ, controls=C_BG, **j)),
+    ("render_hierarchical_view controls=", False, PAIR,
+     lambda s, **j: R.render_hierarchical_view(s.net_c, s.net_f, s.pose, s.cam, NC, NF, n_rays=B, controls=C_BG, **j)),
+    ("render_hierarchical_view controls= occupancy=", False, PAIR,
+     lambda s, **j: R.render_hierarchical_view(s.net_c, s.net_f, s.pose, s.cam, NC, NF, n_rays=B, occupancy=s.occ, controls=C_BG,
+                                               **j)),
+    ("render_nerf_masked controls=", True, ONE, lambda s, **j: T.render_nerf_masked(s.rays, s.net, N, s.occ, controls=C_NOISE, **j)),
+    ("train_step flat keywords", True, ONE,
+     lambda s, **j: _train(s, None, background=BG, sigma_noise=0.5, noise_seed=11, distortion=LAM, **j)),
+    ("train_step controls=", True, ONE, lambda s, **j: _train(s, None, controls=C_ALL, **j)),
+    ("train_step occupancy= controls=", True, ONE, lambda s, **j: _train(s, s.occ, controls=C_ALL, **j)),
+    ("train_step_hierarchical controls=", True, PAIR, lambda s, **j: _train_pair(s, None, controls=C_NOISE, **j)),
+    ("train_step_hierarchical occupancy= controls=", True, PAIR, lambda s, **j: _train_pair(s, s.occ, controls=C_NOISE, **j)),
+    ("train_step_guided distortion=", True, PAIR, lambda s, **j: _train_guided(s, None, distortion=LAM, **j)),
+    ("train_step_guided occupancy= controls=", True, PAIR, lambda s, **j: _train_guided(s, s.occ, controls=C_ALL, **j)),
+)
+
 
 def run(s, row, mode, **extra):
     """One call of ``row`` from the fixed seed -> (flat outputs, generator state behind it).  mode 'default': the entry
@@ -150,7 +193,7 @@ def digest(t):
 def main():
     assert torch.cuda.is_available(), "the entry points run on the GPU; there is nothing to hash without one"
     s = scene(torch.device("cuda:0"))
-    for row in ROWS:
+    for row in ROWS + CONTROL_ROWS:
         for mode in ("default", "explicit", "device_rng"):
             out, state = run(s, row, mode)
             tail = ""
