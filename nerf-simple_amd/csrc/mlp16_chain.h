@@ -32,7 +32,9 @@
 //     from LDS (16 rows x 32 k, 1 KiB) feeds two MFMAs (the two column blocks);
 //   * the chunk barrier sits three fragments before the END of a chunk and the next chunk's first fragments are
 //     requested right behind it, so no chunk starts with an LDS round trip; the next chunk's DMA pieces go out one per
-//     four MFMAs.
+//     four MFMAs;
+//   * in the inference kernels a wave's issue priority falls in four steps over a chunk, so that the two waves of a SIMD
+//     stay in step and neither runs the end of a chunk alone (chunk_prio below).
 #pragma once
 #include "nerf_device.h"
 #include <utility>
@@ -100,6 +102,62 @@ __host__ __device__ constexpr bool plan_fits() {
     for (int cc = 0; cc < NUM_CHUNKS<P>; ++cc)
         if (chunk_kib<P>(cc) * 1024 > LDS_WBUF) return false;
     return NUM_CHUNKS<P> % 2 == 0;
+}
+
+// ---- issue priority inside a chunk (inference; DESIGN.md section 5, "Keeping a SIMD's two waves in step") -----------
+// The two waves of a SIMD share its matrix pipe, and issue between them goes by priority first, then age.  At equal
+// priority the older wave takes every slot it can use, finishes its MFMAs of a chunk first and waits in the chunk
+// barrier while its partner runs the rest alone -- and one in-order wave, with a weight read, a conversion and a ReLU
+// between its MFMAs, does not fill the pipe.  So a wave's priority FALLS as it advances through the chunk: PRIO_LEVELS
+// steps of equal length, top level at the first MFMA, level 0 from the last step on (the barrier, BARRIER_TAIL
+// fragments before the end, lies in it: both waves leave it together and nothing needs favouring there).  The wave
+// that is behind is in an earlier step and outranks its partner, whichever of the two is the older one: same code in
+// every wave, no wave-id test, no branch.  A level changes only between weight fragments (both column-block MFMAs of a
+// fragment issue at one level).  The cut-off, by the stamps of every chunk barrier (profiles/chunk_priority_stamp_chunks_*.txt):
+// chunks under PRIO_MIN_MFMAS MFMAs hold level 0 -- the sigma tile (16), the rgb tile (8), the 32-MFMA halves of layer 0:
+// a step of theirs would be a few MFMAs, shorter than the lag it is to bound -- and so does layer 0 as a whole (the
+// sigma-only plan runs it as one 64-MFMA chunk): its lag is the prologue's, the leader waits longer there than the
+// chunk's own MFMAs take.  Every chunk ends at level 0, so the prologue, the ring barrier and compositing run at
+// level 0 in all waves.  Rules tried and their A/B: DESIGN.md section 5.
+constexpr int BARRIER_TAIL = 3;       // the chunk barrier sits this many weight fragments before the end of a chunk
+constexpr int PRIO_LEVELS = 4;
+constexpr int PRIO_MIN_MFMAS = 64;
+static_assert(PRIO_LEVELS >= 2 && PRIO_LEVELS <= 4, "s_setprio has levels 0..3");
+__host__ __device__ constexpr bool chunk_stepped(int L, int mfmas) { return L >= 1 && mfmas >= PRIO_MIN_MFMAS; }
+// level of chunk-linear MFMA m = fragment * NCB + column block, in a stepped chunk of `mfmas` MFMAs
+__host__ __device__ constexpr int chunk_prio(int m, int mfmas, int levels) {
+    const int step = mfmas / NCB / levels;            // weight fragments per level
+    const int lv = levels - 1 - (m / NCB) / step;
+    return lv > 0 ? lv : 0;
+}
+// what chunk_step relies on, for one chunk of F fragments whose barrier sits in front of fragment FB
+__host__ __device__ constexpr bool chunk_prio_ok(int L, int F, int FB) {
+    const int M = F * NCB;
+    if (!chunk_stepped(L, M)) return true;            // held at level 0: constant by construction
+    if (chunk_prio(0, M, PRIO_LEVELS) != PRIO_LEVELS - 1) return false;
+    for (int m = 1; m < M; ++m) {
+        if (chunk_prio(m, M, PRIO_LEVELS) > chunk_prio(m - 1, M, PRIO_LEVELS)) return false;       // never rises
+        if (m >= FB * NCB && chunk_prio(m, M, PRIO_LEVELS) != 0) return false;                     // level 0 from the barrier on
+        if (m % NCB != 0 && chunk_prio(m, M, PRIO_LEVELS) != chunk_prio(m - 1, M, PRIO_LEVELS)) return false;   // one level per fragment
+    }
+    return true;
+}
+template <class P>
+__host__ __device__ constexpr bool plan_prio_ok() {
+    for (int cc = 0; cc < NUM_CHUNKS<P>; ++cc) {
+        const int F = chunk_kib<P>(cc);               // a weight fragment is 1 KiB
+        if (!chunk_prio_ok(chunk_layer<P>(cc), F, F <= BARRIER_TAIL ? F : F - BARRIER_TAIL)) return false;
+    }
+    return true;
+}
+// s_setprio takes an immediate: the unrolled chunk loop folds this to the one instruction
+__device__ __forceinline__ void set_prio(int level) {
+    switch (level) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+    }
 }
 
 struct Ctx {
@@ -309,8 +367,12 @@ __device__ __forceinline__ void chunk_step(const Ctx& c, St& st, ex8 (&in)[NCB][
     constexpr int NBIAS_OFF = LDS_BIAS + (P::bias_off(NL) + 16 * (NCC - chunk_first<P>(NL)) * P::tpc(NL)) * 4;
     const unsigned nwb = c.b_wread[NCC & 1];
     // Where the chunk's barrier sits, as a fragment index: TAIL fragments before the end of the chunk.
-    constexpr int TAIL = 3;
+    constexpr int TAIL = BARRIER_TAIL;
     constexpr int FB = F <= TAIL ? F : F - TAIL;
+    // Falling issue priority over the chunk (chunk_prio above).  Not in the training forward, which is issue-bound in
+    // another regime (counted vmcnt waits, stores in every epilogue piece) and keeps its machine code.
+    constexpr bool STEPPED = !SAVE && chunk_stepped(L, F * NCB);
+    static_assert(plan_prio_ok<P>(), "priority: top level at MFMA 0, never rising, one level per fragment, 0 from the barrier on");
     // The training forward's counted wait: vector-memory instructions this wave issues between its DMA pieces
     // (first in the chunk) and the barrier, i.e. the activation / mask stores of the epilogue pieces that sit in
     // front of MFMA FB * NCB (piece 4 cb + 3 of a pair carries column block cb's stores); the ones behind the
@@ -382,6 +444,11 @@ __device__ __forceinline__ void chunk_step(const Ctx& c, St& st, ex8 (&in)[NCB][
             if (t + 1 < NT && ks == KS / 2) {
                 acc[0][t + 1 < NT ? t + 1 : 0] = lds_load<f32x4>(c.b_bias, BIAS_OFF + 64 * (t + 1));
                 for (int cb = 1; cb < NCB; ++cb) acc[cb][t + 1 < NT ? t + 1 : 0] = acc[0][t + 1 < NT ? t + 1 : 0];
+            }
+            if constexpr (STEPPED) {
+                // every chunk is entered at level 0 (the previous one ended there): emitted only where the level changes
+                const int lv = chunk_prio(f * NCB, F * NCB, PRIO_LEVELS);
+                if (lv != (f == 0 ? 0 : chunk_prio((f - 1) * NCB, F * NCB, PRIO_LEVELS))) set_prio(lv);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

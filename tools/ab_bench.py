@@ -99,6 +99,7 @@ for v in variants:
     tf = B * N * 1186816 / (statistics.median(t) * 1e-3) / 1e12
     print(f"{v.name}: median {statistics.median(t):.3f} ms  min {min(t):.3f}  max {max(t):.3f}  -> {tf:.0f} TFLOP/s "
           f"({tf / 25:.1f}% of 2.5 PF)")
+    print("    rounds: " + " ".join(f"{x:.3f}" for x in t))
 for i in range(1, len(variants)):
     if outs[i].shape == outs[0].shape:
         print(f"max |out[{variants[i].name}] - out[{variants[0].name}]| =", float((outs[i] - outs[0]).abs().max()),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Do the kernels of the working tree compile to the machine code of another commit?
 
-    python tools/isa_diff.py [--base REV] [--show N] [--map OLD=NEW ...] [[base:]file.hip[:-DFLAG] ...] > profiles/<name>_isa_diff.txt
+    python tools/isa_diff.py [--base REV] [--show N] [--mix] [--map OLD=NEW ...] [[base:]file.hip[:-DFLAG] ...] > profiles/<name>_isa_diff.txt
 
 For a change that only moves source around (a shared header, a renamed helper) the proof that nothing happened to a
 kernel is that its instructions did not change.  The tool exports nerf-simple_amd/csrc and include/ of REV (default
@@ -16,9 +16,13 @@ compares the instruction text kernel by kernel after normalisation:
     tree no longer has is listed as base:file.hip[:-DFLAG]: it is assembled from the base alone, and every kernel of it has
     to be mapped into a listed file of the working tree.
 One line per kernel: instruction count, MFMA count, identical yes / no; --show N prints the first N differing lines of a
-kernel that is not identical.  Exit status 1 when any kernel differs, is missing or is new.  Needs hipcc and git; no GPU.
+kernel that is not identical; --mix prints, for such a kernel, the counts of the chain's instruction classes (MIX) on both
+sides and how many differing lines are anything but `s_setprio` / `s_nop`, and whether those are the same opcodes on
+both sides (register allocation, a wait moved by a slot) -- for a change that is meant to add only those.
+Exit status 1 when any kernel differs, is missing or is new.  Needs hipcc and git; no GPU.
 """
 import argparse
+import collections
 import concurrent.futures
 import difflib
 import io
@@ -37,6 +41,8 @@ CSRC = os.path.join("nerf-simple_amd", "csrc")
 DEFAULT = ["mlp_bf16_16.hip", "mlp_bf16_16.hip:-DNERF_HALF", "density.hip", "density.hip:-DNERF_HALF", "mlp_bwd_16.hip",
            "mlp_f32.hip", "dw_gemm.hip", "dw_gemm_f8.hip"]
 LABEL = re.compile(r"\.L\w+")
+MIX = (("v_mfma", r"v_mfma"), ("ds_read_b128", r"ds_read_b128"), ("v_cvt_pk_*", r"v_cvt_pk_"), ("v_pk_max_i16", r"v_pk_max_i16"),
+       ("buffer_load ... lds", r"buffer_load\S* .* lds$"), ("s_barrier", r"s_barrier"), ("s_setprio", r"s_setprio"), ("s_nop", r"s_nop"))
 
 
 def normalise(lines):
@@ -70,6 +76,7 @@ def main():
     ap.add_argument("--show", type=int, default=0, help="print this many differing lines of a kernel that differs")
     ap.add_argument("--map", action="append", default=[], metavar="OLD=NEW",
                     help="a renamed kernel: re.sub(OLD, NEW) on the symbols of the base")
+    ap.add_argument("--mix", action="store_true", help="instruction-class counts of a kernel that differs, both sides")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("files", nargs="*", default=DEFAULT)
     args = ap.parse_args()
@@ -106,6 +113,16 @@ def main():
                     rc |= not same
                     print(f"  {name}: {count(b)[0]} instructions, {count(b)[1]} MFMAs, identical {'yes' if same else 'no'}"
                           + ("" if same else " (base: %d instructions, %d MFMAs)" % count(a)))
+                    if not same and args.mix:
+                        for label, pat in MIX:
+                            na, nb = (sum(re.match(pat, ln) is not None for ln in side) for side in (a, b))
+                            print(f"      {label:20s} base {na:5d}   working tree {nb:5d}" + ("" if na == nb else "   <-- differs"))
+                        other = [d for d in difflib.unified_diff(a, b, lineterm="", n=0)
+                                 if d[:1] in "+-" and not d.startswith(("+++", "---")) and not d[1:].startswith(("s_setprio", "s_nop"))]
+                        ops = [collections.Counter(d[1:].split()[0] for d in other if d[0] == sign) for sign in "-+"]
+                        print(f"      differing lines other than s_setprio / s_nop: {len(other)}"
+                              + ("" if not other else " (the same opcodes on both sides: other registers or another slot)"
+                                 if ops[0] == ops[1] else " (OTHER OPCODES)"))
                     if not same and args.show:
                         diff = [d for d in difflib.unified_diff(a, b, "base", "working tree", lineterm="", n=0)]
                         print("\n".join("      " + d for d in diff[:args.show]))
