@@ -497,6 +497,34 @@ int nerf_amd_adam_step_hyper(float* params, const float* grads, float* exp_avg, 
 int64_t nerf_amd_pinned_device_address(const void* host);
 int nerf_amd_hyper_fetch(const float* ring_dev, int slots, float* hyper, uint32_t* counter, void* stream);
 
+/* ---- gradient guard: global-norm clipping and the non-finite step guard, all in device memory -------------------------
+ * Between the gradients (behind a data-parallel exchange, so every rank decides alike) and Adam.  `guard` is a record of
+ * eight 32-bit words in device memory, 16-byte aligned, allocated and zeroed (but for word 0) by the caller:
+ *   0  f32  INPUT max_norm: > 0; +inf = guard only (never clips); may be overwritten in place between launches / replays
+ *   1  f32  norm of this step, before clipping, as computed (NaN / inf on a skipped step)
+ *   2  f32  coef (0 on a skipped step)
+ *   3  u32  skip, 0 / 1
+ *   4  u32  steps seen     5  u32  steps skipped     6  u32  steps clipped (coef < 1)     7  0
+ * Words 4..6 are running totals kept by one thread with ordinary loads and stores.  Definition, for g = grads[0..n):
+ *   S    = sum g_i^2, every square and the sum in double, in a fixed order (a fixed partition of g over a fixed number of
+ *          workgroups; per-thread, then wave / block tree, then the block sums in index order; no atomics): two runs
+ *          write the same bytes, and a finite fp32 gradient neither overflows nor underflows S
+ *   norm = fl32(sqrt(S));   skip <=> norm is not finite (some g_i is NaN or +-inf, or the norm exceeds the fp32 range)
+ *   coef = min(1, max_norm / (norm + 1e-6)), three fp32 operations each rounded on its own (torch's clip_grad_norm_);
+ *          max_norm = +inf gives exactly 1.  n == 0: norm 0, coef 1, no skip.
+ * nerf_amd_grad_guard fills the record (two launches); workspace: nerf_amd_grad_guard_workspace_bytes(n) bytes, 8-byte
+ * aligned, contents irrelevant.  grads may be NULL when n == 0. */
+int64_t nerf_amd_grad_guard_workspace_bytes(int64_t n);
+int nerf_amd_grad_guard(const float* grads, int64_t n, void* workspace, void* guard, void* stream);
+/* nerf_amd_adam_step_hyper behind the guard: by definition, bit for bit, nerf_amd_adam_step_hyper on g' = fl32(coef g_i)
+ * (one rounded product per element; where coef == 1 the gradient is read as it is) -- and nothing at all where the
+ * record's skip word is set: params, exp_avg and exp_avg_sq keep their bits.  The bias corrections in `hyper` stay the
+ * caller's, those of the ATTEMPTED step: time passes on a skipped step, so after k skips they are those of step t, not
+ * t - k (a relative difference of beta^(t-k) - beta^t, nothing beyond the first few hundred steps).  `guard`: the record
+ * nerf_amd_grad_guard filled on the same stream (required whatever n is). */
+int nerf_amd_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                               int64_t n, const float* hyper, const void* guard, void* stream);
+
 /* ---- networks of other sizes: Nerf(Lp, Ld, H), reference utils/nets.py:9-32 ---------------- */
 /* The fused kernels implement the one configuration the reference constructs (Nerf() = (10, 4, 256): train.py:41,
  * test.py:27).  Every nn.Linear (+ nn.ReLU) of any other size, and its backward (dX = dY W, dW = dY^T X, db = dY^T 1),

@@ -173,6 +173,9 @@ _SIGNATURES = {
     "nerf_amd_volume_render_masked_mse_backward_pdf_bg": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _i64,
                                                                  ctypes.c_float, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                                                  _i32, _i32, _vp]),
+    "nerf_amd_grad_guard_workspace_bytes": (_i64, [_i64]),
+    "nerf_amd_grad_guard": (_i32, [_vp, _i64, _vp, _vp, _vp]),
+    "nerf_amd_adam_step_guarded": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "nerf_amd_volume_render_masked_mse_backward_pdf": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _vp,
                                                               _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
 }

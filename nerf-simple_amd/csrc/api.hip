@@ -796,6 +796,25 @@ int nerf_amd_adam_step_hyper(float* params, const float* grads, float* exp_avg, 
     return nerf_amd_launch_adam_hyper(params, grads, exp_avg, exp_avg_sq, n, hyper, S(stream));
 }
 
+int64_t nerf_amd_grad_guard_workspace_bytes(int64_t n) { return n < 0 ? NERF_AMD_EINVAL : grad_guard_ws_bytes(); }
+
+int nerf_amd_grad_guard(const float* grads, int64_t n, void* workspace, void* guard, void* stream) {
+    if (n < 0) return NERF_AMD_EINVAL;
+    if (bad_guard_record(guard) || !workspace || misaligned(workspace, 8)) return NERF_AMD_EINVAL;
+    if (n > 0 && (!grads || misaligned(grads, 4))) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_grad_guard(grads, n, reinterpret_cast<double*>(workspace), reinterpret_cast<unsigned*>(guard), S(stream));
+}
+
+int nerf_amd_adam_step_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                               const float* hyper, const void* guard, void* stream) {
+    if (n < 0) return NERF_AMD_EINVAL;
+    if (bad_guard_record(guard)) return NERF_AMD_EINVAL;          // looked at before the empty problem: a record is always needed
+    if (n == 0) return 0;
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !hyper) return NERF_AMD_EINVAL;
+    return nerf_amd_launch_adam_guarded(params, grads, exp_avg, exp_avg_sq, n, hyper, reinterpret_cast<const unsigned*>(guard),
+                                        S(stream));
+}
+
 // ---- camera optimiser: rays from (stored pose, correction, pixel), their backward, the corrected poses ------------------
 int nerf_amd_camera_rays(const float* poses, const float* xi, const int64_t* ids, int64_t* ids_copy, int H, int W, float f,
                          float* rays, int64_t B, int64_t M, void* stream) {

@@ -6,6 +6,7 @@
 #pragma once
 #include "nerf_device.h"
 #include "sample_pdf_device.h"
+#include "launchers.h"
 #include "../../include/nerf_amd.h"
 
 using nerf_layout::align256;
@@ -70,6 +71,11 @@ inline bool bad_box(const float* h_lo, const float* h_hi) {
     }
     return false;
 }
+
+// the gradient guard (nerf_amd_grad_guard, nerf_amd_adam_step_guarded): the record is eight 32-bit words in device memory,
+// 16-byte aligned; the workspace holds one double per workgroup of the reduction's fixed partition, whatever n is
+inline bool bad_guard_record(const void* guard) { return !guard || misaligned(guard, 16); }
+inline int64_t grad_guard_ws_bytes() { return align256((int64_t)GRAD_GUARD_BLOCKS * 8); }
 
 // the rays and jitter of a rays-mode launch whose kernels form the sample positions themselves
 inline MlpArgs rays_args(const float* rays, const float* u, const float* tbins, uint32_t flags, uint64_t seed, int64_t ray_id0,

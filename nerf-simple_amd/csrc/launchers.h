@@ -75,6 +75,8 @@ struct MaskedBackwardArgs {
     float* loss_ray;                                   // [B] or NULL
 };
 constexpr long long MASKED_NO_CLAMP = 0x7fffffffffffffffll;
+// the gradient guard's fixed number of workgroups = the doubles of its workspace (adam.hip, nerf_amd_grad_guard_workspace_bytes)
+constexpr int GRAD_GUARD_BLOCKS = 256;
 
 // the plain MSE head under the clamp `capacity`: what the three capped heads share; the sampler's and the terms' fields zero
 inline MaskedBackwardArgs capped_head_args(const float* raw_live, const uint64_t* mask, const int64_t* offsets, const float* gt,
@@ -147,6 +149,9 @@ int nerf_amd_launch_select_rays(const uint32_t*, unsigned long long, const unsig
 int nerf_amd_host_mt19937_jump_poly(long long, const uint32_t*, uint32_t*);
 int nerf_amd_launch_adam_hyper(float*, const float*, float*, float*, long long, const float*, hipStream_t);
 int nerf_amd_launch_hyper_fetch(const float*, int, float*, unsigned*, hipStream_t);
+// the gradient guard (adam.hip): `partial` holds GRAD_GUARD_BLOCKS doubles, `guard` is the 8-word record
+int nerf_amd_launch_grad_guard(const float*, long long, double*, unsigned*, hipStream_t);
+int nerf_amd_launch_adam_guarded(float*, const float*, float*, float*, long long, const float*, const unsigned*, hipStream_t);
 int nerf_amd_launch_linear_f32(const float*, long long, long long, const float*, const float*, long long, long long, const float*,
                                float*, long long, long long, long long, long long, int, hipStream_t);
 int nerf_amd_launch_adam(float*, const float*, float*, float*, long long, float, float, float, float, float, float,

@@ -16,16 +16,48 @@
 parameters, in the order given and state_dict order within each, share ONE flat vector (2 x 595,844
 elements), so one Adam launch updates both; each module's packed images are then re-derived from its
 own slice.  ``nets`` is that tuple (None for a single module) and ``slices`` their views of ``flat``.
+
+``FusedAdam(net, max_grad_norm=x)``: global-norm gradient clipping and a non-finite step guard, both
+decided in device memory between the gradients and the update (nerf_amd_grad_guard, nerf_amd_adam_step_guarded; the
+definition is in include/nerf_amd.h).  ``x`` is a float > 0 -- ``float('inf')`` never clips and only guards -- and the norm
+is ONE norm over the optimiser's whole flat gradient (both networks of a pair, as ``clip_grad_norm_`` over all parameters
+gives).  A step whose norm is not finite (a NaN / inf gradient element, or a norm beyond fp32) is WITHHELD: parameters, both
+moments and the packed images keep their bits.  Time still passes: ``step_count`` counts attempted steps and the bias
+corrections stay those of the attempted step t, so after k skips they are those of step t, not t - k (a relative difference
+of beta^(t-k) - beta^t: nothing beyond the first few hundred steps).  ``guard`` is the record (8 words, float32 view:
+max_norm, norm, coef, then as int32 skip / steps / skipped / clipped / 0), ``grad_norm`` a 0-d device view of the last
+step's pre-clip norm (no sync), ``set_max_grad_norm(x)`` rewrites the limit in place (captured graphs read it at every
+replay), ``guard_stats()`` reads the record (one host read).  ``None`` (the default) launches exactly what it always did.
 """
+import math
+
 import torch
 
 from . import _lib
 
 
+def check_max_grad_norm(x):
+    """``max_grad_norm`` as a float: a number > 0, ``float('inf')`` included; NaN, 0, a negative number or a non-number is a
+    ValueError."""
+    import numbers
+    if isinstance(x, bool) or not isinstance(x, numbers.Real) or not float(x) > 0.0:
+        raise ValueError(f"max_grad_norm must be a number > 0 (float('inf') = guard only) or None, got {x!r}")
+    return float(x)
+
+
+def _f32(x):
+    """``x`` rounded to fp32, as a Python float (what a C ``float`` argument holds)."""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
 class FusedAdam:
     nets = None
+    guard = None                 # the guard record on the device (max_grad_norm given), else None
+    max_grad_norm = None
 
-    def __init__(self, net, lr=5e-4, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, net, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
+        if max_grad_norm is not None:
+            max_grad_norm = check_max_grad_norm(max_grad_norm)       # before the device is looked at
         if isinstance(net, (list, tuple)):
             nets = tuple(net)
             if not nets or len({id(n) for n in nets}) != len(nets):
@@ -55,6 +87,38 @@ class FusedAdam:
         self.param_groups = [{"params": self.params, "lr": lr, "betas": betas, "eps": eps}]
         self.step_count = 0
         self._grad = torch.empty_like(self.flat)
+        if max_grad_norm is not None:
+            # allocated here, before any capture: the record (word 0 = the limit), the reduction's workspace, and the device
+            # vector of the eager step's six scalars (a graphed stepper feeds its own)
+            self.max_grad_norm = max_grad_norm
+            self.guard = torch.zeros(8, dtype=torch.float32, device=dev)
+            self.guard[0] = max_grad_norm
+            self._guard_ws = _lib.workspace(_lib.lib().nerf_amd_grad_guard_workspace_bytes(self.flat.numel()), dev)
+            self._hyper = torch.zeros(8, dtype=torch.float32, device=dev)
+
+    @property
+    def grad_norm(self):
+        """The last step's gradient norm before clipping (NaN / inf on a withheld step): a 0-d device view of the record,
+        no sync.  None without ``max_grad_norm``."""
+        return None if self.guard is None else self.guard[1]
+
+    def set_max_grad_norm(self, x):
+        """A new limit, written into the record in place: the next step -- eager or a replay of a captured graph -- reads it."""
+        if self.guard is None:
+            raise RuntimeError("this FusedAdam was built without max_grad_norm: there is no guard to set a limit on "
+                               "(build it with max_grad_norm=float('inf') to guard without clipping)")
+        self.max_grad_norm = check_max_grad_norm(x)
+        self.guard[0:1].fill_(self.max_grad_norm)
+
+    def guard_stats(self):
+        """The record, read now (one host read, synchronises): the last step's ``norm`` and ``coef``, whether it was withheld
+        (``skipped_last``), and the running totals ``steps`` / ``skipped`` / ``clipped``.  None without ``max_grad_norm``."""
+        if self.guard is None:
+            return None
+        h = self.guard.cpu()
+        w = h.view(torch.int32)
+        return {"norm": float(h[1]), "coef": float(h[2]), "skipped_last": bool(w[3]), "steps": int(w[4]), "skipped": int(w[5]),
+                "clipped": int(w[6])}
 
     def zero_grad(self, set_to_none=True):
         for p in self.params:
@@ -78,8 +142,19 @@ class FusedAdam:
         g = self._flat_grad()
         pg = self.param_groups[0]
         self.step_count += 1
-        _lib.launch("nerf_amd_adam_step", self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), float(pg["lr"]),
-                    float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), self.step_count, dev=self.flat.device)
+        if self.guard is None:
+            _lib.launch("nerf_amd_adam_step", self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), float(pg["lr"]),
+                        float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), self.step_count, dev=self.flat.device)
+        else:
+            # the six scalars nerf_amd_adam_step forms from its arguments (betas as fp32, the bias corrections in double from
+            # those), in device memory: with max_grad_norm = inf and a finite gradient this step IS the plain one, bit for bit
+            b1, b2 = _f32(pg["betas"][0]), _f32(pg["betas"][1])
+            t, n, dev = self.step_count, self.flat.numel(), self.flat.device
+            self._hyper[:6] = torch.tensor([float(pg["lr"]), b1, b2, float(pg["eps"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)],
+                                           dtype=torch.float32)
+            _lib.launch("nerf_amd_grad_guard", g, n, self._guard_ws, self.guard, dev=dev)
+            _lib.launch("nerf_amd_adam_step_guarded", self.flat, g, self.exp_avg, self.exp_avg_sq, n, self._hyper, self.guard,
+                        dev=dev)
         # the kernel wrote through the flat buffer (the parameters' _version did not move):
         # re-derive the packed images now and stamp the cache with the current versions
         if self.nets is None:

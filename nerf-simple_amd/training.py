@@ -924,6 +924,27 @@ class _CountsWatch:
         return done
 
 
+class _GuardWatch(_CountsWatch):
+    """Asynchronous read-back of a guarded optimiser's record (``FusedAdam(max_grad_norm=)``: eight 32-bit words), after
+    _CountsWatch: ``push`` enqueues the 32-byte copy into pinned memory behind graph B, ``risen`` hands back, for each
+    completed copy whose skipped counter stands above the last one seen, (step, steps withheld since) -- no host wait."""
+
+    def __init__(self, slots=4):
+        self.bufs = [torch.zeros(8, dtype=torch.int32).pin_memory() for _ in range(slots)]
+        self.pending, self.k, self.skipped = [], 0, 0
+
+    def push(self, guard, step):
+        super().push(guard.view(torch.int32), step)
+
+    def risen(self):
+        out = []
+        for step, *words in self.poll():
+            if words[5] > self.skipped:
+                out.append((step, words[5] - self.skipped))
+                self.skipped = words[5]
+        return out
+
+
 def _capacity_points(capacity, total, what):
     """A capacity argument as points: an int is a number of points, a float a fraction of ``total`` (GraphedMaskedTrainStep's
     rule).  ``what`` names the argument in the messages."""
@@ -1195,6 +1216,16 @@ class GraphedTrainStep:
     ``check_every`` (default 16, 0 = never): every so many steps the forward's range flag is copied back without
     waiting; a later ``step`` raises FloatingPointError once such a copy shows non-finite values inside the network
     (NaN / inf weights or inputs: a diverged run) -- the reference would show a NaN loss there.
+
+    An optimiser built with ``FusedAdam(..., max_grad_norm=x)`` puts global-norm clipping and the
+    non-finite step guard into graph B and the whole-iteration graph: nerf_amd_grad_guard and nerf_amd_adam_step_guarded in
+    place of nerf_amd_adam_step_hyper, in every subclass (masked, box, hierarchical, guided, masked guided; the two steppers
+    with a per-image table refuse such an optimiser).  The pair sits behind the data-parallel exchange: the norm is that of
+    the reduced gradient, the global one, and every rank takes the same decision.  A step whose gradient norm is not finite
+    is withheld on the device -- weights, moments and images keep their bits, the next step trains -- with no host
+    synchronisation; on the steps ``check_every`` samples the record is copied back without waiting and a later ``step``
+    emits one RuntimeWarning naming how many steps were withheld.  ``stepper.grad_norm`` is the optimiser's (a 0-d device
+    view of the last norm), ``optimizer.set_max_grad_norm(x)`` takes effect at the next replay without a re-capture.
     """
 
     _distortion = 0.0            # the distortion term's weight (the dense single step and the guided step only)
@@ -1235,6 +1266,7 @@ class GraphedTrainStep:
         self.timing, self._events = bool(timing), []
         self.device_rng, self.seed, self.ray_id0 = bool(device_rng), int(seed), int(ray_id0)
         self.check_every, self._watch = int(check_every), _StatusWatch()
+        self._guard_watch = _GuardWatch() if optimizer.guard is not None else None
         self.B, self.N = int(n_rays), int(N)
         if storage not in ("bf16", "e4m3"):
             raise ValueError("storage must be 'bf16' (the default) or 'e4m3'")
@@ -1446,9 +1478,16 @@ class GraphedTrainStep:
             p.finish(2, _lib.stream_ptr(self.dev))
 
     def _update(self):
-        opt = self.opt
-        _launch("nerf_amd_adam_step_hyper", opt.flat, self.grads, opt.exp_avg, opt.exp_avg_sq, opt.flat.numel(), self.hyper,
-                _lib.stream_ptr(self.dev))
+        """Graph B, and the tail of the whole-iteration graph: the ONE place a graphed stepper launches Adam.  With a guarded
+        optimiser (``FusedAdam(max_grad_norm=)``) the norm / verdict launch and the guarded update stand in its place.  Both
+        sit behind the data-parallel exchange, so every rank sees the same reduced gradient -- the global norm -- and takes
+        the same decision.  The re-pack runs either way (on a withheld step it rewrites the same images)."""
+        opt, n, st = self.opt, self.opt.flat.numel(), _lib.stream_ptr(self.dev)
+        if opt.guard is None:
+            _launch("nerf_amd_adam_step_hyper", opt.flat, self.grads, opt.exp_avg, opt.exp_avg_sq, n, self.hyper, st)
+        else:
+            _launch("nerf_amd_grad_guard", self.grads, n, opt._guard_ws, opt.guard, st)
+            _launch("nerf_amd_adam_step_guarded", opt.flat, self.grads, opt.exp_avg, opt.exp_avg_sq, n, self.hyper, opt.guard, st)
         for net, flat, _ in self._images:                  # every trained module from its slice of the flat vector
             net.repack_from_flat(flat)
 
@@ -1557,6 +1596,7 @@ class GraphedTrainStep:
         if rays is not None and (rays.shape != self.rays.shape or gt.shape != self.gt.shape):
             raise RuntimeError(f"GraphedTrainStep was captured for rays {tuple(self.rays.shape)}, gt {tuple(self.gt.shape)}")
         self._watch.raise_if_diverged("step")
+        self._note_withheld()
         self._own_images()
         if rays is None and self.device_rng and self._primed_for != self.opt.step_count + 1:
             # the first step (or one after the step counter was moved by hand): the graph prefetches batch k + 1 while
@@ -1646,6 +1686,8 @@ class GraphedTrainStep:
                 self._events.append([ev[0], ev[0], ev[1]])
         if not whole:
             self.graph_b.replay()
+        if watch and self.opt.guard is not None:
+            self._guard_watch.push(self.opt.guard, self.opt.step_count)      # behind graph B, which filled it
         # graph B re-packed the two training images; any other image of the module (fp16 / fp32 inference) is now
         # stale -- and the kernels wrote through the flat buffer, so the parameters' versions did not move
         for net, _, _ in self._images:
@@ -1656,6 +1698,21 @@ class GraphedTrainStep:
         return self.loss
 
     __call__ = step
+
+    @property
+    def grad_norm(self):
+        """The optimiser's ``grad_norm``: the last step's gradient norm before clipping, a 0-d device view (no sync); None
+        for an optimiser without ``max_grad_norm``."""
+        return self.opt.grad_norm
+
+    def _note_withheld(self):
+        """First thing in ``step``: one RuntimeWarning per completed sample of the guard record (taken on the steps
+        ``check_every`` samples) whose skipped counter has risen."""
+        import warnings
+        for step, k in (self._guard_watch.risen() if self._guard_watch is not None else ()):
+            warnings.warn(f"{type(self).__name__}: the gradient guard withheld {k} training step{'s' if k != 1 else ''} up to step "
+                          f"{step} (a gradient norm that was not finite: NaN / inf in the batch or the gradients); weights and "
+                          "moments kept their values on those steps", RuntimeWarning, stacklevel=3)
 
     def _range_check(self):
         """The reference's |x| > 1 warning on the stratified pass's first / last samples (the finer passes lie between)."""
@@ -1731,6 +1788,10 @@ class _TableTrainStep(GraphedTrainStep):
             raise RuntimeError(f"the table of rays_from holds {rows} rays, {w['spans'].format(obj)} = {obj.n_rays}")
         if table.device != optimizer.flat.device:
             raise RuntimeError(f"{w['lives']} on {table.device}, the module on {optimizer.flat.device}")
+        if getattr(optimizer, "guard", None) is not None:
+            # the table's own Adam is not guarded: a network step withheld beside a table step taken would be worse than either
+            raise RuntimeError(f"{name} does not take an optimizer with max_grad_norm: the {w['gradient']} table's own Adam is not "
+                               "guarded yet (build FusedAdam without max_grad_norm)")
         self._adam2 = _TableAdam(table, lr, betas, eps)
         self._ids_used = torch.zeros((int(n_rays),), dtype=torch.int64, device=table.device)
 
@@ -1820,7 +1881,7 @@ class GraphedCameraTrainStep(_TableTrainStep):
 
     Refused (RuntimeError, before any launch or RNG draw): ``storage='e4m3'`` (nerf_amd_input_gradients reads bf16 dY),
     ``buckets=2``, a process group that exchanges gradients (``camera_grad`` would need an exchange of its own),
-    ``background`` / ``sigma_noise`` / ``distortion``."""
+    ``background`` / ``sigma_noise`` / ``distortion``, an optimizer built with ``max_grad_norm`` (the camera Adam is not guarded)."""
 
     _one_bucket = True
     _dense_pass_type = _CameraPass               # the dense pass and its buffers, the pose gradient behind its dX chain
@@ -1912,7 +1973,8 @@ class GraphedAppearanceTrainStep(_TableTrainStep):
 
     Refused (RuntimeError, before any launch or RNG draw): a process group that exchanges gradients (``appearance_grad`` has no
     exchange yet), ``background`` / ``sigma_noise`` / ``distortion``, an ``appearance`` whose M HW is not the table's length or
-    that lives on another device.  The masked, hierarchical, guided and camera steppers do not take a correction."""
+    that lives on another device, an optimizer built with ``max_grad_norm`` (the second Adam is not guarded).  The masked,
+    hierarchical, guided and camera steppers do not take a correction."""
 
     _reduce_behind = "dx"        # where the reduction sits on the main branch: behind the "dx" chain or behind the "head"
     _dense_pass_type = _AppearancePass           # the dense pass and its buffers, the loss behind the correction
