@@ -1221,6 +1221,40 @@ int nerf_amd_box_positions(const float* rays, const float* u, const float* tbins
                            int64_t ray_id0, const float* h_lo, const float* h_hi, float tn, float tf, float* ts, float* span,
                            int32_t* hit, int64_t B, int N, void* stream);
 
+/* ---- grid span: a ray's samples placed between its first and its last live cell (csrc/grid_span.hip, grid_span_device.h) ---
+ * The scene box's successor and not in the reference either: the interval is cut PER RAY from an occupancy grid's bits (layout
+ * above, "occupancy grid"), read in place, so nerf_amd_occupancy_from_density between two launches simply takes effect.
+ * tests/grid_span_model.py restates it op for op; DESIGN.md section 39.
+ *
+ * nerf_amd_span_positions: ts[B,N] for the grid of (nx, ny, nz) grid points, C_a = n_a - 1 cells per axis, bounds [h_lo, h_hi]
+ * and h_inv_step = 1 / cell size (HOST float[3] each), K = probes segments.  Per ray (o, d), d un-normalised; fp32, every
+ * operation rounded on its own (fl), no fma contraction:
+ *   1. clip to the grid: [a, b] and hit are the scene box's steps 1-3 with the box [h_lo, h_hi].  A slab miss -- which covers any
+ *      NaN component -- reads nothing: hit = 0 and the interval is [tn, tf].
+ *   2. K segments: edges e_0 = a, e_K = b exactly and e_j = fl(a + fl(fl(b - a) * fl(j / K))) between; segment j is
+ *      [e_j, e_j+1].  The point of an edge is p = fl(o + fl(e * d)) per axis, its cell index floor(fl(fl(p - lo) * inv_step))
+ *      CLAMPED into [0, C - 1] by comparisons that send a NaN to 0, before any address is formed: no input reads outside `bits`.
+ *      Segment j is live iff any of the 8 cells (c0|c1)_x x (c0|c1)_y x (c0|c1)_z of its two edges' indices has its bit set.
+ *   3. the interval: with j0 / j1 the first / last live segment, t0 = e_j0, t1 = e_(j1+1), hit = 1; with no live segment hit = 0
+ *      and [t0, t1] = [tn, tf]: the ray renders as it did, and behind a grid whose outside is empty it is dead as a whole.
+ *   4. ts_i = min(t0 + (t1 - t0) c_i, t1) on the unit positions c of the scene box's step 4: every jitter mode of that rule.
+ * The host rule probes >= 2 max(C_a) makes a segment at most half a cell long per axis, so every cell it crosses is among the
+ * 8: the span is CONSERVATIVE -- no point of the ray in [tn, tf] that lies in a live cell lies outside [t0, t1], up to fp32
+ * rounding at a cell face.  a <= t0 <= t1 <= b, and t0 < t1 unless [a, b] is only a few roundings long.  With every cell live
+ * the result is nerf_amd_box_positions' for the box [h_lo, h_hi], bit for bit.  There is no outside policy: the span speaks for
+ * the grid's cells only.
+ * Outputs and determinism as nerf_amd_box_positions: ts[B,N]; span[B,2] and hit[B] (int32 0 / 1), each skipped when NULL; one
+ * wavefront per ray (64 segments per ballot; the chunks between the first and the last live one are not looked at), every
+ * element written by exactly one lane, no atomics.  Nothing here carries a gradient.
+ * Rules in order -- NERF_AMD_EINVAL: bits NULL; h_lo / h_hi / h_inv_step NULL or not finite, or lo_a >= hi_a; a grid extent
+ * below 2 (or beyond the grid entry points' limits); probes below 64, not a multiple of 64 or below 2 max(C_a); tn / tf, B / N
+ * and the jitter rules as nerf_amd_box_positions.  NERF_AMD_EUNSUP: probes > 1024, N > 768 or B > 2^32.  NERF_AMD_EINVAL: rays
+ * NULL with B > 0, ts NULL with B > 0, a buffer (bits included) off 4 bytes.  B == 0: nothing is launched or written. */
+int nerf_amd_span_positions(const float* rays, const float* u, const float* tbins01, uint32_t flags, uint64_t seed,
+                            int64_t ray_id0, const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, const float* h_lo,
+                            const float* h_hi, const float* h_inv_step, int probes, float tn, float tf, float* ts, float* span,
+                            int32_t* hit, int64_t B, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,8 @@ _SIGNATURES = {
                                                                _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "nerf_amd_box_positions": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp,
                                       _i64, _i32, _vp]),
+    "nerf_amd_span_positions": (_i32, [_vp, _vp, _vp, _u32, _u64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32,
+                                       ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _i32, _vp]),
     "nerf_amd_volume_render_mse_backward_pdf_bg": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_float, _u32, _u64, _vp, _vp,
                                                           _u32, _u64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "nerf_amd_volume_render_masked_mse_backward_pdf_bg": (_i32, [_vp, _vp, _vp, _vp, _u32, _u64, _i64, _vp, _vp, _vp, _vp, _i64,

@@ -1117,4 +1117,22 @@ int nerf_amd_box_positions(const float* rays, const float* u, const float* tbins
     return nerf_amd_launch_box_positions(&a, h_lo, h_hi, tn, tf, ts, span, hit, B, S(stream));
 }
 
+// the grid span: the grid (its bounds are the box the ray is clipped to) and the segment count first, then the box's rules in
+// the box's order; probes > SPAN_MAX_PROBES is a size the kernel does not serve, beside N and B
+int nerf_amd_span_positions(const float* rays, const float* u, const float* tbins01, uint32_t flags, uint64_t seed,
+                            int64_t ray_id0, const uint32_t* bits, int64_t nx, int64_t ny, int64_t nz, const float* h_lo,
+                            const float* h_hi, const float* h_inv_step, int probes, float tn, float tf, float* ts, float* span,
+                            int32_t* hit, int64_t B, int N, void* stream) {
+    if (!bits || bad_box(h_lo, h_hi) || bad_f32x3(h_inv_step)) return NERF_AMD_EINVAL;
+    if (bad_grid(nx, ny, nz) || bad_span_probes(probes, nx, ny, nz)) return NERF_AMD_EINVAL;
+    if (!(tn < tf) || !(tn >= -3.402823466e38f) || !(tf <= 3.402823466e38f)) return NERF_AMD_EINVAL;       // also NaN
+    const int rc = masked_rays_check(rays, u, tbins01, flags, B, N, N > MASKED_MAX_N || probes > SPAN_MAX_PROBES);
+    if (rc) return rc;
+    if (misaligned(rays, 4) || misaligned(u, 4) || misaligned(tbins01, 4) || misaligned(bits, 4)) return NERF_AMD_EINVAL;
+    if ((B > 0 && !ts) || misaligned(ts, 4) || misaligned(span, 4) || misaligned(hit, 4)) return NERF_AMD_EINVAL;
+    if (B == 0) return 0;
+    const MlpArgs a = rays_args(rays, u, tbins01, flags, seed, ray_id0, B, N);
+    return nerf_amd_launch_span_positions(&a, bits, nx, ny, nz, h_lo, h_hi, h_inv_step, probes, tn, tf, ts, span, hit, B, S(stream));
+}
+
 }  // extern "C"

@@ -72,6 +72,21 @@ inline bool bad_box(const float* h_lo, const float* h_hi) {
     return false;
 }
 
+// the segments of a grid span (nerf_amd_span_positions) over a grid of (nx, ny, nz) >= 2 points: K a multiple of 64, at least
+// 64 and at least twice the cells of the longest axis -- what makes 8 cells per segment enough
+constexpr int SPAN_MAX_PROBES = 1024;
+inline bool bad_span_probes(int probes, int64_t nx, int64_t ny, int64_t nz) {
+    const int64_t cells = (nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz)) - 1;
+    return probes < 64 || probes % 64 != 0 || probes < 2 * cells;
+}
+// three HOST floats, each finite
+inline bool bad_f32x3(const float* h) {
+    if (!h) return true;
+    for (int i = 0; i < 3; ++i)
+        if (!(h[i] >= -3.402823466e38f && h[i] <= 3.402823466e38f)) return true;                 // -inf / +inf / NaN
+    return false;
+}
+
 // the gradient guard (nerf_amd_grad_guard, nerf_amd_adam_step_guarded): the record is eight 32-bit words in device memory,
 // 16-byte aligned; the workspace holds one double per workgroup of the reduction's fixed partition, whatever n is
 inline bool bad_guard_record(const void* guard) { return !guard || misaligned(guard, 16); }

@@ -212,4 +212,6 @@ int nerf_amd_launch_appearance_reduce(const float*, const long long*, long long,
                                       long long, long long, hipStream_t);
 int nerf_amd_launch_box_positions(const MlpArgs*, const float*, const float*, float, float, float*, float*, int*, long long,
                                   hipStream_t);
+int nerf_amd_launch_span_positions(const MlpArgs*, const unsigned*, long long, long long, long long, const float*, const float*,
+                                   const float*, int, float, float, float*, float*, int*, long long, hipStream_t);
 }

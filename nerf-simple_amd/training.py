@@ -498,7 +498,7 @@ def render_nerf_masked(rays, net, N, occupancy, tn=2, tf=6, *, u=None, ts=None, 
     sample draws what the dense render gives that sample; a dead one stays dead) and rgb + (1 - acc) background behind the
     masked compositor; ``w.ts`` then holds the sample positions.  The distortion term belongs to the step: a non-zero
     ``controls.distortion`` raises ValueError.
-    ``box``: a ``SceneBox`` (utils/box.py) -- the samples are placed inside the box (``box.positions`` with this call's jitter
+    ``box``: a ``SceneBox`` or a ``GridSpan`` (utils/box.py) -- the samples are placed inside the box (``box.positions`` with this call's jitter
     arguments, formed once where the jitter would be drawn) and the call goes on as its ``ts=`` path; the positions carry no
     gradient.  Together with ``ts=``: ValueError."""
     from .utils.box import check_box
@@ -599,7 +599,7 @@ def train_step(net, optimizer, rays, gt, N, *, tn=2, tf=6, u=None, decay=1.0, gr
     controls: a ``Controls`` -- the same four as ONE argument, on the dense path (bit for bit the flat keywords; giving both
     raises ValueError) AND with ``occupancy``: the masked step with the noise on its live rows, the loss behind the background
     and the distortion term on the masked compositor's weights, assembled as the dense step assembles them.
-    box: a ``SceneBox`` (utils/box.py) -- the samples are placed inside the box: the step is this step on
+    box: a ``SceneBox`` or a ``GridSpan`` (utils/box.py; DESIGN.md sections 33 and 39) -- the samples are placed inside the box: the step is this step on
     ``render_nerf(..., box=box)`` / ``render_nerf_masked(..., box=box)``, dense or with ``occupancy``, with the controls, at
     every precision.  The positions carry no gradient; the distortion term keeps the global ``tf`` and its coefficient."""
     from .utils.box import check_box
@@ -2155,14 +2155,30 @@ class _BoxSteps:
     jitter arguments become the PLACEMENT's (on the unit bins ``tbins01``; with ``device_rng`` the seed offset is read from
     device memory, as before), the one pass reads the placed positions ``ts_box`` under NERF_AMD_TS_GIVEN, and
     nerf_amd_box_positions is one more node of graph A in front of the forward.  ``box.lo`` / ``box.hi`` are baked into the
-    graph by value: a SceneBox is frozen, another box is another stepper."""
+    graph by value: a SceneBox is frozen, another box is another stepper.
+    With a ``GridSpan`` the node is nerf_amd_span_positions and what is baked in is the ADDRESS of the
+    span's grid's ``words``: ``TrainingOccupancyGrid.update`` writes the bits in place, so an update between two replays
+    simply takes effect, and ``step`` raises if that tensor was replaced."""
 
     def _bind_box(self, box, N, tn, tf):
-        from .utils.box import check_box, check_interval
+        from .utils.box import GridSpan, check_box, check_interval
         if check_box(box) is None:
-            raise TypeError(f"{type(self).__name__} needs a utils.box.SceneBox")
+            raise TypeError(f"{type(self).__name__} needs a utils.box.SceneBox or GridSpan")
         check_interval(N, tn, tf)
-        self.box, self._box_args = box, (_lib.host_f32x3(box.lo), _lib.host_f32x3(box.hi), float(tn), float(tf))
+        self.box, self._box_interval = box, (float(tn), float(tf))
+        self._span_words_ptr = box.occupancy.words.data_ptr() if isinstance(box, GridSpan) else None
+
+    def _watch_span(self):
+        """First thing in ``step``: the span's grid is still the captured one."""
+        if self._span_words_ptr is not None and self.box.occupancy.words.data_ptr() != self._span_words_ptr:
+            raise RuntimeError("the GridSpan's occupancy grid's words tensor was replaced: its address is baked into the captured "
+                               f"graph (TrainingOccupancyGrid.update writes in place); build a new {type(self).__name__}")
+
+    def step(self, *args, **kw):
+        self._watch_span()
+        return super().step(*args, **kw)
+
+    __call__ = step
 
     def _alloc_pass_buffers(self, tn, tf):
         super()._alloc_pass_buffers(tn, tf)
@@ -2171,14 +2187,15 @@ class _BoxSteps:
         self.tbins01 = _tbins(0, 1, first.N, self.dev)
         self.ts_box = torch.empty((self.B, first.N), dtype=torch.float32, device=self.dev)
         self._box_jitter = (rays, jit, ptr(self.tbins01), flags, seed, rid)
+        self._box_entry, args = self.box.placement(self.dev)
+        self._box_args = (*args, *self._box_interval)
         first.jitter = (ptr(self.rays), ptr(self.ts_box), None, _lib.FLAG_TS_GIVEN, 0, 0)
         if not hasattr(self, "ts"):              # a masked pass keeps no positions of its own: the placed ones are the step's
             self.ts = self.ts_box
 
     def _before_forward(self, st):
         super()._before_forward(st)
-        _launch("nerf_amd_box_positions", *self._box_jitter, *self._box_args, self.ts_box, None, None, self.B,
-                self.passes[0].N, st)
+        _launch(self._box_entry, *self._box_jitter, *self._box_args, self.ts_box, None, None, self.B, self.passes[0].N, st)
 
 
 class GraphedBoxTrainStep(_BoxSteps, GraphedTrainStep):

@@ -15,6 +15,13 @@ coefficient lambda / (B (tf - tn)): the last sample still owns [t_last, tf].
 
 ``box=`` on an entry point resolves the box to ``ts`` once, before anything else is drawn, and then IS that entry point's
 ``ts=`` path; with ``box=None`` the call is the call it was.
+
+The grid span is the box's successor: ``GridSpan(occ)`` cuts each ray's interval from the occupancy
+grid's own bits on the device -- from the ray's first live cell to its last (nerf_amd_span_positions; tests/grid_span_model.py)
+-- and is accepted wherever ``box=`` is.  It holds the grid, not a copy: ``occ.update()`` is seen by the next call.
+
+    span = GridSpan(occ)                                                  # once; follows occ.update() by itself
+    loss = train_step(net, opt, rays, gt, 24, device_rng=True, seed=step, occupancy=occ, box=span)
 """
 import math
 
@@ -91,15 +98,88 @@ class SceneBox:
         ``torch.rand(B, N)`` continued on the device; ``ts`` [B, N] are UNIT positions of the caller's own (0 = t0, 1 = t1).
         ``return_span=True``: (ts, span [B, 2] = (t0, t1), hit [B] int32).  The positions carry no gradient, and nothing else does.  A refused call
         leaves torch's generator where it was."""
-        B, N = _lib.require_rays(rays), int(N)
-        check_interval(N, tn, tf)
-        jit, flags, pending = jitter.single(B, N, rays.device, u=u, ts=ts, device_rng=device_rng)
-        try:
-            out = place(self, rays.detach().contiguous(), jit, flags, seed, ray_id0, N, tn, tf, return_span)
-        finally:
-            if pending is not None:
-                pending.finish()
-        return out if return_span else out[0]
+        return _positions(self, rays, N, tn, tf, u, ts, device_rng, seed, ray_id0, return_span)
+
+    def placement(self, dev):
+        """(entry point, its arguments between ``ray_id0`` and ``tn``): how ``place`` and the graphed steppers launch this box."""
+        return "nerf_amd_box_positions", (_lib.host_f32x3(self.lo), _lib.host_f32x3(self.hi))
+
+
+MAX_SPAN_CELLS, MAX_PROBES = 512, 1024  # cells per axis and segments nerf_amd_span_positions serves (probes >= 2 cells)
+
+
+class GridSpan:
+    """``GridSpan(occupancy, probes=None)``: each ray's interval from its first to its last live cell of ``occupancy`` (an
+    ``OccupancyGrid`` / ``TrainingOccupancyGrid`` whose outside is empty), cut on the device from the grid's bits in place --
+    a frozen, validated value that HOLDS the grid object, so an in-place ``update()`` is seen by the next placement.
+    ``probes``: the segments K a ray's clipped interval is cut into, a multiple of 64 with 2 max(cells per axis) <= K <= 1024;
+    None takes the smallest (256 for a 129^3 grid).  ValueError for an ``outside='live'`` grid (the span speaks for the cells
+    only: what lies outside them would be live and unseen), a bad ``probes`` or a grid beyond 512 cells per axis."""
+
+    __slots__ = ("occupancy", "probes")
+
+    def __init__(self, occupancy, probes=None):
+        from .occupancy import OccupancyGrid
+        if not isinstance(occupancy, OccupancyGrid):
+            raise TypeError("GridSpan takes an OccupancyGrid (utils/occupancy.py)")
+        if occupancy.outside != "empty":
+            raise ValueError("GridSpan needs a grid with outside='empty': behind outside='live' the samples outside the grid "
+                             "are live, and the span of the grid's cells does not cover them")
+        cells = max(r - 1 for r in occupancy.resolution)
+        if cells > MAX_SPAN_CELLS:
+            raise ValueError(f"GridSpan serves grids of up to {MAX_SPAN_CELLS} cells per axis, got {cells}")
+        least = max(64, -(-2 * cells // 64) * 64)
+        if probes is None:
+            probes = least
+        elif isinstance(probes, bool) or int(probes) != probes or probes % 64 or not least <= probes <= MAX_PROBES:
+            raise ValueError(f"probes must be a multiple of 64 in [{least}, {MAX_PROBES}] for this grid (at least twice its "
+                             f"{cells} cells per axis), got {probes!r}")
+        object.__setattr__(self, "occupancy", occupancy)
+        object.__setattr__(self, "probes", int(probes))
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError(f"GridSpan is frozen: build a new one to change {name!r}")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self):
+        return f"GridSpan({type(self.occupancy).__name__}{tuple(self.occupancy.resolution)!r}, probes={self.probes})"
+
+    def __eq__(self, other):
+        return isinstance(other, GridSpan) and self.occupancy is other.occupancy and self.probes == other.probes
+
+    def __hash__(self):
+        return hash((id(self.occupancy), self.probes))
+
+    def positions(self, rays, N, tn=2, tf=6, *, u=None, ts=None, device_rng=False, seed=0, ray_id0=0, return_span=False):
+        """ts [B, N]: the sample positions of ``rays`` between each ray's first and last live cell (nerf_amd_span_positions),
+        read from the grid's bits as they are now.  Arguments, jitter and returns as ``SceneBox.positions``: ``u`` [B, N]
+        uniforms, ``device_rng`` the counter RNG keyed by (seed, ray_id0 + ray), default one reference ``torch.rand(B, N)``;
+        ``ts`` [B, N] are UNIT positions of the caller's own.  ``return_span=True``: (ts, span [B, 2], hit [B] int32); a ray
+        that meets no live cell has hit = 0 and keeps [tn, tf].  The positions carry no gradient, and nothing else does.  A
+        refused call leaves torch's generator where it was."""
+        return _positions(self, rays, N, tn, tf, u, ts, device_rng, seed, ray_id0, return_span)
+
+    def placement(self, dev):
+        occ = self.occupancy
+        _lib.require_same_device("occupancy grid", occ.words, dev)
+        return "nerf_amd_span_positions", (occ.words, *occ.resolution, _lib.host_f32x3(occ.lo), _lib.host_f32x3(occ.bounds[1]),
+                                           _lib.host_f32x3(occ.inv_step), self.probes)
+
+
+def _positions(box, rays, N, tn, tf, u, ts, device_rng, seed, ray_id0, return_span):
+    """``SceneBox.positions`` / ``GridSpan.positions``: the checks, the jitter, one placement."""
+    B, N = _lib.require_rays(rays), int(N)
+    check_interval(N, tn, tf)
+    if isinstance(box, GridSpan):
+        _lib.require_same_device("occupancy grid", box.occupancy.words, rays.device)
+    jit, flags, pending = jitter.single(B, N, rays.device, u=u, ts=ts, device_rng=device_rng)
+    try:
+        out = place(box, rays.detach().contiguous(), jit, flags, seed, ray_id0, N, tn, tf, return_span)
+    finally:
+        if pending is not None:
+            pending.finish()
+    return out if return_span else out[0]
 
 
 def _live_bounds(cells, lo, step, bounds, margin):
@@ -118,12 +198,12 @@ def _live_bounds(cells, lo, step, bounds, margin):
 
 
 def check_box(box, **refused):
-    """``box=`` of an entry point: None or a SceneBox (TypeError otherwise); with a box, every keyword of ``refused`` that is
-    not None raises ValueError (``ts=``: the box places the positions)."""
+    """``box=`` of an entry point: None, a SceneBox or a GridSpan (TypeError otherwise); with one, every keyword of ``refused``
+    that is not None raises ValueError (``ts=``: the box places the positions)."""
     if box is None:
         return None
-    if not isinstance(box, SceneBox):
-        raise TypeError(f"box must be a utils.box.SceneBox (or None), got {type(box).__name__}")
+    if not isinstance(box, (SceneBox, GridSpan)):
+        raise TypeError(f"box must be a utils.box.SceneBox or GridSpan (or None), got {type(box).__name__}")
     for name, v in refused.items():
         if v is not None:
             raise ValueError(f"box= places the sample positions itself: not together with {name}=")
@@ -147,14 +227,15 @@ def check_interval(N, tn, tf):
 
 
 def place(box, rays, jit, flags, seed, ray_id0, N, tn, tf, want_span=False):
-    """One launch of nerf_amd_box_positions for settled jitter arguments -> (ts, span or None, hit or None)."""
+    """One launch of the box's placement (nerf_amd_box_positions, or nerf_amd_span_positions for a GridSpan) for settled
+    jitter arguments -> (ts, span or None, hit or None)."""
     B, dev = rays.size(0), rays.device
+    name, args = box.placement(dev)
     ts = torch.empty((B, N), dtype=torch.float32, device=dev)
     span = torch.empty((B, 2), dtype=torch.float32, device=dev) if want_span else None
     hit = torch.empty((B,), dtype=torch.int32, device=dev) if want_span else None
     tb = jitter.tbins(0, 1, N, dev, flags)
-    _lib.launch("nerf_amd_box_positions", rays, jit, tb, flags, int(seed), int(ray_id0), _lib.host_f32x3(box.lo),
-                _lib.host_f32x3(box.hi), float(tn), float(tf), ts, span, hit, B, N, dev=dev)
+    _lib.launch(name, rays, jit, tb, flags, int(seed), int(ray_id0), *args, float(tn), float(tf), ts, span, hit, B, N, dev=dev)
     return ts, span, hit
 
 

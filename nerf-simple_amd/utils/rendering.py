@@ -113,7 +113,7 @@ def render_nerf(rays, net, N, tn=2, tf=6, *, u=None, ts=None, outputs=ALL_OUTPUT
     the other four outputs are what they were.  ``controls.sigma_noise > 0`` behind a grid raises the regulariser's
     RuntimeError, a non-zero ``controls.distortion`` ValueError, ``terminate=`` with it RuntimeError.
 
-    box: a ``SceneBox`` (utils/box.py) -- each ray's N samples are placed inside the box instead of in
+    box: a ``SceneBox`` or a ``GridSpan`` (utils/box.py; DESIGN.md sections 33 and 39) -- each ray's N samples are placed inside the box instead of in
     [tn, tf] (a ray that misses keeps [tn, tf]): ``box.positions(rays, N, tn, tf, u=, device_rng=, seed=, ray_id0=)`` is formed
     once, where the jitter would be drawn, and the call goes on as its ``ts=`` path -- so it composes with everything that
     path serves (``occupancy``, ``terminate``, the controls, every precision, foreign nets).  The positions are constants:
@@ -442,7 +442,7 @@ def render_view(net, pose, cam_params, *, N=128, tn=2, tf=6, u=None, ray0=0, n_r
     and acc, then one small blend launch (without a background: the one call it was).  Not with occupancy / terminate.
     controls: a ``training.Controls`` -- ``render_nerf``'s: without a grid it stands for ``background``; with ``occupancy`` the
     masked render through the five-output masked compositor (so that acc exists), then the blend and the clip behind it.
-    box: a ``SceneBox`` -- device ray generation -> the box's positions (nerf_amd_box_positions, jitter keyed by global pixel
+    box: a ``SceneBox`` or a ``GridSpan`` -- device ray generation -> the box's positions (nerf_amd_box_positions, jitter keyed by global pixel
     id) -> the render, the background render or the masked / terminated render on the materialised rays under those given
     positions, as the ``occupancy=`` branch already runs; by definition ``render_nerf(generate_rays(...), ..., box=box)`` and
     the clip.  Not inside the one-launch image kernel."""
