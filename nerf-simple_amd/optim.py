@@ -50,6 +50,19 @@ def _f32(x):
     return float(torch.tensor(float(x), dtype=torch.float32))
 
 
+def adam_scalars(lr, betas, eps, t):
+    """The six scalars of Adam's step ``t`` (1-based) as every Adam kernel of the library takes them -- {lr, beta1, beta2, eps,
+    1 - beta1^t, sqrt(1 - beta2^t)} -- by the rule of nerf_amd_adam_step (include/nerf_amd.h), which is the definition: the
+    betas are the fp32 values the kernel multiplies by, and the two bias corrections are formed in double FROM THOSE rounded
+    betas (``math.sqrt``, as the C ``sqrt``), so the update is Adam's for exactly the betas the kernel holds.  Python floats;
+    storing them as fp32 is the one rounding left.  The ONE place this formula lives on the Python side: the guarded eager
+    step, the graphed steppers and the per-image tables' optimiser all call it."""
+    b1, b2, t = _f32(betas[0]), _f32(betas[1]), int(t)
+    if t < 1:
+        raise ValueError(f"Adam's step count is 1-based, got {t}")
+    return (float(lr), b1, b2, float(eps), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t))
+
+
 class FusedAdam:
     nets = None
     guard = None                 # the guard record on the device (max_grad_norm given), else None
@@ -146,12 +159,10 @@ class FusedAdam:
             _lib.launch("nerf_amd_adam_step", self.flat, g, self.exp_avg, self.exp_avg_sq, self.flat.numel(), float(pg["lr"]),
                         float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]), self.step_count, dev=self.flat.device)
         else:
-            # the six scalars nerf_amd_adam_step forms from its arguments (betas as fp32, the bias corrections in double from
-            # those), in device memory: with max_grad_norm = inf and a finite gradient this step IS the plain one, bit for bit
-            b1, b2 = _f32(pg["betas"][0]), _f32(pg["betas"][1])
-            t, n, dev = self.step_count, self.flat.numel(), self.flat.device
-            self._hyper[:6] = torch.tensor([float(pg["lr"]), b1, b2, float(pg["eps"]), 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)],
-                                           dtype=torch.float32)
+            # the six scalars nerf_amd_adam_step forms from its arguments, in device memory: with max_grad_norm = inf and a
+            # finite gradient this step IS the plain one, bit for bit
+            n, dev = self.flat.numel(), self.flat.device
+            self._hyper[:6] = torch.tensor(adam_scalars(pg["lr"], pg["betas"], pg["eps"], self.step_count), dtype=torch.float32)
             _lib.launch("nerf_amd_grad_guard", g, n, self._guard_ws, self.guard, dev=dev)
             _lib.launch("nerf_amd_adam_step_guarded", self.flat, g, self.exp_avg, self.exp_avg_sq, n, self._hyper, self.guard,
                         dev=dev)

@@ -812,8 +812,13 @@ class _HyperRing:
     """Pinned host ring for the per-step scalars (Adam's six floats + the jitter seed offset as an int64): one slot per
     step, written by the host before it launches the step and read on the device by the first node of graph A
     (nerf_amd_hyper_fetch: slot = device counter % slots) -- no copy between two graph launches.  A slot is rewritten only
-    after the event recorded behind the launch that read it has completed; host index and device counter advance in
-    lockstep (``reset`` puts both back to 0)."""
+    after the event recorded behind the launch that read it has completed.
+
+    Lockstep: the host index ``k`` must name the slot the device counter names.  ``push`` opens a
+    step (``pending``) and ``launched`` closes it; a ``push`` that finds the previous step still open -- an exception or a
+    KeyboardInterrupt between the two, with the replay enqueued or not: the host cannot know -- takes ``k`` from the device
+    counter itself (one wait for the stream, on that path only), so the slot it writes is the one the next replay reads.
+    ``reset`` puts both back to 0."""
 
     def __init__(self, dev, slots=16):
         self.ring = torch.zeros((slots, 8), dtype=torch.float32).pin_memory()
@@ -823,13 +828,23 @@ class _HyperRing:
             raise RuntimeError("the pinned host ring of the step's scalars is not mapped into the device's address space")
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.events = [None] * slots
-        self.k = 0
+        self.k, self.pending = 0, False
 
     def reset(self):
-        self.k = 0
+        self.k, self.pending = 0, False
         self.counter.zero_()
 
+    def _resync(self):
+        """The step before this one never reached ``launched``: the device counter says how many replays were enqueued.
+        Reading it waits for all of them, so no slot is in flight any more."""
+        torch.cuda.synchronize(self.counter.device)
+        self.k = int(self.counter.item()) & 0xffffffff
+        self.events = [None] * len(self.events)
+
     def push(self, values, seed_offset=0):
+        if self.pending:
+            self._resync()
+        self.pending = True
         i = self.k % self.ring.shape[0]
         if self.events[i] is not None:
             self.events[i].synchronize()
@@ -846,7 +861,8 @@ class _HyperRing:
     def launched(self, dev):
         """The launch that reads the slot just pushed is in the stream."""
         i = self.k % self.ring.shape[0]
-        self.k += 1
+        self.k = (self.k + 1) & 0xffffffff                      # the device counter is 32 bits wide and wraps with it
+        self.pending = False
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
         self.events[i] = ev
@@ -1492,10 +1508,9 @@ class GraphedTrainStep:
             net.repack_from_flat(flat)
 
     def _set_hyper(self, step):
+        from .optim import adam_scalars
         pg = self.opt.param_groups[0]
-        b1, b2 = float(pg["betas"][0]), float(pg["betas"][1])
-        self._ring.push((float(pg["lr"]), b1, b2, float(pg["eps"]), 1.0 - b1 ** step, (1.0 - b2 ** step) ** 0.5),
-                        seed_offset=step)
+        self._ring.push(adam_scalars(pg["lr"], pg["betas"], pg["eps"], step), seed_offset=step)
 
     def _capture(self):
         with torch.cuda.device(self.dev):
@@ -1645,6 +1660,11 @@ class GraphedTrainStep:
                 session.finish()
 
     def _enqueue_step(self, decay):
+        """``opt.step_count`` counts the steps ATTEMPTED: it advances here, in front of the replay, and the scalars pushed are
+        that count's.  If ``replay()`` itself raises, or anything behind it does before the ring's ``launched``, the count
+        stays advanced -- time passes on such a step as it does on a step the gradient guard withholds -- and the next
+        ``_set_hyper`` finds the ring's step still open and takes the slot index from the device counter (_HyperRing), so
+        the next replay runs with its own scalars whether the failed one was enqueued or not."""
         from . import parallel
         self.opt.step_count += 1
         self._set_hyper(self.opt.step_count)
@@ -1740,9 +1760,9 @@ class GraphedTrainStep:
 
 class _TableAdam:
     """The optimiser of a per-image table (``table`` [M,6]) trained beside the network inside the captured graph: an Adam of
-    its own -- nerf_amd_adam_step_hyper on (table, ``grad``) -- with scalars of its own, fed through a ring of its own.
-    The kernel reads its betas as fp32 and forms 1 - beta from them: ``betas`` are held rounded to fp32 and the bias
-    corrections are formed from the same rounded values, so the update is Adam's for exactly the betas held here."""
+    its own -- nerf_amd_adam_step_hyper on (table, ``grad``) -- with scalars of its own (``optim.adam_scalars``: the update
+    is Adam's for exactly the fp32 betas the kernel holds), fed through a ring of its own.  ``steps`` counts the steps
+    attempted, as ``FusedAdam.step_count`` does: ``push`` advances it in front of the replay and writes that step's scalars."""
 
     def __init__(self, table, lr, betas, eps):
         self.table, self.lr, self.eps, self.steps = table, float(lr), float(eps), 0
@@ -1752,8 +1772,9 @@ class _TableAdam:
         self.hyper, self.ring = torch.zeros(8, dtype=torch.float32, device=table.device), _HyperRing(table.device)
 
     def push(self):
-        t, (b1, b2) = self.steps + 1, self.betas
-        self.ring.push((self.lr, b1, b2, self.eps, 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5))
+        from .optim import adam_scalars
+        self.steps += 1
+        self.ring.push(adam_scalars(self.lr, self.betas, self.eps, self.steps))
 
     def update(self):
         _launch("nerf_amd_adam_step_hyper", self.table, self.grad, self.m, self.v, self.table.numel(), self.hyper,
@@ -1813,13 +1834,14 @@ class _TableTrainStep(GraphedTrainStep):
         self._adam2.update()
 
     def _capture(self):
+        steps = self._adam2.steps
         super()._capture()
-        self._adam2.ring.reset()                     # the warm-up consumed a slot
+        self._adam2.ring.reset()                     # the warm-up consumed a slot ...
+        self._adam2.steps = steps                    # ... and was no step
 
     def _enqueue_step(self, decay):
         loss = super()._enqueue_step(decay)
         self._adam2.ring.launched(self.dev)
-        self._adam2.steps += 1
         return loss
 
     def _table_step(self, rays, gt, u, decay, table_decay):
